@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: 2048 x 2048 uint16 slices/s destriped + achieved HBM GB/s (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--shape HxW] [--shading]
+    python bench.py --gpus N --steps K --warmup W [--shape HxW] [--shading] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the result line.  --full adds what the headline figure does not
+need: the CPU baseline (rank 0 of a one-GPU run) and the output verification below.  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy (see dump_outputs), so that two builds can be compared output for output.
 
 One "step" = one pass of the hot path (filter_stripes semantics, production parameters,
 uint16 in -> uint16 out) over a batch of 256 synthetic striped slices that is already resident in
@@ -14,7 +18,7 @@ is one RCCL broadcast of the filter-constant blob before the timed region; it, t
 max-over-ranks of the time go straight through the C ABI (dsx_comm_*, librccl.so; no torch).
 A failing collective or a result that does not verify ends the run with a non-zero exit code.
 
-After the timed region the output is VERIFIED: planes 0 and 1 against the reference's golden samples
+With --full, after the timed region the output is VERIFIED: planes 0 and 1 against the reference's golden samples
 (tests/golden/large_stats.npz, written by the real reference), and one plane from every sub-cohort
 stream part against a single-stream re-run of the same plane (bit-identical), so every stream's output
 is tied to the reference.
@@ -188,6 +192,39 @@ def verify(engine, stack, d_out, h, w, batch, cohort, n_streams, shading, wavele
     return ok, details
 
 
+DUMP_SLICES_BYTES = 32 << 20  # whole slices
+DUMP_SAMPLE_BYTES = 16 << 20  # the same seeded pixels of every slice
+
+
+def dump_outputs(out_dir, d_out, cfg, h, w, batch):
+    """What a caller of the timed path receives -- the uint16 slices and the config each slice was filtered with --
+    written as float32 .npy files (48 MiB in all at most; every uint16 value is exact in float32), positions as float64:
+
+      config.npy        [batch]        0 = no-cells config, 1 = cells config
+      slices.npy        [k, H, W]      whole slices at slice_index.npy (k evenly spaced slices, first and last included)
+      sample.npy        [batch, S]     every slice at the S flat pixel positions of sample_index.npy (seed 0)
+
+    The selection depends on (batch, H, W) only, so two runs with the same arguments dump the same positions."""
+    os.makedirs(out_dir, exist_ok=True)
+    k = min(batch, DUMP_SLICES_BYTES // (4 * h * w))
+    slice_index = np.unique(np.linspace(0, batch - 1, k).round().astype(np.int64)) if k > 0 else np.zeros(0, np.int64)
+    n_sample = max(1, min(h * w, DUMP_SAMPLE_BYTES // (4 * batch + 8)))  # sample.npy + sample_index.npy
+    sample_index = np.sort(np.random.RandomState(0).choice(h * w, n_sample, replace=False))
+    slices = np.empty((len(slice_index), h, w), np.float32)
+    sample = np.empty((batch, n_sample), np.float32)
+    for z in range(batch):
+        plane = d_out.download((h, w), np.uint16, offset=z * h * w * 2)
+        sample[z] = plane.reshape(-1)[sample_index]
+        hit = np.flatnonzero(slice_index == z)
+        if hit.size:
+            slices[hit[0]] = plane
+    np.save(os.path.join(out_dir, "config.npy"), np.asarray(cfg, np.float32))
+    np.save(os.path.join(out_dir, "slices.npy"), slices)
+    np.save(os.path.join(out_dir, "slice_index.npy"), slice_index.astype(np.float64))
+    np.save(os.path.join(out_dir, "sample.npy"), sample)
+    np.save(os.path.join(out_dir, "sample_index.npy"), sample_index.astype(np.float64))
+
+
 def requested_gpus(argv):
     """--gpus N of the command line (without building the whole parser: the launcher path runs before anything else)."""
     for i, a in enumerate(argv):
@@ -273,12 +310,16 @@ def main():
                     "any other PyWavelets name runs the tap-count-generic level kernels; not the headline metric)")
     ap.add_argument("--cohort", type=int, default=int(os.environ.get("DSX_COHORT", "256")),
                     help="planes per launch chain (workspace size)")  # fmt: skip
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline and verify the output (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-planes", type=int, default=None,
-                    help="planes of the CPU baseline sample (default: 16 per process; 0 = skip)")
+                    help="with --full: planes of the CPU baseline sample (default: 16 per process; 0 = skip)")
     ap.add_argument("--cpu-procs", type=int, default=min(16, os.cpu_count() or 1),
-                    help="single-thread oracle processes of the CPU baseline")
+                    help="with --full: single-thread oracle processes of the CPU baseline")
     ap.add_argument("--kernel-breakdown", action="store_true", help="one extra untimed step with per-kernel events")
-    ap.add_argument("--no-verify", action="store_true", help="skip the output verification (profiling runs)")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the output verification (profiling runs)")
     ap.add_argument("--settle", type=float, default=SETTLE_SECONDS,
                     help="seconds of untimed back-to-back steps before the warm-up (0 for profiler runs)")
     args = ap.parse_args()
@@ -300,7 +341,7 @@ def main():
 
     # CPU baseline first (rank 0, N = 1): its workers are spawned, which must not happen once this process holds the GPU
     cpu = None
-    if world == 1 and args.cpu_planes != 0 and args.wavelet == "db3":
+    if args.full and world == 1 and args.cpu_planes != 0 and args.wavelet == "db3":
         cpu = cpu_baseline(args.cpu_planes or 16 * args.cpu_procs, args.cpu_procs, H, W)
         log("[bench] cpu baseline: {}".format(cpu))
 
@@ -360,8 +401,10 @@ def main():
     cfg = d_cfg.download((args.batch,), np.int32)
     n_cells = int(cfg.sum())
     n_streams = int(os.environ.get("DSX_STREAMS", "4"))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_out, cfg, H, W, args.batch)
     verified, vdetails = (None, {"skipped": True})
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         verified, vdetails = verify(engine, stack, d_out, H, W, args.batch, min(args.cohort, args.batch), n_streams, shading, args.wavelet)
         verified = bool(group.allreduce([1.0 if verified else 0.0], "min")[0] == 1.0)
 

@@ -996,7 +996,7 @@ def test_bench_self_launch_two_ranks_on_the_one_gpu():
     env["DSX_SHARE_GPU"] = "1"
     r = subprocess.run(
         [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "32",
-         "--settle", "0", "--shape", "512x512"],
+         "--settle", "0", "--shape", "512x512", "--full"],
         capture_output=True, text=True, timeout=600, env=env)  # fmt: skip
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1022,7 +1022,7 @@ def test_bench_under_a_launcher_with_a_real_rccl_communicator():
     env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", DSX_FORCE_COMM="1")
     r = subprocess.run(
         [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32",
-         "--settle", "0", "--shape", "512x512", "--cpu-planes", "0"],
+         "--settle", "0", "--shape", "512x512", "--cpu-planes", "0", "--full"],
         capture_output=True, text=True, timeout=600, env=env)  # fmt: skip
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -1030,3 +1030,48 @@ def test_bench_under_a_launcher_with_a_real_rccl_communicator():
     assert d["n_gpus"] == 1 and d["verified"] is True
     assert c["rank_transport"] == "rccl" and c["rccl_ranks"] == 1 and c["rccl_error"] is None, c
     assert c["constants_broadcast_bytes"] > 0
+
+
+def test_bench_plain_run_dumps_what_its_last_timed_step_computed(engine, tmp_path):
+    """`bench.py` without --full times the steps and nothing else (no CPU baseline, no verification); --dump-outputs
+    writes the last timed step's slices and configs, which must be what the engine computes for the same stack."""
+    import json
+    import subprocess
+    import sys
+
+    n, h, w = 32, 512, 512
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DSX_RDZV_DIR")}
+    out_dir = tmp_path / "dump"
+    r = subprocess.run(
+        [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(n),
+         "--settle", "0", "--shape", "{}x{}".format(h, w), "--dump-outputs", str(out_dir)],
+        capture_output=True, text=True, timeout=600, env=env)  # fmt: skip
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["verified"] is None and "cpu_baseline" not in d
+    assert abs(d["value"] - n * 3 / (d["ms_per_step"] * 3e-3)) < 1e-2 * d["value"]
+    files = {f: np.load(str(out_dir / f), allow_pickle=False) for f in os.listdir(str(out_dir))}
+    assert set(files) == {"config.npy", "slices.npy", "slice_index.npy", "sample.npy", "sample_index.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(os.path.getsize(str(out_dir / f)) for f in files) <= 64 * 2**20
+
+    stack = synth.synthetic_stack(n, h, w)
+    engine.plan(h, w, synth.CELLS_CONFIG, synth.NO_CELLS_CONFIG, synth.ZARR_PATH_HIGH_INT, max_batch=n)
+    d_in, d_out, d_cfg = engine.alloc(stack.nbytes), engine.alloc(stack.nbytes), engine.alloc(4 * n)
+    try:
+        d_in.upload(stack)
+        engine.run_device(d_in, np.uint16, n, d_out, np.uint16, d_cfg)
+        engine.sync()
+        out = d_out.download((n, h, w), np.uint16).astype(np.float32)
+        cfg = d_cfg.download((n,), np.int32)
+    finally:
+        for b in (d_in, d_out, d_cfg):
+            b.free()
+    slice_index = files["slice_index.npy"].astype(np.int64)
+    assert slice_index[0] == 0 and slice_index[-1] == n - 1
+    np.testing.assert_array_equal(files["config.npy"], cfg)
+    np.testing.assert_array_equal(files["slices.npy"], out[slice_index])
+    np.testing.assert_array_equal(files["sample.npy"], out.reshape(n, -1)[:, files["sample_index.npy"].astype(np.int64)])
