@@ -22,6 +22,7 @@
 #include "dsx_wavelet.h"
 #include "dsx_plan.h"
 #include "dsx_io.h"
+#include "dsx_streaks.h"
 
 namespace {
 
@@ -168,6 +169,15 @@ struct dsx_ctx {
   unsigned long long graph_clock = 0;
   int graph_mode = 0;  // DSX_GRAPH=1 turns graphs on; back to 0 when a capture fails on this runtime
   unsigned long long graph_launches = 0, graph_captures = 0;
+  // dual-band filter (dsx_plan_streaks): when set, dsx_run_* run this plan instead of the log-space one
+  bool streaks = false;
+  dsx::st::StreaksPlan sp;
+  float* st_ws = nullptr;         // [regions of sp][P virtual planes]
+  float* st_mat = nullptr;        // row-filter operators, sp.lv[l].mat_off[band]
+  unsigned* st_mm = nullptr;      // [max_batch][2] min / max keys
+  unsigned* st_hist = nullptr;    // [max_batch][kStBins]
+  float* st_t = nullptr;          // [max_batch] threshold per plane
+  dsx::st::OtsuOut* st_info = nullptr;
 };
 
 namespace {
@@ -1040,6 +1050,177 @@ int check_sticky(dsx_ctx* ctx) {
                                "(a float32 pixel is NaN, infinite or <= -1); that plane's result is not valid");
 }
 
+// ---- dual-band filter (dsx_plan_streaks) ----------------------------------------------------------------------------
+void free_streaks(dsx_ctx* c) {
+  auto fr = [](void* p) { if (p) (void)hipFree(p); };
+  fr(c->st_ws); c->st_ws = nullptr;
+  fr(c->st_mat); c->st_mat = nullptr;
+  fr(c->st_mm); c->st_mm = nullptr;
+  fr(c->st_hist); c->st_hist = nullptr;
+  fr(c->st_t); c->st_t = nullptr;
+  fr(c->st_info); c->st_info = nullptr;
+  c->streaks = false;
+}
+
+__global__ __launch_bounds__(256) void k_st_mminit(unsigned* mm, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { mm[2 * i] = 0xffffffffu; mm[2 * i + 1] = 0u; }
+}
+
+inline unsigned st_blocks(size_t total) { return (unsigned)((total + 255) / 256); }
+
+template <typename TI, typename TO>
+void st_final(hipStream_t s, const dsx::st::StreaksPlan& p, const void* in, const float* r, int nb, const float* t,
+              void* out) {
+  const size_t total = (size_t)p.H * p.W * nb;
+  dsx::st::k_st_final<TI, TO><<<st_blocks(total), 256, 0, s>>>((const TI*)in, r, nb, nb, p.H, p.W, p.Hp, p.Wp,
+                                                               p.bands, t, 1.0f / p.crossover, (TO*)out);
+}
+
+// One cohort (nb <= max_batch planes) of the dual-band filter on stream s.
+int streaks_cohort(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d_out, int out_dtype) {
+  using namespace dsx::st;
+  const StreaksPlan& p = ctx->sp;
+  hipStream_t s = use_main(ctx);
+  const size_t px = (size_t)p.H * p.W;
+  const bool u16 = in_dtype == DSX_U16;
+  // 1. threshold per plane
+  if (p.otsu) {
+    k_st_mminit<<<st_blocks(nb), 256, 0, s>>>(ctx->st_mm, nb);
+    DSX_HIP(hipMemsetAsync(ctx->st_hist, 0, sizeof(unsigned) * kStBins * nb, s));
+    const unsigned bx = (unsigned)std::max<size_t>(1, std::min<size_t>(128, px / (256 * 32)));
+    const dim3 g(bx, nb);
+    if (u16) {
+      k_st_minmax<uint16_t><<<g, 256, 0, s>>>((const uint16_t*)d_in, px, ctx->st_mm);
+      k_st_hist<uint16_t><<<g, 256, 0, s>>>((const uint16_t*)d_in, px, ctx->st_mm, ctx->st_hist);
+      k_st_otsu<true><<<nb, kOtsuThreads, 0, s>>>(ctx->st_mm, ctx->st_hist, ctx->st_t, ctx->st_info);
+    } else {
+      k_st_minmax<float><<<g, 256, 0, s>>>((const float*)d_in, px, ctx->st_mm);
+      k_st_hist<float><<<g, 256, 0, s>>>((const float*)d_in, px, ctx->st_mm, ctx->st_hist);
+      k_st_otsu<false><<<nb, kOtsuThreads, 0, s>>>(ctx->st_mm, ctx->st_hist, ctx->st_t, ctx->st_info);
+    }
+  } else {
+    k_st_fill<<<st_blocks(nb), 256, 0, s>>>(ctx->st_t, nb, p.threshold);
+  }
+  // 2. log(1 + band) of the padded plane
+  float* ws = ctx->st_ws;
+  const int P = p.bands * nb;  // workspace planes of this cohort, band-major (v = band * nb + plane)
+  {
+    const size_t total = (size_t)p.Hp * p.Wp * nb * p.bands;
+    if (u16)
+      k_st_prep<uint16_t><<<st_blocks(total), 256, 0, s>>>((const uint16_t*)d_in, nb, nb, p.H, p.W, p.Hp, p.Wp,
+                                                           p.bands, ctx->st_t, ws + p.y, ctx->d_sticky);
+    else
+      k_st_prep<float><<<st_blocks(total), 256, 0, s>>>((const float*)d_in, nb, nb, p.H, p.W, p.Hp, p.Wp, p.bands,
+                                                        ctx->st_t, ws + p.y, ctx->d_sticky);
+  }
+  // 3. analysis: axis 0 into the temporaries, axis 1 into approx / cV (from lo) and cH / cD (from hi)
+  int h = p.Hp, w = p.Wp;
+  size_t src = p.y;
+  for (int l = 0; l < p.L; ++l) {
+    const StLevel& v = p.lv[l];
+    // every kernel writes its outputs dense: [P][rows][columns]
+    const size_t ps_in = (size_t)h * w;
+    k_st_dwt<0><<<st_blocks((size_t)v.h * w * P), 256, 0, s>>>(ws + src, P, h, w, w, ps_in, ws + p.t0, ws + p.t1, p.F,
+                                                               p.dec);
+    const size_t ps_t = (size_t)v.h * w;
+    k_st_dwt<1><<<st_blocks((size_t)v.h * v.w * P), 256, 0, s>>>(ws + p.t0, P, v.h, w, w, ps_t, ws + v.a, ws + v.cv,
+                                                                 p.F, p.dec);
+    k_st_dwt<1><<<st_blocks((size_t)v.h * v.w * P), 256, 0, s>>>(ws + p.t1, P, v.h, w, w, ps_t, ws + v.ch, ws + v.cd,
+                                                                 p.F, p.dec);
+    src = v.a;
+    h = v.h;
+    w = v.w;
+  }
+  // 4. row filter of every cH: per level and band over the nb planes of that band, Z = cH U into the first temporary
+  //    (free between analysis and synthesis), then cH' = cH + Z V
+  for (int l = 0; l < p.L; ++l) {
+    const StLevel& v = p.lv[l];
+    const size_t pl = (size_t)v.h * v.w;
+    const int R = nb * v.h;
+    for (int b = 0; b < p.bands; ++b) {
+      const int K = v.rank[b];
+      const float* U = ctx->st_mat + v.mat[b];
+      const float* V = U + (size_t)v.w * K;
+      const float* X = ws + v.ch + (size_t)b * nb * pl;
+      k_st_rowmat<<<dim3((K + kMmT - 1) / kMmT, (R + kMmT - 1) / kMmT), 256, 0, s>>>(X, U, nullptr, ws + p.t0, R, v.w, K);
+      k_st_rowmat<<<dim3((v.w + kMmT - 1) / kMmT, (R + kMmT - 1) / kMmT), 256, 0, s>>>(
+          ws + p.t0, V, X, ws + v.cf + (size_t)b * nb * pl, R, K, v.w);
+    }
+  }
+  // 5. synthesis, coarsest level first: axis 1 (approx + cV, filtered cH + cD), then axis 0
+  for (int l = p.L - 1; l >= 0; --l) {
+    const StLevel& v = p.lv[l];
+    const size_t pl = (size_t)v.h * v.w;
+    const size_t pa = (size_t)v.rh * v.rw;  // approx: forward output (top level) or the rebuild of level l + 1
+    const int wo = 2 * v.w - p.F + 2, ho = 2 * v.h - p.F + 2;
+    k_st_idwt<1><<<st_blocks((size_t)v.h * wo * P), 256, 0, s>>>(ws + v.a, v.rw, pa, ws + v.cv, v.w, pl, P, v.h, v.w,
+                                                                 ws + p.t0, p.F, p.rec);
+    k_st_idwt<1><<<st_blocks((size_t)v.h * wo * P), 256, 0, s>>>(ws + v.cf, v.w, pl, ws + v.cd, v.w, pl, P, v.h, v.w,
+                                                                 ws + p.t1, p.F, p.rec);
+    const size_t pt = (size_t)v.h * wo;
+    float* dst = l == 0 ? ws + p.y : ws + p.lv[l - 1].a;
+    k_st_idwt<0><<<st_blocks((size_t)ho * wo * P), 256, 0, s>>>(ws + p.t0, wo, pt, ws + p.t1, wo, pt, P, v.h, wo, dst,
+                                                                p.F, p.rec);
+  }
+  // 6. exp(r) - 1, blend, crop, store
+  if (u16 && out_dtype == DSX_U16) st_final<uint16_t, uint16_t>(s, p, d_in, ws + p.y, nb, ctx->st_t, d_out);
+  else if (u16) st_final<uint16_t, float>(s, p, d_in, ws + p.y, nb, ctx->st_t, d_out);
+  else if (out_dtype == DSX_U16) st_final<float, uint16_t>(s, p, d_in, ws + p.y, nb, ctx->st_t, d_out);
+  else st_final<float, float>(s, p, d_in, ws + p.y, nb, ctx->st_t, d_out);
+  DSX_HIP(hipGetLastError());
+  ctx->last_n = nb;
+  return DSX_OK;
+}
+
+// dsx_run_host (host = true: staged through the context's device buffers) / dsx_run_device of a streaks plan
+int streaks_run(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, int out_dtype, bool host) {
+  if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, DSX_EINVAL, "bad plane pointers / count");
+  if ((in_dtype != DSX_U16 && in_dtype != DSX_F32) || (out_dtype != DSX_U16 && out_dtype != DSX_F32))
+    return fail(ctx, DSX_EINVAL, "unknown element type");
+  DSX_HIP(hipSetDevice(ctx->device));
+  const dsx::st::StreaksPlan& p = ctx->sp;
+  const size_t in_plane = (size_t)p.H * p.W * elem_size(in_dtype);
+  const size_t out_plane = (size_t)p.H * p.W * elem_size(out_dtype);
+  const int B = p.B;
+  if (host) {
+    if (ctx->stage_in_bytes < in_plane * B) {
+      if (ctx->d_stage_in) (void)hipFree(ctx->d_stage_in);
+      ctx->d_stage_in = nullptr; ctx->stage_in_bytes = 0;
+      DSX_HIP(hipMalloc(&ctx->d_stage_in, in_plane * B));
+      ctx->stage_in_bytes = in_plane * B;
+    }
+    if (ctx->stage_out_bytes < out_plane * B) {
+      if (ctx->d_stage_out) (void)hipFree(ctx->d_stage_out);
+      ctx->d_stage_out = nullptr; ctx->stage_out_bytes = 0;
+      DSX_HIP(hipMalloc(&ctx->d_stage_out, out_plane * B));
+      ctx->stage_out_bytes = out_plane * B;
+    }
+  }
+  if (host) {  // a value error of an earlier asynchronous call is reported now, not wiped by this call's check
+    DSX_HIP(hipStreamSynchronize(use_main(ctx)));
+    if (int rc = check_sticky(ctx)) return rc;
+  }
+  for (int start = 0; start < n; start += B) {
+    const int nb = std::min(B, n - start);
+    const char* src = (const char*)in + start * in_plane;
+    char* dst = (char*)out + start * out_plane;
+    if (host) {
+      DSX_HIP(hipMemcpyAsync(ctx->d_stage_in, src, in_plane * nb, hipMemcpyHostToDevice, use_main(ctx)));
+      if (int rc = streaks_cohort(ctx, ctx->d_stage_in, in_dtype, nb, ctx->d_stage_out, out_dtype)) return rc;
+      DSX_HIP(hipMemcpyAsync(dst, ctx->d_stage_out, out_plane * nb, hipMemcpyDeviceToHost, use_main(ctx)));
+      DSX_HIP(hipStreamSynchronize(use_main(ctx)));
+      if (ctx->h_sticky && __atomic_exchange_n(ctx->h_sticky, 0u, __ATOMIC_ACQ_REL) != 0u)
+        return fail(ctx, DSX_EVALUE, "a plane of " + std::to_string(start) + " .. " + std::to_string(start + nb - 1) +
+                                         ": autodetected range of [nan, nan] is not finite (a pixel is NaN, infinite "
+                                         "or <= -1)");
+    } else if (int rc = streaks_cohort(ctx, src, in_dtype, nb, dst, out_dtype)) {
+      return rc;
+    }
+  }
+  return DSX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1122,6 +1303,7 @@ void dsx_destroy(dsx_ctx* ctx) {
   (void)dsx_comm_destroy(ctx);
   for (auto& r : ctx->prof) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
   free_plan_buffers(ctx);
+  free_streaks(ctx);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);
   if (ctx->t1) (void)hipEventDestroy(ctx->t1);
   for (int i = 1; i < dsx_ctx::kMaxStreams; ++i) {
@@ -1154,6 +1336,7 @@ int dsx_plan(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_cfg* 
   DSX_HIP(hipSetDevice(ctx->device));
   DSX_HIP(hipStreamSynchronize(use_main(ctx)));
   free_plan_buffers(ctx);
+  free_streaks(ctx);
 
   const dsx_cfg* src[2] = {no_cells_config, cells_config};  // index 1 == cells_config
   for (int c = 0; c < 2; ++c) {
@@ -1303,6 +1486,7 @@ int dsx_plan_info(const dsx_ctx* ctx, dsx_plan_info_t* info) {
 int dsx_run_device(dsx_ctx* ctx, const void* d_in, int in_dtype, int n, void* d_out, int out_dtype,
                    int32_t* d_cfg_used) {
   if (!ctx) return DSX_EINVAL;
+  if (ctx->streaks) return streaks_run(ctx, d_in, in_dtype, n, d_out, out_dtype, false);
   if (!ctx->planned) return fail(ctx, DSX_ENOPLAN, "dsx_plan has not been called");
   if (n < 0 || (n > 0 && (!d_in || !d_out))) return fail(ctx, DSX_EINVAL, "bad plane pointers / count");
   if ((in_dtype != DSX_U16 && in_dtype != DSX_F32) || (out_dtype != DSX_U16 && out_dtype != DSX_F32))
@@ -1334,6 +1518,7 @@ int dsx_sync(dsx_ctx* ctx) {
 int dsx_run_host(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, int out_dtype,
                  int32_t* cfg_used) {
   if (!ctx) return DSX_EINVAL;
+  if (ctx->streaks) return streaks_run(ctx, in, in_dtype, n, out, out_dtype, true);
   if (!ctx->planned) return fail(ctx, DSX_ENOPLAN, "dsx_plan has not been called");
   if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, DSX_EINVAL, "bad plane pointers / count");
   if ((in_dtype != DSX_U16 && in_dtype != DSX_F32) || (out_dtype != DSX_U16 && out_dtype != DSX_F32))
@@ -1875,6 +2060,92 @@ int dsx_get_level(dsx_ctx* ctx, int plane, int level, int stage, float* out) {
   const float* src = ctx->d_ws + (size_t)plane * ctx->plan.plane_floats + off;
   DSX_HIP(hipMemcpy2D(out, sizeof(float) * lp.w, src, sizeof(float) * pitch, sizeof(float) * lp.w, lp.h,
                       hipMemcpyDeviceToHost));
+  return DSX_OK;
+}
+
+int dsx_plan_streaks(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_streaks_cfg* cfg) {
+  if (!ctx) return DSX_EINVAL;
+  if (!cfg) return fail(ctx, DSX_EINVAL, "config is NULL");
+  if (height < 1 || width < 1) return fail(ctx, DSX_EINVAL, "plane must be at least 1 x 1");
+  if (max_batch < 1) return fail(ctx, DSX_EINVAL, "max_batch must be >= 1");
+  if (!(cfg->sigma_fg > 0.f) || !(cfg->sigma_bg > 0.f)) return fail(ctx, DSX_EINVAL, "sigma must be positive");
+  if (!(cfg->crossover > 0.f)) return fail(ctx, DSX_EINVAL, "crossover must be positive");
+  if (cfg->level < 0) return fail(ctx, DSX_EINVAL, "level must be >= 0");
+  if (cfg->otsu == 0 && !(fabsf(cfg->threshold) < 1e30f)) return fail(ctx, DSX_EINVAL, "threshold is not finite");
+  if (cfg->wavelet != DSX_WAVELET_DB3 && cfg->wavelet != DSX_WAVELET_BANK)
+    return fail(ctx, DSX_EINVAL, "unknown wavelet id");
+  if (cfg->wavelet == DSX_WAVELET_BANK && !ctx->wl_set)
+    return fail(ctx, DSX_EINVAL, "DSX_WAVELET_BANK needs a filter bank (dsx_set_wavelet)");
+  if ((size_t)height * width > ((size_t)1 << 30)) return fail(ctx, DSX_ELIMIT, "plane larger than 2^30 pixels");
+  DSX_HIP(hipSetDevice(ctx->device));
+  DSX_HIP(hipStreamSynchronize(use_main(ctx)));
+  free_plan_buffers(ctx);
+  free_streaks(ctx);
+  dsx::st::StreaksPlan& p = ctx->sp;
+  p = dsx::st::StreaksPlan();
+  p.H = height; p.W = width; p.B = max_batch;
+  p.bands = cfg->sigma_fg == cfg->sigma_bg ? 1 : 2;
+  p.sigma[0] = p.bands == 1 ? cfg->sigma_fg : cfg->sigma_bg;
+  p.sigma[1] = cfg->sigma_fg;
+  p.crossover = cfg->crossover;
+  p.otsu = cfg->otsu ? 1 : 0;
+  p.threshold = cfg->threshold;
+  if (cfg->wavelet == DSX_WAVELET_DB3) {
+    static const double db3[6] = {0.03522629188570953, -0.08544127388202666, -0.13501102001025458,
+                                  0.45987750211849154, 0.8068915093110925,   0.33267055295008263};
+    p.F = 6;
+    for (int t = 0; t < 6; ++t) {
+      p.dec.lo[t] = (float)db3[t];
+      p.dec.hi[t] = (float)((t & 1 ? 1.0 : -1.0) * db3[5 - t]);  // dec_hi[t] = (-1)^(t+1) dec_lo[F-1-t]
+      p.rec.lo[t] = (float)db3[5 - t];
+      p.rec.hi[t] = (float)((t & 1 ? -1.0 : 1.0) * db3[t]);       // rec_hi = dec_hi reversed
+    }
+  } else {
+    p.F = ctx->wl_bank_len;
+    for (int t = 0; t < p.F; ++t) {
+      p.dec.lo[t] = ctx->wl_bank[0][t];
+      p.dec.hi[t] = ctx->wl_bank[1][t];
+      p.rec.lo[t] = ctx->wl_bank[2][t];
+      p.rec.hi[t] = ctx->wl_bank[3][t];
+    }
+  }
+  if (!dsx::st::st_build_plan(p, cfg->level)) return fail(ctx, DSX_ELIMIT, "decomposition level out of range");
+  for (int l = 0; l < p.L; ++l)
+    if ((size_t)max_batch * p.lv[l].h > (size_t)65535 * dsx::st::kMmT)
+      return fail(ctx, DSX_ELIMIT, "max_batch too large for this plane height");
+  std::vector<float> mats(std::max<size_t>(p.mat_floats, 1));
+  for (int l = 0; l < p.L; ++l)
+    for (int b = 0; b < p.bands; ++b)
+      dsx::st::st_notch_factors(p.lv[l].w, (double)p.lv[l].h * p.sigma[b] / p.Hp, p.lv[l].rank[b],
+                                mats.data() + p.lv[l].mat[b], mats.data() + p.lv[l].mat[b] + (size_t)p.lv[l].w * p.lv[l].rank[b]);
+  auto alloc = [&](void** ptr, size_t bytes) -> int {
+    hipError_t e = hipMalloc(ptr, std::max<size_t>(bytes, 4));
+    if (e != hipSuccess) {
+      *ptr = nullptr;
+      free_streaks(ctx);
+      return fail(ctx, DSX_ENOMEM, std::string("hipMalloc (streaks plan): ") + hipGetErrorString(e));
+    }
+    return DSX_OK;
+  };
+  if (int rc = alloc((void**)&ctx->st_ws, sizeof(float) * p.ws_floats)) return rc;
+  if (int rc = alloc((void**)&ctx->st_mat, sizeof(float) * mats.size())) return rc;
+  if (int rc = alloc((void**)&ctx->st_mm, sizeof(unsigned) * 2 * max_batch)) return rc;
+  if (int rc = alloc((void**)&ctx->st_hist, sizeof(unsigned) * dsx::st::kStBins * max_batch)) return rc;
+  if (int rc = alloc((void**)&ctx->st_t, sizeof(float) * max_batch)) return rc;
+  if (int rc = alloc((void**)&ctx->st_info, sizeof(dsx::st::OtsuOut) * max_batch)) return rc;
+  DSX_HIP(hipMemcpy(ctx->st_mat, mats.data(), sizeof(float) * mats.size(), hipMemcpyHostToDevice));
+  ctx->streaks = true;
+  ctx->last_n = 0;
+  return DSX_OK;
+}
+
+int dsx_get_streaks_threshold(dsx_ctx* ctx, int plane, float* threshold) {
+  if (!ctx || !threshold) return DSX_EINVAL;
+  if (!ctx->streaks) return fail(ctx, DSX_ENOPLAN, "dsx_plan_streaks has not been called");
+  if (plane < 0 || plane >= ctx->last_n) return fail(ctx, DSX_EINVAL, "plane index out of range");
+  DSX_HIP(hipSetDevice(ctx->device));
+  DSX_HIP(hipStreamSynchronize(use_main(ctx)));
+  DSX_HIP(hipMemcpy(threshold, ctx->st_t + plane, sizeof(float), hipMemcpyDeviceToHost));
   return DSX_OK;
 }
 

@@ -1,0 +1,512 @@
+// dsx_streaks.h -- kernels of the dual-band wavelet-FFT stripe filter (filter_streaks with sigma = (fg, bg)).
+//
+// The filter (README "filter_streaks", the upstream pystripe form with the reference's own helpers):
+//   t      per-plane Otsu threshold of the input (skimage threshold_otsu: one bin per integer for uint16,
+//          256 NumPy bins for float32), or a fixed value
+//   band   y = log(1 + z) of the edge-padded even plane, wavedec2 (mode symmetric), every cH row filtered with
+//          irfft(rfft(cH) * notch), waverec2, exp(r) - 1
+//   blend  b = band(min(x, t), sigma_bg), f = band(max(x, t), sigma_fg), w = sigmoid((x - t) / crossover),
+//          out = f w + b (1 - w); a single band (sigma_fg == sigma_bg) is band(x, sigma_fg)
+//
+// Layout: the P = bands * nb "virtual planes" of a cohort of nb planes are band-major (v = band * nb + plane), so the
+// cH rows of one band are contiguous and one row-filter launch covers them.  Every kernel maps one thread to one
+// output element and checks it against the element count; none uses scratch memory.
+//
+//   k_st_minmax   per-plane min / max (order-preserving uint keys, atomics)
+//   k_st_hist     per-plane histogram: uint16 one bin per integer of [min, max] (<= 65536 bins, counted in LDS
+//                 windows of kStWin bins, flushed to global memory); float32 the 256 bins of numpy.histogram
+//   k_st_otsu     class-variance arg-max in float64, first maximum (skimage); one block per plane
+//   k_st_prep     log(1 + min(x, t)) and log(1 + max(x, t)) (or log(1 + x)) of the edge-padded plane
+//   k_st_dwt<A>   one analysis pass along axis A (lo and hi outputs)
+//   k_st_rowmat   the row filter as two thin products per level and band: Z = cH U (n x K), cH' = cH + Z V (K x n),
+//                 the low-rank form of irfft(rfft(cH) * g) - cH (only K ~ 6.4 s packed gains differ from 1)
+//   k_st_idwt<A>  one synthesis pass along axis A
+//   k_st_final    exp(r) - 1 per band, sigmoid blend, crop, float32 / uint16 store
+#ifndef DSX_STREAKS_H
+#define DSX_STREAKS_H
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "dsx_wavelet.h"
+
+namespace dsx {
+namespace st {
+
+constexpr int kStWin = 8192;    // uint16 histogram bins per LDS window (32 KiB)
+constexpr int kStBins = 65536;  // global histogram capacity per plane
+constexpr int kOtsuThreads = 1024;
+
+struct Taps {
+  float lo[kMaxTaps], hi[kMaxTaps];  // kMaxTaps: dsx_wavelet.h, the bound dsx_set_wavelet enforces
+};
+
+__device__ __forceinline__ unsigned f32_key(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_f32(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+template <typename T>
+__device__ __forceinline__ float pix(const T* p, size_t i) { return (float)p[i]; }
+
+// mm[2 b] = min key, mm[2 b + 1] = max key (uint16: the value itself); grid (blocks, planes)
+template <typename T>
+__global__ __launch_bounds__(256) void k_st_minmax(const T* __restrict__ in, size_t plane_px, unsigned* mm) {
+  const T* p = in + (size_t)blockIdx.y * plane_px;
+  unsigned lo = 0xffffffffu, hi = 0u;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < plane_px; i += (size_t)gridDim.x * blockDim.x) {
+    const unsigned k = sizeof(T) == 2 ? (unsigned)p[i] : f32_key(pix(p, i));
+    lo = min(lo, k);
+    hi = max(hi, k);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = min(lo, (unsigned)__shfl_xor((int)lo, o));
+    hi = max(hi, (unsigned)__shfl_xor((int)hi, o));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMin(mm + 2 * blockIdx.y, lo);
+    atomicMax(mm + 2 * blockIdx.y + 1, hi);
+  }
+}
+
+// numpy.histogram(x, bins=256) edges of NumPy 1.26: float64 arange(257) * ((last - first) / 256) + first, last edge
+// exact, rounded to float32 (oracle.destripe_oracle.histogram256); no contraction into fma
+__device__ __forceinline__ void f32_range(const unsigned* mm, float& first, float& last) {
+  first = key_f32(mm[0]);
+  last = key_f32(mm[1]);
+  if (first == last) { first -= 0.5f; last += 0.5f; }
+}
+__device__ __forceinline__ float f32_edge(float first, float last, int k) {
+  if (k >= 256) return last;
+  const double step = __ddiv_rn(__dsub_rn((double)last, (double)first), 256.0);
+  return (float)__dadd_rn(__dmul_rn((double)k, step), (double)first);
+}
+
+// grid (blocks, planes); hist[b * kStBins + k]
+template <typename T>
+__global__ __launch_bounds__(256) void k_st_hist(const T* __restrict__ in, size_t plane_px, const unsigned* mm,
+                                                 unsigned* hist) {
+  __shared__ unsigned h[kStWin];
+  __shared__ float edges[257];
+  const T* p = in + (size_t)blockIdx.y * plane_px;
+  unsigned* gh = hist + (size_t)blockIdx.y * kStBins;
+  const size_t start = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+  if (sizeof(T) == 2) {
+    const unsigned vmin = mm[2 * blockIdx.y], vmax = mm[2 * blockIdx.y + 1];
+    const unsigned nbins = vmax - vmin + 1;
+    for (unsigned base = 0; base < nbins; base += kStWin) {
+      for (int k = threadIdx.x; k < kStWin; k += blockDim.x) h[k] = 0u;
+      __syncthreads();
+      for (size_t i = start; i < plane_px; i += step) {
+        const unsigned k = (unsigned)p[i] - vmin - base;
+        if (k < (unsigned)kStWin) atomicAdd(&h[k], 1u);
+      }
+      __syncthreads();
+      for (int k = threadIdx.x; k < kStWin && base + k < nbins; k += blockDim.x)
+        if (h[k]) atomicAdd(gh + base + k, h[k]);
+      __syncthreads();
+    }
+  } else {
+    float first, last;
+    f32_range(mm + 2 * blockIdx.y, first, last);
+    for (int k = threadIdx.x; k < 257; k += blockDim.x) edges[k] = f32_edge(first, last, k);
+    for (int k = threadIdx.x; k < 256; k += blockDim.x) h[k] = 0u;
+    __syncthreads();
+    const float denom = last - first;
+    for (size_t i = start; i < plane_px; i += step) {
+      const float a = pix(p, i);
+      int idx = (int)(__fmul_rn(__fdiv_rn(__fsub_rn(a, first), denom), 256.0f));
+      idx = min(max(idx, 0), 256);
+      if (idx == 256) idx = 255;
+      if (a < edges[idx]) idx -= 1;
+      if (idx < 0) idx = 0;
+      if (a >= edges[idx + 1] && idx != 255) idx += 1;
+      atomicAdd(&h[idx], 1u);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < 256; k += blockDim.x)
+      if (h[k]) atomicAdd(gh + k, h[k]);
+  }
+}
+
+// skimage threshold_otsu on the histogram: first arg-max of w1[i] w2[i+1] (m1[i] - m2[i+1])^2, i < nbins - 1, in
+// float64.  uint16: bin centres min + k (every sum an exact integer, so the curve is skimage's to the bit);
+// float32: centres (e[k] + e[k+1]) / 2 in float32.  A constant plane returns its value.  One block per plane.
+struct OtsuOut {
+  double t;
+  int bin;
+  int nbins;
+};
+
+template <bool U16>
+__device__ __forceinline__ double bin_centre(int k, unsigned vmin, float first, float last) {
+  if (U16) return (double)(vmin + (unsigned)k);
+  return (double)((f32_edge(first, last, k) + f32_edge(first, last, k + 1)) * 0.5f);
+}
+
+template <bool U16>
+__global__ __launch_bounds__(kOtsuThreads) void k_st_otsu(const unsigned* mm, const unsigned* hist, float* t_out,
+                                                         OtsuOut* info) {
+  __shared__ unsigned long long sw[kOtsuThreads];
+  __shared__ double ss[kOtsuThreads];
+  __shared__ double bv[kOtsuThreads];
+  __shared__ int bi[kOtsuThreads];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const unsigned* h = hist + (size_t)b * kStBins;
+  const unsigned vmin = mm[2 * b], vmax = mm[2 * b + 1];
+  float first = 0.f, last = 0.f;
+  int nbins;
+  if (U16) {
+    nbins = (int)(vmax - vmin + 1);
+  } else {
+    f32_range(mm + 2 * b, first, last);
+    nbins = 256;
+  }
+  const bool constant = vmin == vmax;
+  if (constant) {
+    if (tid == 0) {
+      const double v = U16 ? (double)vmin : (double)key_f32(vmin);
+      t_out[b] = (float)v;
+      info[b].t = v;
+      info[b].bin = 0;
+      info[b].nbins = 1;
+    }
+    return;
+  }
+  const int per = (nbins + kOtsuThreads - 1) / kOtsuThreads;
+  const int k0 = min(tid * per, nbins), k1 = min(k0 + per, nbins);
+  unsigned long long w = 0;
+  double s = 0.0;
+  for (int k = k0; k < k1; ++k) {
+    w += h[k];
+    s += (double)h[k] * bin_centre<U16>(k, vmin, first, last);
+  }
+  sw[tid] = w;
+  ss[tid] = s;
+  __syncthreads();
+  // inclusive scan (Hillis-Steele) of the per-thread sums
+  for (int o = 1; o < kOtsuThreads; o <<= 1) {
+    const unsigned long long aw = tid >= o ? sw[tid - o] : 0ull;
+    const double as = tid >= o ? ss[tid - o] : 0.0;
+    __syncthreads();
+    sw[tid] += aw;
+    ss[tid] += as;
+    __syncthreads();
+  }
+  const unsigned long long wtot = sw[kOtsuThreads - 1];
+  const double stot = ss[kOtsuThreads - 1];
+  unsigned long long w1 = tid ? sw[tid - 1] : 0ull;
+  double s1 = tid ? ss[tid - 1] : 0.0;
+  double best = -1.0;
+  int besti = 0x7fffffff;
+  for (int k = k0; k < k1 && k < nbins - 1; ++k) {
+    w1 += h[k];
+    s1 += (double)h[k] * bin_centre<U16>(k, vmin, first, last);
+    const unsigned long long w2 = wtot - w1;
+    const double m1 = s1 / (double)w1, m2 = (stot - s1) / (double)w2;
+    const double d = m1 - m2;
+    const double v = (double)(w1 * w2) * (d * d);
+    if (v > best) { best = v; besti = k; }
+  }
+  bv[tid] = best;
+  bi[tid] = besti;
+  __syncthreads();
+  for (int o = kOtsuThreads / 2; o > 0; o >>= 1) {
+    if (tid < o) {
+      const double v2 = bv[tid + o];
+      const int i2 = bi[tid + o];
+      if (v2 > bv[tid] || (v2 == bv[tid] && i2 < bi[tid])) { bv[tid] = v2; bi[tid] = i2; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const int k = bi[0] == 0x7fffffff ? 0 : bi[0];
+    const double t = bin_centre<U16>(k, vmin, first, last);
+    t_out[b] = (float)t;
+    info[b].t = t;
+    info[b].bin = k;
+    info[b].nbins = nbins;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_st_fill(float* t, int n, float v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) t[i] = v;
+}
+
+// y[v][i][j], v = band * B + b: log(1 + min(x, t)) (band 0), log(1 + max(x, t)) (band 1), or log(1 + x) for a
+// single band; x of the plane edge-padded to Hp x Wp (last row / column repeated)
+template <typename T>
+__global__ __launch_bounds__(256) void k_st_prep(const T* __restrict__ in, int nb, int B, int H, int W, int Hp, int Wp,
+                                                 int bands, const float* t, float* y, unsigned* sticky) {
+  const size_t per = (size_t)Hp * Wp, total = per * nb * bands;
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int j = (int)(idx % Wp);
+  const int i = (int)((idx / Wp) % Hp);
+  const int b = (int)((idx / per) % nb);
+  const int band = (int)(idx / (per * nb));
+  const float x = pix(in, (size_t)b * H * W + (size_t)min(i, H - 1) * W + min(j, W - 1));
+  // a float32 pixel that is NaN, infinite or <= -1 has no finite log(1 + x): the reference's threshold_otsu raises
+  // ValueError for such a plane; flag it in the context's host-mapped word (read by dsx_run_host / dsx_sync)
+  if (sizeof(T) == 4 && band == 0 && !(x > -1.0f && x < INFINITY) && sticky != nullptr) *(volatile unsigned*)sticky = 1u;
+  float z = x;
+  if (bands == 2) z = band == 0 ? fminf(x, t[b]) : fmaxf(x, t[b]);
+  y[((size_t)band * B + b) * per + (size_t)i * Wp + j] = logf(1.0f + z);
+}
+
+__device__ __forceinline__ int st_refl(int i, int n) {  // half-sample symmetric extension, any distance
+  const int p = 2 * n;
+  i %= p;
+  if (i < 0) i += p;
+  return i < n ? i : p - 1 - i;
+}
+
+// one analysis pass along axis A of [P][h][w] planes (row pitch ld_in); lo / hi [P][ho][wo] dense
+template <int A>
+__global__ __launch_bounds__(256) void k_st_dwt(const float* __restrict__ x, int P, int h, int w, int ld_in,
+                                                size_t ps_in, float* lo, float* hi, int F, Taps tp) {
+  const int n = A == 0 ? h : w;
+  const int m = (n + F - 1) / 2;
+  const int ho = A == 0 ? m : h, wo = A == 0 ? w : m;
+  const size_t per = (size_t)ho * wo, total = per * P;
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % wo), r = (int)((idx / wo) % ho), v = (int)(idx / per);
+  const float* src = x + (size_t)v * ps_in;
+  const int o = A == 0 ? r : c;
+  float sl = 0.f, sh = 0.f;
+  for (int k = 0; k < F; ++k) {
+    const int q = st_refl(2 * o + 1 - k, n);
+    const float xv = A == 0 ? src[(size_t)q * ld_in + c] : src[(size_t)r * ld_in + q];
+    sl = fmaf(tp.lo[k], xv, sl);
+    sh = fmaf(tp.hi[k], xv, sh);
+  }
+  lo[idx] = sl;
+  hi[idx] = sh;
+}
+
+// one synthesis pass along axis A: a [P][h][w] (pitch lda, plane stride psa) and d (pitch ldd, stride psd), both read
+// over the h x w of d (a may be one longer: waverec2 trims it); out [P][ho][wo] with pitch wo, n_out = 2 m - F + 2
+template <int A>
+__global__ __launch_bounds__(256) void k_st_idwt(const float* __restrict__ a, int lda, size_t psa,
+                                                 const float* __restrict__ d, int ldd, size_t psd, int P, int h, int w,
+                                                 float* out, int F, Taps tp) {
+  const int m = A == 0 ? h : w;
+  const int no = 2 * m - F + 2;
+  const int ho = A == 0 ? no : h, wo = A == 0 ? w : no;
+  const size_t per = (size_t)ho * wo, total = per * P;
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % wo), r = (int)((idx / wo) % ho), v = (int)(idx / per);
+  const float* sa = a + (size_t)v * psa;
+  const float* sd = d + (size_t)v * psd;
+  const int nn = A == 0 ? r : c;
+  const int p = nn >> 1, bit = nn & 1;
+  float s = 0.f;
+  for (int j = 0; j < F / 2; ++j) {
+    const int tix = F - 2 - 2 * j + bit;
+    const size_t ia = A == 0 ? (size_t)(p + j) * lda + c : (size_t)r * lda + (p + j);
+    const size_t id = A == 0 ? (size_t)(p + j) * ldd + c : (size_t)r * ldd + (p + j);
+    s = fmaf(sa[ia], tp.lo[tix], s);
+    s = fmaf(sd[id], tp.hi[tix], s);
+  }
+  out[idx] = s;
+}
+
+// C[R][N] = X[R][Kd] M[Kd][N] (+ E[R][N] when E is given), all row-major and dense; 64 x 64 tiles, 4 x 4 results per
+// thread.  E may alias nothing else (C != X, C != E).
+constexpr int kMmT = 64, kMmK = 16;
+__global__ __launch_bounds__(256) void k_st_rowmat(const float* __restrict__ X, const float* __restrict__ M,
+                                                   const float* __restrict__ E, float* __restrict__ C, int R, int Kd,
+                                                   int N) {
+  __shared__ float xs[kMmK][kMmT + 4];
+  __shared__ float ms[kMmK][kMmT + 4];
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int row0 = blockIdx.y * kMmT, col0 = blockIdx.x * kMmT;
+  float acc[4][4] = {};
+  for (int k0 = 0; k0 < Kd; k0 += kMmK) {
+    for (int e = threadIdx.x; e < kMmT * kMmK; e += 256) {
+      const int rr = e / kMmK, kk = e % kMmK;  // X tile: 64 rows x 16 k
+      const int gr = row0 + rr, gk = k0 + kk;
+      xs[kk][rr] = (gr < R && gk < Kd) ? X[(size_t)gr * Kd + gk] : 0.f;
+      const int mk = e / kMmT, mc = e % kMmT;  // M tile: 16 k x 64 cols
+      const int gk2 = k0 + mk, gc = col0 + mc;
+      ms[mk][mc] = (gk2 < Kd && gc < N) ? M[(size_t)gk2 * N + gc] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < kMmK; ++kk) {
+      float xa[4], mb[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        xa[q] = xs[kk][ty + 16 * q];
+        mb[q] = ms[kk][tx + 16 * q];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(xa[i], mb[j], acc[i][j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int gr = row0 + ty + 16 * i;
+    if (gr >= R) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int gc = col0 + tx + 16 * j;
+      if (gc < N) C[(size_t)gr * N + gc] = E ? E[(size_t)gr * N + gc] + acc[i][j] : acc[i][j];
+    }
+  }
+}
+
+// out[b][i][j], i < H, j < W: exp(r) - 1 per band (r: [P][Hp][Wp], band-major), blend, store
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void k_st_final(const TI* __restrict__ in, const float* __restrict__ r, int nb, int B,
+                                                  int H, int W, int Hp, int Wp, int bands, const float* t,
+                                                  float inv_crossover, TO* out) {
+  const size_t per = (size_t)H * W, total = per * nb;
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int j = (int)(idx % W), i = (int)((idx / W) % H), b = (int)(idx / per);
+  const size_t pp = (size_t)Hp * Wp, off = (size_t)i * Wp + j;
+  float res;
+  if (bands == 1) {
+    res = expm1f(r[(size_t)b * pp + off]);
+  } else {
+    const float bg = expm1f(r[(size_t)b * pp + off]);
+    const float fg = expm1f(r[((size_t)B + b) * pp + off]);
+    const float x = pix(in, idx);
+    const float wf = 1.0f / (1.0f + expf(-(x - t[b]) * inv_crossover));
+    res = fg * wf + bg * (1.0f - wf);
+  }
+  if (sizeof(TO) == 2) {
+    const float c = fminf(fmaxf(res, 0.0f), 65535.0f);
+    out[idx] = (TO)(unsigned)c;
+  } else {
+    out[idx] = (TO)res;
+  }
+}
+
+// ---- host side: geometry of a plan and the row-filter operators ---------------------------------------------------
+constexpr int kStMaxLevels = 32;
+
+struct StLevel {
+  int h, w;          // cH_l shape
+  int rh, rw;        // shape of the reconstruction of this level's approximation (from level l + 1; <= h + 1, w + 1)
+  size_t a, ch, cv, cd, cf;  // region offsets (floats) in the workspace: approx, cH, cV, cD, filtered cH
+  size_t mat[2];     // per band: offset (floats) of U [w][K] in the operator blob, V [K][w] follows
+  int rank[2];       // K per band
+};
+
+struct StreaksPlan {
+  int H = 0, W = 0, Hp = 0, Wp = 0, L = 0, F = 0, bands = 1, B = 0;
+  float sigma[2] = {0.f, 0.f};  // band 0 (background / single), band 1 (foreground)
+  float crossover = 10.f, threshold = 0.f;
+  int otsu = 1;
+  StLevel lv[kStMaxLevels];
+  size_t y = 0, t0 = 0, t1 = 0;  // region offsets: padded log plane / level-0 reconstruction, two pass temporaries
+  size_t ws_floats = 0, mat_floats = 0;
+  Taps dec, rec;
+};
+
+inline int st_max_level(int n, int F) {  // pywt.dwt_max_level
+  if (n < F - 1) return 0;
+  int l = 0;
+  for (long long q = n / (F - 1); q > 1; q >>= 1) ++l;
+  return l;
+}
+
+// Low-rank form of the notch: x -> fftpack.irfft(fftpack.rfft(x) * g), g[q] = 1 - exp(-q^2 / (2 s^2)) on the PACKED
+// index q (the reference's gaussian_filter), equals x + (x U) V with
+//   U[k][q] = packed rfft basis: 1 (q = 0), cos(2 pi m k / n) (q = 2m - 1), -sin(2 pi m k / n) (q = 2m),
+//             (-1)^k (q = n - 1, n even: the Nyquist term)
+//   V[q][j] = -(1 - g[q]) * packed irfft basis: 1 / n, 2 cos(2 pi m j / n) / n, -2 sin(2 pi m j / n) / n, (-1)^j / n
+// and only the first K packed indices carry 1 - g[q] = exp(-q^2 / (2 s^2)) >= 1e-9 relative (q < 6.44 s): beyond
+// them the term is below float32 resolution of the row.  Returns K; U is [n][K], V is [K][n].
+inline int st_notch_rank(int n, double s) { return std::min(n, (int)ceil(6.44 * s) + 1); }
+
+inline void st_notch_factors(int n, double s, int K, float* U, float* V) {
+  std::vector<double> cs((size_t)n), sn((size_t)n);
+  for (int q = 0; q < n; ++q) {
+    cs[q] = cos(2.0 * M_PI * q / n);
+    sn[q] = sin(2.0 * M_PI * q / n);
+  }
+  for (int q = 0; q < K; ++q) {
+    const double lowpass = exp(-((double)q * q) / (2.0 * s * s));  // 1 - g[q]
+    const bool nyquist = (n & 1) == 0 && q == n - 1;
+    const int m = (q + 1) / 2;
+    for (int k = 0; k < n; ++k) {
+      const size_t r = (size_t)(((long long)m * k) % n);
+      double u, v;
+      if (q == 0) { u = 1.0; v = 1.0 / n; }
+      else if (nyquist) { u = (k & 1) ? -1.0 : 1.0; v = u / n; }
+      else if (q & 1) { u = cs[r]; v = 2.0 * cs[r] / n; }
+      else { u = -sn[r]; v = -2.0 * sn[r] / n; }
+      U[(size_t)k * K + q] = (float)u;
+      V[(size_t)q * n + k] = (float)(-lowpass * v);
+    }
+  }
+}
+
+// Geometry of a plan for P = bands * B virtual planes; returns false when a level count is out of range
+inline bool st_build_plan(StreaksPlan& p, int level) {
+  p.Hp = p.H + (p.H & 1);
+  p.Wp = p.W + (p.W & 1);
+  p.L = level > 0 ? level : st_max_level(std::min(p.Hp, p.Wp), p.F);
+  if (p.L >= kStMaxLevels) return false;
+  const size_t P = (size_t)p.bands * p.B;
+  size_t off = 0;
+  auto region = [&](size_t floats) { const size_t o = off; off += floats * P; return o; };
+  p.y = region((size_t)p.Hp * p.Wp);
+  int h = p.Hp, w = p.Wp;
+  size_t tmp = 0, mat = 0;
+  for (int l = 0; l < p.L; ++l) {
+    StLevel& v = p.lv[l];
+    tmp = std::max(tmp, (size_t)((h + p.F - 1) / 2) * (w + 1));
+    v.h = (h + p.F - 1) / 2;
+    v.w = (w + p.F - 1) / 2;
+    v.a = region((size_t)(v.h + 1) * (v.w + 1));
+    v.ch = region((size_t)v.h * v.w);
+    v.cv = region((size_t)v.h * v.w);
+    v.cd = region((size_t)v.h * v.w);
+    v.cf = region((size_t)v.h * v.w);
+    for (int b = 0; b < p.bands; ++b) {
+      v.rank[b] = st_notch_rank(v.w, (double)v.h * p.sigma[b] / p.Hp);
+      v.mat[b] = mat;
+      mat += 2 * (size_t)v.w * v.rank[b];
+    }
+    h = v.h;
+    w = v.w;
+  }
+  for (int l = 0; l < p.L; ++l) {  // what the inverse pass of level l + 1 rebuilds in place of approx l
+    if (l + 1 < p.L) {
+      p.lv[l].rh = 2 * p.lv[l + 1].h - p.F + 2;
+      p.lv[l].rw = 2 * p.lv[l + 1].w - p.F + 2;
+    } else {
+      p.lv[l].rh = p.lv[l].h;
+      p.lv[l].rw = p.lv[l].w;
+    }
+    if (p.lv[l].rh > p.lv[l].h + 1 || p.lv[l].rw > p.lv[l].w + 1 || p.lv[l].rh < p.lv[l].h || p.lv[l].rw < p.lv[l].w)
+      return false;
+  }
+  p.t0 = region(tmp);
+  p.t1 = region(tmp);
+  p.ws_floats = off;
+  p.mat_floats = mat;
+  return true;
+}
+
+}  // namespace st
+}  // namespace dsx
+
+#endif  // DSX_STREAKS_H

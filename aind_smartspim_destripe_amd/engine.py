@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = [
     "dsx_malloc_host", "dsx_free_host", "dsx_memcpy_h2d_async", "dsx_memcpy_d2h_async",
     "dsx_stream_wait", "dsx_stream_sync", "dsx_event_record", "dsx_event_sync",
     "dsx_io_read_chunks", "dsx_io_write_chunks", "dsx_io_write_chunks_blosc", "dsx_blosc_decode", "dsx_blosc_encode",
-    "dsx_png_unfilter",
+    "dsx_png_unfilter", "dsx_plan_streaks", "dsx_get_streaks_threshold",
 ]  # fmt: skip
 
 
@@ -57,6 +57,18 @@ class _Cfg(ctypes.Structure):
         ("level", ctypes.c_int32),
         ("sigma", ctypes.c_float),
         ("max_threshold", ctypes.c_float),
+    ]
+
+
+class _StreaksCfg(ctypes.Structure):
+    _fields_ = [
+        ("wavelet", ctypes.c_int32),
+        ("level", ctypes.c_int32),
+        ("sigma_fg", ctypes.c_float),
+        ("sigma_bg", ctypes.c_float),
+        ("crossover", ctypes.c_float),
+        ("otsu", ctypes.c_int32),
+        ("threshold", ctypes.c_float),
     ]
 
 
@@ -152,6 +164,8 @@ def load_library(path=None):
     lib.dsx_io_write_chunks_blosc.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp),
                                               ctypes.POINTER(ctypes.c_size_t), i32, i32, i32, i32, i32]  # fmt: skip
     lib.dsx_png_unfilter.argtypes = [vp, i32, i32, i32]
+    lib.dsx_plan_streaks.argtypes = [vp, i32, i32, i32, ctypes.POINTER(_StreaksCfg)]
+    lib.dsx_get_streaks_threshold.argtypes = [vp, i32, f32p]
     lib.dsx_blosc_decode.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t]
     lib.dsx_blosc_encode.argtypes = [vp, ctypes.c_size_t, i32, i32, i32, vp, ctypes.c_size_t,
                                      ctypes.POINTER(ctypes.c_size_t)]  # fmt: skip
@@ -327,6 +341,37 @@ class DestripeEngine:
                         dark.shape[0], dark.shape[1])  # fmt: skip
         self.info = info
         return info
+
+    def plan_streaks(self, height, width, sigma_fg, sigma_bg, wavelet="db3", level=0, crossover=10.0,
+                     threshold=None, max_batch=32):  # fmt: skip
+        """Plan the dual-band filter (``dsx_plan_streaks``); ``threshold=None``: Otsu per plane.  Replaces any plan of
+        this engine; :meth:`run` / :meth:`run_device` then return ``[n, height, width]``."""
+        key = _wavelet_key({"wavelet": wavelet})
+        wid = DSX_WAVELET_DB3 if key == "db3" else DSX_WAVELET_BANK
+        if wid == DSX_WAVELET_BANK:
+            bank = [np.ascontiguousarray(f, dtype=np.float64) for f in wavelets.filter_bank(key)]
+            dp = ctypes.POINTER(ctypes.c_double)
+            rc = self._lib.dsx_set_wavelet(self._ctx, *[f.ctypes.data_as(dp) for f in bank], len(bank[0]))
+            if rc == -1:
+                raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
+            self._check(rc)
+        cfg = _StreaksCfg(wid, int(level or 0), float(sigma_fg), float(sigma_bg), float(crossover),
+                          1 if threshold is None else 0, 0.0 if threshold is None else float(threshold))  # fmt: skip
+        rc = self._lib.dsx_plan_streaks(self._ctx, int(height), int(width), int(max_batch), ctypes.byref(cfg))
+        if rc == -1:
+            raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
+        self._check(rc)
+        info = _PlanInfo()
+        info.height, info.width, info.out_height, info.out_width = int(height), int(width), int(height), int(width)
+        info.max_batch = int(max_batch)
+        self.info = info
+        return info
+
+    def streaks_threshold(self, plane):
+        """Threshold ``t`` of a plane of the last cohort of a streaks run (``dsx_get_streaks_threshold``)."""
+        t = ctypes.c_float()
+        self._check(self._lib.dsx_get_streaks_threshold(self._ctx, int(plane), ctypes.byref(t)))
+        return float(t.value)
 
     def graph_stats(self):
         """``(graph launches, captures)`` of this context (``dsx_graph_stats``)."""

@@ -6,8 +6,9 @@ Same names, argument meaning and error behaviour as the reference
 * :func:`filter_stripes` (reference ``:417-491``) and :func:`log_space_fft_filtering`
   (``:139-224``) ALWAYS run through the HIP engine (``libdsx_hip.so``); there is no CPU
   fallback -- without the library or a GPU they raise :class:`~.engine.DsxError`.
-* :func:`filter_streaks` is the alias BASELINE.json's north star names (the reference has no such
-  function; it forwards to :func:`log_space_fft_filtering`).
+* :func:`filter_streaks` is the name BASELINE.json's north star keeps (upstream pystripe's): a scalar ``sigma``
+  forwards to :func:`log_space_fft_filtering`; ``sigma = (fg, bg)`` runs the dual-band wavelet-FFT filter built from
+  the reference's ``foreground_fraction`` / ``gaussian_filter`` helpers (:func:`destripe_streaks_planes` batched).
 * :func:`destripe_planes` is the batched form the Zarr chunk map uses instead of the per-plane
   z-loop of ``execute_worker`` (``zarr_destriper.py:319-327``).
 * :func:`get_foreground_background_mean` (``:54-88``) and :func:`flatfield_correction` (``:338-414``) called
@@ -304,9 +305,104 @@ def log_space_fft_filtering(
     return out.astype(np.float64)
 
 
-def filter_streaks(image, **params):
-    """Alias named by BASELINE.json (upstream pystripe name): ``log_space_fft_filtering(image, **params)``."""
-    return log_space_fft_filtering(input_image=image, **params)
+def _streaks_params(sigma, level, wavelet, crossover, threshold):
+    """Checks of the dual-band form (every one before any device call); returns (sigma_fg, sigma_bg, level)."""
+    if isinstance(sigma, (str, bytes)) or np.ndim(sigma) != 1 or len(sigma) != 2:
+        raise ValueError("sigma must be a number or a pair (sigma_fg, sigma_bg)")
+    sigma_fg, sigma_bg = (float(v) for v in sigma)
+    if not (sigma_fg > 0 and sigma_bg > 0):
+        raise ValueError("sigma must be positive")
+    if not (float(crossover) > 0):
+        raise ValueError("crossover must be positive")
+    if threshold is None or not np.isfinite(float(threshold)):
+        raise ValueError("threshold must be -1 (Otsu) or a finite value")
+    if level is not None and level < 0:
+        raise ValueError("Level value of %d is too low . Minimum level is 0." % level)
+    _wavelets.filter_bank(_engine._wavelet_key({"wavelet": wavelet}))  # ValueError for names the engine refuses
+    return sigma_fg, sigma_bg, 0 if level is None else int(level)
+
+
+def _streaks_engine(shape, sigma_fg, sigma_bg, level, wavelet, crossover, threshold, max_batch, device):
+    fixed = None if float(threshold) == -1 else float(threshold)
+    key = (device, "streaks", tuple(shape), sigma_fg, sigma_bg, level, _engine._wavelet_key({"wavelet": wavelet}),
+           float(crossover), fixed, int(max_batch))  # fmt: skip
+    eng = _ENGINES.get(key)
+    if eng is not None:
+        _ENGINES.move_to_end(key)
+        return eng[0]
+    while len(_ENGINES) >= _MAX_CACHED_PLANS:
+        _, old = _ENGINES.popitem(last=False)
+        old[0].close()
+    e = _engine.DestripeEngine(device)
+    e.plan_streaks(shape[0], shape[1], sigma_fg, sigma_bg, wavelet=wavelet, level=level, crossover=crossover,
+                   threshold=fixed, max_batch=max_batch)  # fmt: skip
+    _ENGINES[key] = (e, None, None)
+    return e
+
+
+def _warn_streaks_level(shape, level, wavelet):
+    padded = [s + (s & 1) for s in shape]
+    mx = _max_level((min(padded), min(padded)), _wavelets.filter_length(_engine._wavelet_key({"wavelet": wavelet})))
+    if level > mx:
+        warnings.warn(
+            f"Level value of {level} is too high: all coefficients will experience boundary effects.", UserWarning
+        )
+
+
+def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, threshold=-1, **params):
+    """The stripe filter under its upstream (pystripe) name, in two forms.
+
+    * Scalar ``sigma``: ``log_space_fft_filtering(image, sigma=sigma, level=level, wavelet=wavelet, **params)``,
+      unchanged (``crossover`` / ``threshold`` are not arguments of that filter).
+    * ``sigma = (sigma_fg, sigma_bg)``: the dual-band wavelet-FFT filter on the GPU (``dsx_plan_streaks``).  ``t`` is
+      ``threshold``, or skimage's ``threshold_otsu`` of the plane for ``threshold == -1``; the edge-padded plane is
+      split into ``min(x, t)`` and ``max(x, t)``, each band goes through log(1 + z), ``wavedec2`` (``level`` 0 / None
+      = the maximum depth), a packed-index notch on every cH row (``s = cH.shape[0] * sigma / H'``), ``waverec2`` and
+      exp(r) - 1, and the bands are blended with ``foreground_fraction(x, t, crossover)``.  Equal sigmas run one band
+      on the unclipped plane.  Returns float64 ``[H, W]`` (computed in float32 on the device).
+    """
+    if not isinstance(sigma, (str, bytes)) and np.ndim(sigma) == 0:
+        if "crossover" in params or crossover != 10 or threshold != -1:
+            raise TypeError("crossover / threshold belong to the dual-band form: pass sigma=(sigma_fg, sigma_bg)")
+        return log_space_fft_filtering(input_image=image, sigma=sigma, level=level, wavelet=wavelet, **params)
+    if params:
+        raise TypeError("filter_streaks got unexpected arguments: {}".format(sorted(params)))
+    sigma_fg, sigma_bg, level = _streaks_params(sigma, level, wavelet, crossover, threshold)
+    image = np.asarray(image)
+    if image.ndim != 2 or image.size == 0:
+        raise ValueError("filter_streaks takes one non-empty 2-D plane; use destripe_streaks_planes for a stack")
+    out = destripe_streaks_planes(image[None], (sigma_fg, sigma_bg), level=level, wavelet=wavelet, crossover=crossover,
+                                  threshold=threshold, out_dtype=np.float32, max_batch=1)  # fmt: skip
+    return out[0].astype(np.float64)
+
+
+def destripe_streaks_planes(planes, sigma, level=0, wavelet="db3", crossover=10, threshold=-1, out_dtype=np.uint16,
+                            max_batch=32, device=0, return_threshold=False):  # fmt: skip
+    """Batched dual-band :func:`filter_streaks` over ``planes[n, H, W]`` (uint16 or float32), every plane on its own
+    (with ``threshold=-1`` each takes its own Otsu ``t``).  ``out_dtype`` uint16: clip to [0, 65535] and truncate, as
+    the Zarr path stores; float32: the filter's value.  ``return_threshold``: also the per-plane ``t`` (float64)."""
+    sigma_fg, sigma_bg, level = _streaks_params(sigma, level, wavelet, crossover, threshold)
+    planes = np.asarray(planes)
+    if planes.ndim != 3:
+        raise ValueError("planes must be [n, H, W]")
+    if planes.shape[1] == 0 or planes.shape[2] == 0:
+        raise ValueError("planes must not be empty")
+    if planes.dtype != np.uint16 and planes.dtype != np.float32:
+        planes = np.stack([_as_plane_dtype(p) for p in planes]) if len(planes) else planes.astype(np.float32)
+        if planes.dtype not in (np.uint16, np.float32):
+            planes = planes.astype(np.float32)
+    _warn_streaks_level(planes.shape[1:], level, wavelet)
+    n = planes.shape[0]
+    max_batch = max(1, min(int(max_batch), max(n, 1)))
+    eng = _streaks_engine(planes.shape[1:], sigma_fg, sigma_bg, level, wavelet, crossover, threshold, max_batch, device)
+    out = np.empty(planes.shape, dtype=out_dtype)
+    ts = np.zeros(n, dtype=np.float64)
+    for start in range(0, n, max_batch):
+        stop = min(n, start + max_batch)
+        out[start:stop] = eng.run(np.ascontiguousarray(planes[start:stop]), out_dtype=out_dtype)
+        if return_threshold:
+            ts[start:stop] = [eng.streaks_threshold(k) for k in range(stop - start)]
+    return (out, ts) if return_threshold else out
 
 
 def _resolve_shading(shadow_correction, input_tile_path):

@@ -252,6 +252,27 @@ int dsx_comm_broadcast(dsx_ctx* ctx, void* d_buf, size_t bytes, int root);
 /* Host doubles (n <= 64) reduced over the ranks: op 0 = sum, 1 = max, 2 = min. */
 int dsx_comm_allreduce_f64(dsx_ctx* ctx, double* values, int n, int op);
 
+/* ---- dual-band wavelet-FFT stripe filter (filter_streaks with sigma = (fg, bg)) -------------- */
+/* The upstream pystripe filter built from the reference's helpers (foreground_fraction, gaussian_filter,
+ * filtering.py:25-51, 91-136): per plane a threshold t (skimage threshold_otsu of the input, or fixed), the
+ * edge-padded even plane split into min(x, t) and max(x, t), each band log(1 + z) -> wavedec2 (mode symmetric) ->
+ * every cH row irfft(rfft(cH) * notch(s)), s = h_l * sigma / H' -> waverec2 -> exp(r) - 1, then
+ * out = f * w + b * (1 - w), w = sigmoid((x - t) / crossover), cropped to [H, W].  sigma_fg == sigma_bg runs ONE
+ * band on the unclipped plane.  A streaks plan replaces any plan of the context (dsx_plan replaces it in turn);
+ * dsx_run_host / dsx_run_device then run it: [n, H, W] in, [n, H, W] out (uint16: clip + truncate).          */
+typedef struct dsx_streaks_cfg {
+  int32_t wavelet;    /* DSX_WAVELET_DB3, or DSX_WAVELET_BANK (the bank of the last dsx_set_wavelet)        */
+  int32_t level;      /* 0 == maximum level (pywt.dwt_max_level(min(H', W'), filter length)), else the depth */
+  float sigma_fg;     /* > 0                                                                               */
+  float sigma_bg;     /* > 0                                                                               */
+  float crossover;    /* > 0                                                                               */
+  int32_t otsu;       /* 1: t = threshold_otsu of each plane; 0: t = threshold                             */
+  float threshold;
+} dsx_streaks_cfg;
+int dsx_plan_streaks(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_streaks_cfg* cfg);
+/* t of a plane of the last cohort of the last run (a bin centre for float32 planes, an integer for uint16). */
+int dsx_get_streaks_threshold(dsx_ctx* ctx, int plane, float* threshold);
+
 /* ---- parity / debug hooks (state of the LAST cohort of the last run) ----------------------- */
 /* Per plane of the last cohort: fore/back means and chosen config (filtering.py:459-462). */
 int dsx_get_stats(dsx_ctx* ctx, int plane, double* fore_mean, double* back_mean,
