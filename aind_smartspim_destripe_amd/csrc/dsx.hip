@@ -23,6 +23,7 @@
 #include "dsx_plan.h"
 #include "dsx_io.h"
 #include "dsx_streaks.h"
+#include "dsx_zenc_kernels.h"
 
 namespace {
 
@@ -114,6 +115,10 @@ struct dsx_ctx {
   // the call; the next synchronising entry point (dsx_sync, dsx_event_sync, dsx_stream_sync, dsx_get_stats) reports
   // DSX_EVALUE instead and clears the word.
   unsigned* h_sticky = nullptr;
+  // dsx_blosc_encode_device: encoded zstd blocks (slots) and their sizes, grown on demand
+  uint8_t* zenc_slots = nullptr;
+  uint32_t* zenc_sizes = nullptr;
+  size_t zenc_blocks = 0;
   unsigned* d_sticky = nullptr;
   // dsx_set_stack_mode: the planes of a call share ONE Otsu threshold per level (the reference's 3-D input mode)
   bool stack_mode = false;
@@ -1318,6 +1323,8 @@ void dsx_destroy(dsx_ctx* ctx) {
   for (int i = 0; i < 2; ++i)
     if (ctx->copy_stream[i]) { (void)hipStreamSynchronize(ctx->copy_stream[i]); (void)hipStreamDestroy(ctx->copy_stream[i]); }
   if (ctx->h_sticky) (void)hipHostFree(ctx->h_sticky);
+  if (ctx->zenc_slots) (void)hipFree(ctx->zenc_slots);
+  if (ctx->zenc_sizes) (void)hipFree(ctx->zenc_sizes);
   if (ctx->ev_xs) (void)hipEventDestroy(ctx->ev_xs);
   for (int i = 0; i < dsx_ctx::kEventSlots; ++i)
     if (ctx->ev_slot[i]) (void)hipEventDestroy(ctx->ev_slot[i]);
@@ -1994,6 +2001,60 @@ int dsx_blosc_encode(const void* src, size_t bytes, int typesize, int clevel, in
   if (out.size() > frame_capacity) return fail(nullptr, DSX_EINVAL, "frame buffer too small (bytes + 16 always fits)");
   memcpy(frame, out.data(), out.size());
   *frame_bytes = out.size();
+  return DSX_OK;
+}
+
+namespace {
+const char* zenc_params(int n_chunks, size_t chunk_bytes, int typesize, int clevel) {
+  if (typesize != 2) return "blosc_encode: the zstd encoder supports typesize 2 only";
+  if (n_chunks < 0 || chunk_bytes % 2 || clevel < 0 || clevel > 9) return "blosc_encode: bad parameters";
+  if (chunk_bytes > 0x7FFFFFEFu) return "blosc_encode: chunk larger than a frame can hold";
+  return nullptr;
+}
+}  // namespace
+
+int dsx_blosc_encode_ref(const void* src, int n_chunks, size_t chunk_bytes, int typesize, int clevel, void* frames,
+                         int64_t* offsets) {
+  if ((!src && n_chunks > 0 && chunk_bytes) || !frames || !offsets) return DSX_EINVAL;
+  if (const char* e = zenc_params(n_chunks, chunk_bytes, typesize, clevel)) return fail(nullptr, DSX_EINVAL, e);
+  dsx::zenc::blosc_encode_host((const uint16_t*)src, (uint64_t)n_chunks, chunk_bytes, clevel, (uint8_t*)frames, offsets);
+  return DSX_OK;
+}
+
+int dsx_blosc_encode_device(dsx_ctx* ctx, const void* d_src, int n_chunks, size_t chunk_bytes, int typesize,
+                            int clevel, void* d_frames, int64_t* d_offsets) {
+  if (!ctx || (!d_src && n_chunks > 0 && chunk_bytes) || !d_frames || !d_offsets) return DSX_EINVAL;
+  if (const char* e = zenc_params(n_chunks, chunk_bytes, typesize, clevel)) return fail(ctx, DSX_EINVAL, e);
+  namespace z = dsx::zenc;
+  DSX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = use_main(ctx);
+  const bool store = chunk_bytes < (size_t)z::kBloscMinBuffer || clevel == 0;
+  const z::Geometry g(chunk_bytes ? chunk_bytes : 1);
+  const size_t nblocks = store ? 0 : (size_t)n_chunks * g.nblocks * z::kZPerBlosc;
+  if ((size_t)n_chunks * g.nblocks > 0x7FFFFFFFu / z::kZPerBlosc)
+    return fail(ctx, DSX_ELIMIT, "blosc_encode: too many blocks per call");
+  if (nblocks > ctx->zenc_blocks) {
+    DSX_HIP(hipStreamSynchronize(s));
+    if (ctx->zenc_slots) DSX_HIP(hipFree(ctx->zenc_slots));
+    if (ctx->zenc_sizes) DSX_HIP(hipFree(ctx->zenc_sizes));
+    ctx->zenc_slots = nullptr;
+    ctx->zenc_sizes = nullptr;
+    ctx->zenc_blocks = 0;
+    if (hipMalloc(&ctx->zenc_slots, nblocks * (size_t)z::kSlotStride) != hipSuccess ||
+        hipMalloc(&ctx->zenc_sizes, nblocks * sizeof(uint32_t)) != hipSuccess)
+      return fail(ctx, DSX_ENOMEM, "blosc_encode: cannot allocate the work buffer");
+    ctx->zenc_blocks = nblocks;
+  }
+  if (!store && nblocks)
+    hipLaunchKernelGGL(z::k_zenc_block, dim3((unsigned)nblocks), dim3(z::kEncThreads), 0, s,
+                       z::EncArgs{(const uint16_t*)d_src, ctx->zenc_slots, ctx->zenc_sizes, (uint64_t)chunk_bytes,
+                                  g.nblocks});
+  z::PackArgs pa{(const uint16_t*)d_src, ctx->zenc_slots, ctx->zenc_sizes, (uint8_t*)d_frames, d_offsets,
+                 (uint64_t)chunk_bytes, n_chunks, store ? 1 : g.nblocks, store};
+  hipLaunchKernelGGL(z::k_zenc_scan, dim3(1), dim3(256), 0, s, pa);
+  if (n_chunks > 0)
+    hipLaunchKernelGGL(z::k_zenc_copy, dim3((unsigned)(n_chunks * pa.nblocks)), dim3(256), 0, s, pa);
+  DSX_HIP(hipGetLastError());
   return DSX_OK;
 }
 

@@ -1,0 +1,491 @@
+// dsx_zstd_enc.h -- entropy-only zstd inside Blosc frames: the encoder core shared by the host reference and the
+// device kernels (dsx_zenc_kernels.h).  Plain C++; g++ builds it for the CPU tests (tests/host/zstd_enc_check.cpp).
+//
+// Format (RFC 8878): one zstd frame per Blosc block -- magic, single-segment frame header with the content size, no
+// checksum -- holding zstd blocks of <= 128 KiB.  A block whose bytes are all equal is an RLE block; otherwise its
+// literals are Huffman-coded (4 streams, Size_Format 11, 6-byte jump table, code lengths <= 11 bits, weights
+// FSE-compressed with table log 6 and two interleaved states, or in the direct 4-bit form when that is smaller) with a
+// sequences section of zero sequences; a block that does not get smaller is stored raw.  No match finder: about
+// 1.1-1.2x the bytes of zstd level 5 on byte-shuffled uint16 image bricks.
+//
+// Blosc container: what dsx_io.h blosc_encode writes -- version 2, 256 KiB blocks, byte shuffle, "don't split", a
+// stream as long as its block = stored; a frame not smaller than its data becomes a memcpyed frame.  Typesize 2 only.
+//
+// Determinism: every choice below (the histogram, the sort key, the code lengths, the weight normalisation) is a
+// function of the block's bytes, so the device kernels write exactly the bytes of the host build.
+#ifndef DSX_ZSTD_ENC_H
+#define DSX_ZSTD_ENC_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#if defined(__HIP__) || defined(__CUDACC__)
+#define DSX_ZHD __host__ __device__
+#else
+#define DSX_ZHD
+#endif
+
+namespace dsx {
+namespace zenc {
+
+constexpr int kZBlock = 128 * 1024;             // zstd Block_Maximum_Size
+constexpr int kBloscBlock = 256 * 1024;         // Blosc block of the host writer
+constexpr int kBloscHeader = 16;
+constexpr int kBloscMinBuffer = 128;            // shorter buffers are stored (c-blosc MIN_BUFFERSIZE)
+constexpr int kMaxBits = 11;                    // Huffman code length limit
+constexpr int kMinHuf = 64;                     // shorter blocks: raw or RLE (4 streams need a few literals each)
+constexpr int kSlotStride = kZBlock + 16;       // one encoded zstd block: 3-byte header + <= 128 KiB
+constexpr int kTreeCap = 160;                   // Huffman tree description: 1 + <= 128 bytes (+ slack for FSE)
+constexpr int kFseLog = 6;                      // table log of the weight FSE
+enum BlockType { kRaw = 0, kRle = 1, kCompressed = 2 };
+
+// Working state of one zstd block (LDS on the device, ~8 KB).
+struct HufWork {
+  uint32_t scount[4][256];  // histogram per literal stream
+  uint32_t count[256];      // histogram of the block
+  uint32_t sorted[256];     // (count << 8 | symbol) of the present symbols, ascending
+  uint32_t a[256];          // code-length construction
+  uint16_t code[256];
+  uint8_t len[256];
+  uint8_t wgt[256];
+  uint8_t tree[kTreeCap];   // Huffman tree description (header byte + weights)
+  uint8_t fse_sym[1 << kFseLog];
+  uint16_t fse_state[1 << kFseLog];
+  int16_t norm[16];
+  uint32_t wc[16];          // (the small tables of the single-thread parts live here too: no private arrays)
+  int32_t dnb[16], dfs[16], cumul[17];
+  int bl[kMaxBits + 2];
+  uint32_t start[kMaxBits + 2];
+  uint32_t stream_bytes[4];
+  int nsym, type, tree_bytes, block_bytes, max_bits, prefix_bytes;
+  uint8_t rle_byte;
+};
+
+DSX_ZHD inline int highbit(uint32_t v) {  // v > 0
+  int r = 0;
+  while (v >>= 1) ++r;
+  return r;
+}
+
+// little-endian bit writer of the single-thread parts (FSE weights, host streams)
+struct BitW {
+  uint8_t* out;
+  int cap, pos, nb;
+  uint64_t acc;
+  bool ovf;
+  DSX_ZHD BitW(uint8_t* o, int c) : out(o), cap(c), pos(0), nb(0), acc(0), ovf(false) {}
+  DSX_ZHD void add(uint32_t v, int n) {
+    acc |= (uint64_t)(v & ((n >= 32) ? 0xFFFFFFFFu : ((1u << n) - 1u))) << nb;
+    nb += n;
+    while (nb >= 8) {
+      if (pos < cap) out[pos] = (uint8_t)acc;
+      else ovf = true;
+      ++pos;
+      acc >>= 8;
+      nb -= 8;
+    }
+  }
+  DSX_ZHD int flush() {  // pad to a byte; bytes written, -1 on overflow
+    if (nb > 0) add(0, 8 - nb);
+    return ovf ? -1 : pos;
+  }
+  DSX_ZHD int close() {  // end mark + pad (backward-read streams)
+    add(1, 1);
+    return flush();
+  }
+};
+
+DSX_ZHD inline void put_le(uint8_t* p, uint64_t v, int n) {
+  for (int i = 0; i < n; ++i) p[i] = (uint8_t)(v >> (8 * i));
+}
+
+// literal stream k of a block of n literals covers [stream_begin(k), stream_begin(k + 1))
+DSX_ZHD inline int stream_begin(int n, int k) {
+  const int seg = (n + 3) / 4;
+  return k * seg < n ? k * seg : n;
+}
+
+// sort key of symbol s (only symbols with count > 0 take part): rank = keys below it
+DSX_ZHD inline uint32_t sort_key(const HufWork& w, int s) { return (w.count[s] << 8) | (uint32_t)s; }
+DSX_ZHD inline int sort_rank(const HufWork& w, int s) {
+  const uint32_t k = sort_key(w, s);
+  int r = 0;
+  for (int t = 0; t < 256; ++t) r += (w.count[t] != 0 && sort_key(w, t) < k) ? 1 : 0;
+  return r;
+}
+
+// Minimum-redundancy code lengths in place (Moffat & Katajainen 1995): a[0 .. n) ascending weights -> lengths
+// (a[0] the longest).  n >= 2.
+DSX_ZHD inline void mk_lengths(uint32_t* a, int n) {
+  a[0] += a[1];
+  int root = 0, leaf = 2;
+  for (int next = 1; next < n - 1; ++next) {
+    if (leaf >= n || a[root] < a[leaf]) { a[next] = a[root]; a[root++] = next; }
+    else a[next] = a[leaf++];
+    if (leaf >= n || (root < next && a[root] < a[leaf])) { a[next] += a[root]; a[root++] = next; }
+    else a[next] += a[leaf++];
+  }
+  a[n - 2] = 0;
+  for (int next = n - 3; next >= 0; --next) a[next] = a[a[next]] + 1;
+  int avbl = 1, used = 0, dpth = 0, root2 = n - 2, next = n - 1;
+  while (avbl > 0) {
+    while (root2 >= 0 && (int)a[root2] == dpth) { ++used; --root2; }
+    while (avbl > used) { a[next--] = dpth; --avbl; }
+    avbl = 2 * used;
+    ++dpth;
+    used = 0;
+  }
+}
+
+// FSE-compressed Huffman weights w[0 .. nw) -> out (table log 6, two interleaved states, as zstd's
+// FSE_compress_usingCTable).  Returns the bytes, or 0 when FSE does not apply / does not fit `cap`.
+DSX_ZHD inline int fse_weights(HufWork& h, const uint8_t* w, int nw, uint8_t* out, int cap) {
+  constexpr int L = kFseLog, T = 1 << kFseLog;
+  uint32_t* wc = h.wc;
+  for (int v = 0; v < 16; ++v) wc[v] = 0;
+  for (int i = 0; i < nw; ++i) wc[w[i]]++;
+  int distinct = 0, maxv = 0;
+  for (int v = 0; v < 16; ++v) if (wc[v]) { ++distinct; maxv = v; }
+  if (nw <= 2 || distinct < 2) return 0;
+  // normalised counts: every present weight >= 1, sum 64
+  int16_t* norm = h.norm;
+  int sum = 0;
+  for (int v = 0; v < 16; ++v) {
+    norm[v] = (int16_t)(wc[v] ? (int)(wc[v] * T / (uint32_t)nw) : 0);
+    if (wc[v] && norm[v] < 1) norm[v] = 1;
+    sum += norm[v];
+  }
+  while (sum > T) {
+    int best = -1;
+    for (int v = 0; v < 16; ++v) if (norm[v] > 1 && (best < 0 || norm[v] > norm[best])) best = v;
+    norm[best]--;
+    --sum;
+  }
+  if (sum < T) {
+    int best = 0;
+    for (int v = 1; v < 16; ++v) if (wc[v] > wc[best]) best = v;
+    norm[best] = (int16_t)(norm[best] + (T - sum));
+  }
+  BitW bw(out, cap);
+  // table description (FSE_writeNCount)
+  bw.add(L - 5, 4);
+  {
+    int remaining = T + 1, threshold = T, nbBits = L + 1;
+    int sym = 0;
+    bool prev0 = false;
+    while (sym <= maxv && remaining > 1) {
+      if (prev0) {
+        int start = sym;
+        while (sym <= maxv && !norm[sym]) ++sym;
+        while (sym >= start + 24) { start += 24; bw.add(0xFFFFu, 16); }
+        while (sym >= start + 3) { start += 3; bw.add(3, 2); }
+        bw.add((uint32_t)(sym - start), 2);
+      }
+      int count = norm[sym++];
+      const int max = (2 * threshold - 1) - remaining;
+      remaining -= count;
+      ++count;
+      if (count >= threshold) count += max;
+      bw.add((uint32_t)count, count < max ? nbBits - 1 : nbBits);
+      prev0 = (count == 1);
+      while (remaining < threshold) { --nbBits; threshold >>= 1; }
+    }
+  }
+  if (bw.nb > 0) bw.add(0, 8 - bw.nb);  // the header ends on a byte boundary
+  // symbol spread and encoding table (FSE_buildCTable)
+  uint8_t* tsym = h.fse_sym;
+  uint16_t* st = h.fse_state;
+  {
+    const int step = (T >> 1) + (T >> 3) + 3;
+    int pos = 0;
+    for (int v = 0; v <= maxv; ++v)
+      for (int i = 0; i < norm[v]; ++i) { tsym[pos] = (uint8_t)v; pos = (pos + step) & (T - 1); }
+    int32_t* cumul = h.cumul;
+    cumul[0] = 0;
+    for (int v = 0; v < 16; ++v) cumul[v + 1] = cumul[v] + norm[v];
+    for (int u = 0; u < T; ++u) st[cumul[tsym[u]]++] = (uint16_t)(T + u);
+  }
+  int32_t* dnb = h.dnb;
+  int32_t* dfs = h.dfs;
+  // (the first state of symbol v is cumul[v] - norm[v]: the table build above advanced cumul past v's states.  A
+  //  running sum here instead was miscompiled for gfx950 -- dfs of the second symbol came out wrong.)
+  for (int v = 0; v < 16; ++v) {
+    if (!norm[v]) { dnb[v] = 0; dfs[v] = 0; continue; }
+    if (norm[v] == 1) {
+      dnb[v] = (L << 16) - T;
+    } else {
+      const int maxBitsOut = L - highbit((uint32_t)(norm[v] - 1));
+      const int minStatePlus = norm[v] << maxBitsOut;
+      dnb[v] = (maxBitsOut << 16) - minStatePlus;
+    }
+    dfs[v] = (h.cumul[v] - norm[v]) - norm[v];
+  }
+  auto init_state = [&](int v) -> uint32_t {
+    const uint32_t nbo = (uint32_t)((dnb[v] + (1 << 15)) >> 16);
+    const uint32_t val = (nbo << 16) - (uint32_t)dnb[v];
+    return st[(val >> nbo) + dfs[v]];
+  };
+  auto encode = [&](uint32_t& state, int v) {
+    const uint32_t nbo = (uint32_t)((int32_t)state + dnb[v]) >> 16;
+    bw.add(state, (int)nbo);
+    state = st[(state >> nbo) + dfs[v]];
+  };
+  // symbol i goes through state 1 when i is even, state 2 when odd; encoded last to first
+  uint32_t s1, s2;
+  int i = nw;
+  if (nw & 1) {
+    s1 = init_state(w[--i]);
+    s2 = init_state(w[--i]);
+    encode(s1, w[--i]);
+  } else {
+    s2 = init_state(w[--i]);
+    s1 = init_state(w[--i]);
+  }
+  while (i > 0) {
+    encode(s2, w[--i]);
+    encode(s1, w[--i]);
+  }
+  bw.add(s2, L);
+  bw.add(s1, L);
+  const int n = bw.close();
+  return n > 0 ? n : 0;
+}
+
+// The code of one block from its histograms (count, scount, sorted, nsym filled): lengths, canonical codes, tree
+// description, stream sizes, block type and size.  Single-threaded.
+DSX_ZHD inline void plan_block(HufWork& h, int n) {
+  h.block_bytes = 3 + n;
+  h.type = kRaw;
+  h.prefix_bytes = 3;
+  if (h.nsym == 1) {
+    h.type = kRle;
+    h.rle_byte = (uint8_t)(h.sorted[0] & 255u);
+    h.block_bytes = 4;
+    return;
+  }
+  if (n < kMinHuf) return;
+  const int ns = h.nsym;
+  for (int i = 0; i < ns; ++i) h.a[i] = h.sorted[i] >> 8;
+  mk_lengths(h.a, ns);
+  int* bl = h.bl;
+  for (int l = 0; l <= kMaxBits; ++l) bl[l] = 0;
+  for (int i = 0; i < ns; ++i) bl[h.a[i] > (uint32_t)kMaxBits ? kMaxBits : h.a[i]]++;
+  int kraft = 0;
+  for (int l = 1; l <= kMaxBits; ++l) kraft += bl[l] << (kMaxBits - l);
+  while (kraft != (1 << kMaxBits)) {  // over-subscribed after the clamp: lengthen codes one unit at a time
+    bl[kMaxBits]--;
+    for (int l = kMaxBits - 1; l > 0; --l)
+      if (bl[l]) { bl[l]--; bl[l + 1] += 2; break; }
+    --kraft;
+  }
+  for (int s = 0; s < 256; ++s) h.len[s] = 0;
+  {
+    int i = 0;
+    for (int l = kMaxBits; l >= 1; --l)
+      for (int k = 0; k < bl[l]; ++k) h.len[h.sorted[i++] & 255u] = (uint8_t)l;
+  }
+  int mb = kMaxBits;
+  while (!bl[mb]) --mb;
+  h.max_bits = mb;
+  {
+    uint32_t* start = h.start;
+    start[mb] = 0;
+    for (int l = mb - 1; l >= 1; --l) start[l] = (start[l + 1] + (uint32_t)bl[l + 1]) >> 1;
+    for (int s = 0; s < 256; ++s) h.code[s] = h.len[s] ? (uint16_t)start[h.len[s]]++ : 0;
+  }
+  int max_sym = 255;
+  while (!h.len[max_sym]) --max_sym;
+  for (int s = 0; s < 256; ++s) h.wgt[s] = h.len[s] ? (uint8_t)(mb + 1 - h.len[s]) : 0;
+  const int nw = max_sym;  // weights described; the last one is implied
+  const int direct = nw <= 128 ? 1 + (nw + 1) / 2 : 0;
+  const int fse = fse_weights(h, h.wgt, nw, h.tree + 1, 127);
+  if (fse > 0 && (direct == 0 || 1 + fse < direct)) {
+    h.tree[0] = (uint8_t)fse;
+    h.tree_bytes = 1 + fse;
+  } else if (direct) {
+    h.tree[0] = (uint8_t)(127 + nw);
+    for (int i = 0; i < nw; i += 2) h.tree[1 + i / 2] = (uint8_t)((h.wgt[i] << 4) | (i + 1 < nw ? h.wgt[i + 1] : 0));
+    h.tree_bytes = direct;
+  } else {
+    return;
+  }
+  uint32_t lit_c = (uint32_t)h.tree_bytes + 6;
+  for (int k = 0; k < 4; ++k) {
+    uint64_t bits = 0;
+    for (int s = 0; s < 256; ++s) bits += (uint64_t)h.scount[k][s] * h.len[s];
+    h.stream_bytes[k] = (uint32_t)(bits / 8 + 1);  // + the end mark
+    if (k < 3 && h.stream_bytes[k] > 65535u) return;
+    lit_c += h.stream_bytes[k];
+  }
+  const uint32_t content = 5 + lit_c + 1;  // literals header + literals + sequences section (0 sequences)
+  if (content >= (uint32_t)n) return;
+  h.type = kCompressed;
+  h.block_bytes = 3 + (int)content;
+  h.prefix_bytes = 3 + 5 + h.tree_bytes + 6;
+}
+
+// Block header, literals header, tree description and jump table of a compressed block (prefix_bytes), and the
+// sequences byte at its end; the four streams go in between.  For RLE / raw blocks: the 3-byte header (+ the byte).
+DSX_ZHD inline void write_block_frame(const HufWork& h, int n, bool last, uint8_t* out) {
+  if (h.type == kRle) {
+    put_le(out, (uint32_t)last | (1u << 1) | ((uint32_t)n << 3), 3);
+    out[3] = h.rle_byte;
+    return;
+  }
+  if (h.type == kRaw) {
+    put_le(out, (uint32_t)last | ((uint32_t)n << 3), 3);
+    return;
+  }
+  const uint32_t content = (uint32_t)h.block_bytes - 3;
+  put_le(out, (uint32_t)last | (2u << 1) | (content << 3), 3);
+  const uint64_t lit_c = content - 5 - 1;
+  put_le(out + 3, 2u | (3u << 2) | ((uint64_t)n << 4) | (lit_c << 22), 5);
+  for (int i = 0; i < h.tree_bytes; ++i) out[8 + i] = h.tree[i];
+  uint8_t* jt = out + 8 + h.tree_bytes;
+  for (int k = 0; k < 3; ++k) put_le(jt + 2 * k, h.stream_bytes[k], 2);
+  out[h.block_bytes - 1] = 0;
+}
+
+// zstd frame header of a frame with `size` bytes of content (single segment, no checksum, no dictionary)
+DSX_ZHD inline int frame_header(uint32_t size, uint8_t* out) {
+  put_le(out, 0xFD2FB528u, 4);
+  if (size < 256) { out[4] = 0x20; out[5] = (uint8_t)size; return 6; }
+  if (size < 65536 + 256) { out[4] = 0x60; put_le(out + 5, size - 256, 2); return 7; }
+  out[4] = 0xA0;
+  put_le(out + 5, size, 4);
+  return 9;
+}
+DSX_ZHD inline int frame_header_bytes(uint32_t size) { return size < 256 ? 6 : (size < 65536 + 256 ? 7 : 9); }
+
+// Blosc geometry of one chunk of n bytes (n even, >= kBloscMinBuffer)
+struct Geometry {
+  uint32_t blocksize;  // 256 KiB or the whole chunk
+  int nblocks;         // Blosc blocks
+  DSX_ZHD Geometry(uint64_t n) {
+    blocksize = (uint32_t)(n < (uint64_t)kBloscBlock ? n : (uint64_t)kBloscBlock);
+    nblocks = blocksize ? (int)((n + blocksize - 1) / blocksize) : 0;
+  }
+  DSX_ZHD uint32_t bsize(uint64_t n, int b) const {
+    const uint64_t left = n - (uint64_t)b * blocksize;
+    return (uint32_t)(left < blocksize ? left : blocksize);
+  }
+};
+constexpr int kZPerBlosc = kBloscBlock / kZBlock;  // zstd blocks per Blosc block (at most)
+
+// byte p of a byte-shuffled typesize-2 Blosc block of `ne` elements starting at `e`
+DSX_ZHD inline uint8_t shuffled_byte(const uint16_t* e, uint32_t ne, uint32_t p) {
+  return p < ne ? (uint8_t)(e[p] & 255u) : (uint8_t)(e[p - ne] >> 8);
+}
+
+// Stream length of Blosc block b (zstd frame, or bsize = stored) from the encoded zstd block sizes zs[kZPerBlosc]
+DSX_ZHD inline uint32_t blosc_stream_bytes(const uint32_t* zs, uint32_t bsize) {
+  uint32_t f = (uint32_t)frame_header_bytes(bsize);
+  for (int j = 0; j < kZPerBlosc; ++j) f += zs[j];
+  return f < bsize ? f : bsize;
+}
+
+// Frame bytes of one chunk (n bytes) from the zstd block sizes of its Blosc blocks zs[nblocks][kZPerBlosc];
+// store = the chunk is stored as a whole (short chunk or clevel <= 0).
+DSX_ZHD inline uint64_t chunk_frame_bytes(const uint32_t* zs, uint64_t n, bool store) {
+  if (store) return kBloscHeader + n;
+  const Geometry g(n);
+  uint64_t f = kBloscHeader + 4ull * g.nblocks;
+  for (int b = 0; b < g.nblocks; ++b) f += 4 + blosc_stream_bytes(zs + b * kZPerBlosc, g.bsize(n, b));
+  return f < kBloscHeader + n ? f : kBloscHeader + n;  // not smaller than the data: memcpyed frame
+}
+
+DSX_ZHD inline void blosc_header(uint8_t* out, uint64_t n, uint32_t blocksize, uint64_t cbytes, bool memcpyed) {
+  out[0] = 2;
+  out[1] = 1;
+  out[2] = (uint8_t)((memcpyed ? 0x2 : 0) | 0x1 | 0x10 | (4 << 5));  // [memcpyed] | shuffle | don't split | zstd
+  out[3] = 2;
+  put_le(out + 4, n, 4);
+  put_le(out + 8, memcpyed ? (uint32_t)n : blocksize, 4);
+  put_le(out + 12, cbytes, 4);
+}
+
+// ---- host build: one zstd block, and whole chunks ------------------------------------------------------------
+// literals lit[0 .. n) -> slot (block header included); returns the block's bytes.  h: caller's work space.
+inline int encode_block_host(HufWork& h, const uint8_t* lit, int n, bool last, uint8_t* slot) {
+  for (int k = 0; k < 4; ++k) {
+    for (int s = 0; s < 256; ++s) h.scount[k][s] = 0;
+    for (int i = stream_begin(n, k); i < stream_begin(n, k + 1); ++i) h.scount[k][lit[i]]++;
+  }
+  h.nsym = 0;
+  for (int s = 0; s < 256; ++s) {
+    h.count[s] = h.scount[0][s] + h.scount[1][s] + h.scount[2][s] + h.scount[3][s];
+    h.nsym += h.count[s] != 0;
+  }
+  for (int s = 0; s < 256; ++s) if (h.count[s]) h.sorted[sort_rank(h, s)] = sort_key(h, s);
+  plan_block(h, n);
+  write_block_frame(h, n, last, slot);
+  if (h.type == kRaw) {
+    for (int i = 0; i < n; ++i) slot[3 + i] = lit[i];
+  } else if (h.type == kCompressed) {
+    int at = h.prefix_bytes;
+    for (int k = 0; k < 4; ++k) {
+      BitW bw(slot + at, (int)h.stream_bytes[k]);
+      for (int i = stream_begin(n, k + 1) - 1; i >= stream_begin(n, k); --i) bw.add(h.code[lit[i]], h.len[lit[i]]);
+      bw.close();
+      at += (int)h.stream_bytes[k];
+    }
+  }
+  return h.block_bytes;
+}
+
+// n_chunks chunks of chunk_bytes (uint16) -> packed frames + offsets[n_chunks + 1] (the device encoder's output).
+// frames: n_chunks * (chunk_bytes + 16) bytes at most.
+inline void blosc_encode_host(const uint16_t* src, uint64_t n_chunks, uint64_t chunk_bytes, int clevel,
+                              uint8_t* frames, int64_t* offsets) {
+  HufWork* h = new HufWork;
+  uint8_t* slot = new uint8_t[(size_t)kSlotStride * kZPerBlosc];
+  uint8_t* lit = new uint8_t[kBloscBlock];
+  const bool store = chunk_bytes < (uint64_t)kBloscMinBuffer || clevel <= 0;
+  const Geometry g(chunk_bytes ? chunk_bytes : 1);
+  uint64_t at = 0;
+  offsets[0] = 0;
+  for (uint64_t c = 0; c < n_chunks; ++c) {
+    const uint16_t* e = src + c * (chunk_bytes / 2);
+    uint8_t* out = frames + at;
+    uint64_t pos = kBloscHeader + 4ull * g.nblocks;
+    bool memcpyed = store;
+    for (int b = 0; b < g.nblocks && !memcpyed; ++b) {
+      const uint32_t bsize = g.bsize(chunk_bytes, b);
+      for (uint32_t p = 0; p < bsize; ++p) lit[p] = shuffled_byte(e + (uint64_t)b * (g.blocksize / 2), bsize / 2, p);
+      uint32_t zs[kZPerBlosc] = {};
+      for (int j = 0; j < kZPerBlosc && (uint32_t)j * kZBlock < bsize; ++j) {
+        const uint32_t z0 = (uint32_t)j * kZBlock, z1 = bsize - z0 < (uint32_t)kZBlock ? bsize : z0 + kZBlock;
+        zs[j] = (uint32_t)encode_block_host(*h, lit + z0, (int)(z1 - z0), z1 == bsize, slot + (size_t)j * kSlotStride);
+      }
+      const uint32_t sb = blosc_stream_bytes(zs, bsize);
+      if (pos + 4 + sb >= kBloscHeader + chunk_bytes) { memcpyed = true; break; }
+      put_le(out + kBloscHeader + 4 * b, pos, 4);
+      put_le(out + pos, sb, 4);
+      uint8_t* d = out + pos + 4;
+      if (sb == bsize) {
+        for (uint32_t p = 0; p < bsize; ++p) d[p] = lit[p];
+      } else {
+        d += frame_header(bsize, d);
+        for (int j = 0; j < kZPerBlosc; ++j)
+          for (uint32_t i = 0; i < zs[j]; ++i) *d++ = slot[(size_t)j * kSlotStride + i];
+      }
+      pos += 4 + sb;
+    }
+    if (memcpyed) {
+      const uint8_t* raw = (const uint8_t*)e;
+      for (uint64_t i = 0; i < chunk_bytes; ++i) out[kBloscHeader + i] = raw[i];
+      pos = kBloscHeader + chunk_bytes;
+    }
+    blosc_header(out, chunk_bytes, g.blocksize, pos, memcpyed);
+    at += pos;
+    offsets[c + 1] = (int64_t)at;
+  }
+  delete[] lit;
+  delete[] slot;
+  delete h;
+}
+
+}  // namespace zenc
+}  // namespace dsx
+
+#endif  // DSX_ZSTD_ENC_H

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = [
     "dsx_stream_wait", "dsx_stream_sync", "dsx_event_record", "dsx_event_sync",
     "dsx_io_read_chunks", "dsx_io_write_chunks", "dsx_io_write_chunks_blosc", "dsx_blosc_decode", "dsx_blosc_encode",
     "dsx_png_unfilter", "dsx_plan_streaks", "dsx_get_streaks_threshold",
+    "dsx_blosc_encode_device", "dsx_blosc_encode_ref",
 ]  # fmt: skip
 
 
@@ -169,6 +170,8 @@ def load_library(path=None):
     lib.dsx_blosc_decode.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t]
     lib.dsx_blosc_encode.argtypes = [vp, ctypes.c_size_t, i32, i32, i32, vp, ctypes.c_size_t,
                                      ctypes.POINTER(ctypes.c_size_t)]  # fmt: skip
+    lib.dsx_blosc_encode_device.argtypes = [vp, vp, i32, ctypes.c_size_t, i32, i32, vp, vp]
+    lib.dsx_blosc_encode_ref.argtypes = [vp, i32, ctypes.c_size_t, i32, i32, vp, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("dsx_destroy", "dsx_last_error"):
@@ -422,6 +425,14 @@ class DestripeEngine:
     def sync(self):
         self._check(self._lib.dsx_sync(self._ctx))
 
+    def blosc_encode_device(self, d_src, n_chunks, chunk_bytes, d_frames, d_offsets, typesize=2, clevel=3):
+        """Blosc-zstd frames of ``n_chunks`` chunks of ``chunk_bytes`` (device buffer ``d_src``), encoded on the device
+        into ``d_frames`` (capacity ``n_chunks * (chunk_bytes + 16)``), packed back to back; ``d_offsets`` receives
+        ``n_chunks + 1`` int64 frame offsets.  Asynchronous on the engine stream."""
+        self._check(self._lib.dsx_blosc_encode_device(self._ctx, ctypes.c_void_p(d_src.ptr), int(n_chunks),
+                                                      int(chunk_bytes), int(typesize), int(clevel),
+                                                      ctypes.c_void_p(d_frames.ptr), ctypes.c_void_p(d_offsets.ptr)))  # fmt: skip
+
     def timer_start(self):
         self._check(self._lib.dsx_timer_start(self._ctx))
 
@@ -628,3 +639,21 @@ class DestripeEngine:
         self._check(self._lib.dsx_get_level(self._ctx, int(plane), int(level), int(stage),
                                             out.ctypes.data_as(ctypes.c_void_p)))  # fmt: skip
         return out
+
+
+def blosc_encode_ref(chunks, clevel=3):
+    """Host build of the device encoder (``dsx_blosc_encode_ref``): ``chunks`` = uint16 array ``[n, ...]`` (one chunk
+    per leading index) -> ``(frames: bytes, offsets: int64 [n + 1])``, byte-identical to ``Engine.blosc_encode_device``."""
+    lib = load_library()
+    a = np.ascontiguousarray(chunks)
+    if a.dtype != np.uint16:
+        raise ValueError("the device Blosc-zstd encoder supports uint16 (typesize 2) only")
+    n = a.shape[0] if a.ndim else 0
+    chunk_bytes = a.nbytes // n if n else 0
+    frames = np.empty(n * (chunk_bytes + 16) + 1, np.uint8)
+    offsets = np.zeros(n + 1, np.int64)
+    rc = lib.dsx_blosc_encode_ref(a.ctypes.data_as(ctypes.c_void_p), int(n), int(chunk_bytes), 2, int(clevel),
+                                  frames.ctypes.data_as(ctypes.c_void_p), offsets.ctypes.data_as(ctypes.c_void_p))  # fmt: skip
+    if rc != 0:
+        raise DsxError(rc, (lib.dsx_last_error(None) or b"blosc_encode_ref failed").decode())
+    return frames[: offsets[-1]].tobytes(), offsets

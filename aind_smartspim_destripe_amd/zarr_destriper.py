@@ -265,11 +265,15 @@ class _DeviceBlocks:
     upload(b) -> compute(b) -> download(b);  upload(b + 2) after compute(b) (it refills the same device
     buffer);  compute(b + 2) after download(b) (it overwrites the same output bricks).  The host waits on
     event slots before it refills a pinned input buffer or hands a pinned output buffer to the writers.
+
+    With ``device_codec`` the output bricks are Blosc-zstd frames before they leave the device
+    (``dsx_blosc_encode_device`` on the compute stream, after ``planes_to_bricks``): the download stream brings back
+    the frame offsets, then only the packed frames, and the I/O threads write each byte range as it is.
     """
 
     N_BUF = 2
 
-    def __init__(self, eng, src, dst, zyx, block_z, io_threads):
+    def __init__(self, eng, src, dst, zyx, block_z, io_threads, device_codec=False):
         self.eng, self.src, self.dst, self.zyx, self.block_z = eng, src, dst, zyx, block_z
         self.ci, self.co = tuple(src.chunks[-3:]), tuple(dst.chunks[-3:])
         _, H, W = zyx
@@ -288,11 +292,23 @@ class _DeviceBlocks:
         self.d_bricks_out = [eng.alloc(out_bytes) for _ in range(self.N_BUF)]
         self.d_planes = eng.alloc(block_z * H * W * 2)
         self.d_out = eng.alloc(block_z * H * W * 2)
+        self.device_codec = bool(device_codec)
+        self.d_frames, self.d_offsets, self.h_frames, self.h_offsets = [], [], [], []
+        if self.device_codec:
+            n_chunks = int(np.prod(self.go))
+            cap = n_chunks * (self.out_brick * 2 + 16)
+            self.d_frames = [eng.alloc(cap) for _ in range(self.N_BUF)]
+            self.d_offsets = [eng.alloc(8 * (n_chunks + 1)) for _ in range(self.N_BUF)]
+            self.h_frames = [eng.alloc_host(cap) for _ in range(self.N_BUF)]
+            self.h_offsets = [eng.alloc_host(8 * (n_chunks + 1)) for _ in range(self.N_BUF)]
+            self.frames = [h.array((cap,), np.uint8) for h in self.h_frames]
+            self.offsets = [h.array((n_chunks + 1,), np.int64) for h in self.h_offsets]
         self.io_threads = int(io_threads)
         self.timing = {"read_s": 0.0, "write_s": 0.0}
 
     def close(self):
-        for b in self.d_bricks_in + self.d_bricks_out + [self.d_planes, self.d_out] + self.h_in + self.h_out:
+        for b in (self.d_bricks_in + self.d_bricks_out + [self.d_planes, self.d_out] + self.h_in + self.h_out
+                  + self.d_frames + self.d_offsets + self.h_frames + self.h_offsets):
             b.free()
 
     # -- host stages (I/O threads) -------------------------------------------------------------
@@ -318,6 +334,13 @@ class _DeviceBlocks:
         oz0 = z0 // self.co[0]
         out = self.stage_out[k]
         odx = list(itertools.product(range(nbo), range(self.go[1]), range(self.go[2])))
+        paths = [self.dst._chunk_path(lead + (oz0 + i[0], i[1], i[2])) for i in odx]
+        if self.device_codec:  # finished frames: chunk c is bytes [offsets[c], offsets[c + 1]) of the packed buffer
+            frames, offs = self.frames[k], self.offsets[k]
+            self.eng.io_write_chunks(paths, [frames[offs[c] : offs[c + 1]] for c in range(len(odx))],
+                                     threads=self.io_threads, zlib_level=-1)  # fmt: skip
+            self.timing["write_s"] += time.perf_counter() - t0
+            return
         comp = self.dst.compressor
         level = -1 if comp is None else int(comp[1])
         self.eng.io_write_chunks([self.dst._chunk_path(lead + (oz0 + i[0], i[1], i[2])) for i in odx],
@@ -338,10 +361,29 @@ class _DeviceBlocks:
         eng.run_device(self.d_planes, np.uint16, Z, self.d_out, np.uint16, None)
         eng.stream_wait(C, D)             # (the wait lands before planes_to_bricks:) after download(b - 2 .. b - 1)
         eng.planes_to_bricks(self.d_out, self.d_bricks_out[k], (Z, H, W), self.co, 0)
-        eng.stream_wait(D, C)             # download(b) after compute(b)
         nbo = -(-Z // self.co[0])
+        if self.device_codec:
+            n_chunks = nbo * self.go[1] * self.go[2]
+            eng.blosc_encode_device(self.d_bricks_out[k], n_chunks, self.out_brick * 2, self.d_frames[k],
+                                    self.d_offsets[k], typesize=2, clevel=int(self.dst.compressor[1]))  # fmt: skip
+            eng.stream_wait(D, C)
+            eng.copy_d2h_async(self.offsets[k][: n_chunks + 1], self.d_offsets[k], D)
+            eng.event_record(self.N_BUF + k, D)  # the frame offsets of block b are here once this has passed
+            return
+        eng.stream_wait(D, C)             # download(b) after compute(b)
         eng.copy_d2h_async(self.stage_out[k][:nbo], self.d_bricks_out[k], D)
         eng.event_record(self.N_BUF + k, D)  # pinned output buffer k holds block b once this has passed
+
+    def _fetch_frames(self, z0, z1, k):
+        """(device codec; the offsets of block [z0, z1) are on the host) Download exactly its packed frames."""
+        from .engine import STREAM_DOWNLOAD as D
+
+        n_chunks = -(-(z1 - z0) // self.co[0]) * self.go[1] * self.go[2]
+        total = int(self.offsets[k][n_chunks])
+        if total:
+            self.eng.copy_d2h_async(self.frames[k][:total], self.d_frames[k], D)
+        self.eng.event_record(self.N_BUF + k, D)
+        self.eng.event_sync(self.N_BUF + k)
 
     def run_range(self, z_start, z_stop):
         """All blocks of ``[z_start, z_stop)`` through the pipeline; returns the number of planes."""
@@ -364,9 +406,13 @@ class _DeviceBlocks:
                 if b >= 1:
                     kp = (b - 1) % self.N_BUF
                     self.eng.event_sync(self.N_BUF + kp)  # download(b - 1) complete
+                    if self.device_codec:
+                        self._fetch_frames(*blocks[b - 1], kp)
                     writes.append(writer.submit(self._write, *blocks[b - 1], kp))
             if nb:
                 self.eng.event_sync(self.N_BUF + (nb - 1) % self.N_BUF)
+                if self.device_codec:
+                    self._fetch_frames(*blocks[nb - 1], (nb - 1) % self.N_BUF)
                 writes.append(writer.submit(self._write, *blocks[nb - 1], (nb - 1) % self.N_BUF))
             for w in writes:
                 w.result()
@@ -380,10 +426,10 @@ LAST_RUN = {}  # what the last destripe_zarr_store call of this process resolved
 _BLOCKS = {}  # one set of staging buffers per process: page-locking 2 GB of host memory costs ~0.4 s per call
 
 
-def _device_blocks(eng, src, dst, zyx, block_z, io_threads):
+def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False):
     """Staging buffers for this geometry, reused from the previous tile when nothing but the stores changed
     (a channel is tens of tiles of one shape, ``zarr_destriper.py:1231``)."""
-    key = (id(eng), tuple(zyx[1:]), tuple(src.chunks[-3:]), tuple(dst.chunks[-3:]), int(block_z))
+    key = (id(eng), tuple(zyx[1:]), tuple(src.chunks[-3:]), tuple(dst.chunks[-3:]), int(block_z), bool(device_codec))
     cached = _BLOCKS.get("blocks")
     if cached is not None and cached[0] == key and cached[1].eng._ctx is not None:
         blocks = cached[1]
@@ -395,7 +441,7 @@ def _device_blocks(eng, src, dst, zyx, block_z, io_threads):
             cached[1].close()
         except Exception:  # the engine of the cached buffers may be gone already
             pass
-    blocks = _DeviceBlocks(eng, src, dst, zyx, block_z, io_threads)
+    blocks = _DeviceBlocks(eng, src, dst, zyx, block_z, io_threads, device_codec)
     _BLOCKS["blocks"] = (key, blocks)
     return blocks
 
@@ -438,6 +484,8 @@ def destripe_zarr_store(
     io_threads=None,
     tile_name=None,
     group=None,
+    *,
+    device_codec=False,
 ):
     """Chunk map of ``destripe_zarr`` (``zarr_destriper.py:909-1211``) over a Zarr-v2 directory store -- the engine-level
     form (explicit configs and ``shadow_correction``); :func:`destripe_zarr` is the entry point with the reference's
@@ -467,6 +515,11 @@ def destripe_zarr_store(
     ``device_retile``: ``True`` = chunks are re-tiled into planes and back on the GPU (row f1; needs a
     uint16 store and chunk-aligned z blocks), ``False`` = host gather / scatter through
     :func:`execute_worker`, ``None`` = the device path whenever it applies.
+
+    ``device_codec``: ``True`` = the output chunks are encoded into Blosc-zstd frames on the GPU
+    (``dsx_blosc_encode_device``: Huffman-coded literals, no matches -- about 1.1x the host writer's bytes, any c-blosc
+    reader decodes them) and the host only writes finished bytes.  Needs a Blosc-zstd output with byte shuffle and the
+    device re-tiling path; anything else raises ``ValueError``.  Off by default.
     """
     logger = logger or logging.getLogger("dsx.zarr")
     if io_threads is None:
@@ -504,16 +557,24 @@ def destripe_zarr_store(
     can = z1 > z0 and _device_retile_ok(src, dst, zyx, block_z, z0, z1)
     if device_retile and not can:
         raise ValueError("device_retile needs a uint16 store, even planes and output-chunk-aligned z blocks")
+    if device_codec:
+        comp = dst.compressor
+        if comp is None or comp[0] != "blosc" or comp[2] != "zstd" or comp[3] != 1 or dst.dtype != np.uint16:
+            raise ValueError("device_codec needs a Blosc-zstd uint16 output with byte shuffle, not {!r}".format(comp))
+        if not can or device_retile is False:
+            raise ValueError("device_codec needs the device re-tiling path (a uint16 store, even planes and "
+                             "output-chunk-aligned z blocks)")  # fmt: skip
     if can and device_retile is not False:
         flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
         eng = fl.get_engine(zyx[1:], cells_config, no_cells_config, 2500, flatfield, darkfield,
                             max_batch=min(block_z, 64), device=dev)  # fmt: skip
-        blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads)
+        blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec)
         n_planes = blocks.run_range(z0, z1)
         eng.sync()
         dt = time.perf_counter() - t0
-        logger.info("rank %d: %d planes z[%d:%d) in %.2f s (device re-tiling, overlapped; read %.2f s, write %.2f s)",
-                    rank, n_planes, z0, z1, dt, blocks.timing["read_s"], blocks.timing["write_s"])  # fmt: skip
+        logger.info("rank %d: %d planes z[%d:%d) in %.2f s (device re-tiling%s, overlapped; read %.2f s, write %.2f s)",
+                    rank, n_planes, z0, z1, dt, ", device codec" if device_codec else "", blocks.timing["read_s"],
+                    blocks.timing["write_s"])  # fmt: skip
         return n_planes, dt
     for sc, internal in iter_blocks(zyx, prediction_chunksize, (z0, z1)):
         lead = (0,) * (len(src.shape) - 3)
@@ -662,6 +723,7 @@ def destripe_zarr(
     device_retile=None,
     io_threads=None,
     group=None,
+    device_codec=False,
 ):
     """``destripe_zarr`` of the reference (``zarr_destriper.py:909-1211``) with its 14 parameters, on the GPU chunk map.
 
@@ -686,7 +748,8 @@ def destripe_zarr(
 
     Keyword-only extras (the engine's): ``rank`` / ``world_size`` / ``group`` (one process per GPU, chunk-aligned
     z-ranges; with a ``distributed.RankGroup`` rank 0 alone reads the dark plane and broadcasts it), ``device``,
-    ``compressor`` / ``output_chunks`` of the output, ``n_levels``, ``device_retile``, ``io_threads``.
+    ``compressor`` / ``output_chunks`` of the output, ``n_levels``, ``device_retile``, ``io_threads``, ``device_codec``
+    (level 0 encoded on the GPU, :func:`destripe_zarr_store`).
     Returns ``(planes processed by this rank, seconds)``.
     """
     no_cells_config = parameters["no_cells_config"]
@@ -756,6 +819,7 @@ def destripe_zarr(
         io_threads=io_threads,
         tile_name=dataset_name,
         group=group,
+        device_codec=device_codec,
     )
     if group is not None and world_size > 1:
         group.barrier()  # level 0 of this tile is complete on every rank: the pyramid may read it
@@ -802,6 +866,7 @@ def destripe_channel(
     group=None,
     io_threads=None,
     device_retile=None,
+    device_codec=False,
 ):
     """``destripe_channel`` of the reference (``zarr_destriper.py:1214-1267``), same eight parameters (the reference's
     caller passes them by keyword, ``run_capsule.py:394-403``), wired to the GPU chunk map.
@@ -815,7 +880,7 @@ def destripe_channel(
 
     Keyword-only extras: ``rank`` / ``world_size`` / ``group`` / ``device`` (one process per GPU), output codec and
     chunks, ``multiscale`` (the reference hard-codes ``"0"``), ``prediction_chunksize`` (the reference hard-codes the
-    production tile, ``(64, 1600, 2000)``), ``io_threads``, ``device_retile``.  ``world_size > 1`` needs ``group`` (anything with
+    production tile, ``(64, 1600, 2000)``), ``io_threads``, ``device_retile``, ``device_codec``.  ``world_size > 1`` needs ``group`` (anything with
     ``barrier()``): the pyramid of a tile may only be computed once EVERY rank has written its z-range.  With a
     ``distributed.RankGroup`` rank 0 alone reads the flat and dark planes of a tile and broadcasts them (RCCL).
     """
@@ -864,6 +929,7 @@ def destripe_channel(
             io_threads=io_threads,
             device_retile=device_retile,
             group=group,
+            device_codec=device_codec,
         )
         done[tile_path.name] = n
     return done

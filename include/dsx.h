@@ -204,6 +204,19 @@ int dsx_blosc_decode(const void* frame, size_t frame_bytes, void* dst, size_t ds
 int dsx_blosc_encode(const void* src, size_t bytes, int typesize, int clevel, int shuffle, void* frame,
                      size_t frame_capacity, size_t* frame_bytes);
 
+/* Blosc-zstd frames of n_chunks uint16 chunks of chunk_bytes each, encoded on the device (csrc/dsx_zstd_enc.h:
+ * entropy-only zstd -- Huffman literals, no matches -- in the container dsx_blosc_encode writes: 256 KiB blocks,
+ * byte shuffle, "don't split"; a chunk that does not get smaller is a memcpyed frame).  d_src: the chunks back to
+ * back (device); d_frames: the frames packed back to back, capacity n_chunks * (chunk_bytes + 16); d_offsets:
+ * n_chunks + 1 int64 -- frame i is bytes [d_offsets[i], d_offsets[i + 1]).  typesize must be 2, chunk_bytes even;
+ * clevel 0 stores every chunk, 1 ... 9 encode (the level does not change the encoding).  Asynchronous on the context
+ * stream; the context keeps a work buffer of ~chunk_bytes + 64 per chunk.
+ * dsx_blosc_encode_ref: the host build of the same encoder, byte-identical output (host pointers, synchronous). */
+int dsx_blosc_encode_device(dsx_ctx* ctx, const void* d_src, int n_chunks, size_t chunk_bytes, int typesize,
+                            int clevel, void* d_frames, int64_t* d_offsets);
+int dsx_blosc_encode_ref(const void* src, int n_chunks, size_t chunk_bytes, int typesize, int clevel, void* frames,
+                         int64_t* offsets);
+
 /* PNG scanline reconstruction for the directory mode's reader (imageio's iio.imread, readers.py:86-87): `height`
  * rows of one filter-type byte + `stride` bytes, un-filtered in place (Sub / Up / Average / Paeth).  Host only.  */
 int dsx_png_unfilter(void* rows, int height, int stride, int bytes_per_pixel);

@@ -2,7 +2,12 @@
 """End-to-end chunk map throughput: an uncompressed uint16 Zarr-v2 store of N planes
 2048 x 2048, chunks (1,1,64,128,128), through destripe_zarr (device re-tiling, overlapped upload / filter /
 download) into another store.  Prints one JSON line; the roofline of this path is the host link
-(PCIe Gen5 x16, 63 GB/s spec: 16.8 MB per plane both ways -> <= 3.7 k planes/s), not HBM."""
+(PCIe Gen5 x16, 63 GB/s spec: 16.8 MB per plane both ways -> <= 3.7 k planes/s), not HBM.
+
+    bench_zarr.py N [raw|zlib|blosc] [device-codec]
+
+`device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
+line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block)."""
 import json, logging, os, shutil, sys, tempfile, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,7 +16,8 @@ from aind_smartspim_destripe_amd.mini_zarr import MiniZarrArray
 
 logging.basicConfig(level=logging.INFO, stream=sys.stderr)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-codec = sys.argv[2] if len(sys.argv) > 2 else None  # None (raw chunks), "zlib" or "blosc" (Blosc-zstd, the production codec)
+codec = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2] != "raw" else None  # None (raw chunks), "zlib" or "blosc" (Blosc-zstd)
+device_codec = "device-codec" in sys.argv[3:]
 H = W = 2048
 root = tempfile.mkdtemp(prefix="dsx_zarr_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
@@ -27,10 +33,22 @@ try:
             t0 = time.perf_counter()
             planes, dt = zd.destripe_zarr_store(os.path.join(root, "in.zarr"), os.path.join(root, "out.zarr"), synth.CELLS_CONFIG,
                                           synth.NO_CELLS_CONFIG, None, prediction_chunksize=(64, H, W),
-                                          output_chunks=(1, 1, 64, 128, 128), device=0, device_retile=True, io_threads=16, compressor=codec, **kw)
+                                          output_chunks=(1, 1, 64, 128, 128), device=0, device_retile=True, io_threads=16, compressor=codec,
+                                          device_codec=device_codec, **kw)
             res[name] = {"planes": planes, "seconds": round(time.perf_counter() - t0, 3)}
     out = MiniZarrArray.open(os.path.join(root, "out.zarr"))
     chk = int(out[0, 0, 0].astype(np.uint64).sum())
+    sizes = {}
+    if codec == "blosc":  # bytes on disk; the host writer's frames of the first block's chunks for comparison
+        from aind_smartspim_destripe_amd import mini_zarr
+        written = sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(os.path.join(root, "out.zarr"))
+                      for f in fs if not f.startswith("."))
+        first = [out._chunk_path((0, 0, 0, y, x)) for y in range(H // 128) for x in range(W // 128)]
+        got = sum(os.path.getsize(p) for p in first)
+        host = sum(len(mini_zarr.blosc_encode(out._read_chunk((0, 0, 0, y, x)).tobytes(), 2, clevel=3, shuffle=True))
+                   for y in range(H // 128) for x in range(W // 128))
+        sizes = {"bytes_written": written, "raw_bytes": n * H * W * 2, "ratio_to_raw": round(written / (n * H * W * 2), 4),
+                 "first_block_bytes": got, "first_block_host_writer_bytes": host, "size_ratio_to_host_writer": round(got / host, 4)}
     v = res["overlapped"]["planes"] / res["overlapped"]["seconds"]
     # ---- verification (tests/test_zarr_chunk_map.py::test_chunk_map_at_production_geometry_against_the_oracle holds the
     # same statement on a 192-plane store): one plane of every stream part of the first, a middle and the last block --
@@ -59,10 +77,11 @@ try:
                 except AssertionError as e:
                     verified = False
                     print("oracle mismatch", e, file=sys.stderr)
-    print(json.dumps({"metric": "2048x2048 uint16 slices/s, Zarr store to Zarr store ({} chunks, tmpfs)".format(codec or "raw"), "value": round(v, 1),
+    label = (codec or "raw") + (", encoded on the device" if device_codec else "")
+    print(json.dumps({"metric": "2048x2048 uint16 slices/s, Zarr store to Zarr store ({} chunks, tmpfs)".format(label), "value": round(v, 1),
                       "planes": n, "seconds": res["overlapped"]["seconds"], "store_make_s": round(t_make, 1),
                       "roofline": {"bound": "host link", "peak_planes_per_s": 3750, "frac": round(v / 3750.0, 3)},
-                      "plane0_checksum": chk, "verified": verified,
+                      "plane0_checksum": chk, "verified": verified, **sizes,
                       "verification": {"planes_bit_identical_to_single_plane_runs": checked,
                                        "planes_against_the_cpu_oracle": oracle_checked, "blocks": blocks}}))
     if not verified:
