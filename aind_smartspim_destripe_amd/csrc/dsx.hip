@@ -24,6 +24,7 @@
 #include "dsx_io.h"
 #include "dsx_streaks.h"
 #include "dsx_zenc_kernels.h"
+#include "dsx_zdec_kernels.h"
 
 namespace {
 
@@ -119,6 +120,9 @@ struct dsx_ctx {
   uint8_t* zenc_slots = nullptr;
   uint32_t* zenc_sizes = nullptr;
   size_t zenc_blocks = 0;
+  // dsx_blosc_decode_device: shuffled blocks are decoded here before the un-shuffle, grown on demand
+  uint8_t* zdec_scratch = nullptr;
+  size_t zdec_bytes = 0;
   unsigned* d_sticky = nullptr;
   // dsx_set_stack_mode: the planes of a call share ONE Otsu threshold per level (the reference's 3-D input mode)
   bool stack_mode = false;
@@ -1325,6 +1329,7 @@ void dsx_destroy(dsx_ctx* ctx) {
   if (ctx->h_sticky) (void)hipHostFree(ctx->h_sticky);
   if (ctx->zenc_slots) (void)hipFree(ctx->zenc_slots);
   if (ctx->zenc_sizes) (void)hipFree(ctx->zenc_sizes);
+  if (ctx->zdec_scratch) (void)hipFree(ctx->zdec_scratch);
   if (ctx->ev_xs) (void)hipEventDestroy(ctx->ev_xs);
   for (int i = 0; i < dsx_ctx::kEventSlots; ++i)
     if (ctx->ev_slot[i]) (void)hipEventDestroy(ctx->ev_slot[i]);
@@ -2054,6 +2059,63 @@ int dsx_blosc_encode_device(dsx_ctx* ctx, const void* d_src, int n_chunks, size_
   hipLaunchKernelGGL(z::k_zenc_scan, dim3(1), dim3(256), 0, s, pa);
   if (n_chunks > 0)
     hipLaunchKernelGGL(z::k_zenc_copy, dim3((unsigned)(n_chunks * pa.nblocks)), dim3(256), 0, s, pa);
+  DSX_HIP(hipGetLastError());
+  return DSX_OK;
+}
+
+int dsx_io_read_frames(dsx_ctx* ctx, const char* const* paths, int n, size_t chunk_bytes, int threads,
+                       uint16_t fill_value, void* packed, size_t packed_capacity, void* tasks, int task_capacity,
+                       size_t* packed_bytes, int* n_tasks, uint8_t* routes) {
+  if (n < 0 || (n > 0 && (!paths || !packed || !tasks)) || !packed_bytes || !n_tasks || task_capacity < 0)
+    return DSX_EINVAL;
+  const std::string e = dsx::io_read_frames(paths, n, chunk_bytes, threads, fill_value, (unsigned char*)packed,
+                                            packed_capacity, (dsx::zdec::DecTask*)tasks, (size_t)task_capacity,
+                                            packed_bytes, n_tasks, routes);
+  if (!e.empty()) return fail(ctx, DSX_EIO, e);
+  return DSX_OK;
+}
+
+int dsx_blosc_decode_ref(const void* packed, size_t packed_bytes, const void* tasks, int n_tasks, void* out,
+                         size_t out_bytes, int32_t* status) {
+  if ((!packed && packed_bytes) || (!tasks && n_tasks) || n_tasks < 0 || (!out && out_bytes) || (!status && n_tasks))
+    return DSX_EINVAL;
+  namespace z = dsx::zdec;
+  const z::DecTask* t = (const z::DecTask*)tasks;
+  z::Tables* work = new z::Tables;
+  std::vector<uint8_t> tmp;
+  for (int i = 0; i < n_tasks; ++i) {
+    const z::DecTask& k = t[i];
+    if (k.dst > out_bytes || k.dst_len > out_bytes - k.dst ||
+        ((k.kind & z::kTaskKindMask) != z::kTaskFill && (k.src > packed_bytes || k.src_len > packed_bytes - k.src))) {
+      status[i] = z::kErrOutput;
+      continue;
+    }
+    tmp.resize(k.dst_len);
+    status[i] = z::run_task_host(*work, k, (const uint8_t*)packed, (uint8_t*)out, tmp.data());
+  }
+  delete work;
+  return DSX_OK;
+}
+
+int dsx_blosc_decode_device(dsx_ctx* ctx, const void* d_packed, size_t packed_bytes, const void* d_tasks, int n_tasks,
+                            void* d_out, size_t out_bytes, int32_t* d_status) {
+  if (!ctx || n_tasks < 0 || (n_tasks > 0 && (!d_packed || !d_tasks || !d_out || !d_status))) return DSX_EINVAL;
+  namespace z = dsx::zdec;
+  DSX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = use_main(ctx);
+  if (out_bytes > ctx->zdec_bytes) {
+    DSX_HIP(hipStreamSynchronize(s));
+    if (ctx->zdec_scratch) DSX_HIP(hipFree(ctx->zdec_scratch));
+    ctx->zdec_scratch = nullptr;
+    ctx->zdec_bytes = 0;
+    if (hipMalloc(&ctx->zdec_scratch, out_bytes) != hipSuccess)
+      return fail(ctx, DSX_ENOMEM, "blosc_decode: cannot allocate the work buffer");
+    ctx->zdec_bytes = out_bytes;
+  }
+  if (n_tasks > 0)
+    hipLaunchKernelGGL(z::k_zdec, dim3((unsigned)n_tasks), dim3(z::kDecThreads), 0, s,
+                       z::DecArgs{(const uint8_t*)d_packed, (const z::DecTask*)d_tasks, (uint8_t*)d_out,
+                                  ctx->zdec_scratch, d_status, (uint64_t)packed_bytes, (uint64_t)out_bytes});
   DSX_HIP(hipGetLastError());
   return DSX_OK;
 }

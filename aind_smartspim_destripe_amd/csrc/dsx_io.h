@@ -31,6 +31,8 @@
 #include <unistd.h>
 #include <zlib.h>
 
+#include "dsx_zstd_dec.h"
+
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -485,6 +487,108 @@ inline std::string io_read_chunks(const char* const* paths, void* const* dst, co
       return std::string("zlib: bad chunk ") + paths[i];
     return "";
   });
+}
+
+// ---- Blosc frames for the device decoder (dsx_blosc_decode_device) -------------------------------------------------
+// Which frames go to the device is decided here from header bytes only (16-byte Blosc header, block table, the zstd
+// frame descriptor of each block): c-blosc 1.x, typesize 2, no shuffle or byte shuffle, zstd inside, unsplit streams,
+// at most frame_tasks_per_chunk blocks -> one task per block (a zstd frame, or a stored stream); memcpyed frames -> one
+// copy task; a missing file -> one fill task.  Any other frame is decoded here by blosc_decode (its error is the
+// error of the read) and shipped as a copy task.
+inline size_t frame_tasks_per_chunk(size_t chunk_bytes) { return chunk_bytes / 8192 + 1; }
+enum FrameRoute { kRouteDevice = 0, kRouteHost = 1, kRouteFill = 2 };
+
+// Tasks of one frame (src offsets relative to the frame, dst offsets relative to the chunk) if the device takes it
+inline bool blosc_device_route(const unsigned char* src, size_t n, size_t want, size_t max_tasks,
+                               std::vector<zdec::DecTask>& out, size_t* frame_bytes) {
+  out.clear();
+  if (n < (size_t)kBloscHeader || n > want + kBloscHeader) return false;
+  const unsigned version = src[0], flags = src[2], typesize = src[3];
+  const size_t nbytes = le32(src + 4), blocksize = le32(src + 8), cbytes = le32(src + 12);
+  if (version < 1 || version > 2 || nbytes != want || nbytes == 0 || cbytes > n || cbytes < (size_t)kBloscHeader)
+    return false;
+  *frame_bytes = cbytes;
+  if (flags & kBloscMemcpyed) {
+    if (cbytes < kBloscHeader + nbytes) return false;
+    out.push_back(zdec::DecTask{(uint64_t)kBloscHeader, 0, (uint32_t)nbytes, (uint32_t)nbytes, zdec::kTaskCopy, 0});
+    return true;
+  }
+  if (typesize != 2 || ((flags >> 5) & 7) != kInnerZstd || (flags & kBloscBitshuffle)) return false;
+  const uint32_t shuf = (flags & kBloscShuffle) ? zdec::kTaskShuffle : 0u;
+  const bool dont_split = (flags & kBloscDontSplit) != 0;
+  if (blocksize == 0 || blocksize > nbytes) return false;
+  const size_t nblocks = (nbytes + blocksize - 1) / blocksize;
+  if (nblocks > max_tasks || kBloscHeader + 4 * nblocks > cbytes) return false;
+  for (size_t b = 0; b < nblocks; ++b) {
+    const size_t bsize = (b + 1 == nblocks) ? nbytes - b * blocksize : blocksize;
+    const bool leftover = bsize != blocksize;
+    if (!dont_split && !leftover && blocksize / typesize >= (size_t)kBloscMinBuffer) return false;  // split streams
+    size_t pos = le32(src + kBloscHeader + 4 * b);
+    if (pos + 4 > cbytes) return false;
+    const size_t cs = le32(src + pos);
+    pos += 4;
+    if (cs > cbytes - pos) return false;
+    uint32_t kind = zdec::kTaskStored;
+    if (cs != bsize) {
+      if (!zdec::device_frame(src + pos, (uint32_t)cs, (uint32_t)bsize)) return false;
+      kind = zdec::kTaskZstd;
+    }
+    out.push_back(zdec::DecTask{(uint64_t)pos, (uint64_t)(b * blocksize), (uint32_t)cs, (uint32_t)bsize, kind | shuf, 0});
+  }
+  return true;
+}
+
+// n chunk files (chunk_bytes decompressed each; chunk i lands at i * chunk_bytes of the output) -> the frames packed
+// back to back into `packed` (capacity n * (chunk_bytes + 16)) and the tasks (capacity n * frame_tasks_per_chunk),
+// in no particular order.  routes (optional): FrameRoute per chunk.
+inline std::string io_read_frames(const char* const* paths, int n, size_t chunk_bytes, int threads, uint16_t fill,
+                                  unsigned char* packed, size_t packed_cap, zdec::DecTask* tasks, size_t task_cap,
+                                  size_t* packed_bytes, int* n_tasks, unsigned char* routes) {
+  const size_t per = frame_tasks_per_chunk(chunk_bytes);
+  if (chunk_bytes > 0x7FFFFFEFu) return "io_read_frames: chunk larger than a frame can hold";
+  if (packed_cap < (size_t)n * (chunk_bytes + kBloscHeader) || task_cap < (size_t)n * per)
+    return "io_read_frames: packed buffer or task table too small";
+  std::atomic<size_t> at(0), nt(0);
+  const std::string err = io_parallel(n, threads, [&](int i) -> std::string {
+    const uint64_t dst = (uint64_t)i * chunk_bytes;
+    struct stat st;
+    if (stat(paths[i], &st) != 0) {
+      if (errno != ENOENT) return std::string("cannot stat chunk ") + paths[i];
+      tasks[nt.fetch_add(1)] = zdec::DecTask{fill, dst, 0, (uint32_t)chunk_bytes, zdec::kTaskFill, (uint32_t)i};
+      if (routes) routes[i] = kRouteFill;
+      return "";
+    }
+    static thread_local std::vector<unsigned char> raw;
+    static thread_local std::vector<zdec::DecTask> local;
+    raw.resize((size_t)st.st_size);
+    if (io_read_file(paths[i], raw.data(), raw.size()) != (long long)raw.size())
+      return std::string("short or failed read of chunk ") + paths[i];
+    size_t fbytes = 0;
+    if (blosc_device_route(raw.data(), raw.size(), chunk_bytes, per, local, &fbytes)) {
+      const size_t off = at.fetch_add(fbytes);
+      memcpy(packed + off, raw.data(), fbytes);
+      const size_t j = nt.fetch_add(local.size());
+      for (size_t k = 0; k < local.size(); ++k) {
+        zdec::DecTask t = local[k];
+        t.src += off;
+        t.dst += dst;
+        t.chunk = (uint32_t)i;
+        tasks[j + k] = t;
+      }
+      if (routes) routes[i] = kRouteDevice;
+      return "";
+    }
+    const size_t off = at.fetch_add(chunk_bytes);
+    const std::string e = blosc_decode(raw.data(), raw.size(), packed + off, chunk_bytes);
+    if (!e.empty()) return e + " (" + paths[i] + ")";
+    tasks[nt.fetch_add(1)] = zdec::DecTask{off, dst, (uint32_t)chunk_bytes, (uint32_t)chunk_bytes, zdec::kTaskCopy,
+                                           (uint32_t)i};
+    if (routes) routes[i] = kRouteHost;
+    return "";
+  });
+  *packed_bytes = at.load();
+  *n_tasks = (int)nt.load();
+  return err;
 }
 
 // src[i] (bytes[i]) -> chunk file paths[i]; zlib_level < 0: raw; blosc_typesize > 0: Blosc-zstd frames of that element

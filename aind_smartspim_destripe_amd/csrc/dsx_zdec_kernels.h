@@ -1,0 +1,375 @@
+// dsx_zdec_kernels.h -- Blosc blocks decoded on the device (dsx_blosc_decode_device): one wave per task of
+// dsx_io_read_frames (dsx_zstd_dec.h DecTask).
+//
+//   k_zdec   grid = tasks, 64 threads.  Fill / copy / stored tasks are wide copies (with the 2-byte un-shuffle where
+//            the frame is shuffled).  A zstd task runs the decoder core of dsx_zstd_dec.h: lane 0 parses the headers
+//            and builds the Huffman and FSE tables in LDS; the four literal streams are decoded by lanes 0 .. 3 into
+//            the end of the task's output, reading their bits from LDS, where the wave stages kLitWin bytes of each
+//            stream per round; lane 0 decodes and validates a batch of up to kSeqBatch sequences into LDS
+//            and the wave executes them (literal copy, then the match).  A match may read bytes the wave stored
+//            earlier: the wave keeps a watermark of output made visible by the last barrier (whose workgroup-scope
+//            fence orders the global stores before the loads that follow) and passes another barrier only when the
+//            match source reaches above it.  A shuffled task decodes into scratch and is un-shuffled into the bricks
+//            after one more barrier.  One int32 status per task (dsx_zstd_dec.h Status; 0 = exact output).
+#ifndef DSX_ZDEC_KERNELS_H
+#define DSX_ZDEC_KERNELS_H
+
+#include <hip/hip_runtime.h>
+
+#include "dsx_zstd_dec.h"
+
+namespace dsx {
+namespace zdec {
+
+constexpr int kDecThreads = 64;  // one wave per task
+constexpr int kSeqBatch = 128;
+constexpr int kLitWin = 2048;    // bytes of each literal stream staged in LDS per round
+
+struct DecArgs {
+  const uint8_t* packed;
+  const DecTask* tasks;
+  uint8_t* out;      // the bricks
+  uint8_t* scratch;  // shuffled tasks decode here first (same offsets as out)
+  int32_t* status;
+  uint64_t packed_bytes, out_bytes;
+};
+
+// n bytes src -> dst by the wave, 8 loads in flight per lane.  Rounds go forward in step for the whole wave and every
+// load of a round precedes its stores, so dst may overlap src from below (dst <= src: the literal copies out of the
+// end of the output).
+__device__ inline void wave_copy(uint8_t* dst, const uint8_t* src, uint32_t n, int lane) {
+  uint32_t base = 0;
+  for (; base + 8 * 64 <= n; base += 8 * 64) {
+    uint8_t v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = src[base + (uint32_t)lane + 64u * u];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) dst[base + (uint32_t)lane + 64u * u] = v[u];
+  }
+  for (; base < n; base += 64)
+    if (base + (uint32_t)lane < n) dst[base + (uint32_t)lane] = src[base + (uint32_t)lane];
+}
+
+// match of ml bytes at dst whose source starts `off` bytes back, off < ml: the last `off` bytes repeat
+__device__ inline void wave_pattern(uint8_t* dst, uint32_t off, uint32_t ml, int lane) {
+  const uint8_t* src = dst - off;
+  uint32_t jj = (uint32_t)lane % off;
+  const uint32_t step = 64u % off;
+  uint32_t i = (uint32_t)lane;
+  for (; i + 3 * 64 < ml; i += 4 * 64) {
+    uint8_t v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      v[u] = src[jj];
+      jj += step;
+      if (jj >= off) jj -= off;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) dst[i + 64 * u] = v[u];
+  }
+  for (; i < ml; i += 64) {
+    dst[i] = src[jj];
+    jj += step;
+    if (jj >= off) jj -= off;
+  }
+}
+
+// 2-byte un-shuffle of n bytes s -> d (bytes [0, n/2) are the low bytes; an odd tail byte as is)
+__device__ inline void wave_unshuffle(uint8_t* d, const uint8_t* s, uint32_t n, int lane) {
+  const uint32_t ne = n / 2;
+  if ((((uintptr_t)d | (uintptr_t)s | ne) & 3u) == 0) {
+    const uint32_t* lo = (const uint32_t*)s;
+    const uint32_t* hi = (const uint32_t*)(s + ne);
+    uint2* d8 = (uint2*)d;
+    for (uint32_t q = (uint32_t)lane; q < ne / 4; q += 64) {
+      const uint32_t a = lo[q], b = hi[q];
+      const uint32_t w0 = (a & 0xFFu) | ((b & 0xFFu) << 8) | ((a & 0xFF00u) << 8) | ((b & 0xFF00u) << 16);
+      const uint32_t w1 = ((a >> 16) & 0xFFu) | (((b >> 16) & 0xFFu) << 8) | ((a >> 24) << 16) | ((b >> 24) << 24);
+      d8[q] = make_uint2(w0, w1);
+    }
+  } else {
+    for (uint32_t i = (uint32_t)lane; i < ne; i += 64) {
+      d[2 * i] = s[i];
+      d[2 * i + 1] = s[ne + i];
+    }
+  }
+  if ((n & 1u) && lane == 0) d[n - 1] = s[n - 1];
+}
+
+__global__ void __launch_bounds__(kDecThreads) k_zdec(DecArgs a) {
+  __shared__ Tables t;
+  __shared__ Seq batch[kSeqBatch];
+  __shared__ Streams ss;
+  __shared__ int32_t sh_st, sh_cnt, sh_lst[4];
+  __shared__ uint32_t sh_u[8];  // broadcast scalars of lane 0
+  __shared__ uint32_t sh_blo[4];
+  __shared__ uint8_t lbuf[4][kLitWin];
+  const int lane = threadIdx.x;
+  const DecTask k = a.tasks[blockIdx.x];
+  const uint32_t kind = k.kind & kTaskKindMask;
+  const bool shuf = (k.kind & kTaskShuffle) != 0;
+  const uint32_t out_n = k.dst_len, n = k.src_len;
+  if (k.dst > a.out_bytes || out_n > a.out_bytes - k.dst ||
+      (kind != kTaskFill && (k.src > a.packed_bytes || n > a.packed_bytes - k.src))) {
+    if (lane == 0) a.status[blockIdx.x] = kErrOutput;
+    return;
+  }
+  uint8_t* d = a.out + k.dst;
+  if (kind == kTaskFill) {
+    for (uint32_t i = (uint32_t)lane; i < out_n; i += 64) d[i] = (uint8_t)(k.src >> (8 * (i & 1)));
+    if (lane == 0) a.status[blockIdx.x] = kOk;
+    return;
+  }
+  const uint8_t* s = a.packed + k.src;
+  if (kind != kTaskZstd) {  // copy / stored
+    if (n != out_n) {
+      if (lane == 0) a.status[blockIdx.x] = kErrOutput;
+      return;
+    }
+    if (shuf) wave_unshuffle(d, s, n, lane);
+    else wave_copy(d, s, n, lane);
+    if (lane == 0) a.status[blockIdx.x] = kOk;
+    return;
+  }
+
+  uint8_t* o = shuf ? a.scratch + k.dst : d;
+  SeqState q;  // lane 0's sequence decoder (its repeat offsets live for the frame)
+  if (lane == 0) {
+    FrameHdr fh;
+    int st = frame_header(s, n, fh);
+    if (!st && fh.content >= 0 && fh.content != (int64_t)out_n) st = kErrOutput;
+    t.huf_log = 0;
+    t.ll_log = t.of_log = t.ml_log = -1;
+    q.rep0 = 1; q.rep1 = 4; q.rep2 = 8;
+    sh_st = st;
+    sh_u[0] = st ? 0u : fh.bytes;
+  }
+  __syncthreads();
+  int st = sh_st;
+  uint32_t ip = sh_u[0], op = 0;
+  while (!st) {
+    // ---- block header (lane 0) and the literals section
+    if (lane == 0) {
+      int e = kOk;
+      uint32_t bh = 0;
+      if (n - ip < 3) e = kErrTruncated;
+      else bh = le(s + ip, 3);
+      const uint32_t type = (bh >> 1) & 3, bs = bh >> 3;
+      if (!e && type == 3) e = kErrReserved;
+      if (!e && bs > kBlockMax) e = kErrBlockSize;
+      if (!e && type == 0 && (bs > n - ip - 3)) e = kErrTruncated;
+      if (!e && type == 1 && n - ip - 3 < 1) e = kErrTruncated;
+      if (!e && type < 2 && bs > out_n - op) e = kErrOutput;
+      if (!e && type == 2 && bs > n - ip - 3) e = kErrTruncated;
+      sh_u[1] = bh;
+      if (!e && type == 2) {  // literals: header, tree, streams
+        const uint8_t* b = s + ip + 3;
+        LitHdr lh;
+        e = lit_header(b, bs, lh);
+        if (!e && lh.regen > out_n - op) e = kErrOutput;
+        uint32_t tree = 0;
+        if (!e && lh.type == 2) {
+          const int used = read_huf_tree(t, b + lh.hdr, lh.csize);
+          if (used < 0) e = -used;
+          else tree = (uint32_t)used;
+        } else if (!e && lh.type == 3 && t.huf_log == 0) {
+          e = kErrHuffman;
+        }
+        if (!e && lh.type >= 2) e = split_streams(b + lh.hdr + tree, lh.csize - tree, lh.regen, lh.streams, ss);
+        sh_u[2] = (uint32_t)lh.type;
+        sh_u[3] = lh.regen;
+        sh_u[4] = lh.hdr + tree;                     // the literals (raw) or the streams start here in the block
+        sh_u[5] = lh.hdr + lh.csize;                 // the sequences section starts here
+        sh_u[6] = lh.type >= 2 ? (uint32_t)lh.streams : 0u;
+      }
+      sh_st = e;
+    }
+    __syncthreads();
+    st = sh_st;
+    if (st) break;
+    const uint32_t bh = sh_u[1], type = (bh >> 1) & 3, bs = bh >> 3;
+    const bool last = bh & 1;
+    ip += 3;
+    if (type == 0) {
+      wave_copy(o + op, s + ip, bs, lane);
+      ip += bs;
+      op += bs;
+    } else if (type == 1) {
+      const uint8_t v = s[ip];
+      for (uint32_t i = (uint32_t)lane; i < bs; i += 64) o[op + i] = v;
+      ip += 1;
+      op += bs;
+    } else {
+      const uint8_t* b = s + ip;
+      const uint32_t lt = sh_u[2], regen = sh_u[3], lit_at = sh_u[4], seq_at = sh_u[5];
+      const int streams = (int)sh_u[6];
+      uint8_t* lit_dst = o + (out_n - regen);
+      const uint8_t* lit = lt == 0 ? b + lit_at : lit_dst;
+      if (lt == 1) {
+        const uint8_t v = b[lit_at];  // the RLE byte follows the header
+        for (uint32_t i = (uint32_t)lane; i < regen; i += 64) lit_dst[i] = v;
+      } else if (lt >= 2) {
+        // lanes 0 .. streams-1 decode one stream each (dsx_zstd_dec.h huf_stream) from bytes the wave stages in LDS,
+        // kLitWin per stream and round, the top of what each lane has not read yet
+        const uint8_t* base = b + lit_at + (lane < streams ? ss.off[lane] : 0u);
+        const uint32_t len = lane < streams ? ss.len[lane] : 0u;
+        uint32_t left = lane < streams ? ss.cnt[lane] : 0u;
+        uint8_t* dst = lit_dst;
+        for (int j = 0; j < lane && j < streams; ++j) dst += ss.cnt[j];
+        int lst = kOk;
+        int64_t pos = 0;    // unread bits of the stream: [0, pos)
+        uint64_t acc = 0;   // its top `avail` bits, [pos - avail, pos); pos - avail is a byte boundary
+        int avail = 0;
+        if (lane < streams) {
+          if (len == 0 || base[len - 1] == 0) {
+            lst = kErrBitstream;
+          } else {
+            avail = hibit(base[len - 1]);
+            pos = 8 * (int64_t)(len - 1) + avail;
+            acc = base[len - 1] & ((1u << avail) - 1u);
+          }
+        }
+        const int log = t.huf_log;
+        for (;;) {
+          const bool act = lane < streams && lst == kOk && left > 0;
+          uint32_t blo = 0;
+          if (act) {
+            const int64_t top = (pos - avail) / 8;  // bytes [0, top) are still to be read
+            blo = top > kLitWin ? (uint32_t)(top - kLitWin) : 0u;
+          }
+          if (lane < 4) {
+            sh_lst[lane] = act ? 1 : 0;
+            sh_blo[lane] = blo;
+          }
+          __syncthreads();
+          const int any = sh_lst[0] | sh_lst[1] | sh_lst[2] | sh_lst[3];
+          if (!any) break;
+          for (int j = 0; j < streams; ++j) {
+            if (!sh_lst[j]) continue;
+            const uint8_t* sb = b + lit_at + ss.off[j];
+            const uint32_t lo = sh_blo[j], sl = ss.len[j];
+            for (uint32_t i0 = 0; i0 < (uint32_t)kLitWin; i0 += 8 * 64) {
+              uint8_t v[8];
+#pragma unroll
+              for (int u = 0; u < 8; ++u) {
+                const uint32_t q = lo + i0 + (uint32_t)lane + 64u * u;
+                v[u] = q < sl ? sb[q] : (uint8_t)0;
+              }
+#pragma unroll
+              for (int u = 0; u < 8; ++u) lbuf[j][i0 + (uint32_t)lane + 64u * u] = v[u];
+            }
+          }
+          __syncthreads();
+          if (act) {
+            const uint8_t* buf = lbuf[lane];
+            const uint32_t mask = (1u << log) - 1u;
+            while (left > 0) {
+              if (avail < log) {
+                int64_t q = (pos - avail) / 8;
+                if (blo > 0 && q < (int64_t)blo + 8) break;  // the next bytes are below the staged ones
+                while (avail <= 56 && q > 0) {
+                  --q;
+                  acc = (acc << 8) | buf[q - blo];
+                  avail += 8;
+                }
+              }
+              const uint32_t idx = avail >= log ? (uint32_t)(acc >> (avail - log)) & mask
+                                                : (uint32_t)(acc << (log - avail)) & mask;  // zeros below bit 0
+              const HufEntry e = t.huf[idx];
+              *dst++ = e.sym;
+              --left;
+              pos -= e.nb;
+              if (pos < 0) {
+                lst = kErrBitstream;
+                break;
+              }
+              avail -= e.nb;
+            }
+            if (lst == kOk && left == 0 && pos != 0) lst = kErrBitstream;
+          }
+          __syncthreads();  // the staged bytes may be replaced
+        }
+        if (lane < streams) sh_lst[lane] = lst;
+      }
+      __syncthreads();  // the literals are visible to the wave
+      if (lane == 0) {
+        int e = kOk;
+        for (int j = 0; j < streams && !e; ++j) e = sh_lst[j];
+        uint32_t nseq = 0;
+        q.op = op;
+        q.lit_used = 0;
+        q.nlit = regen;
+        if (!e) e = seq_header(t, b + seq_at, bs - seq_at, q, &nseq);
+        if (!e) q.left = nseq;
+        else q.left = 0;
+        sh_st = e;
+        sh_u[7] = nseq;
+      }
+      __syncthreads();
+      st = sh_st;
+      if (st) break;
+      const uint32_t nseq = sh_u[7];
+      uint32_t wop = op, lp = 0, fenced = op;
+      for (uint32_t done = 0; done < nseq;) {
+        if (lane == 0) {
+          int e = kOk, c = 0;
+          while (c < kSeqBatch && done + (uint32_t)c < nseq) {
+            Seq e1;
+            e = next_seq(t, q, out_n, e1);
+            if (e) break;
+            batch[c++] = e1;
+          }
+          if (!e && done + (uint32_t)c == nseq) e = seq_end(q);
+          sh_st = e;
+          sh_cnt = c;
+        }
+        __syncthreads();
+        const int c = sh_cnt;
+        for (int j = 0; j < c; ++j) {
+          const Seq e1 = batch[j];
+          wave_copy(o + wop, lit + lp, e1.ll, lane);  // (writes stay below the literals not yet read)
+          wop += e1.ll;
+          lp += e1.ll;
+          const uint32_t src = wop - e1.off;
+          const uint32_t span = e1.ml < e1.off ? e1.ml : e1.off;
+          if (src + span > fenced) {
+            __syncthreads();  // (uniform: every lane runs the same batch) earlier stores before the match loads
+            fenced = wop;
+          }
+          if (e1.off >= e1.ml) wave_copy(o + wop, o + src, e1.ml, lane);
+          else wave_pattern(o + wop, e1.off, e1.ml, lane);  // overlapping: the last `off` bytes repeat
+          wop += e1.ml;
+        }
+        done += (uint32_t)c;
+        st = sh_st;
+        __syncthreads();  // the batch may be refilled; the stores above are visible
+        fenced = wop;
+        if (st) break;
+      }
+      if (st) break;
+      // trailing literals
+      const uint32_t rest = regen - lp;
+      if (rest > out_n - wop || wop + rest - op > kBlockMax) {
+        st = rest > out_n - wop ? kErrOutput : kErrBlockSize;
+        break;
+      }
+      wave_copy(o + wop, lit + lp, rest, lane);
+      op = wop + rest;
+      ip += bs;
+    }
+    __syncthreads();  // this block's output is visible to the next block's matches
+    if (last) break;
+  }
+  if (!st && op != out_n) st = kErrOutput;
+  if (!st && ip != n) st = kErrTruncated;
+  if (!st && shuf) {
+    __syncthreads();
+    wave_unshuffle(d, o, out_n, lane);
+  }
+  if (lane == 0) a.status[blockIdx.x] = st;
+}
+
+}  // namespace zdec
+}  // namespace dsx
+
+#endif  // DSX_ZDEC_KERNELS_H

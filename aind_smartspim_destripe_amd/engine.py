@@ -21,6 +21,14 @@ DSX_WAVELET_DB3 = 3
 DSX_WAVELET_BANK = 0  # filter bank handed over with dsx_set_wavelet
 STAGE_APPROX, STAGE_DETAIL = 0, 1
 STREAM_COMPUTE, STREAM_UPLOAD, STREAM_DOWNLOAD = 0, 1, 2
+
+# Blosc block tasks of the device decoder (csrc/dsx_zstd_dec.h DecTask): kinds, the un-shuffle flag, routes per chunk
+TASK_FILL, TASK_COPY, TASK_STORED, TASK_ZSTD = 0, 1, 2, 3
+TASK_SHUFFLE = 0x100
+ROUTE_DEVICE, ROUTE_HOST, ROUTE_FILL = 0, 1, 2
+TASK_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<u4"), ("dst_len", "<u4"), ("kind", "<u4"),
+                       ("chunk", "<u4")])  # fmt: skip
+
 COMM_ID_BYTES = 128
 _ERRORS = {-1: "DSX_EINVAL", -2: "DSX_ENOPLAN", -3: "DSX_EHIP", -4: "DSX_ENOMEM", -5: "DSX_ELIMIT",
            -6: "DSX_ECOMM", -7: "DSX_EIO", -8: "DSX_EVALUE"}  # fmt: skip
@@ -40,7 +48,20 @@ EXPORTED_SYMBOLS = [
     "dsx_io_read_chunks", "dsx_io_write_chunks", "dsx_io_write_chunks_blosc", "dsx_blosc_decode", "dsx_blosc_encode",
     "dsx_png_unfilter", "dsx_plan_streaks", "dsx_get_streaks_threshold",
     "dsx_blosc_encode_device", "dsx_blosc_encode_ref",
+    "dsx_io_read_frames", "dsx_blosc_decode_device", "dsx_blosc_decode_ref",
 ]  # fmt: skip
+
+
+def frame_tasks_per_chunk(chunk_bytes):
+    """Most tasks one chunk may take (``csrc/dsx_io.h frame_tasks_per_chunk``)."""
+    return int(chunk_bytes) // 8192 + 1
+
+
+def decode_task(src, dst, src_len, dst_len, kind, chunk=0):
+    """One task as a ``TASK_DTYPE`` array of length 1 (tests, tools)."""
+    t = np.zeros(1, TASK_DTYPE)
+    t[0] = (src, dst, src_len, dst_len, kind, chunk)
+    return t
 
 
 class DsxError(RuntimeError):
@@ -172,6 +193,11 @@ def load_library(path=None):
                                      ctypes.POINTER(ctypes.c_size_t)]  # fmt: skip
     lib.dsx_blosc_encode_device.argtypes = [vp, vp, i32, ctypes.c_size_t, i32, i32, vp, vp]
     lib.dsx_blosc_encode_ref.argtypes = [vp, i32, ctypes.c_size_t, i32, i32, vp, vp]
+    lib.dsx_io_read_frames.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), i32, ctypes.c_size_t, i32, ctypes.c_uint16,
+                                       vp, ctypes.c_size_t, vp, i32, ctypes.POINTER(ctypes.c_size_t),
+                                       ctypes.POINTER(i32), vp]  # fmt: skip
+    lib.dsx_blosc_decode_device.argtypes = [vp, vp, ctypes.c_size_t, vp, i32, vp, ctypes.c_size_t, vp]
+    lib.dsx_blosc_decode_ref.argtypes = [vp, ctypes.c_size_t, vp, i32, vp, ctypes.c_size_t, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("dsx_destroy", "dsx_last_error"):
@@ -467,6 +493,15 @@ class DestripeEngine:
         ptr = d_ptr.ptr if isinstance(d_ptr, DeviceBuffer) else d_ptr
         self._check(self._lib.dsx_comm_broadcast(self._ctx, ctypes.c_void_p(ptr), int(nbytes), int(root)))
 
+    def blosc_decode_device(self, d_packed, packed_bytes, d_tasks, n_tasks, d_out, d_status, out_bytes=None):
+        """The tasks of :meth:`io_read_frames` (device buffers: packed frames, ``TASK_DTYPE`` table) decoded into
+        ``d_out``; ``d_status`` receives one int32 per task (0 = exact output).  Asynchronous on the engine stream."""
+        self._check(self._lib.dsx_blosc_decode_device(self._ctx, ctypes.c_void_p(d_packed.ptr), int(packed_bytes),
+                                                      ctypes.c_void_p(d_tasks.ptr), int(n_tasks),
+                                                      ctypes.c_void_p(d_out.ptr),
+                                                      int(d_out.nbytes if out_bytes is None else out_bytes),
+                                                      ctypes.c_void_p(d_status.ptr)))  # fmt: skip
+
     def comm_allreduce(self, values, op="sum"):
         """All-reduce of a few host doubles over the ranks (also a barrier): op sum / max / min."""
         v = (ctypes.c_double * len(values))(*[float(x) for x in values])
@@ -519,6 +554,14 @@ class DestripeEngine:
                                                             int(typesize), 1 if shuffle else 0))  # fmt: skip
             return
         self._check(self._lib.dsx_io_write_chunks(self._ctx, cp, dp, nb, n, int(threads), int(zlib_level)))
+
+    def io_read_frames(self, paths, chunk_bytes, packed, tasks, threads=16, fill_value=0, routes=None):
+        """Chunk files ``paths[i]`` (Blosc) -> frames packed into the uint8 array ``packed`` and Blosc block tasks
+        into the ``TASK_DTYPE`` array ``tasks`` (``dsx_io_read_frames``); chunk i decodes to bytes
+        ``[i * chunk_bytes, (i + 1) * chunk_bytes)``.  ``routes``: optional uint8 array of ``len(paths)`` (``ROUTE_*``).
+        Returns ``(packed_bytes, n_tasks)``."""
+        return _io_read_frames(self._lib, self._ctx, paths, chunk_bytes, packed, tasks, threads, fill_value, routes,
+                               self._check)  # fmt: skip
 
     def event_record(self, slot, stream):
         self._check(self._lib.dsx_event_record(self._ctx, int(slot), int(stream)))
@@ -657,3 +700,50 @@ def blosc_encode_ref(chunks, clevel=3):
     if rc != 0:
         raise DsxError(rc, (lib.dsx_last_error(None) or b"blosc_encode_ref failed").decode())
     return frames[: offsets[-1]].tobytes(), offsets
+
+
+def _io_read_frames(lib, ctx, paths, chunk_bytes, packed, tasks, threads, fill_value, routes, check):
+    n = len(paths)
+    assert packed.dtype == np.uint8 and packed.flags["C_CONTIGUOUS"] and tasks.dtype == TASK_DTYPE
+    if routes is not None:
+        assert routes.dtype == np.uint8 and routes.size >= n
+    cp = (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths])
+    pb, nt = ctypes.c_size_t(0), ctypes.c_int32(0)
+    check(lib.dsx_io_read_frames(ctx, cp, n, int(chunk_bytes), int(threads), int(fill_value),
+                                 packed.ctypes.data_as(ctypes.c_void_p), packed.nbytes,
+                                 tasks.ctypes.data_as(ctypes.c_void_p), int(tasks.size), ctypes.byref(pb),
+                                 ctypes.byref(nt), routes.ctypes.data_as(ctypes.c_void_p) if routes is not None else None))  # fmt: skip
+    return int(pb.value), int(nt.value)
+
+
+def io_read_frames(paths, chunk_bytes, threads=4, fill_value=0):
+    """:meth:`DestripeEngine.io_read_frames` without an engine, into fresh buffers: ``(packed, tasks, routes)`` trimmed
+    to what was read."""
+    lib = load_library()
+    n = len(paths)
+    packed = np.empty(n * (int(chunk_bytes) + 16) + 1, np.uint8)
+    tasks = np.zeros(n * frame_tasks_per_chunk(chunk_bytes), TASK_DTYPE)
+    routes = np.zeros(n, np.uint8)
+
+    def check(rc):
+        if rc != 0:
+            raise DsxError(rc, (lib.dsx_last_error(None) or b"io_read_frames failed").decode())
+
+    pb, nt = _io_read_frames(lib, None, paths, chunk_bytes, packed, tasks, threads, fill_value, routes, check)
+    return packed[:pb], tasks[:nt], routes
+
+
+def blosc_decode_ref(packed, tasks, out_bytes):
+    """Host build of the device decoder (``dsx_blosc_decode_ref``): ``packed`` uint8 array, ``tasks`` ``TASK_DTYPE``
+    array -> ``(out: uint8 [out_bytes], status: int32 per task)``, byte-identical to ``Engine.blosc_decode_device``."""
+    lib = load_library()
+    p = np.ascontiguousarray(packed, np.uint8)
+    t = np.ascontiguousarray(tasks, TASK_DTYPE)
+    out = np.zeros(int(out_bytes), np.uint8)
+    status = np.zeros(len(t), np.int32)
+    rc = lib.dsx_blosc_decode_ref(p.ctypes.data_as(ctypes.c_void_p), p.nbytes, t.ctypes.data_as(ctypes.c_void_p),
+                                  len(t), out.ctypes.data_as(ctypes.c_void_p), out.nbytes,
+                                  status.ctypes.data_as(ctypes.c_void_p))  # fmt: skip
+    if rc != 0:
+        raise DsxError(rc, (lib.dsx_last_error(None) or b"blosc_decode_ref failed").decode())
+    return out, status

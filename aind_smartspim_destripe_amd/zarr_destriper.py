@@ -37,6 +37,7 @@ from pathlib import Path
 
 import numpy as np
 
+from . import engine as engine_mod
 from . import filtering as fl
 from .distributed import z_shard
 from . import mini_tiff as tif
@@ -269,11 +270,17 @@ class _DeviceBlocks:
     With ``device_codec`` the output bricks are Blosc-zstd frames before they leave the device
     (``dsx_blosc_encode_device`` on the compute stream, after ``planes_to_bricks``): the download stream brings back
     the frame offsets, then only the packed frames, and the I/O threads write each byte range as it is.
+
+    With ``device_decode`` the input chunks are decoded on the device: the I/O threads only read the files and pack
+    the Blosc frames back to back with one task per Blosc block (``dsx_io_read_frames``; frames the device does not
+    take are decoded there and shipped as copies), the upload stream brings the packed frames and the task table, and
+    ``dsx_blosc_decode_device`` fills the input bricks on the compute stream before ``bricks_to_planes``.  Its
+    per-task statuses come back on the compute stream and are checked before the block's output reaches the writers.
     """
 
     N_BUF = 2
 
-    def __init__(self, eng, src, dst, zyx, block_z, io_threads, device_codec=False):
+    def __init__(self, eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False):
         self.eng, self.src, self.dst, self.zyx, self.block_z = eng, src, dst, zyx, block_z
         self.ci, self.co = tuple(src.chunks[-3:]), tuple(dst.chunks[-3:])
         _, H, W = zyx
@@ -284,9 +291,30 @@ class _DeviceBlocks:
         self.out_brick = int(np.prod(self.co))
         in_bytes = int(np.prod(self.gi)) * self.in_brick * 2
         out_bytes = int(np.prod(self.go)) * self.out_brick * 2
-        self.h_in = [eng.alloc_host(in_bytes) for _ in range(self.N_BUF)]
+        self.device_decode = bool(device_decode)
+        self.h_in, self.stage_in = [], []
+        self.h_packed, self.h_tasks, self.h_status, self.d_packed, self.d_tasks, self.d_status = [], [], [], [], [], []
+        if self.device_decode:  # packed frames + task table replace the decompressed staging
+            n_in = int(np.prod(self.gi))
+            cap = n_in * (self.in_brick * 2 + 16)
+            n_tasks = n_in * engine_mod.frame_tasks_per_chunk(self.in_brick * 2)
+            self.h_packed = [eng.alloc_host(cap) for _ in range(self.N_BUF)]
+            self.h_tasks = [eng.alloc_host(n_tasks * engine_mod.TASK_DTYPE.itemsize) for _ in range(self.N_BUF)]
+            self.h_status = [eng.alloc_host(4 * n_tasks) for _ in range(self.N_BUF)]
+            self.d_packed = [eng.alloc(cap) for _ in range(self.N_BUF)]
+            self.d_tasks = [eng.alloc(n_tasks * engine_mod.TASK_DTYPE.itemsize) for _ in range(self.N_BUF)]
+            self.d_status = [eng.alloc(4 * n_tasks) for _ in range(self.N_BUF)]
+            self.packed = [h.array((cap,), np.uint8) for h in self.h_packed]
+            self.tasks = [h.array((n_tasks,), engine_mod.TASK_DTYPE) for h in self.h_tasks]
+            self.status = [h.array((n_tasks,), np.int32) for h in self.h_status]
+            self.read_info = [None] * self.N_BUF  # (packed bytes, tasks, chunk paths) of the block read into buffer k
+            # (tasks, chunk of each task, chunk paths) of the block SUBMITTED from buffer k: the read of block b + 2
+            # refills the task table and read_info of buffer k before block b's statuses are checked
+            self.decode_info = [None] * self.N_BUF
+        else:
+            self.h_in = [eng.alloc_host(in_bytes) for _ in range(self.N_BUF)]
+            self.stage_in = [h.array(self.gi + (self.in_brick,), np.uint16) for h in self.h_in]
         self.h_out = [eng.alloc_host(out_bytes) for _ in range(self.N_BUF)]
-        self.stage_in = [h.array(self.gi + (self.in_brick,), np.uint16) for h in self.h_in]
         self.stage_out = [h.array(self.go + (self.out_brick,), np.uint16) for h in self.h_out]
         self.d_bricks_in = [eng.alloc(in_bytes) for _ in range(self.N_BUF)]
         self.d_bricks_out = [eng.alloc(out_bytes) for _ in range(self.N_BUF)]
@@ -304,11 +332,12 @@ class _DeviceBlocks:
             self.frames = [h.array((cap,), np.uint8) for h in self.h_frames]
             self.offsets = [h.array((n_chunks + 1,), np.int64) for h in self.h_offsets]
         self.io_threads = int(io_threads)
-        self.timing = {"read_s": 0.0, "write_s": 0.0}
+        self.timing = _new_timing()
 
     def close(self):
         for b in (self.d_bricks_in + self.d_bricks_out + [self.d_planes, self.d_out] + self.h_in + self.h_out
-                  + self.d_frames + self.d_offsets + self.h_frames + self.h_offsets):
+                  + self.d_frames + self.d_offsets + self.h_frames + self.h_offsets + self.h_packed + self.h_tasks
+                  + self.h_status + self.d_packed + self.d_tasks + self.d_status):
             b.free()
 
     # -- host stages (I/O threads) -------------------------------------------------------------
@@ -319,6 +348,13 @@ class _DeviceBlocks:
         bz0, zoff = divmod(z0, self.ci[0])
         nbz = -(-(zoff + (z1 - z0)) // self.ci[0])
         idx = list(itertools.product(range(nbz), range(self.gi[1]), range(self.gi[2])))
+        if self.device_decode:
+            paths = [self.src._chunk_path(lead + (bz0 + i[0], i[1], i[2])) for i in idx]
+            pb, nt = self.eng.io_read_frames(paths, self.in_brick * 2, self.packed[k], self.tasks[k],
+                                             threads=self.io_threads, fill_value=int(self.src.fill_value))  # fmt: skip
+            self.read_info[k] = (pb, nt, paths)
+            self.timing["read_s"] += time.perf_counter() - t0
+            return nbz, zoff
         stage = self.stage_in[k]
         self.eng.io_read_chunks([self.src._chunk_path(lead + (bz0 + i[0], i[1], i[2])) for i in idx],
                                 [stage[i] for i in idx], threads=self.io_threads,
@@ -350,15 +386,40 @@ class _DeviceBlocks:
 
     # -- device stage (asynchronous) -----------------------------------------------------------
     def _submit(self, z0, z1, k, nbz, zoff):
-        from .engine import STREAM_COMPUTE as C, STREAM_DOWNLOAD as D, STREAM_UPLOAD as U
+        self._submit_in(z0, z1, k, nbz, zoff)
+        self._submit_out(z0, z1, k)
+
+    def _submit_in(self, z0, z1, k, nbz, zoff):
+        """Upload(b) and compute(b) up to the filter: nothing here touches the output buffers of block b - 2."""
+        from .engine import STREAM_COMPUTE as C, STREAM_UPLOAD as U
 
         eng, (_, H, W), Z = self.eng, self.zyx, z1 - z0
-        eng.copy_h2d_async(self.d_bricks_in[k], self.stage_in[k][:nbz], U)
+        if self.device_decode:
+            pb, nt, paths = self.read_info[k]
+            self.decode_info[k] = (nt, self.tasks[k]["chunk"][:nt].copy(), paths)
+            if pb:
+                eng.copy_h2d_async(self.d_packed[k], self.packed[k][:pb], U)
+            if nt:
+                eng.copy_h2d_async(self.d_tasks[k], self.tasks[k][:nt], U)
+            self.timing["upload_bytes"] += pb + nt * engine_mod.TASK_DTYPE.itemsize
+        else:
+            eng.copy_h2d_async(self.d_bricks_in[k], self.stage_in[k][:nbz], U)
+            self.timing["upload_bytes"] += self.stage_in[k][:nbz].nbytes
         eng.event_record(k, U)            # pinned input buffer k may be refilled once this has passed
         eng.stream_wait(C, U)             # compute(b) after upload(b)
         eng.stream_wait(U, C)             # uploads from now on after compute(b - 1): they refill its buffer
+        if self.device_decode:            # the bricks from the frames; the statuses come back in stream order
+            eng.blosc_decode_device(self.d_packed[k], pb, self.d_tasks[k], nt, self.d_bricks_in[k], self.d_status[k])
+            if nt:
+                eng.copy_d2h_async(self.status[k][:nt], self.d_status[k], C)
         eng.bricks_to_planes(self.d_bricks_in[k], self.d_planes, (Z, H, W), self.ci, zoff)
         eng.run_device(self.d_planes, np.uint16, Z, self.d_out, np.uint16, None)
+
+    def _submit_out(self, z0, z1, k):
+        """Compute(b) from planes_to_bricks on, and download(b): once pinned output buffer k has been written out."""
+        from .engine import STREAM_COMPUTE as C, STREAM_DOWNLOAD as D
+
+        eng, (_, H, W), Z = self.eng, self.zyx, z1 - z0
         eng.stream_wait(C, D)             # (the wait lands before planes_to_bricks:) after download(b - 2 .. b - 1)
         eng.planes_to_bricks(self.d_out, self.d_bricks_out[k], (Z, H, W), self.co, 0)
         nbo = -(-Z // self.co[0])
@@ -372,6 +433,7 @@ class _DeviceBlocks:
             return
         eng.stream_wait(D, C)             # download(b) after compute(b)
         eng.copy_d2h_async(self.stage_out[k][:nbo], self.d_bricks_out[k], D)
+        self.timing["download_bytes"] += self.stage_out[k][:nbo].nbytes
         eng.event_record(self.N_BUF + k, D)  # pinned output buffer k holds block b once this has passed
 
     def _fetch_frames(self, z0, z1, k):
@@ -380,10 +442,23 @@ class _DeviceBlocks:
 
         n_chunks = -(-(z1 - z0) // self.co[0]) * self.go[1] * self.go[2]
         total = int(self.offsets[k][n_chunks])
+        self.timing["download_bytes"] += total + 8 * (n_chunks + 1)
         if total:
             self.eng.copy_d2h_async(self.frames[k][:total], self.d_frames[k], D)
         self.eng.event_record(self.N_BUF + k, D)
         self.eng.event_sync(self.N_BUF + k)
+
+    def _check_decode(self, k):
+        """(device decode; block in buffer k has been computed) A malformed frame raises as the host reader would."""
+        if not self.device_decode:
+            return
+        nt, chunk, paths = self.decode_info[k]
+        st = self.status[k][:nt]  # (written on the compute stream: block b + 2 is not submitted yet)
+        bad = np.flatnonzero(st)
+        if bad.size:
+            i = int(bad[0])
+            raise ValueError("blosc: bad zstd stream ({}) [device decode status {}]".format(paths[int(chunk[i])],
+                                                                                             int(st[i])))  # fmt: skip
 
     def run_range(self, z_start, z_stop):
         """All blocks of ``[z_start, z_stop)`` through the pipeline; returns the number of planes."""
@@ -397,20 +472,27 @@ class _DeviceBlocks:
             for b in range(nb):
                 k = b % self.N_BUF
                 nbz, zoff = reads.pop(b).result()
+                if self.device_decode:  # the decode and the filter need not wait for the writers
+                    self._submit_in(*blocks[b], k, nbz, zoff)
                 if b >= self.N_BUF:
                     writes[b - self.N_BUF].result()  # pinned output buffer k has been written out
-                self._submit(*blocks[b], k, nbz, zoff)
+                if self.device_decode:
+                    self._submit_out(*blocks[b], k)
+                else:
+                    self._submit(*blocks[b], k, nbz, zoff)
                 if b + self.N_BUF < nb:
                     self.eng.event_sync(k)  # upload(b) has left pinned input buffer k
                     reads[b + self.N_BUF] = reader.submit(self._read, *blocks[b + self.N_BUF], k)
                 if b >= 1:
                     kp = (b - 1) % self.N_BUF
                     self.eng.event_sync(self.N_BUF + kp)  # download(b - 1) complete
+                    self._check_decode(kp)
                     if self.device_codec:
                         self._fetch_frames(*blocks[b - 1], kp)
                     writes.append(writer.submit(self._write, *blocks[b - 1], kp))
             if nb:
                 self.eng.event_sync(self.N_BUF + (nb - 1) % self.N_BUF)
+                self._check_decode((nb - 1) % self.N_BUF)
                 if self.device_codec:
                     self._fetch_frames(*blocks[nb - 1], (nb - 1) % self.N_BUF)
                 writes.append(writer.submit(self._write, *blocks[nb - 1], (nb - 1) % self.N_BUF))
@@ -426,22 +508,27 @@ LAST_RUN = {}  # what the last destripe_zarr_store call of this process resolved
 _BLOCKS = {}  # one set of staging buffers per process: page-locking 2 GB of host memory costs ~0.4 s per call
 
 
-def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False):
+def _new_timing():
+    return {"read_s": 0.0, "write_s": 0.0, "upload_bytes": 0, "download_bytes": 0}
+
+
+def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False):
     """Staging buffers for this geometry, reused from the previous tile when nothing but the stores changed
     (a channel is tens of tiles of one shape, ``zarr_destriper.py:1231``)."""
-    key = (id(eng), tuple(zyx[1:]), tuple(src.chunks[-3:]), tuple(dst.chunks[-3:]), int(block_z), bool(device_codec))
+    key = (id(eng), tuple(zyx[1:]), tuple(src.chunks[-3:]), tuple(dst.chunks[-3:]), int(block_z), bool(device_codec),
+           bool(device_decode))  # fmt: skip
     cached = _BLOCKS.get("blocks")
     if cached is not None and cached[0] == key and cached[1].eng._ctx is not None:
         blocks = cached[1]
         blocks.src, blocks.dst, blocks.zyx, blocks.io_threads = src, dst, zyx, int(io_threads)
-        blocks.timing = {"read_s": 0.0, "write_s": 0.0}
+        blocks.timing = _new_timing()
         return blocks
     if cached is not None:
         try:
             cached[1].close()
         except Exception:  # the engine of the cached buffers may be gone already
             pass
-    blocks = _DeviceBlocks(eng, src, dst, zyx, block_z, io_threads, device_codec)
+    blocks = _DeviceBlocks(eng, src, dst, zyx, block_z, io_threads, device_codec, device_decode)
     _BLOCKS["blocks"] = (key, blocks)
     return blocks
 
@@ -486,6 +573,7 @@ def destripe_zarr_store(
     group=None,
     *,
     device_codec=False,
+    device_decode=False,
 ):
     """Chunk map of ``destripe_zarr`` (``zarr_destriper.py:909-1211``) over a Zarr-v2 directory store -- the engine-level
     form (explicit configs and ``shadow_correction``); :func:`destripe_zarr` is the entry point with the reference's
@@ -520,6 +608,12 @@ def destripe_zarr_store(
     (``dsx_blosc_encode_device``: Huffman-coded literals, no matches -- about 1.1x the host writer's bytes, any c-blosc
     reader decodes them) and the host only writes finished bytes.  Needs a Blosc-zstd output with byte shuffle and the
     device re-tiling path; anything else raises ``ValueError``.  Off by default.
+
+    ``device_decode``: ``True`` = the input chunks are decoded on the GPU (``dsx_blosc_decode_device``): the I/O
+    threads only read the files, the compressed frames cross the host link, and a zstd decoder fills the input bricks.
+    Frames the device does not take (other inner codecs, bit shuffle, split streams, zstd checksums) are decoded by the
+    I/O threads as before.  Needs a Blosc uint16 input and the device re-tiling path; anything else raises
+    ``ValueError``.  Off by default; works with ``device_codec`` on or off.
     """
     logger = logger or logging.getLogger("dsx.zarr")
     if io_threads is None:
@@ -564,16 +658,24 @@ def destripe_zarr_store(
         if not can or device_retile is False:
             raise ValueError("device_codec needs the device re-tiling path (a uint16 store, even planes and "
                              "output-chunk-aligned z blocks)")  # fmt: skip
+    if device_decode:
+        if src.compressor is None or src.compressor[0] != "blosc" or src.dtype != np.uint16:
+            raise ValueError("device_decode needs a Blosc uint16 input, not {!r} {}".format(src.compressor, src.dtype))
+        if not can or device_retile is False:
+            raise ValueError("device_decode needs the device re-tiling path (a uint16 store, even planes and "
+                             "output-chunk-aligned z blocks)")  # fmt: skip
+    LAST_RUN.update(device_codec=bool(device_codec), device_decode=bool(device_decode))
     if can and device_retile is not False:
         flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
         eng = fl.get_engine(zyx[1:], cells_config, no_cells_config, 2500, flatfield, darkfield,
                             max_batch=min(block_z, 64), device=dev)  # fmt: skip
-        blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec)
+        blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec, device_decode)
         n_planes = blocks.run_range(z0, z1)
         eng.sync()
         dt = time.perf_counter() - t0
         logger.info("rank %d: %d planes z[%d:%d) in %.2f s (device re-tiling%s, overlapped; read %.2f s, write %.2f s)",
-                    rank, n_planes, z0, z1, dt, ", device codec" if device_codec else "", blocks.timing["read_s"],
+                    rank, n_planes, z0, z1, dt, (", device codec" if device_codec else "")
+                    + (", device decode" if device_decode else ""), blocks.timing["read_s"],
                     blocks.timing["write_s"])  # fmt: skip
         return n_planes, dt
     for sc, internal in iter_blocks(zyx, prediction_chunksize, (z0, z1)):
@@ -724,6 +826,7 @@ def destripe_zarr(
     io_threads=None,
     group=None,
     device_codec=False,
+    device_decode=False,
 ):
     """``destripe_zarr`` of the reference (``zarr_destriper.py:909-1211``) with its 14 parameters, on the GPU chunk map.
 
@@ -748,7 +851,7 @@ def destripe_zarr(
 
     Keyword-only extras (the engine's): ``rank`` / ``world_size`` / ``group`` (one process per GPU, chunk-aligned
     z-ranges; with a ``distributed.RankGroup`` rank 0 alone reads the dark plane and broadcasts it), ``device``,
-    ``compressor`` / ``output_chunks`` of the output, ``n_levels``, ``device_retile``, ``io_threads``, ``device_codec``
+    ``compressor`` / ``output_chunks`` of the output, ``n_levels``, ``device_retile``, ``io_threads``, ``device_codec``, ``device_decode``
     (level 0 encoded on the GPU, :func:`destripe_zarr_store`).
     Returns ``(planes processed by this rank, seconds)``.
     """
@@ -820,6 +923,7 @@ def destripe_zarr(
         tile_name=dataset_name,
         group=group,
         device_codec=device_codec,
+        device_decode=device_decode,
     )
     if group is not None and world_size > 1:
         group.barrier()  # level 0 of this tile is complete on every rank: the pyramid may read it
@@ -867,6 +971,7 @@ def destripe_channel(
     io_threads=None,
     device_retile=None,
     device_codec=False,
+    device_decode=False,
 ):
     """``destripe_channel`` of the reference (``zarr_destriper.py:1214-1267``), same eight parameters (the reference's
     caller passes them by keyword, ``run_capsule.py:394-403``), wired to the GPU chunk map.
@@ -880,7 +985,7 @@ def destripe_channel(
 
     Keyword-only extras: ``rank`` / ``world_size`` / ``group`` / ``device`` (one process per GPU), output codec and
     chunks, ``multiscale`` (the reference hard-codes ``"0"``), ``prediction_chunksize`` (the reference hard-codes the
-    production tile, ``(64, 1600, 2000)``), ``io_threads``, ``device_retile``, ``device_codec``.  ``world_size > 1`` needs ``group`` (anything with
+    production tile, ``(64, 1600, 2000)``), ``io_threads``, ``device_retile``, ``device_codec``, ``device_decode``.  ``world_size > 1`` needs ``group`` (anything with
     ``barrier()``): the pyramid of a tile may only be computed once EVERY rank has written its z-range.  With a
     ``distributed.RankGroup`` rank 0 alone reads the flat and dark planes of a tile and broadcasts them (RCCL).
     """
@@ -930,6 +1035,7 @@ def destripe_channel(
             device_retile=device_retile,
             group=group,
             device_codec=device_codec,
+            device_decode=device_decode,
         )
         done[tile_path.name] = n
     return done

@@ -217,6 +217,27 @@ int dsx_blosc_encode_device(dsx_ctx* ctx, const void* d_src, int n_chunks, size_
 int dsx_blosc_encode_ref(const void* src, int n_chunks, size_t chunk_bytes, int typesize, int clevel, void* frames,
                          int64_t* offsets);
 
+/* Blosc-zstd chunks decoded on the device (csrc/dsx_zstd_dec.h, csrc/dsx_zdec_kernels.h).
+ * dsx_io_read_frames: n chunk files -> their frames packed back to back into `packed` (host memory, capacity
+ * n * (chunk_bytes + 16)) and one 32-byte task per Blosc block into `tasks` (capacity n * (chunk_bytes / 8192 + 1)):
+ * {uint64 src, uint64 dst, uint32 src_len, uint32 dst_len, uint32 kind, uint32 chunk}; chunk i decodes to bytes
+ * [i * chunk_bytes, (i + 1) * chunk_bytes) of the output.  The device takes frames of typesize 2, no or byte shuffle,
+ * zstd inside, unsplit streams, at most chunk_bytes / 8192 + 1 Blosc blocks (a zstd frame or a stored stream per
+ * block), memcpyed frames and missing files (fill); any other frame is decoded on the I/O threads (dsx_blosc_decode)
+ * and shipped as a copy.  routes (optional, n bytes): 0 device, 1 host, 2 fill.  Synchronous, no GPU involved (ctx may
+ * be NULL).
+ * dsx_blosc_decode_device: the tasks into d_out (out_bytes), asynchronous on the context stream; d_status receives
+ * one int32 per task (0, or a dsx_zstd_dec.h Status for a malformed frame).  The context keeps a work buffer of
+ * out_bytes.
+ * dsx_blosc_decode_ref: the host build of the same decoder, byte-identical output (host pointers, synchronous). */
+int dsx_io_read_frames(dsx_ctx* ctx, const char* const* paths, int n, size_t chunk_bytes, int threads,
+                       uint16_t fill_value, void* packed, size_t packed_capacity, void* tasks, int task_capacity,
+                       size_t* packed_bytes, int* n_tasks, uint8_t* routes);
+int dsx_blosc_decode_device(dsx_ctx* ctx, const void* d_packed, size_t packed_bytes, const void* d_tasks, int n_tasks,
+                            void* d_out, size_t out_bytes, int32_t* d_status);
+int dsx_blosc_decode_ref(const void* packed, size_t packed_bytes, const void* tasks, int n_tasks, void* out,
+                         size_t out_bytes, int32_t* status);
+
 /* PNG scanline reconstruction for the directory mode's reader (imageio's iio.imread, readers.py:86-87): `height`
  * rows of one filter-type byte + `stride` bytes, un-filtered in place (Sub / Up / Average / Paeth).  Host only.  */
 int dsx_png_unfilter(void* rows, int height, int stride, int bytes_per_pixel);

@@ -4,10 +4,13 @@
 download) into another store.  Prints one JSON line; the roofline of this path is the host link
 (PCIe Gen5 x16, 63 GB/s spec: 16.8 MB per plane both ways -> <= 3.7 k planes/s), not HBM.
 
-    bench_zarr.py N [raw|zlib|blosc] [device-codec]
+    bench_zarr.py N [raw|zlib|blosc] [device-codec] [device-decode]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
-line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block)."""
+line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
+`device-decode` (Blosc only): the input chunks are decoded on the GPU (destripe_zarr_store(device_decode=True)).
+Every line reports the read / write stage times of the timed pass (I/O threads, summed per block), the bytes that
+crossed the host link each way, and the link fraction those bytes make of the run (63 GB/s per direction)."""
 import json, logging, os, shutil, sys, tempfile, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,6 +21,7 @@ logging.basicConfig(level=logging.INFO, stream=sys.stderr)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 codec = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2] != "raw" else None  # None (raw chunks), "zlib" or "blosc" (Blosc-zstd)
 device_codec = "device-codec" in sys.argv[3:]
+device_decode = "device-decode" in sys.argv[3:]
 H = W = 2048
 root = tempfile.mkdtemp(prefix="dsx_zarr_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
@@ -34,8 +38,14 @@ try:
             planes, dt = zd.destripe_zarr_store(os.path.join(root, "in.zarr"), os.path.join(root, "out.zarr"), synth.CELLS_CONFIG,
                                           synth.NO_CELLS_CONFIG, None, prediction_chunksize=(64, H, W),
                                           output_chunks=(1, 1, 64, 128, 128), device=0, device_retile=True, io_threads=16, compressor=codec,
-                                          device_codec=device_codec, **kw)
+                                          device_codec=device_codec, device_decode=device_decode, **kw)
             res[name] = {"planes": planes, "seconds": round(time.perf_counter() - t0, 3)}
+    timing = dict(zd._BLOCKS["blocks"][1].timing)  # the timed (second) pass
+    secs = res["overlapped"]["seconds"]
+    up, down = int(timing["upload_bytes"]), int(timing["download_bytes"])
+    link = {"upload_bytes": up, "download_bytes": down,
+            "upload_GBps": round(up / secs / 1e9, 2), "download_GBps": round(down / secs / 1e9, 2),
+            "frac": round(max(up, down) / secs / 63e9, 3)}
     out = MiniZarrArray.open(os.path.join(root, "out.zarr"))
     chk = int(out[0, 0, 0].astype(np.uint64).sum())
     sizes = {}
@@ -77,10 +87,11 @@ try:
                 except AssertionError as e:
                     verified = False
                     print("oracle mismatch", e, file=sys.stderr)
-    label = (codec or "raw") + (", encoded on the device" if device_codec else "")
+    label = (codec or "raw") + (", encoded on the device" if device_codec else "") + (", decoded on the device" if device_decode else "")
     print(json.dumps({"metric": "2048x2048 uint16 slices/s, Zarr store to Zarr store ({} chunks, tmpfs)".format(label), "value": round(v, 1),
                       "planes": n, "seconds": res["overlapped"]["seconds"], "store_make_s": round(t_make, 1),
                       "roofline": {"bound": "host link", "peak_planes_per_s": 3750, "frac": round(v / 3750.0, 3)},
+                      "read_s": round(timing["read_s"], 3), "write_s": round(timing["write_s"], 3), "host_link": link,
                       "plane0_checksum": chk, "verified": verified, **sizes,
                       "verification": {"planes_bit_identical_to_single_plane_runs": checked,
                                        "planes_against_the_cpu_oracle": oracle_checked, "blocks": blocks}}))
