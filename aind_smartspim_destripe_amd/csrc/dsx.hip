@@ -19,6 +19,7 @@
 #include "../../include/dsx.h"
 #include "dsx_kernels.h"
 #include "dsx_retile.h"
+#include "dsx_pyramid.h"
 #include "dsx_wavelet.h"
 #include "dsx_plan.h"
 #include "dsx_io.h"
@@ -1795,6 +1796,93 @@ int dsx_downsample2_u16(dsx_ctx* ctx, const void* d_src, void* d_dst, int Z, int
   if (vec) hipLaunchKernelGGL(dsx::k_downsample2<true>, grid, dim3(256), 0, use_main(ctx), a);
   else hipLaunchKernelGGL(dsx::k_downsample2<false>, grid, dim3(256), 0, use_main(ctx), a);
   DSX_HIP(hipGetLastError());
+  return DSX_OK;
+}
+
+/* ---- f3 fused into the chunk map: the pyramid levels of one block (dsx_pyramid.h) ---------------------------- */
+namespace {
+// Checks the per-level geometry and fills the kernels' view of it; n_out = levels with a non-empty share.
+const char* pyramid_levels(int Z, int H, int W, int n_levels, const dsx_pyramid_level* levels, void* const* bricks,
+                           dsx::pyr::Level* out, int* n_out) {
+  *n_out = 0;
+  if (Z <= 0 || H <= 0 || W <= 0) return "pyramid: the block must not be empty";
+  if (n_levels < 1 || n_levels > dsx::pyr::kMaxLevels) return "pyramid: n_levels out of range";
+  if (n_levels > 1 && (!levels || !bricks)) return "pyramid: level table is NULL";
+  for (int l = 1; l < n_levels; ++l) {
+    const dsx_pyramid_level& g = levels[l - 1];
+    dsx::pyr::Level& o = out[l - 1];
+    o.Z = dsx::pyr::extent(Z, l); o.H = dsx::pyr::extent(H, l); o.W = dsx::pyr::extent(W, l);
+    if (o.Z <= 0 || o.H <= 0 || o.W <= 0) break;
+    if (!bricks[l - 1]) return "pyramid: brick buffer is NULL";
+    if (g.cz <= 0 || g.cy <= 0 || g.cx <= 0 || g.rows <= 0 || g.z0 < 0) return "pyramid: shapes must be positive";
+    if ((long long)g.z0 + o.Z > (long long)g.rows * g.cz) return "pyramid: the block's share does not fit the chunk rows";
+    o.bricks = (uint16_t*)bricks[l - 1];
+    o.cz = g.cz; o.cy = g.cy; o.cx = g.cx; o.z0 = g.z0;
+    o.nby = (o.H + g.cy - 1) / g.cy; o.nbx = (o.W + g.cx - 1) / g.cx;
+    *n_out = l;
+  }
+  return nullptr;
+}
+}  // namespace
+
+int dsx_pyramid_work_bytes(int Z, int H, int W, int n_levels, size_t* bytes) {
+  if (!bytes || Z < 0 || H < 0 || W < 0 || n_levels < 1 || n_levels > dsx::pyr::kMaxLevels) return DSX_EINVAL;
+  *bytes = dsx::pyr::work_bytes(Z, H, W, n_levels);
+  return DSX_OK;
+}
+
+int dsx_pyramid_block_ref(const void* planes, int Z, int H, int W, int n_levels, const dsx_pyramid_level* levels,
+                          void* const* bricks) {
+  if (!planes) return DSX_EINVAL;
+  dsx::pyr::Level lv[dsx::pyr::kMaxLevels] = {};
+  int n = 0;
+  if (const char* e = pyramid_levels(Z, H, W, n_levels, levels, bricks, lv, &n)) return fail(nullptr, DSX_EINVAL, e);
+  for (int l = 1; l <= n; ++l)
+    if (levels[l - 1].zero) memset(lv[l - 1].bricks, 0, (size_t)levels[l - 1].rows * dsx::pyr::row_elems(lv[l - 1]) * 2);
+  dsx::pyr::pyramid_block_host((const uint16_t*)planes, H, W, n + 1, lv);
+  return DSX_OK;
+}
+
+int dsx_pyramid_block_u16(dsx_ctx* ctx, const void* d_planes, int Z, int H, int W, int n_levels,
+                          const dsx_pyramid_level* levels, void* const* d_bricks, void* d_work, size_t work_bytes) {
+  if (!ctx || !d_planes) return DSX_EINVAL;
+  namespace p = dsx::pyr;
+  p::Level lv[p::kMaxLevels] = {};
+  int n = 0;
+  if (const char* e = pyramid_levels(Z, H, W, n_levels, levels, d_bricks, lv, &n)) return fail(ctx, DSX_EINVAL, e);
+  if (n == 0) return DSX_OK;
+  if (n > 2 && (!d_work || work_bytes < p::work_bytes(Z, H, W, n + 1) || (uintptr_t)d_work % 16))
+    return fail(ctx, DSX_EINVAL, "pyramid: the work buffer is smaller than dsx_pyramid_work_bytes");
+  if ((lv[0].H + 1) / 2 > 65535 || (lv[0].Z + 1) / 2 > 65535)
+    return fail(ctx, DSX_ELIMIT, "pyramid: more than 65535 row or plane groups per call");
+  DSX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = use_main(ctx);
+  for (int l = 1; l <= n; ++l)
+    if (levels[l - 1].zero)
+      DSX_HIP(hipMemsetAsync(lv[l - 1].bricks, 0, (size_t)levels[l - 1].rows * p::row_elems(lv[l - 1]) * 2, s));
+  dsx::PyrBlockArgs a = {};
+  a.src = (const uint16_t*)d_planes; a.Z = Z; a.H = H; a.W = W;
+  a.l1 = lv[0];
+  if (n >= 2) a.l2 = lv[1];
+  uint8_t* work = (uint8_t*)d_work;
+  if (n > 2) a.dense2 = (uint16_t*)work;
+  const bool vec = W % 8 == 0 && a.l1.cx % 4 == 0 && (n < 2 || a.l2.cx % 2 == 0) && (uintptr_t)d_planes % 16 == 0 &&
+                   (uintptr_t)a.l1.bricks % 8 == 0 && (uintptr_t)a.l2.bricks % 4 == 0;
+  const dim3 grid(((a.l1.W + 3) / 4 + 255) / 256, (a.l1.H + 1) / 2, (a.l1.Z + 1) / 2);
+  if (vec) hipLaunchKernelGGL(dsx::k_pyramid_block<true>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(dsx::k_pyramid_block<false>, grid, dim3(256), 0, s, a);
+  DSX_HIP(hipGetLastError());
+  for (int l = 3; l <= n; ++l) {  // dense level l - 1 (in the work buffer) -> level l
+    dsx::PyrLevelArgs b = {};
+    const p::Level& prev = lv[l - 2];
+    b.src = (const uint16_t*)work; b.Y = prev.H; b.X = prev.W;
+    work += ((size_t)prev.Z * prev.H * prev.W * 2 + 15) & ~(size_t)15;
+    b.out = lv[l - 1];
+    b.dense = l < n ? (uint16_t*)work : nullptr;
+    const dim3 g((b.out.W + 255) / 256, b.out.H, b.out.Z);
+    hipLaunchKernelGGL(dsx::k_pyramid_level, g, dim3(256), 0, s, b);
+    DSX_HIP(hipGetLastError());
+  }
   return DSX_OK;
 }
 

@@ -1,0 +1,92 @@
+// dsx_pyramid_geom.h -- window arithmetic and brick addressing of the fused pyramid, shared by the device kernels
+// (dsx_pyramid.h) and the host build of the same computation (pyramid_block_host below).  Plain C++.
+//
+// A block is a dense [Z, H, W] uint16 stack whose first plane lies at a multiple of 2^(levels - 1) in the volume, so
+// every 2 x 2 x 2 window of every level lies inside it.  Level l of the block is (Z >> l, H >> l, W >> l): trailing odd
+// planes / rows / columns are cropped per level, never averaged.  Every level is the truncated mean of the TRUNCATED
+// previous level (compute_pyramid, zarr_destriper.py:365-407: windowed_mean + preserve_dtype), not of level 0.
+#ifndef DSX_PYRAMID_GEOM_H
+#define DSX_PYRAMID_GEOM_H
+
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#if defined(__HIP__) || defined(__CUDACC__)
+#define DSX_PHD __host__ __device__
+#else
+#define DSX_PHD
+#endif
+
+namespace dsx {
+namespace pyr {
+
+constexpr int kMaxLevels = 16;  // level 0 included
+
+// One level's share of a block and where it goes: brick order [rows][nby][nbx][cz][cy][cx], plane 0 of the block's
+// level at plane z0 of the brick grid.
+struct Level {
+  uint16_t* bricks;
+  int Z, H, W;     // extent of this level of the block
+  int cz, cy, cx;  // chunk shape of the level (already clamped to the level's volume)
+  int nby, nbx;    // bricks per axis (ceil)
+  int z0;
+};
+
+DSX_PHD inline int extent(int n, int level) { return level < 31 ? n >> level : 0; }
+DSX_PHD inline uint32_t mean8(uint32_t sum_of_8) { return sum_of_8 >> 3; }  // float64 mean, astype(uint16): floor
+
+DSX_PHD inline size_t brick_offset(const Level& g, int z, int y, int x) {
+  const int bz = z / g.cz, iz = z - bz * g.cz;
+  const int by = y / g.cy, iy = y - by * g.cy;
+  const int bx = x / g.cx, ix = x - bx * g.cx;
+  const size_t brick = ((size_t)bz * g.nby + by) * g.nbx + bx;
+  return ((brick * g.cz + iz) * g.cy + iy) * (size_t)g.cx + ix;
+}
+
+inline size_t row_elems(const Level& g) { return (size_t)g.nby * g.nbx * g.cz * g.cy * g.cx; }
+
+// Dense levels 2 .. n_levels - 2 of a block (what the levels >= 3 are computed from), each padded to 16 bytes.
+inline size_t work_bytes(int Z, int H, int W, int n_levels) {
+  size_t total = 0;
+  for (int l = 2; l <= n_levels - 2; ++l) {
+    const size_t n = (size_t)extent(Z, l) * extent(H, l) * extent(W, l) * sizeof(uint16_t);
+    total += (n + 15) & ~(size_t)15;
+  }
+  return total;
+}
+
+// The host build: level by level, every level dense first, then scattered into its bricks.
+inline void pyramid_block_host(const uint16_t* planes, int H, int W, int n_levels, const Level* levels) {
+  std::vector<uint16_t> prev, next;
+  const uint16_t* src = planes;
+  int sy = H, sx = W;
+  for (int l = 1; l < n_levels; ++l) {
+    const Level& g = levels[l - 1];
+    if (g.Z <= 0 || g.H <= 0 || g.W <= 0) break;
+    next.assign((size_t)g.Z * g.H * g.W, 0);
+    for (int z = 0; z < g.Z; ++z)
+      for (int y = 0; y < g.H; ++y)
+        for (int x = 0; x < g.W; ++x) {
+          uint32_t s = 0;
+          for (int dz = 0; dz < 2; ++dz)
+            for (int dy = 0; dy < 2; ++dy) {
+              const uint16_t* p = src + ((size_t)(2 * z + dz) * sy + (2 * y + dy)) * sx + 2 * x;
+              s += (uint32_t)p[0] + p[1];
+            }
+          const uint16_t v = (uint16_t)mean8(s);
+          next[((size_t)z * g.H + y) * g.W + x] = v;
+          g.bricks[brick_offset(g, g.z0 + z, y, x)] = v;
+        }
+    prev.swap(next);
+    src = prev.data();
+    sy = g.H; sx = g.W;
+  }
+}
+
+}  // namespace pyr
+}  // namespace dsx
+
+#endif  // DSX_PYRAMID_GEOM_H

@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "dsx_png_unfilter", "dsx_plan_streaks", "dsx_get_streaks_threshold",
     "dsx_blosc_encode_device", "dsx_blosc_encode_ref",
     "dsx_io_read_frames", "dsx_blosc_decode_device", "dsx_blosc_decode_ref",
+    "dsx_pyramid_work_bytes", "dsx_pyramid_block_u16", "dsx_pyramid_block_ref",
 ]  # fmt: skip
 
 
@@ -92,6 +93,10 @@ class _StreaksCfg(ctypes.Structure):
         ("otsu", ctypes.c_int32),
         ("threshold", ctypes.c_float),
     ]
+
+
+class _PyramidLevel(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("cz", "cy", "cx", "rows", "z0", "zero")]
 
 
 class _PlanInfo(ctypes.Structure):
@@ -198,6 +203,10 @@ def load_library(path=None):
                                        ctypes.POINTER(i32), vp]  # fmt: skip
     lib.dsx_blosc_decode_device.argtypes = [vp, vp, ctypes.c_size_t, vp, i32, vp, ctypes.c_size_t, vp]
     lib.dsx_blosc_decode_ref.argtypes = [vp, ctypes.c_size_t, vp, i32, vp, ctypes.c_size_t, vp]
+    lib.dsx_pyramid_work_bytes.argtypes = [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    lib.dsx_pyramid_block_u16.argtypes = [vp, vp, i32, i32, i32, i32, ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp),
+                                          vp, ctypes.c_size_t]  # fmt: skip
+    lib.dsx_pyramid_block_ref.argtypes = [vp, i32, i32, i32, i32, ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("dsx_destroy", "dsx_last_error"):
@@ -604,6 +613,26 @@ class DestripeEngine:
             raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
         self._check(rc)
 
+    def pyramid_block(self, d_planes, zyx, chunks, d_bricks, z0s=None, zero=None, rows=None, d_work=None):
+        """Pyramid levels ``1 .. len(chunks)`` of the dense uint16 block ``d_planes`` (``zyx``), each stored in chunk
+        order into ``d_bricks[l - 1]`` (``dsx_pyramid_block_u16``; ``zarr_destriper.py:365-407, 746-782``).
+
+        ``chunks[l - 1]``: the level's (clamped) chunk shape; ``z0s[l - 1]``: first plane of the block's share inside the
+        level's brick grid (default 0); ``zero[l - 1]``: zero the level's buffer first (default True); ``rows[l - 1]``:
+        chunk rows the buffer holds (default: what the share needs).  ``d_work``: ``pyramid_work_bytes`` bytes when there
+        are more than two levels.  Asynchronous on the engine stream."""
+        table = _pyramid_table(zyx, chunks, z0s, zero, rows)
+        n = len(chunks)
+        for lv, g, b in zip(range(1, n + 1), table, d_bricks):
+            assert b.nbytes >= pyramid_level_elems(zyx, lv, (g.cz, g.cy, g.cx), g.rows) * 2, "pyramid brick buffer too small"
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[b.ptr for b in d_bricks])
+        rc = self._lib.dsx_pyramid_block_u16(self._ctx, ctypes.c_void_p(d_planes.ptr), *map(int, zyx), n + 1, table, ptrs,
+                                             ctypes.c_void_p(d_work.ptr) if d_work is not None else None,
+                                             d_work.nbytes if d_work is not None else 0)  # fmt: skip
+        if rc == -1:
+            raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
+        self._check(rc)
+
     def foreground_background(self, image, cutoff, want_mask=True):
         """``(fore_mean, back_mean, mask uint8)`` of a host image (uint16 / float32, any shape)."""
         a = np.ascontiguousarray(image)
@@ -682,6 +711,63 @@ class DestripeEngine:
         self._check(self._lib.dsx_get_level(self._ctx, int(plane), int(level), int(stage),
                                             out.ctypes.data_as(ctypes.c_void_p)))  # fmt: skip
         return out
+
+
+def _pyramid_table(zyx, chunks, z0s, zero, rows):
+    n = len(chunks)
+    table = (_PyramidLevel * max(n, 1))()
+    for i, ck in enumerate(chunks):
+        z0 = int(z0s[i]) if z0s is not None else 0
+        share = int(zyx[0]) >> (i + 1)
+        need = max(1, -(-(z0 + share) // int(ck[0])))
+        table[i] = _PyramidLevel(int(ck[0]), int(ck[1]), int(ck[2]), int(rows[i]) if rows is not None else need, z0,
+                                 1 if zero is None or zero[i] else 0)  # fmt: skip
+    return table
+
+
+def pyramid_level_elems(zyx, level, chunk, rows=1):
+    """uint16 elements of ``rows`` chunk rows of pyramid level ``level`` of a ``[.., H, W]`` volume in chunk order."""
+    nby = -(-(int(zyx[1]) >> level) // int(chunk[1]))
+    nbx = -(-(int(zyx[2]) >> level) // int(chunk[2]))
+    return int(rows) * nby * nbx * int(chunk[0]) * int(chunk[1]) * int(chunk[2])
+
+
+def pyramid_work_bytes(zyx, n_levels):
+    """Bytes of the work buffer :meth:`DestripeEngine.pyramid_block` needs for ``n_levels`` levels (level 0 counted)."""
+    lib = load_library()
+    n = ctypes.c_size_t(0)
+    if lib.dsx_pyramid_work_bytes(*map(int, zyx), int(n_levels), ctypes.byref(n)) != 0:
+        raise ValueError("pyramid_work_bytes: bad geometry {} / {} levels".format(tuple(zyx), n_levels))
+    return int(n.value)
+
+
+def pyramid_block_ref(planes, chunks, z0s=None, bricks=None, rows=None):
+    """Host build of :meth:`DestripeEngine.pyramid_block` (``dsx_pyramid_block_ref``): ``planes`` uint16 ``[Z, H, W]``
+    -> one uint16 array ``[rows, nby, nbx, cz, cy, cx]`` per level ``1 .. len(chunks)``.  ``bricks``: arrays of an
+    earlier call to write into (a chunk row filled by several blocks); fresh zeroed ones otherwise."""
+    lib = load_library()
+    a = np.ascontiguousarray(planes)
+    if a.dtype != np.uint16 or a.ndim != 3:
+        raise ValueError("the pyramid kernels take uint16 [Z, H, W] blocks")
+    table = _pyramid_table(a.shape, chunks, z0s, [bricks is None] * len(chunks), rows)
+    out = []
+    for i, ck in enumerate(chunks):
+        g = table[i]
+        shape = (g.rows, -(-(a.shape[1] >> (i + 1)) // g.cy) if a.shape[1] >> (i + 1) else 0,
+                 -(-(a.shape[2] >> (i + 1)) // g.cx) if a.shape[2] >> (i + 1) else 0, g.cz, g.cy, g.cx)  # fmt: skip
+        if bricks is None:
+            out.append(np.zeros(shape, np.uint16))
+        else:
+            b = bricks[i]
+            if b.dtype != np.uint16 or b.shape != shape or not b.flags["C_CONTIGUOUS"]:
+                raise ValueError("level {}: bricks must be C-contiguous uint16 {}".format(i + 1, shape))
+            out.append(b)
+    n = len(chunks)
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[o.ctypes.data for o in out])  # (a level with an empty share is not touched)
+    rc = lib.dsx_pyramid_block_ref(a.ctypes.data_as(ctypes.c_void_p), *a.shape, n + 1, table, ptrs)
+    if rc != 0:
+        raise ValueError((lib.dsx_last_error(None) or b"pyramid_block_ref failed").decode())
+    return out
 
 
 def blosc_encode_ref(chunks, clevel=3):

@@ -8,9 +8,12 @@ is the 2 x 2 x 2 windowed mean of the previous one, truncated back to uint16 -- 
 between levels.  No CPU fallback.
 """
 
+from collections import namedtuple
+
 import numpy as np
 
 from . import engine as _engine
+from .distributed import z_shard
 from .mini_zarr import MiniZarrArray
 
 
@@ -18,6 +21,69 @@ def _check_scale(scale_axis):
     scale = [int(s) for s in scale_axis]
     if len(scale) < 3 or any(s != 1 for s in scale[:-3]) or scale[-3:] != [2, 2, 2]:
         raise ValueError("only scale factors (.., 2, 2, 2) are implemented (production setting, zarr_destriper.py:1176)")
+
+
+# ---- the pyramid fused into the destripe pass (zarr_destriper.destripe_zarr_store(pyramid_group=...)) -----------------
+# One level of the plan: its index, its [Z, Y, X] shape and its chunk shape (clamped to the shape).
+FusedLevel = namedtuple("FusedLevel", "level shape chunks")
+# One level's share of one z block: chunk row, first plane inside the row, planes, whether the block is the first to
+# touch the row (the row must be zeroed) and whether the row leaves after this block.
+BlockShare = namedtuple("BlockShare", "level row offset planes first flush")
+
+
+def fused_levels(zyx, chunks, n_levels):
+    """Levels ``1 .. n_levels - 1`` as :func:`write_pyramid_levels` writes them: shape ``n // 2`` of the previous
+    level, chunks ``min(c, n)``, stopping at a source level with an axis shorter than 2."""
+    levels, cur = [], tuple(int(n) for n in zyx)
+    for i in range(1, int(n_levels)):
+        if min(cur) < 2:
+            break
+        cur = tuple(n // 2 for n in cur)
+        levels.append(FusedLevel(i, cur, tuple(min(int(c), n) for c, n in zip(tuple(chunks)[-3:], cur))))
+    return levels
+
+
+def fused_z_chunk(z_chunk, levels):
+    """z alignment of the rank shards: one chunk row of the deepest level, in level-0 planes
+    (``cz << (levels written - 1)``), so that every chunk of every level is written by exactly one rank."""
+    return int(z_chunk) << len(levels)
+
+
+def fused_z_range(n_slices, world_size, rank, z_chunk, levels):
+    return z_shard(n_slices, world_size, rank, z_chunk=fused_z_chunk(z_chunk, levels))
+
+
+def fused_check_blocks(levels, block_z):
+    """``ValueError`` unless z blocks of ``block_z`` planes hold whole windows of every level and fill whole chunk rows."""
+    if levels and block_z % (1 << len(levels)):
+        raise ValueError("fused_pyramid needs z blocks of a multiple of {} planes (2 x 2 x 2 windows of {} levels), "
+                         "not {}".format(1 << len(levels), len(levels), block_z))  # fmt: skip
+    for lv in levels:
+        if lv.shape[0] > lv.chunks[0] and (lv.chunks[0] << lv.level) % block_z:
+            raise ValueError("fused_pyramid needs z blocks that fill whole chunk rows of every level: {} planes do not "
+                             "divide the {} of a level-{} chunk row".format(block_z, lv.chunks[0] << lv.level, lv.level))  # fmt: skip
+
+
+def fused_schedule(levels, z_start, z_stop, block_z):
+    """What every z block of ``[z_start, z_stop)`` (a :func:`fused_z_range`) gives to every level:
+    ``[((z0, z1), [BlockShare per level])]``.  A chunk row leaves (``flush``) with the block that completes it, or with
+    the last block of the range when it holds anything."""
+    out, filled = [], [0] * len(levels)
+    starts = list(range(z_start, z_stop, block_z))
+    for z0 in starts:
+        z1, shares = min(z0 + block_z, z_stop), []
+        for i, lv in enumerate(levels):
+            p0, n, cz = z0 >> lv.level, (min(z0 + block_z, z_stop) - z0) >> lv.level, lv.chunks[0]
+            row, off = divmod(p0, cz)
+            if n and off + n > cz:
+                raise ValueError("a z block straddles a level-{} chunk row (fused_check_blocks)".format(lv.level))
+            filled[i] += n
+            done = filled[i] > 0 and ((p0 + n) % cz == 0 or z0 == starts[-1])
+            shares.append(BlockShare(lv.level, row, off, n, off == 0, done))
+            if done:
+                filled[i] = 0
+        out.append(((z0, z1), shares))
+    return out
 
 
 def compute_pyramid(data, n_lvls, scale_axis, chunks="auto", device=0, engine=None):

@@ -276,12 +276,25 @@ class _DeviceBlocks:
     take are decoded there and shipped as copies), the upload stream brings the packed frames and the task table, and
     ``dsx_blosc_decode_device`` fills the input bricks on the compute stream before ``bricks_to_planes``.  Its
     per-task statuses come back on the compute stream and are checked before the block's output reaches the writers.
+
+    With ``pyr`` (``fused_pyramid``) the pyramid levels are built in the same pass: next to ``planes_to_bricks``,
+    ``dsx_pyramid_block_u16`` reduces the block's planes (``d_out``) into one chunk row per level, in brick order, at the
+    block's z offset inside that row (``pyramid.fused_schedule``).  A row that the block completes leaves the way level 0
+    does, in the block's own slot: its encode is enqueued on the compute stream behind the kernel and its download on
+    the download stream BEFORE the slot's event is recorded, so the one event covers level 0 and the rows.  The same
+    two rules hold for them.  The host hands a pinned row (or its frames) to the writers only after that event, inside
+    the ``_write`` of the block, and ``writes[b - 2]`` has returned before block b may flush into the same pinned row
+    again (a level flushes at most once per block, and its rows alternate between two buffers).  The kernel refills a
+    device row only behind ``stream_wait(compute, download)`` at the top of ``_submit_out``, issued after the host has
+    enqueued the encode / download (and, with ``device_codec``, the frame fetch) of the row that used the buffer two
+    flushes ago.
     """
 
     N_BUF = 2
 
-    def __init__(self, eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False):
+    def __init__(self, eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False, pyr=None):
         self.eng, self.src, self.dst, self.zyx, self.block_z = eng, src, dst, zyx, block_z
+        self.pyr_levels, self.pyr_arrays = pyr if pyr else ([], [])
         self.ci, self.co = tuple(src.chunks[-3:]), tuple(dst.chunks[-3:])
         _, H, W = zyx
         grid = lambda c, zspan: (-(-zspan // c[0]), -(-H // c[1]), -(-W // c[2]))  # noqa: E731
@@ -331,11 +344,36 @@ class _DeviceBlocks:
             self.h_offsets = [eng.alloc_host(8 * (n_chunks + 1)) for _ in range(self.N_BUF)]
             self.frames = [h.array((cap,), np.uint8) for h in self.h_frames]
             self.offsets = [h.array((n_chunks + 1,), np.int64) for h in self.h_offsets]
+        # fused pyramid: per level two device chunk rows in brick order + what carries a finished row to the host
+        self.d_row, self.h_row, self.stage_row, self.pyr_bufs = [], [], [], []
+        self.d_pframes, self.d_poffsets, self.h_pframes, self.h_poffsets, self.pframes, self.poffsets = [], [], [], [], [], []
+        for lv in self.pyr_levels:
+            ny, nx = -(-lv.shape[1] // lv.chunks[1]), -(-lv.shape[2] // lv.chunks[2])
+            brick = int(np.prod(lv.chunks))
+            row_bytes = ny * nx * brick * 2
+            self.d_row.append([eng.alloc(row_bytes) for _ in range(self.N_BUF)])
+            if self.device_codec:
+                cap = ny * nx * (brick * 2 + 16)
+                self.d_pframes.append([eng.alloc(cap) for _ in range(self.N_BUF)])
+                self.d_poffsets.append([eng.alloc(8 * (ny * nx + 1)) for _ in range(self.N_BUF)])
+                self.h_pframes.append([eng.alloc_host(cap) for _ in range(self.N_BUF)])
+                self.h_poffsets.append([eng.alloc_host(8 * (ny * nx + 1)) for _ in range(self.N_BUF)])
+                self.pframes.append([h.array((cap,), np.uint8) for h in self.h_pframes[-1]])
+                self.poffsets.append([h.array((ny * nx + 1,), np.int64) for h in self.h_poffsets[-1]])
+            else:
+                self.h_row.append([eng.alloc_host(row_bytes) for _ in range(self.N_BUF)])
+                self.stage_row.append([h.array((ny, nx, brick), np.uint16) for h in self.h_row[-1]])
+        work = engine_mod.pyramid_work_bytes((block_z, H, W), len(self.pyr_levels) + 1) if self.pyr_levels else 0
+        self.d_work = eng.alloc(work) if work else None
+        if self.pyr_levels:
+            self.pyr_bufs = [b for per_level in (self.d_row + self.h_row + self.d_pframes + self.d_poffsets + self.h_pframes
+                                                 + self.h_poffsets) for b in per_level] + ([self.d_work] if work else [])  # fmt: skip
+        self.pyr_schedule, self.pyr_cur, self.pyr_flushes = {}, [0] * len(self.pyr_levels), [[] for _ in range(self.N_BUF)]
         self.io_threads = int(io_threads)
         self.timing = _new_timing()
 
     def close(self):
-        for b in (self.d_bricks_in + self.d_bricks_out + [self.d_planes, self.d_out] + self.h_in + self.h_out
+        for b in (self.pyr_bufs + self.d_bricks_in + self.d_bricks_out + [self.d_planes, self.d_out] + self.h_in + self.h_out
                   + self.d_frames + self.d_offsets + self.h_frames + self.h_offsets + self.h_packed + self.h_tasks
                   + self.h_status + self.d_packed + self.d_tasks + self.d_status):
             b.free()
@@ -362,9 +400,35 @@ class _DeviceBlocks:
         self.timing["read_s"] += time.perf_counter() - t0
         return nbz, zoff
 
-    def _write(self, z0, z1, k):
-        """Compress / store the output bricks of planes ``[z0, z1)`` from pinned buffer ``k``."""
+    def _write_rows(self, flushes):
+        """The pyramid chunk rows that left with a block: ``(level index, buffer, chunk row)`` each."""
+        for i, j, row in flushes:
+            arr, lv = self.pyr_arrays[i], self.pyr_levels[i]
+            lead = (0,) * (arr.ndim - 3)
+            ny, nx = -(-lv.shape[1] // lv.chunks[1]), -(-lv.shape[2] // lv.chunks[2])
+            idx = list(itertools.product(range(ny), range(nx)))
+            paths = [arr._chunk_path(lead + (row, y, x)) for y, x in idx]
+            if self.device_codec:
+                frames, offs = self.pframes[i][j], self.poffsets[i][j]
+                self.eng.io_write_chunks(paths, [frames[offs[c] : offs[c + 1]] for c in range(len(idx))],
+                                         threads=self.io_threads, zlib_level=-1)  # fmt: skip
+                continue
+            comp = arr.compressor
+            self.eng.io_write_chunks(paths, [self.stage_row[i][j][y, x] for y, x in idx], threads=self.io_threads,
+                                     zlib_level=-1 if comp is None else int(comp[1]),
+                                     blosc=arr.blosc_write_params() if comp and comp[0] == "blosc" else None)  # fmt: skip
+
+    def _write(self, z0, z1, k, flushes=()):
+        """Compress / store the output bricks of planes ``[z0, z1)`` from pinned buffer ``k`` (and the pyramid rows that
+        left with the block)."""
         t0 = time.perf_counter()
+        try:
+            self._write_level0(z0, z1, k)
+            self._write_rows(flushes)
+        finally:
+            self.timing["write_s"] += time.perf_counter() - t0
+
+    def _write_level0(self, z0, z1, k):
         lead = (0,) * (self.dst.ndim - 3)
         nbo = -(-(z1 - z0) // self.co[0])
         oz0 = z0 // self.co[0]
@@ -375,14 +439,12 @@ class _DeviceBlocks:
             frames, offs = self.frames[k], self.offsets[k]
             self.eng.io_write_chunks(paths, [frames[offs[c] : offs[c + 1]] for c in range(len(odx))],
                                      threads=self.io_threads, zlib_level=-1)  # fmt: skip
-            self.timing["write_s"] += time.perf_counter() - t0
             return
         comp = self.dst.compressor
         level = -1 if comp is None else int(comp[1])
         self.eng.io_write_chunks([self.dst._chunk_path(lead + (oz0 + i[0], i[1], i[2])) for i in odx],
                                  [out[i] for i in odx], threads=self.io_threads, zlib_level=level,
                                  blosc=self.dst.blosc_write_params() if comp and comp[0] == "blosc" else None)  # fmt: skip
-        self.timing["write_s"] += time.perf_counter() - t0
 
     # -- device stage (asynchronous) -----------------------------------------------------------
     def _submit(self, z0, z1, k, nbz, zoff):
@@ -422,6 +484,7 @@ class _DeviceBlocks:
         eng, (_, H, W), Z = self.eng, self.zyx, z1 - z0
         eng.stream_wait(C, D)             # (the wait lands before planes_to_bricks:) after download(b - 2 .. b - 1)
         eng.planes_to_bricks(self.d_out, self.d_bricks_out[k], (Z, H, W), self.co, 0)
+        flushes = self.pyr_flushes[k] = self._submit_pyramid(z0, z1)
         nbo = -(-Z // self.co[0])
         if self.device_codec:
             n_chunks = nbo * self.go[1] * self.go[2]
@@ -429,12 +492,47 @@ class _DeviceBlocks:
                                     self.d_offsets[k], typesize=2, clevel=int(self.dst.compressor[1]))  # fmt: skip
             eng.stream_wait(D, C)
             eng.copy_d2h_async(self.offsets[k][: n_chunks + 1], self.d_offsets[k], D)
-            eng.event_record(self.N_BUF + k, D)  # the frame offsets of block b are here once this has passed
+            for i, j, _ in flushes:
+                eng.copy_d2h_async(self.poffsets[i][j], self.d_poffsets[i][j], D)
+            eng.event_record(self.N_BUF + k, D)  # the frame offsets of block b (and of its rows) are here once this has passed
             return
         eng.stream_wait(D, C)             # download(b) after compute(b)
         eng.copy_d2h_async(self.stage_out[k][:nbo], self.d_bricks_out[k], D)
         self.timing["download_bytes"] += self.stage_out[k][:nbo].nbytes
-        eng.event_record(self.N_BUF + k, D)  # pinned output buffer k holds block b once this has passed
+        for i, j, _ in flushes:
+            eng.copy_d2h_async(self.stage_row[i][j], self.d_row[i][j], D)
+            self._count_pyramid(self.stage_row[i][j].nbytes)
+        eng.event_record(self.N_BUF + k, D)  # pinned output buffer k (and the rows) hold block b once this has passed
+
+    def _count_pyramid(self, nbytes):
+        self.timing["download_bytes"] += nbytes
+        self.timing["pyramid_download_bytes"] += nbytes
+
+    def _submit_pyramid(self, z0, z1):
+        """(compute stream, behind the wait that protects the output buffers) The block's share of every pyramid level
+        into the levels' current device rows; the rows it completes are encoded (``device_codec``) and returned as
+        ``(level index, buffer, chunk row)`` for the download."""
+        if not self.pyr_levels:
+            return []
+        eng, (_, H, W) = self.eng, self.zyx
+        shares = self.pyr_schedule[(z0, z1)]
+        cur = self.pyr_cur
+        eng.pyramid_block(self.d_out, (z1 - z0, H, W), [lv.chunks for lv in self.pyr_levels],
+                          [self.d_row[i][cur[i]] for i in range(len(shares))], z0s=[s.offset for s in shares],
+                          zero=[s.first for s in shares], rows=[1] * len(shares), d_work=self.d_work)  # fmt: skip
+        flushes = []
+        for i, (s, lv) in enumerate(zip(shares, self.pyr_levels)):
+            if not s.flush:
+                continue
+            j = cur[i]
+            if self.device_codec:
+                n_chunks = -(-lv.shape[1] // lv.chunks[1]) * -(-lv.shape[2] // lv.chunks[2])
+                eng.blosc_encode_device(self.d_row[i][j], n_chunks, int(np.prod(lv.chunks)) * 2, self.d_pframes[i][j],
+                                        self.d_poffsets[i][j], typesize=2,
+                                        clevel=int(self.pyr_arrays[i].compressor[1]))  # fmt: skip
+            flushes.append((i, j, s.row))
+            cur[i] = (j + 1) % self.N_BUF
+        return flushes
 
     def _fetch_frames(self, z0, z1, k):
         """(device codec; the offsets of block [z0, z1) are on the host) Download exactly its packed frames."""
@@ -445,6 +543,12 @@ class _DeviceBlocks:
         self.timing["download_bytes"] += total + 8 * (n_chunks + 1)
         if total:
             self.eng.copy_d2h_async(self.frames[k][:total], self.d_frames[k], D)
+        for i, j, _ in self.pyr_flushes[k]:  # the rows that left with the block: their offsets came with level 0's
+            offs = self.poffsets[i][j]
+            total = int(offs[-1])
+            self._count_pyramid(total + offs.nbytes)
+            if total:
+                self.eng.copy_d2h_async(self.pframes[i][j][:total], self.d_pframes[i][j], D)
         self.eng.event_record(self.N_BUF + k, D)
         self.eng.event_sync(self.N_BUF + k)
 
@@ -464,6 +568,11 @@ class _DeviceBlocks:
         """All blocks of ``[z_start, z_stop)`` through the pipeline; returns the number of planes."""
         blocks = [(z, min(z + self.block_z, z_stop)) for z in range(z_start, z_stop, self.block_z)]
         nb = len(blocks)
+        if self.pyr_levels:
+            from . import pyramid
+
+            self.pyr_schedule = dict(pyramid.fused_schedule(self.pyr_levels, z_start, z_stop, self.block_z))
+            self.pyr_cur = [0] * len(self.pyr_levels)
         reader = ThreadPoolExecutor(max_workers=1)   # stage drivers: one read and one write in flight,
         writer = ThreadPoolExecutor(max_workers=1)   # each fanning its chunks out over the I/O pool
         try:
@@ -489,13 +598,14 @@ class _DeviceBlocks:
                     self._check_decode(kp)
                     if self.device_codec:
                         self._fetch_frames(*blocks[b - 1], kp)
-                    writes.append(writer.submit(self._write, *blocks[b - 1], kp))
+                    writes.append(writer.submit(self._write, *blocks[b - 1], kp, list(self.pyr_flushes[kp])))
             if nb:
                 self.eng.event_sync(self.N_BUF + (nb - 1) % self.N_BUF)
                 self._check_decode((nb - 1) % self.N_BUF)
                 if self.device_codec:
                     self._fetch_frames(*blocks[nb - 1], (nb - 1) % self.N_BUF)
-                writes.append(writer.submit(self._write, *blocks[nb - 1], (nb - 1) % self.N_BUF))
+                writes.append(writer.submit(self._write, *blocks[nb - 1], (nb - 1) % self.N_BUF,
+                                            list(self.pyr_flushes[(nb - 1) % self.N_BUF])))
             for w in writes:
                 w.result()
         finally:
@@ -509,18 +619,19 @@ _BLOCKS = {}  # one set of staging buffers per process: page-locking 2 GB of hos
 
 
 def _new_timing():
-    return {"read_s": 0.0, "write_s": 0.0, "upload_bytes": 0, "download_bytes": 0}
+    return {"read_s": 0.0, "write_s": 0.0, "upload_bytes": 0, "download_bytes": 0, "pyramid_download_bytes": 0}
 
 
-def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False):
+def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False, pyr=None):
     """Staging buffers for this geometry, reused from the previous tile when nothing but the stores changed
     (a channel is tens of tiles of one shape, ``zarr_destriper.py:1231``)."""
     key = (id(eng), tuple(zyx[1:]), tuple(src.chunks[-3:]), tuple(dst.chunks[-3:]), int(block_z), bool(device_codec),
-           bool(device_decode))  # fmt: skip
+           bool(device_decode), tuple((lv.level, lv.shape[1:], lv.chunks) for lv in (pyr[0] if pyr else ())))  # fmt: skip
     cached = _BLOCKS.get("blocks")
     if cached is not None and cached[0] == key and cached[1].eng._ctx is not None:
         blocks = cached[1]
         blocks.src, blocks.dst, blocks.zyx, blocks.io_threads = src, dst, zyx, int(io_threads)
+        blocks.pyr_levels, blocks.pyr_arrays = pyr if pyr else ([], [])
         blocks.timing = _new_timing()
         return blocks
     if cached is not None:
@@ -528,7 +639,7 @@ def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False, 
             cached[1].close()
         except Exception:  # the engine of the cached buffers may be gone already
             pass
-    blocks = _DeviceBlocks(eng, src, dst, zyx, block_z, io_threads, device_codec, device_decode)
+    blocks = _DeviceBlocks(eng, src, dst, zyx, block_z, io_threads, device_codec, device_decode, pyr)
     _BLOCKS["blocks"] = (key, blocks)
     return blocks
 
@@ -574,6 +685,8 @@ def destripe_zarr_store(
     *,
     device_codec=False,
     device_decode=False,
+    pyramid_group=None,
+    n_levels=1,
 ):
     """Chunk map of ``destripe_zarr`` (``zarr_destriper.py:909-1211``) over a Zarr-v2 directory store -- the engine-level
     form (explicit configs and ``shadow_correction``); :func:`destripe_zarr` is the entry point with the reference's
@@ -614,7 +727,19 @@ def destripe_zarr_store(
     Frames the device does not take (other inner codecs, bit shuffle, split streams, zstd checksums) are decoded by the
     I/O threads as before.  Needs a Blosc uint16 input and the device re-tiling path; anything else raises
     ``ValueError``.  Off by default; works with ``device_codec`` on or off.
+
+    ``pyramid_group`` / ``n_levels`` (what ``destripe_zarr(fused_pyramid=True)`` is implemented with): with a group
+    folder and ``n_levels > 1`` the pyramid levels ``1 .. n_levels - 1`` are written to ``<pyramid_group>/<i>`` in the
+    same pass, from the filtered planes while they are in device memory (``dsx_pyramid_block_u16``) and through the same
+    encode / download / write pipeline as level 0 -- the arrays, chunk files and voxels
+    ``pyramid.write_pyramid_levels`` would produce from the finished level 0.  Every rank writes the levels of its own z
+    range, which is then aligned to one chunk row of the deepest level (``output z chunk << (levels written - 1)``).
+    Needs the device re-tiling path and z blocks that hold whole 2 x 2 x 2 windows of every level and fill whole chunk
+    rows; anything else raises ``ValueError``.  Works with ``device_codec`` / ``device_decode`` on or off and with raw,
+    zlib and Blosc outputs.
     """
+    from . import pyramid
+
     logger = logger or logging.getLogger("dsx.zarr")
     if io_threads is None:
         io_threads = default_io_threads(world_size)
@@ -624,24 +749,34 @@ def destripe_zarr_store(
         raise ValueError("blocks must cover whole planes: the stripe filter is a per-plane operation")
     out_shape = (1,) * (5 - len(src.shape)) + tuple(src.shape)
     out_chunks = tuple(output_chunks)[-len(out_shape):]
+    fused = pyramid_group is not None and int(n_levels) > 1
+    levels = pyramid.fused_levels(zyx, out_chunks, n_levels) if fused else []
+    lead = out_shape[:-3]
+    level_arrays = [(os.path.join(str(pyramid_group), str(lv.level)), lead + lv.shape, (1,) * len(lead) + lv.chunks)
+                    for lv in levels]  # fmt: skip
     if rank == 0:
-        MiniZarrArray.create(output_path, out_shape, out_chunks, np.uint16, compressor=compressor,
-                             dimension_separator="/")  # fmt: skip
+        for path, shape, chunks in [(output_path, out_shape, out_chunks)] + level_arrays:
+            MiniZarrArray.create(path, shape, chunks, np.uint16, compressor=compressor, dimension_separator="/")
     if group is not None and world_size > 1:
         group.barrier()
-    dst = None
-    for _ in range(1200):  # without a group: wait for rank 0's metadata of this geometry
-        try:
-            dst = MiniZarrArray.open(output_path)
-            if dst.matches(out_shape, out_chunks, np.uint16, compressor):
-                break
-        except (FileNotFoundError, ValueError):
-            pass
-        dst = None
-        time.sleep(0.05)
-    if dst is None:
-        raise TimeoutError("rank {}: the output array {} was not created with shape {}".format(rank, output_path, out_shape))
-    z0, z1 = z_shard(zyx[0], world_size, rank, z_chunk=output_chunks[-3])
+
+    def open_created(path, shape, chunks):
+        for _ in range(1200):  # without a group: wait for rank 0's metadata of this geometry
+            try:
+                arr = MiniZarrArray.open(path)
+                if arr.matches(shape, chunks, np.uint16, compressor):
+                    return arr
+            except (FileNotFoundError, ValueError):
+                pass
+            time.sleep(0.05)
+        raise TimeoutError("rank {}: the output array {} was not created with shape {}".format(rank, path, shape))
+
+    dst = open_created(output_path, out_shape, out_chunks)
+    pyr_arrays = [open_created(*a) for a in level_arrays]
+    if levels:  # every chunk of every level written by one rank: shards of whole chunk rows of the deepest level
+        z0, z1 = pyramid.fused_z_range(zyx[0], world_size, rank, output_chunks[-3], levels)
+    else:
+        z0, z1 = z_shard(zyx[0], world_size, rank, z_chunk=output_chunks[-3])
     dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device
     LAST_RUN.update(rank=rank, world_size=world_size, z_range=(z0, z1), io_threads=int(io_threads), device=dev)
     # dataset_name of the reference = the tile folder (X_..._Y_....zarr), also when level "0" is opened
@@ -664,18 +799,26 @@ def destripe_zarr_store(
         if not can or device_retile is False:
             raise ValueError("device_decode needs the device re-tiling path (a uint16 store, even planes and "
                              "output-chunk-aligned z blocks)")  # fmt: skip
-    LAST_RUN.update(device_codec=bool(device_codec), device_decode=bool(device_decode))
+    if levels and z1 > z0:
+        if not can or device_retile is False:
+            raise ValueError("fused_pyramid needs the device re-tiling path (a uint16 store, even planes and "
+                             "output-chunk-aligned z blocks)")  # fmt: skip
+        pyramid.fused_check_blocks(levels, block_z)
+    LAST_RUN.update(device_codec=bool(device_codec), device_decode=bool(device_decode), fused_pyramid=bool(levels),
+                    pyramid_levels=[lv.level for lv in levels])  # fmt: skip
     if can and device_retile is not False:
         flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
         eng = fl.get_engine(zyx[1:], cells_config, no_cells_config, 2500, flatfield, darkfield,
                             max_batch=min(block_z, 64), device=dev)  # fmt: skip
-        blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec, device_decode)
+        blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec, device_decode,
+                                (levels, pyr_arrays) if levels else None)  # fmt: skip
         n_planes = blocks.run_range(z0, z1)
         eng.sync()
         dt = time.perf_counter() - t0
         logger.info("rank %d: %d planes z[%d:%d) in %.2f s (device re-tiling%s, overlapped; read %.2f s, write %.2f s)",
                     rank, n_planes, z0, z1, dt, (", device codec" if device_codec else "")
-                    + (", device decode" if device_decode else ""), blocks.timing["read_s"],
+                    + (", device decode" if device_decode else "")
+                    + (", pyramid levels 1..{} fused".format(len(levels)) if levels else ""), blocks.timing["read_s"],
                     blocks.timing["write_s"])  # fmt: skip
         return n_planes, dt
     for sc, internal in iter_blocks(zyx, prediction_chunksize, (z0, z1)):
@@ -827,6 +970,7 @@ def destripe_zarr(
     group=None,
     device_codec=False,
     device_decode=False,
+    fused_pyramid=False,
 ):
     """``destripe_zarr`` of the reference (``zarr_destriper.py:909-1211``) with its 14 parameters, on the GPU chunk map.
 
@@ -852,7 +996,9 @@ def destripe_zarr(
     Keyword-only extras (the engine's): ``rank`` / ``world_size`` / ``group`` (one process per GPU, chunk-aligned
     z-ranges; with a ``distributed.RankGroup`` rank 0 alone reads the dark plane and broadcasts it), ``device``,
     ``compressor`` / ``output_chunks`` of the output, ``n_levels``, ``device_retile``, ``io_threads``, ``device_codec``, ``device_decode``
-    (level 0 encoded on the GPU, :func:`destripe_zarr_store`).
+    (level 0 encoded / decoded on the GPU, :func:`destripe_zarr_store`), ``fused_pyramid`` (levels ``1 .. n_levels - 1``
+    are written by every rank in the level-0 pass, from the filtered planes in device memory, instead of by
+    :func:`compute_multiscale` on rank 0 afterwards; same stores; z shards of ``output z chunk << (levels - 1)`` planes).
     Returns ``(planes processed by this rank, seconds)``.
     """
     no_cells_config = parameters["no_cells_config"]
@@ -905,6 +1051,11 @@ def destripe_zarr(
         # flatfield_correction dereferences the dark plane (filtering.py:371-377): nothing to correct with
         raise ValueError(f"No darkfield for the shading correction: {derivatives_path} does not exist")
     level0 = output_destriped_zarr.joinpath("0")
+    scale_factor = [2, 2, 2]
+    if fused_pyramid:
+        from . import pyramid
+
+        pyramid._check_scale([1, 1] + scale_factor)
     n_planes, seconds = destripe_zarr_store(
         str(src),
         str(level0),
@@ -924,16 +1075,18 @@ def destripe_zarr(
         group=group,
         device_codec=device_codec,
         device_decode=device_decode,
+        pyramid_group=str(output_destriped_zarr) if fused_pyramid else None,
+        n_levels=n_levels if fused_pyramid else 1,
     )
     if group is not None and world_size > 1:
         group.barrier()  # level 0 of this tile is complete on every rank: the pyramid may read it
-    if rank == 0 and n_levels > 1:
+    if rank == 0 and n_levels > 1 and not fused_pyramid:
         dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device
         t0 = time.perf_counter()
         compute_multiscale(
             output_zarr=str(level0),
             zarr_group=str(output_destriped_zarr),
-            scale_factor=[2, 2, 2],
+            scale_factor=scale_factor,
             n_workers=co_cpus,
             voxel_size=[xyz_resolution[-1], xyz_resolution[-2], xyz_resolution[-3]] if xyz_resolution is not None else None,
             image_name=dataset_name,
@@ -972,6 +1125,7 @@ def destripe_channel(
     device_retile=None,
     device_codec=False,
     device_decode=False,
+    fused_pyramid=False,
 ):
     """``destripe_channel`` of the reference (``zarr_destriper.py:1214-1267``), same eight parameters (the reference's
     caller passes them by keyword, ``run_capsule.py:394-403``), wired to the GPU chunk map.
@@ -985,7 +1139,7 @@ def destripe_channel(
 
     Keyword-only extras: ``rank`` / ``world_size`` / ``group`` / ``device`` (one process per GPU), output codec and
     chunks, ``multiscale`` (the reference hard-codes ``"0"``), ``prediction_chunksize`` (the reference hard-codes the
-    production tile, ``(64, 1600, 2000)``), ``io_threads``, ``device_retile``, ``device_codec``, ``device_decode``.  ``world_size > 1`` needs ``group`` (anything with
+    production tile, ``(64, 1600, 2000)``), ``io_threads``, ``device_retile``, ``device_codec``, ``device_decode``, ``fused_pyramid`` (:func:`destripe_zarr`).  ``world_size > 1`` needs ``group`` (anything with
     ``barrier()``): the pyramid of a tile may only be computed once EVERY rank has written its z-range.  With a
     ``distributed.RankGroup`` rank 0 alone reads the flat and dark planes of a tile and broadcasts them (RCCL).
     """
@@ -1036,6 +1190,7 @@ def destripe_channel(
             group=group,
             device_codec=device_codec,
             device_decode=device_decode,
+            fused_pyramid=fused_pyramid,
         )
         done[tile_path.name] = n
     return done

@@ -177,6 +177,29 @@ int dsx_planes_to_bricks_u16(dsx_ctx* ctx, const void* d_planes, void* d_bricks,
  * xarray_multiscale.reducers.windowed_mean + preserve_dtype.  Asynchronous on the context stream. */
 int dsx_downsample2_u16(dsx_ctx* ctx, const void* d_src, void* d_dst, int Z, int Y, int X);
 
+/* The pyramid levels of one filtered block, computed from the block where it lies and stored in chunk order: what
+ * compute_pyramid (zarr_destriper.py:365-407) and the level loop of compute_multiscale (:746-782) produce for the
+ * voxels under this block, without reading level 0 back.  d_planes: dense [Z][H][W] uint16 whose plane 0 lies at a
+ * multiple of 2^(n_levels - 1) in the volume.  n_levels counts level 0; levels[l - 1] / d_bricks[l - 1] describe level
+ * l = 1 .. n_levels - 1, whose share of the block is (Z >> l, H >> l, W >> l) -- every level the floor(sum of 8 / 8)
+ * of the TRUNCATED previous one, trailing odd planes / rows / columns cropped per level.  A level (and all below it)
+ * with an empty share is skipped.  d_bricks[l - 1]: [rows][nby][nbx][cz][cy][cx] with nb* = ceil((H or W) >> l / c*);
+ * positions outside the level's volume are not written, so the first block of a chunk row sets `zero`.
+ * Levels 1 and 2 come from one kernel that reads the block once; levels >= 3 from one plain kernel each, through
+ * d_work (dsx_pyramid_work_bytes; may be NULL when that is 0).  Asynchronous on the context stream.
+ * dsx_pyramid_block_ref: the host build of the same arithmetic (host pointers, synchronous, identical output). */
+typedef struct dsx_pyramid_level {
+  int32_t cz, cy, cx; /* chunk shape of the level, already clamped to the level's volume */
+  int32_t rows;       /* chunk rows the level's brick buffer holds */
+  int32_t z0;         /* first plane of this block's share inside that brick grid */
+  int32_t zero;       /* non-zero: the whole brick buffer is zeroed first */
+} dsx_pyramid_level;
+int dsx_pyramid_work_bytes(int Z, int H, int W, int n_levels, size_t* bytes);
+int dsx_pyramid_block_u16(dsx_ctx* ctx, const void* d_planes, int Z, int H, int W, int n_levels,
+                          const dsx_pyramid_level* levels, void* const* d_bricks, void* d_work, size_t work_bytes);
+int dsx_pyramid_block_ref(const void* planes, int Z, int H, int W, int n_levels, const dsx_pyramid_level* levels,
+                          void* const* bricks);
+
 /* Host side of the chunk map: n Zarr chunk files <-> memory (normally the pinned staging buffers) on
  * `threads` native threads -- what zarr / numcodecs do under the reference's worker processes
  * (zarr_destriper.py:336, 1042-1074).  codec: raw chunks, zlib streams, or Blosc frames -- the production

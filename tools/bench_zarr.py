@@ -4,11 +4,15 @@
 download) into another store.  Prints one JSON line; the roofline of this path is the host link
 (PCIe Gen5 x16, 63 GB/s spec: 16.8 MB per plane both ways -> <= 3.7 k planes/s), not HBM.
 
-    bench_zarr.py N [raw|zlib|blosc] [device-codec] [device-decode]
+    bench_zarr.py N [raw|zlib|blosc] [device-codec] [device-decode] [pyramid|fused-pyramid]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
 line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
 `device-decode` (Blosc only): the input chunks are decoded on the GPU (destripe_zarr_store(device_decode=True)).
+`pyramid`: after the timed level-0 pass, compute_multiscale(n_levels=3) on the store is timed too (the two-pass route);
+`fused-pyramid`: level 0 and levels 1-2 in one destripe_zarr_store call (pyramid_group / n_levels).  Both add level-0,
+pyramid and total seconds, the levels' bytes on disk (with the host writer's frames of each level's first chunk row for
+comparison) and a check of the first level-1 / level-2 planes against the NumPy oracle.
 Every line reports the read / write stage times of the timed pass (I/O threads, summed per block), the bytes that
 crossed the host link each way, and the link fraction those bytes make of the run (63 GB/s per direction)."""
 import json, logging, os, shutil, sys, tempfile, time
@@ -22,6 +26,7 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 codec = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2] != "raw" else None  # None (raw chunks), "zlib" or "blosc" (Blosc-zstd)
 device_codec = "device-codec" in sys.argv[3:]
 device_decode = "device-decode" in sys.argv[3:]
+two_pass, fused = "pyramid" in sys.argv[3:], "fused-pyramid" in sys.argv[3:]
 H = W = 2048
 root = tempfile.mkdtemp(prefix="dsx_zarr_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
@@ -32,26 +37,37 @@ try:
         src[0, 0, z : z + 64] = synth.synthetic_stack(min(64, n - z), H, W, bank=bank)
     t_make = time.perf_counter() - t0
     res = {}
-    for name, kw in (("overlapped", {}),):
+    group = os.path.join(root, "out.zarr")
+    level0 = os.path.join(group, "0") if two_pass or fused else group
+    for name, kw in (("overlapped", {"pyramid_group": group, "n_levels": 3} if fused else {}),):
         for rep in range(2):  # second pass: plan + pinned buffers exist, page cache warm
             t0 = time.perf_counter()
-            planes, dt = zd.destripe_zarr_store(os.path.join(root, "in.zarr"), os.path.join(root, "out.zarr"), synth.CELLS_CONFIG,
+            planes, dt = zd.destripe_zarr_store(os.path.join(root, "in.zarr"), level0, synth.CELLS_CONFIG,
                                           synth.NO_CELLS_CONFIG, None, prediction_chunksize=(64, H, W),
                                           output_chunks=(1, 1, 64, 128, 128), device=0, device_retile=True, io_threads=16, compressor=codec,
                                           device_codec=device_codec, device_decode=device_decode, **kw)
             res[name] = {"planes": planes, "seconds": round(time.perf_counter() - t0, 3)}
     timing = dict(zd._BLOCKS["blocks"][1].timing)  # the timed (second) pass
     secs = res["overlapped"]["seconds"]
+    pyr = {}
+    if two_pass or fused:
+        pyramid_s = 0.0
+        if two_pass:  # the route destripe_zarr takes by default: rank 0 reads level 0 back and writes the levels
+            t0 = time.perf_counter()
+            zd.compute_multiscale(level0, group, [2, 2, 2], 1, None, "bench", n_levels=3, compressor=codec, device=0)
+            pyramid_s = time.perf_counter() - t0
+        pyr = {"route": "fused" if fused else "two-pass", "level0_s": round(secs, 3), "pyramid_s": round(pyramid_s, 3),
+               "total_s": round(secs + pyramid_s, 3), "pyramid_download_bytes": int(timing["pyramid_download_bytes"])}
     up, down = int(timing["upload_bytes"]), int(timing["download_bytes"])
     link = {"upload_bytes": up, "download_bytes": down,
             "upload_GBps": round(up / secs / 1e9, 2), "download_GBps": round(down / secs / 1e9, 2),
             "frac": round(max(up, down) / secs / 63e9, 3)}
-    out = MiniZarrArray.open(os.path.join(root, "out.zarr"))
+    out = MiniZarrArray.open(level0)
     chk = int(out[0, 0, 0].astype(np.uint64).sum())
     sizes = {}
     if codec == "blosc":  # bytes on disk; the host writer's frames of the first block's chunks for comparison
         from aind_smartspim_destripe_amd import mini_zarr
-        written = sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(os.path.join(root, "out.zarr"))
+        written = sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(level0)
                       for f in fs if not f.startswith("."))
         first = [out._chunk_path((0, 0, 0, y, x)) for y in range(H // 128) for x in range(W // 128)]
         got = sum(os.path.getsize(p) for p in first)
@@ -59,6 +75,22 @@ try:
                    for y in range(H // 128) for x in range(W // 128))
         sizes = {"bytes_written": written, "raw_bytes": n * H * W * 2, "ratio_to_raw": round(written / (n * H * W * 2), 4),
                  "first_block_bytes": got, "first_block_host_writer_bytes": host, "size_ratio_to_host_writer": round(got / host, 4)}
+    if pyr:
+        from oracle import format_oracle as fo
+        want = fo.pyramid(out[0, 0, 0:8], 3)
+        pyr["levels"], pyr["verified"] = {}, True
+        for lvl in (1, 2):
+            arr = MiniZarrArray.open(os.path.join(group, str(lvl)))
+            pyr["verified"] = pyr["verified"] and bool(np.array_equal(arr[0, 0, 0 : 8 >> lvl], want[lvl]))
+            info = {"shape": list(arr.shape), "chunks": list(arr.chunks),
+                    "bytes_written": sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(arr.path)
+                                         for f in fs if not f.startswith("."))}
+            if codec == "blosc":  # the level's first chunk row: bytes on disk against the host writer's frames
+                idx = [(0, 0, 0, y, x) for y in range(-(-arr.shape[3] // arr.chunks[3])) for x in range(-(-arr.shape[4] // arr.chunks[4]))]
+                info["first_row_bytes"] = sum(os.path.getsize(arr._chunk_path(i)) for i in idx)
+                info["first_row_host_writer_bytes"] = sum(len(mini_zarr.blosc_encode(arr._read_chunk(i).tobytes(), 2, clevel=3, shuffle=True)) for i in idx)
+                info["size_ratio_to_host_writer"] = round(info["first_row_bytes"] / info["first_row_host_writer_bytes"], 4)
+            pyr["levels"][str(lvl)] = info
     v = res["overlapped"]["planes"] / res["overlapped"]["seconds"]
     # ---- verification (tests/test_zarr_chunk_map.py::test_chunk_map_at_production_geometry_against_the_oracle holds the
     # same statement on a 192-plane store): one plane of every stream part of the first, a middle and the last block --
@@ -88,14 +120,15 @@ try:
                     verified = False
                     print("oracle mismatch", e, file=sys.stderr)
     label = (codec or "raw") + (", encoded on the device" if device_codec else "") + (", decoded on the device" if device_decode else "")
+    label += ", pyramid fused" if fused else ""
     print(json.dumps({"metric": "2048x2048 uint16 slices/s, Zarr store to Zarr store ({} chunks, tmpfs)".format(label), "value": round(v, 1),
                       "planes": n, "seconds": res["overlapped"]["seconds"], "store_make_s": round(t_make, 1),
                       "roofline": {"bound": "host link", "peak_planes_per_s": 3750, "frac": round(v / 3750.0, 3)},
                       "read_s": round(timing["read_s"], 3), "write_s": round(timing["write_s"], 3), "host_link": link,
-                      "plane0_checksum": chk, "verified": verified, **sizes,
+                      "plane0_checksum": chk, "verified": verified, **sizes, **({"pyramid": pyr} if pyr else {}),
                       "verification": {"planes_bit_identical_to_single_plane_runs": checked,
                                        "planes_against_the_cpu_oracle": oracle_checked, "blocks": blocks}}))
-    if not verified:
+    if not verified or not pyr.get("verified", True):
         sys.exit(3)
 finally:
     shutil.rmtree(root, ignore_errors=True)
