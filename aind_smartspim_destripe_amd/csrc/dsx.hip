@@ -121,6 +121,8 @@ struct dsx_ctx {
   uint8_t* zenc_slots = nullptr;
   uint32_t* zenc_sizes = nullptr;
   size_t zenc_blocks = 0;
+  uint8_t* zenc_lits = nullptr;  // runs mode: the literals the runs leave, per zstd block
+  size_t zenc_lit_blocks = 0;
   // dsx_blosc_decode_device: shuffled blocks are decoded here before the un-shuffle, grown on demand
   uint8_t* zdec_scratch = nullptr;
   size_t zdec_bytes = 0;
@@ -1330,6 +1332,7 @@ void dsx_destroy(dsx_ctx* ctx) {
   if (ctx->h_sticky) (void)hipHostFree(ctx->h_sticky);
   if (ctx->zenc_slots) (void)hipFree(ctx->zenc_slots);
   if (ctx->zenc_sizes) (void)hipFree(ctx->zenc_sizes);
+  if (ctx->zenc_lits) (void)hipFree(ctx->zenc_lits);
   if (ctx->zdec_scratch) (void)hipFree(ctx->zdec_scratch);
   if (ctx->ev_xs) (void)hipEventDestroy(ctx->ev_xs);
   for (int i = 0; i < dsx_ctx::kEventSlots; ++i)
@@ -2098,7 +2101,8 @@ int dsx_blosc_encode(const void* src, size_t bytes, int typesize, int clevel, in
 }
 
 namespace {
-const char* zenc_params(int n_chunks, size_t chunk_bytes, int typesize, int clevel) {
+const char* zenc_params(int n_chunks, size_t chunk_bytes, int typesize, int clevel, int mode) {
+  if (mode != DSX_ZENC_LITERALS && mode != DSX_ZENC_RUNS) return "blosc_encode: unknown mode";
   if (typesize != 2) return "blosc_encode: the zstd encoder supports typesize 2 only";
   if (n_chunks < 0 || chunk_bytes % 2 || clevel < 0 || clevel > 9) return "blosc_encode: bad parameters";
   if (chunk_bytes > 0x7FFFFFEFu) return "blosc_encode: chunk larger than a frame can hold";
@@ -2106,18 +2110,28 @@ const char* zenc_params(int n_chunks, size_t chunk_bytes, int typesize, int clev
 }
 }  // namespace
 
+int dsx_blosc_encode_ref_ex(const void* src, int n_chunks, size_t chunk_bytes, int typesize, int clevel, void* frames,
+                            int64_t* offsets, int mode) {
+  if ((!src && n_chunks > 0 && chunk_bytes) || !frames || !offsets) return DSX_EINVAL;
+  if (const char* e = zenc_params(n_chunks, chunk_bytes, typesize, clevel, mode)) return fail(nullptr, DSX_EINVAL, e);
+  dsx::zenc::blosc_encode_host((const uint16_t*)src, (uint64_t)n_chunks, chunk_bytes, clevel, (uint8_t*)frames, offsets,
+                               mode);
+  return DSX_OK;
+}
 int dsx_blosc_encode_ref(const void* src, int n_chunks, size_t chunk_bytes, int typesize, int clevel, void* frames,
                          int64_t* offsets) {
-  if ((!src && n_chunks > 0 && chunk_bytes) || !frames || !offsets) return DSX_EINVAL;
-  if (const char* e = zenc_params(n_chunks, chunk_bytes, typesize, clevel)) return fail(nullptr, DSX_EINVAL, e);
-  dsx::zenc::blosc_encode_host((const uint16_t*)src, (uint64_t)n_chunks, chunk_bytes, clevel, (uint8_t*)frames, offsets);
-  return DSX_OK;
+  return dsx_blosc_encode_ref_ex(src, n_chunks, chunk_bytes, typesize, clevel, frames, offsets, DSX_ZENC_LITERALS);
 }
 
 int dsx_blosc_encode_device(dsx_ctx* ctx, const void* d_src, int n_chunks, size_t chunk_bytes, int typesize,
                             int clevel, void* d_frames, int64_t* d_offsets) {
+  return dsx_blosc_encode_device_ex(ctx, d_src, n_chunks, chunk_bytes, typesize, clevel, d_frames, d_offsets,
+                                    DSX_ZENC_LITERALS);
+}
+int dsx_blosc_encode_device_ex(dsx_ctx* ctx, const void* d_src, int n_chunks, size_t chunk_bytes, int typesize,
+                               int clevel, void* d_frames, int64_t* d_offsets, int mode) {
   if (!ctx || (!d_src && n_chunks > 0 && chunk_bytes) || !d_frames || !d_offsets) return DSX_EINVAL;
-  if (const char* e = zenc_params(n_chunks, chunk_bytes, typesize, clevel)) return fail(ctx, DSX_EINVAL, e);
+  if (const char* e = zenc_params(n_chunks, chunk_bytes, typesize, clevel, mode)) return fail(ctx, DSX_EINVAL, e);
   namespace z = dsx::zenc;
   DSX_HIP(hipSetDevice(ctx->device));
   hipStream_t s = use_main(ctx);
@@ -2138,10 +2152,23 @@ int dsx_blosc_encode_device(dsx_ctx* ctx, const void* d_src, int n_chunks, size_
       return fail(ctx, DSX_ENOMEM, "blosc_encode: cannot allocate the work buffer");
     ctx->zenc_blocks = nblocks;
   }
-  if (!store && nblocks)
-    hipLaunchKernelGGL(z::k_zenc_block, dim3((unsigned)nblocks), dim3(z::kEncThreads), 0, s,
-                       z::EncArgs{(const uint16_t*)d_src, ctx->zenc_slots, ctx->zenc_sizes, (uint64_t)chunk_bytes,
-                                  g.nblocks});
+  if (mode == DSX_ZENC_RUNS && nblocks > ctx->zenc_lit_blocks) {
+    DSX_HIP(hipStreamSynchronize(s));
+    if (ctx->zenc_lits) DSX_HIP(hipFree(ctx->zenc_lits));
+    ctx->zenc_lits = nullptr;
+    ctx->zenc_lit_blocks = 0;
+    if (hipMalloc(&ctx->zenc_lits, nblocks * (size_t)z::kSlotStride) != hipSuccess)
+      return fail(ctx, DSX_ENOMEM, "blosc_encode: cannot allocate the work buffer");
+    ctx->zenc_lit_blocks = nblocks;
+  }
+  const z::EncArgs ea{(const uint16_t*)d_src, ctx->zenc_slots, ctx->zenc_sizes, (uint64_t)chunk_bytes, g.nblocks};
+  if (!store && nblocks) {
+    if (mode == DSX_ZENC_RUNS)
+      hipLaunchKernelGGL(z::k_zenc_block_runs, dim3((unsigned)nblocks), dim3(z::kEncThreads), 0, s,
+                         z::RunArgs{ea, ctx->zenc_lits});
+    else
+      hipLaunchKernelGGL(z::k_zenc_block, dim3((unsigned)nblocks), dim3(z::kEncThreads), 0, s, ea);
+  }
   z::PackArgs pa{(const uint16_t*)d_src, ctx->zenc_slots, ctx->zenc_sizes, (uint8_t*)d_frames, d_offsets,
                  (uint64_t)chunk_bytes, n_chunks, store ? 1 : g.nblocks, store};
   hipLaunchKernelGGL(z::k_zenc_scan, dim3(1), dim3(256), 0, s, pa);

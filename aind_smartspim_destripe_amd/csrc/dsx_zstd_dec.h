@@ -226,19 +226,19 @@ DSX_ZHD inline void rle_table(FseEntry* d, uint8_t sym) {
 }
 
 // predefined distributions (RFC 8878 3.1.1.3.2.2), written as ranges: no constant arrays in device code (scratch)
+// (predefined_norm / predefined_symbols / predefined_log are what the encoder of dsx_zstd_enc.h builds its tables from)
+DSX_ZHD inline int predefined_symbols(int which) { return which == 0 ? 36 : (which == 1 ? 29 : 53); }  // 0 LL, 1 OF, 2 ML
+DSX_ZHD inline int predefined_log(int which) { return which == 1 ? 5 : 6; }
+DSX_ZHD inline int predefined_norm(int which, int i) {
+  if (which == 0)
+    return i == 0 ? 4 : i == 1 ? 3 : i < 13 ? 2 : i < 16 ? 1 : i < 25 ? 2 : i == 25 ? 3 : i == 26 ? 2 : i < 32 ? 1 : -1;
+  if (which == 1) return i < 6 ? 1 : i < 9 ? 2 : i < 24 ? 1 : -1;
+  return i == 0 ? 1 : i == 1 ? 4 : i == 2 ? 3 : i < 9 ? 2 : i < 46 ? 1 : -1;
+}
 DSX_ZHD inline int predefined(Tables& t, int which) {  // 0 LL, 1 OF, 2 ML; returns nsym
-  if (which == 0) {
-    for (int i = 0; i < 36; ++i)
-      t.norm[i] = (int16_t)(i == 0 ? 4 : i == 1 ? 3 : i < 13 ? 2 : i < 16 ? 1 : i < 25 ? 2 : i == 25 ? 3 : i == 26 ? 2
-                            : i < 32 ? 1 : -1);
-    return 36;
-  }
-  if (which == 1) {
-    for (int i = 0; i < 29; ++i) t.norm[i] = (int16_t)(i < 6 ? 1 : i < 9 ? 2 : i < 24 ? 1 : -1);
-    return 29;
-  }
-  for (int i = 0; i < 53; ++i) t.norm[i] = (int16_t)(i == 0 ? 1 : i == 1 ? 4 : i == 2 ? 3 : i < 9 ? 2 : i < 46 ? 1 : -1);
-  return 53;
+  const int nsym = predefined_symbols(which);
+  for (int i = 0; i < nsym; ++i) t.norm[i] = (int16_t)predefined_norm(which, i);
+  return nsym;
 }
 
 // ---- Huffman -----------------------------------------------------------------------------------------------------
@@ -476,7 +476,7 @@ DSX_ZHD inline int seq_table(Tables& t, int which, int mode, const uint8_t* s, u
   const int max_log = which == 0 ? kLogLL : (which == 1 ? kLogOF : kLogML);
   if (mode == 0) {
     const int nsym = predefined(t, which);
-    const int al = which == 1 ? 5 : 6;
+    const int al = predefined_log(which);
     const int st = build_fse(t, d, nsym, al);
     if (st) return -st;
     *lg = al;

@@ -47,7 +47,7 @@ EXPORTED_SYMBOLS = [
     "dsx_stream_wait", "dsx_stream_sync", "dsx_event_record", "dsx_event_sync",
     "dsx_io_read_chunks", "dsx_io_write_chunks", "dsx_io_write_chunks_blosc", "dsx_blosc_decode", "dsx_blosc_encode",
     "dsx_png_unfilter", "dsx_plan_streaks", "dsx_get_streaks_threshold",
-    "dsx_blosc_encode_device", "dsx_blosc_encode_ref",
+    "dsx_blosc_encode_device", "dsx_blosc_encode_ref", "dsx_blosc_encode_device_ex", "dsx_blosc_encode_ref_ex",
     "dsx_io_read_frames", "dsx_blosc_decode_device", "dsx_blosc_decode_ref",
     "dsx_pyramid_work_bytes", "dsx_pyramid_block_u16", "dsx_pyramid_block_ref",
 ]  # fmt: skip
@@ -198,6 +198,8 @@ def load_library(path=None):
                                      ctypes.POINTER(ctypes.c_size_t)]  # fmt: skip
     lib.dsx_blosc_encode_device.argtypes = [vp, vp, i32, ctypes.c_size_t, i32, i32, vp, vp]
     lib.dsx_blosc_encode_ref.argtypes = [vp, i32, ctypes.c_size_t, i32, i32, vp, vp]
+    lib.dsx_blosc_encode_device_ex.argtypes = [vp, vp, i32, ctypes.c_size_t, i32, i32, vp, vp, i32]
+    lib.dsx_blosc_encode_ref_ex.argtypes = [vp, i32, ctypes.c_size_t, i32, i32, vp, vp, i32]
     lib.dsx_io_read_frames.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), i32, ctypes.c_size_t, i32, ctypes.c_uint16,
                                        vp, ctypes.c_size_t, vp, i32, ctypes.POINTER(ctypes.c_size_t),
                                        ctypes.POINTER(i32), vp]  # fmt: skip
@@ -460,13 +462,16 @@ class DestripeEngine:
     def sync(self):
         self._check(self._lib.dsx_sync(self._ctx))
 
-    def blosc_encode_device(self, d_src, n_chunks, chunk_bytes, d_frames, d_offsets, typesize=2, clevel=3):
+    def blosc_encode_device(self, d_src, n_chunks, chunk_bytes, d_frames, d_offsets, typesize=2, clevel=3,
+                            mode="literals"):
         """Blosc-zstd frames of ``n_chunks`` chunks of ``chunk_bytes`` (device buffer ``d_src``), encoded on the device
         into ``d_frames`` (capacity ``n_chunks * (chunk_bytes + 16)``), packed back to back; ``d_offsets`` receives
-        ``n_chunks + 1`` int64 frame offsets.  Asynchronous on the engine stream."""
-        self._check(self._lib.dsx_blosc_encode_device(self._ctx, ctypes.c_void_p(d_src.ptr), int(n_chunks),
-                                                      int(chunk_bytes), int(typesize), int(clevel),
-                                                      ctypes.c_void_p(d_frames.ptr), ctypes.c_void_p(d_offsets.ptr)))  # fmt: skip
+        ``n_chunks + 1`` int64 frame offsets.  ``mode``: one of :data:`ZENC_MODES` (``"runs"``: runs of equal bytes
+        become matches).  Asynchronous on the engine stream."""
+        self._check(self._lib.dsx_blosc_encode_device_ex(self._ctx, ctypes.c_void_p(d_src.ptr), int(n_chunks),
+                                                         int(chunk_bytes), int(typesize), int(clevel),
+                                                         ctypes.c_void_p(d_frames.ptr), ctypes.c_void_p(d_offsets.ptr),
+                                                         zenc_mode(mode)))  # fmt: skip
 
     def timer_start(self):
         self._check(self._lib.dsx_timer_start(self._ctx))
@@ -770,9 +775,22 @@ def pyramid_block_ref(planes, chunks, z0s=None, bricks=None, rows=None):
     return out
 
 
-def blosc_encode_ref(chunks, clevel=3):
-    """Host build of the device encoder (``dsx_blosc_encode_ref``): ``chunks`` = uint16 array ``[n, ...]`` (one chunk
-    per leading index) -> ``(frames: bytes, offsets: int64 [n + 1])``, byte-identical to ``Engine.blosc_encode_device``."""
+# modes of the device Blosc-zstd encoder (DSX_ZENC_* of include/dsx.h)
+ZENC_MODES = {"literals": 0, "runs": 1}
+
+
+def zenc_mode(mode):
+    try:
+        return ZENC_MODES[mode]
+    except (KeyError, TypeError):
+        raise ValueError("unknown encoder mode {!r}: one of {}".format(mode, sorted(ZENC_MODES))) from None
+
+
+def blosc_encode_ref(chunks, clevel=3, mode="literals"):
+    """Host build of the device encoder (``dsx_blosc_encode_ref_ex``): ``chunks`` = uint16 array ``[n, ...]`` (one chunk
+    per leading index) -> ``(frames: bytes, offsets: int64 [n + 1])``, byte-identical to ``Engine.blosc_encode_device``
+    in the same ``mode`` (:data:`ZENC_MODES`)."""
+    mode = zenc_mode(mode)
     lib = load_library()
     a = np.ascontiguousarray(chunks)
     if a.dtype != np.uint16:
@@ -781,8 +799,9 @@ def blosc_encode_ref(chunks, clevel=3):
     chunk_bytes = a.nbytes // n if n else 0
     frames = np.empty(n * (chunk_bytes + 16) + 1, np.uint8)
     offsets = np.zeros(n + 1, np.int64)
-    rc = lib.dsx_blosc_encode_ref(a.ctypes.data_as(ctypes.c_void_p), int(n), int(chunk_bytes), 2, int(clevel),
-                                  frames.ctypes.data_as(ctypes.c_void_p), offsets.ctypes.data_as(ctypes.c_void_p))  # fmt: skip
+    rc = lib.dsx_blosc_encode_ref_ex(a.ctypes.data_as(ctypes.c_void_p), int(n), int(chunk_bytes), 2, int(clevel),
+                                     frames.ctypes.data_as(ctypes.c_void_p), offsets.ctypes.data_as(ctypes.c_void_p),
+                                     mode)  # fmt: skip
     if rc != 0:
         raise DsxError(rc, (lib.dsx_last_error(None) or b"blosc_encode_ref failed").decode())
     return frames[: offsets[-1]].tobytes(), offsets

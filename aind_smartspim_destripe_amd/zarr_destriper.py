@@ -333,7 +333,8 @@ class _DeviceBlocks:
         self.d_bricks_out = [eng.alloc(out_bytes) for _ in range(self.N_BUF)]
         self.d_planes = eng.alloc(block_z * H * W * 2)
         self.d_out = eng.alloc(block_z * H * W * 2)
-        self.device_codec = bool(device_codec)
+        self.codec_mode = device_codec_mode(device_codec)  # None, "literals" or "runs"
+        self.device_codec = self.codec_mode is not None
         self.d_frames, self.d_offsets, self.h_frames, self.h_offsets = [], [], [], []
         if self.device_codec:
             n_chunks = int(np.prod(self.go))
@@ -489,7 +490,8 @@ class _DeviceBlocks:
         if self.device_codec:
             n_chunks = nbo * self.go[1] * self.go[2]
             eng.blosc_encode_device(self.d_bricks_out[k], n_chunks, self.out_brick * 2, self.d_frames[k],
-                                    self.d_offsets[k], typesize=2, clevel=int(self.dst.compressor[1]))  # fmt: skip
+                                    self.d_offsets[k], typesize=2, clevel=int(self.dst.compressor[1]),
+                                    mode=self.codec_mode)  # fmt: skip
             eng.stream_wait(D, C)
             eng.copy_d2h_async(self.offsets[k][: n_chunks + 1], self.d_offsets[k], D)
             for i, j, _ in flushes:
@@ -529,7 +531,7 @@ class _DeviceBlocks:
                 n_chunks = -(-lv.shape[1] // lv.chunks[1]) * -(-lv.shape[2] // lv.chunks[2])
                 eng.blosc_encode_device(self.d_row[i][j], n_chunks, int(np.prod(lv.chunks)) * 2, self.d_pframes[i][j],
                                         self.d_poffsets[i][j], typesize=2,
-                                        clevel=int(self.pyr_arrays[i].compressor[1]))  # fmt: skip
+                                        clevel=int(self.pyr_arrays[i].compressor[1]), mode=self.codec_mode)  # fmt: skip
             flushes.append((i, j, s.row))
             cur[i] = (j + 1) % self.N_BUF
         return flushes
@@ -622,10 +624,21 @@ def _new_timing():
     return {"read_s": 0.0, "write_s": 0.0, "upload_bytes": 0, "download_bytes": 0, "pyramid_download_bytes": 0}
 
 
+def device_codec_mode(device_codec):
+    """The encoder mode a ``device_codec`` argument selects: ``None`` (off), ``"literals"`` (any true value that is
+    not a string: the entropy-only encoder) or ``"runs"`` (the string ``"runs"``).  Any other string: ``ValueError``."""
+    if isinstance(device_codec, str):
+        if device_codec != "runs":
+            raise ValueError("device_codec is False, True or \"runs\", not {!r}".format(device_codec))
+        return "runs"
+    return "literals" if device_codec else None
+
+
 def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False, pyr=None):
     """Staging buffers for this geometry, reused from the previous tile when nothing but the stores changed
     (a channel is tens of tiles of one shape, ``zarr_destriper.py:1231``)."""
-    key = (id(eng), tuple(zyx[1:]), tuple(src.chunks[-3:]), tuple(dst.chunks[-3:]), int(block_z), bool(device_codec),
+    key = (id(eng), tuple(zyx[1:]), tuple(src.chunks[-3:]), tuple(dst.chunks[-3:]), int(block_z),
+           device_codec_mode(device_codec),
            bool(device_decode), tuple((lv.level, lv.shape[1:], lv.chunks) for lv in (pyr[0] if pyr else ())))  # fmt: skip
     cached = _BLOCKS.get("blocks")
     if cached is not None and cached[0] == key and cached[1].eng._ctx is not None:
@@ -719,8 +732,11 @@ def destripe_zarr_store(
 
     ``device_codec``: ``True`` = the output chunks are encoded into Blosc-zstd frames on the GPU
     (``dsx_blosc_encode_device``: Huffman-coded literals, no matches -- about 1.1x the host writer's bytes, any c-blosc
-    reader decodes them) and the host only writes finished bytes.  Needs a Blosc-zstd output with byte shuffle and the
-    device re-tiling path; anything else raises ``ValueError``.  Off by default.
+    reader decodes them) and the host only writes finished bytes.  ``"runs"`` = the same with runs of equal bytes
+    written as zstd matches (``DSX_ZENC_RUNS``): the empty high-byte planes cost a few dozen sequences instead of a bit
+    per voxel, and a chunk is never larger than with ``True``; the pyramid rows of ``pyramid_group`` use the same mode.
+    Any other string raises ``ValueError``; every other value counts by its truth.  Needs a Blosc-zstd output with byte
+    shuffle and the device re-tiling path; anything else raises ``ValueError``.  Off by default.
 
     ``device_decode``: ``True`` = the input chunks are decoded on the GPU (``dsx_blosc_decode_device``): the I/O
     threads only read the files, the compressed frames cross the host link, and a zstd decoder fills the input bricks.
@@ -741,6 +757,8 @@ def destripe_zarr_store(
     from . import pyramid
 
     logger = logger or logging.getLogger("dsx.zarr")
+    codec_mode = device_codec_mode(device_codec)
+    device_codec = codec_mode is not None
     if io_threads is None:
         io_threads = default_io_threads(world_size)
     src = MiniZarrArray.open(dataset_path)
@@ -804,19 +822,19 @@ def destripe_zarr_store(
             raise ValueError("fused_pyramid needs the device re-tiling path (a uint16 store, even planes and "
                              "output-chunk-aligned z blocks)")  # fmt: skip
         pyramid.fused_check_blocks(levels, block_z)
-    LAST_RUN.update(device_codec=bool(device_codec), device_decode=bool(device_decode), fused_pyramid=bool(levels),
-                    pyramid_levels=[lv.level for lv in levels])  # fmt: skip
+    LAST_RUN.update(device_codec=device_codec, device_codec_mode=codec_mode, device_decode=bool(device_decode),
+                    fused_pyramid=bool(levels), pyramid_levels=[lv.level for lv in levels])  # fmt: skip
     if can and device_retile is not False:
         flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
         eng = fl.get_engine(zyx[1:], cells_config, no_cells_config, 2500, flatfield, darkfield,
                             max_batch=min(block_z, 64), device=dev)  # fmt: skip
-        blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec, device_decode,
-                                (levels, pyr_arrays) if levels else None)  # fmt: skip
+        blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, "runs" if codec_mode == "runs" else device_codec,
+                                device_decode, (levels, pyr_arrays) if levels else None)  # fmt: skip
         n_planes = blocks.run_range(z0, z1)
         eng.sync()
         dt = time.perf_counter() - t0
         logger.info("rank %d: %d planes z[%d:%d) in %.2f s (device re-tiling%s, overlapped; read %.2f s, write %.2f s)",
-                    rank, n_planes, z0, z1, dt, (", device codec" if device_codec else "")
+                    rank, n_planes, z0, z1, dt, (", device codec" + (" (runs)" if codec_mode == "runs" else "") if device_codec else "")
                     + (", device decode" if device_decode else "")
                     + (", pyramid levels 1..{} fused".format(len(levels)) if levels else ""), blocks.timing["read_s"],
                     blocks.timing["write_s"])  # fmt: skip
@@ -996,11 +1014,12 @@ def destripe_zarr(
     Keyword-only extras (the engine's): ``rank`` / ``world_size`` / ``group`` (one process per GPU, chunk-aligned
     z-ranges; with a ``distributed.RankGroup`` rank 0 alone reads the dark plane and broadcasts it), ``device``,
     ``compressor`` / ``output_chunks`` of the output, ``n_levels``, ``device_retile``, ``io_threads``, ``device_codec``, ``device_decode``
-    (level 0 encoded / decoded on the GPU, :func:`destripe_zarr_store`), ``fused_pyramid`` (levels ``1 .. n_levels - 1``
+    (level 0 encoded / decoded on the GPU, :func:`destripe_zarr_store`; ``device_codec="runs"`` = with run matches), ``fused_pyramid`` (levels ``1 .. n_levels - 1``
     are written by every rank in the level-0 pass, from the filtered planes in device memory, instead of by
     :func:`compute_multiscale` on rank 0 afterwards; same stores; z shards of ``output z chunk << (levels - 1)`` planes).
     Returns ``(planes processed by this rank, seconds)``.
     """
+    device_codec_mode(device_codec)  # (a wrong string fails before anything is written)
     no_cells_config = parameters["no_cells_config"]
     cells_config = parameters["cells_config"]
     co_cpus = _cpu_limit()
@@ -1145,6 +1164,7 @@ def destripe_channel(
     """
     if world_size > 1 and group is None:
         raise ValueError("destripe_channel with world_size > 1 needs a group to order the pyramid after all ranks")
+    device_codec_mode(device_codec)  # (a wrong string fails before anything is written)
     logger = logger or logging.getLogger("dsx.zarr")
     zarr_dataset_path, results_folder = Path(zarr_dataset_path), Path(results_folder)
     channel_dataset = zarr_dataset_path.joinpath(channel_name)

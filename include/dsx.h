@@ -234,11 +234,24 @@ int dsx_blosc_encode(const void* src, size_t bytes, int typesize, int clevel, in
  * n_chunks + 1 int64 -- frame i is bytes [d_offsets[i], d_offsets[i + 1]).  typesize must be 2, chunk_bytes even;
  * clevel 0 stores every chunk, 1 ... 9 encode (the level does not change the encoding).  Asynchronous on the context
  * stream; the context keeps a work buffer of ~chunk_bytes + 64 per chunk.
- * dsx_blosc_encode_ref: the host build of the same encoder, byte-identical output (host pointers, synchronous). */
+ * dsx_blosc_encode_ref: the host build of the same encoder, byte-identical output (host pointers, synchronous).
+ * The _ex forms take a mode.  DSX_ZENC_LITERALS: the above, byte for byte.  DSX_ZENC_RUNS: a zstd block may carry
+ * sequences -- every run of >= 8 equal bytes inside a 128 KiB zstd block is one literal and one match of offset 1
+ * (predefined FSE tables; at most 1024 sequences per block), the literals left are RLE, raw or Huffman; per zstd block
+ * the smaller of the two encodings is written, so a frame is never larger than in DSX_ZENC_LITERALS.  On synthetic
+ * (64, 128, 128) bricks: 1.00x the bytes of the host writer (zstd level 5) instead of 1.10x
+ * (profiles/device_codec_runs_sizes.json).  No general matches, no offsets other than 1, typesize 2 only.  The
+ * context keeps a second work buffer of the same size in this mode.  Any other mode: DSX_EINVAL. */
+#define DSX_ZENC_LITERALS 0
+#define DSX_ZENC_RUNS 1
 int dsx_blosc_encode_device(dsx_ctx* ctx, const void* d_src, int n_chunks, size_t chunk_bytes, int typesize,
                             int clevel, void* d_frames, int64_t* d_offsets);
 int dsx_blosc_encode_ref(const void* src, int n_chunks, size_t chunk_bytes, int typesize, int clevel, void* frames,
                          int64_t* offsets);
+int dsx_blosc_encode_device_ex(dsx_ctx* ctx, const void* d_src, int n_chunks, size_t chunk_bytes, int typesize,
+                               int clevel, void* d_frames, int64_t* d_offsets, int mode);
+int dsx_blosc_encode_ref_ex(const void* src, int n_chunks, size_t chunk_bytes, int typesize, int clevel, void* frames,
+                            int64_t* offsets, int mode);
 
 /* Blosc-zstd chunks decoded on the device (csrc/dsx_zstd_dec.h, csrc/dsx_zdec_kernels.h).
  * dsx_io_read_frames: n chunk files -> their frames packed back to back into `packed` (host memory, capacity

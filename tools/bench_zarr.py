@@ -4,10 +4,11 @@
 download) into another store.  Prints one JSON line; the roofline of this path is the host link
 (PCIe Gen5 x16, 63 GB/s spec: 16.8 MB per plane both ways -> <= 3.7 k planes/s), not HBM.
 
-    bench_zarr.py N [raw|zlib|blosc] [device-codec] [device-decode] [pyramid|fused-pyramid]
+    bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode] [pyramid|fused-pyramid]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
 line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
+`device-codec-runs`: the same with runs of equal bytes written as matches (device_codec="runs").
 `device-decode` (Blosc only): the input chunks are decoded on the GPU (destripe_zarr_store(device_decode=True)).
 `pyramid`: after the timed level-0 pass, compute_multiscale(n_levels=3) on the store is timed too (the two-pass route);
 `fused-pyramid`: level 0 and levels 1-2 in one destripe_zarr_store call (pyramid_group / n_levels).  Both add level-0,
@@ -24,7 +25,7 @@ from aind_smartspim_destripe_amd.mini_zarr import MiniZarrArray
 logging.basicConfig(level=logging.INFO, stream=sys.stderr)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 codec = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2] != "raw" else None  # None (raw chunks), "zlib" or "blosc" (Blosc-zstd)
-device_codec = "device-codec" in sys.argv[3:]
+device_codec = "runs" if "device-codec-runs" in sys.argv[3:] else "device-codec" in sys.argv[3:]
 device_decode = "device-decode" in sys.argv[3:]
 two_pass, fused = "pyramid" in sys.argv[3:], "fused-pyramid" in sys.argv[3:]
 H = W = 2048
@@ -119,7 +120,7 @@ try:
                 except AssertionError as e:
                     verified = False
                     print("oracle mismatch", e, file=sys.stderr)
-    label = (codec or "raw") + (", encoded on the device" if device_codec else "") + (", decoded on the device" if device_decode else "")
+    label = (codec or "raw") + (", encoded on the device" + (" with run matches" if device_codec == "runs" else "") if device_codec else "") + (", decoded on the device" if device_decode else "")
     label += ", pyramid fused" if fused else ""
     print(json.dumps({"metric": "2048x2048 uint16 slices/s, Zarr store to Zarr store ({} chunks, tmpfs)".format(label), "value": round(v, 1),
                       "planes": n, "seconds": res["overlapped"]["seconds"], "store_make_s": round(t_make, 1),
