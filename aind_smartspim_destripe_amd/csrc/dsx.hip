@@ -2178,16 +2178,24 @@ int dsx_blosc_encode_device_ex(dsx_ctx* ctx, const void* d_src, int n_chunks, si
   return DSX_OK;
 }
 
+int dsx_io_read_frames_ex(dsx_ctx* ctx, const char* const* paths, int n, size_t chunk_bytes, int threads,
+                          uint16_t fill_value, void* packed, size_t packed_capacity, void* tasks, int task_capacity,
+                          size_t* packed_bytes, int* n_tasks, uint8_t* routes, int mode) {
+  if (n < 0 || (n > 0 && (!paths || !packed || !tasks)) || !packed_bytes || !n_tasks || task_capacity < 0)
+    return DSX_EINVAL;
+  if (mode != DSX_ZDEC_ZSTD && mode != DSX_ZDEC_ANY) return DSX_EINVAL;
+  const std::string e = dsx::io_read_frames(paths, n, chunk_bytes, threads, fill_value, (unsigned char*)packed,
+                                            packed_capacity, (dsx::zdec::DecTask*)tasks, (size_t)task_capacity,
+                                            packed_bytes, n_tasks, routes, mode);
+  if (!e.empty()) return fail(ctx, DSX_EIO, e);
+  return DSX_OK;
+}
+
 int dsx_io_read_frames(dsx_ctx* ctx, const char* const* paths, int n, size_t chunk_bytes, int threads,
                        uint16_t fill_value, void* packed, size_t packed_capacity, void* tasks, int task_capacity,
                        size_t* packed_bytes, int* n_tasks, uint8_t* routes) {
-  if (n < 0 || (n > 0 && (!paths || !packed || !tasks)) || !packed_bytes || !n_tasks || task_capacity < 0)
-    return DSX_EINVAL;
-  const std::string e = dsx::io_read_frames(paths, n, chunk_bytes, threads, fill_value, (unsigned char*)packed,
-                                            packed_capacity, (dsx::zdec::DecTask*)tasks, (size_t)task_capacity,
-                                            packed_bytes, n_tasks, routes);
-  if (!e.empty()) return fail(ctx, DSX_EIO, e);
-  return DSX_OK;
+  return dsx_io_read_frames_ex(ctx, paths, n, chunk_bytes, threads, fill_value, packed, packed_capacity, tasks,
+                               task_capacity, packed_bytes, n_tasks, routes, DSX_ZDEC_ZSTD);
 }
 
 int dsx_blosc_decode_ref(const void* packed, size_t packed_bytes, const void* tasks, int n_tasks, void* out,
@@ -2206,7 +2214,7 @@ int dsx_blosc_decode_ref(const void* packed, size_t packed_bytes, const void* ta
       continue;
     }
     tmp.resize(k.dst_len);
-    status[i] = z::run_task_host(*work, k, (const uint8_t*)packed, (uint8_t*)out, tmp.data());
+    status[i] = z::run_task_host_any(*work, k, (const uint8_t*)packed, (uint8_t*)out, tmp.data());
   }
   delete work;
   return DSX_OK;

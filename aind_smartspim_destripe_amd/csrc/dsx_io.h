@@ -31,6 +31,7 @@
 #include <unistd.h>
 #include <zlib.h>
 
+#include "dsx_lz4_dec.h"
 #include "dsx_zstd_dec.h"
 
 #include <algorithm>
@@ -495,12 +496,17 @@ inline std::string io_read_chunks(const char* const* paths, void* const* dst, co
 // at most frame_tasks_per_chunk blocks -> one task per block (a zstd frame, or a stored stream); memcpyed frames -> one
 // copy task; a missing file -> one fill task.  Any other frame is decoded here by blosc_decode (its error is the
 // error of the read) and shipped as a copy task.
+// mode kZdecAny (DSX_ZDEC_ANY) widens the device's share to what dsx_lz4_dec.h decodes: LZ4 / LZ4HC inside, bit
+// shuffle, and split blocks (zstd or LZ4) -- one task per Blosc block still: a split task's src is the length word of
+// its first stream and its src_len spans both streams.  Type sizes other than 2, blosclz / zlib / snappy, zstd
+// checksums and chunks of more than frame_tasks_per_chunk blocks stay on the host.
+constexpr int kZdecZstd = 0, kZdecAny = 1;
 inline size_t frame_tasks_per_chunk(size_t chunk_bytes) { return chunk_bytes / 8192 + 1; }
 enum FrameRoute { kRouteDevice = 0, kRouteHost = 1, kRouteFill = 2 };
 
 // Tasks of one frame (src offsets relative to the frame, dst offsets relative to the chunk) if the device takes it
 inline bool blosc_device_route(const unsigned char* src, size_t n, size_t want, size_t max_tasks,
-                               std::vector<zdec::DecTask>& out, size_t* frame_bytes) {
+                               std::vector<zdec::DecTask>& out, size_t* frame_bytes, int mode = kZdecZstd) {
   out.clear();
   if (n < (size_t)kBloscHeader || n > want + kBloscHeader) return false;
   const unsigned version = src[0], flags = src[2], typesize = src[3];
@@ -513,8 +519,13 @@ inline bool blosc_device_route(const unsigned char* src, size_t n, size_t want, 
     out.push_back(zdec::DecTask{(uint64_t)kBloscHeader, 0, (uint32_t)nbytes, (uint32_t)nbytes, zdec::kTaskCopy, 0});
     return true;
   }
-  if (typesize != 2 || ((flags >> 5) & 7) != kInnerZstd || (flags & kBloscBitshuffle)) return false;
-  const uint32_t shuf = (flags & kBloscShuffle) ? zdec::kTaskShuffle : 0u;
+  const int inner = (flags >> 5) & 7;
+  const bool any = mode == kZdecAny;
+  if (typesize != 2 || (inner != kInnerZstd && !(any && inner == kInnerLz4))) return false;
+  if ((flags & kBloscBitshuffle) && !any) return false;
+  const uint32_t shuf = (flags & kBloscBitshuffle) ? zdec::kTaskBitshuffle
+                                                   : ((flags & kBloscShuffle) ? zdec::kTaskShuffle : 0u);
+  const uint32_t coded = inner == kInnerZstd ? (uint32_t)zdec::kTaskZstd : zdec::kTaskLz4;
   const bool dont_split = (flags & kBloscDontSplit) != 0;
   if (blocksize == 0 || blocksize > nbytes) return false;
   const size_t nblocks = (nbytes + blocksize - 1) / blocksize;
@@ -522,16 +533,30 @@ inline bool blosc_device_route(const unsigned char* src, size_t n, size_t want, 
   for (size_t b = 0; b < nblocks; ++b) {
     const size_t bsize = (b + 1 == nblocks) ? nbytes - b * blocksize : blocksize;
     const bool leftover = bsize != blocksize;
-    if (!dont_split && !leftover && blocksize / typesize >= (size_t)kBloscMinBuffer) return false;  // split streams
     size_t pos = le32(src + kBloscHeader + 4 * b);
+    if (!dont_split && !leftover && blocksize / typesize >= (size_t)kBloscMinBuffer) {  // split streams
+      if (!any || (blocksize % typesize) != 0) return false;
+      const size_t start = pos, ne = bsize / typesize;
+      for (size_t j = 0; j < typesize; ++j) {
+        if (pos + 4 > cbytes) return false;
+        const size_t cs = le32(src + pos);
+        pos += 4;
+        if (cs > cbytes - pos) return false;
+        if (cs != ne && inner == kInnerZstd && !zdec::device_frame(src + pos, (uint32_t)cs, (uint32_t)ne)) return false;
+        pos += cs;
+      }
+      out.push_back(zdec::DecTask{(uint64_t)start, (uint64_t)(b * blocksize), (uint32_t)(pos - start), (uint32_t)bsize,
+                                  coded | zdec::kTaskSplit | shuf, 0});
+      continue;
+    }
     if (pos + 4 > cbytes) return false;
     const size_t cs = le32(src + pos);
     pos += 4;
     if (cs > cbytes - pos) return false;
     uint32_t kind = zdec::kTaskStored;
     if (cs != bsize) {
-      if (!zdec::device_frame(src + pos, (uint32_t)cs, (uint32_t)bsize)) return false;
-      kind = zdec::kTaskZstd;
+      if (inner == kInnerZstd && !zdec::device_frame(src + pos, (uint32_t)cs, (uint32_t)bsize)) return false;
+      kind = coded;
     }
     out.push_back(zdec::DecTask{(uint64_t)pos, (uint64_t)(b * blocksize), (uint32_t)cs, (uint32_t)bsize, kind | shuf, 0});
   }
@@ -543,7 +568,7 @@ inline bool blosc_device_route(const unsigned char* src, size_t n, size_t want, 
 // in no particular order.  routes (optional): FrameRoute per chunk.
 inline std::string io_read_frames(const char* const* paths, int n, size_t chunk_bytes, int threads, uint16_t fill,
                                   unsigned char* packed, size_t packed_cap, zdec::DecTask* tasks, size_t task_cap,
-                                  size_t* packed_bytes, int* n_tasks, unsigned char* routes) {
+                                  size_t* packed_bytes, int* n_tasks, unsigned char* routes, int mode = kZdecZstd) {
   const size_t per = frame_tasks_per_chunk(chunk_bytes);
   if (chunk_bytes > 0x7FFFFFEFu) return "io_read_frames: chunk larger than a frame can hold";
   if (packed_cap < (size_t)n * (chunk_bytes + kBloscHeader) || task_cap < (size_t)n * per)
@@ -564,7 +589,7 @@ inline std::string io_read_frames(const char* const* paths, int n, size_t chunk_
     if (io_read_file(paths[i], raw.data(), raw.size()) != (long long)raw.size())
       return std::string("short or failed read of chunk ") + paths[i];
     size_t fbytes = 0;
-    if (blosc_device_route(raw.data(), raw.size(), chunk_bytes, per, local, &fbytes)) {
+    if (blosc_device_route(raw.data(), raw.size(), chunk_bytes, per, local, &fbytes, mode)) {
       const size_t off = at.fetch_add(fbytes);
       memcpy(packed + off, raw.data(), fbytes);
       const size_t j = nt.fetch_add(local.size());

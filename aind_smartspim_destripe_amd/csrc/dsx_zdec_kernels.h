@@ -11,11 +11,19 @@
 //            fence orders the global stores before the loads that follow) and passes another barrier only when the
 //            match source reaches above it.  A shuffled task decodes into scratch and is un-shuffled into the bricks
 //            after one more barrier.  One int32 status per task (dsx_zstd_dec.h Status; 0 = exact output).
+//            An LZ4 task (dsx_lz4_dec.h) has no tables to build: every lane parses the same token from a window of
+//            the stream staged in LDS (the reads are broadcasts, the wave refills the window together when the parse
+//            leaves it), then the wave copies the literals -- out of the window when they lie in it -- and the match
+//            as the zstd sequences do, behind the same watermark.  A split task holds two streams behind an int32
+//            length each (stored, zstd or LZ4): the wave decodes them one after the other into the two halves of
+//            the block and un-shuffles after both.  A bit-shuffled task is un-shuffled by 8 x 8 bit transposes, 8
+//            elements per lane and round.
 #ifndef DSX_ZDEC_KERNELS_H
 #define DSX_ZDEC_KERNELS_H
 
 #include <hip/hip_runtime.h>
 
+#include "dsx_lz4_dec.h"
 #include "dsx_zstd_dec.h"
 
 namespace dsx {
@@ -96,43 +104,108 @@ __device__ inline void wave_unshuffle(uint8_t* d, const uint8_t* s, uint32_t n, 
   if ((n & 1u) && lane == 0) d[n - 1] = s[n - 1];
 }
 
-__global__ void __launch_bounds__(kDecThreads) k_zdec(DecArgs a) {
-  __shared__ Tables t;
-  __shared__ Seq batch[kSeqBatch];
-  __shared__ Streams ss;
-  __shared__ int32_t sh_st, sh_cnt, sh_lst[4];
-  __shared__ uint32_t sh_u[8];  // broadcast scalars of lane 0
-  __shared__ uint32_t sh_blo[4];
-  __shared__ uint8_t lbuf[4][kLitWin];
-  const int lane = threadIdx.x;
-  const DecTask k = a.tasks[blockIdx.x];
-  const uint32_t kind = k.kind & kTaskKindMask;
-  const bool shuf = (k.kind & kTaskShuffle) != 0;
-  const uint32_t out_n = k.dst_len, n = k.src_len;
-  if (k.dst > a.out_bytes || out_n > a.out_bytes - k.dst ||
-      (kind != kTaskFill && (k.src > a.packed_bytes || n > a.packed_bytes - k.src))) {
-    if (lane == 0) a.status[blockIdx.x] = kErrOutput;
+// bit un-shuffle of n bytes s -> d (dsx_lz4_dec.h unbitshuffle8: 8 elements = 16 bytes per lane and round)
+__device__ __forceinline__ void wave_unbitshuffle(uint8_t* d, const uint8_t* s, uint32_t n, int lane) {
+  if (!bitshuffled(n)) {
+    wave_copy(d, s, n, lane);
     return;
   }
-  uint8_t* d = a.out + k.dst;
-  if (kind == kTaskFill) {
-    for (uint32_t i = (uint32_t)lane; i < out_n; i += 64) d[i] = (uint8_t)(k.src >> (8 * (i & 1)));
-    if (lane == 0) a.status[blockIdx.x] = kOk;
-    return;
-  }
-  const uint8_t* s = a.packed + k.src;
-  if (kind != kTaskZstd) {  // copy / stored
-    if (n != out_n) {
-      if (lane == 0) a.status[blockIdx.x] = kErrOutput;
-      return;
+  const uint32_t row = n / 16;
+  const bool wide = ((uintptr_t)d & 15u) == 0;
+  for (uint32_t j = (uint32_t)lane; j < row; j += 64) {
+    uint64_t w0, w1;
+    unbitshuffle8(s, row, j, &w0, &w1);
+    if (wide) {
+      ((uint4*)d)[j] = make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32));
+    } else {
+      for (int i = 0; i < 8; ++i) {
+        d[16 * j + (uint32_t)i] = (uint8_t)(w0 >> (8 * i));
+        d[16 * j + 8 + (uint32_t)i] = (uint8_t)(w1 >> (8 * i));
+      }
     }
-    if (shuf) wave_unshuffle(d, s, n, lane);
-    else wave_copy(d, s, n, lane);
-    if (lane == 0) a.status[blockIdx.x] = kOk;
-    return;
   }
+  if ((n & 1u) && lane == 0) d[n - 1] = s[n - 1];
+}
 
-  uint8_t* o = shuf ? a.scratch + k.dst : d;
+// LDS of one wave: the tables and staging of the zstd decoder; an LZ4 stream stages its window in lbuf
+struct WaveLds {
+  Tables t;
+  Seq batch[kSeqBatch];
+  Streams ss;
+  int32_t sh_st, sh_cnt, sh_lst[4];
+  uint32_t sh_u[8];  // broadcast scalars of lane 0
+  uint32_t sh_blo[4];
+  uint8_t lbuf[4][kLitWin];
+};
+
+constexpr uint32_t kLz4Win = 2048;  // bytes of an LZ4 stream staged in LDS (within WaveLds::lbuf)
+
+// The bytes of an LZ4 stream for lz4_next, read by every lane alike: a window [lo, lo + cnt) of the stream in LDS
+// that the wave refills together (uniform control flow) at the first byte asked for outside it.
+struct Lz4Window {
+  const uint8_t* s;
+  uint32_t n;
+  uint8_t* win;
+  uint32_t lo, cnt;
+  int lane;
+  __device__ uint8_t at(uint32_t p) {  // p < n
+    if (p - lo >= cnt) {
+      __syncthreads();  // the reads of the window so far
+      lo = p;
+      cnt = n - p < kLz4Win ? n - p : kLz4Win;
+      for (uint32_t i0 = 0; i0 < cnt; i0 += 8 * 64) {
+        uint8_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const uint32_t i = i0 + (uint32_t)lane + 64u * u;
+          v[u] = i < cnt ? s[p + i] : (uint8_t)0;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) win[i0 + (uint32_t)lane + 64u * u] = v[u];  // (kLz4Win is a multiple of 512)
+      }
+      __syncthreads();
+    }
+    return win[p - lo];
+  }
+};
+
+// One bare LZ4 block s[0 .. n) -> o[0 .. out_n) by the wave; returns a status (the same in every lane)
+__device__ __forceinline__ int lz4_wave(uint8_t* win, const uint8_t* s, uint32_t n, uint8_t* o, uint32_t out_n, int lane) {
+  Lz4Window r{s, n, win, 0, 0, lane};
+  uint32_t ip = 0, op = 0, fenced = 0;
+  for (;;) {
+    Lz4Seq q;
+    const uint32_t at = op;
+    const int st = lz4_next(r, n, out_n, ip, op, q);
+    if (st) return st;
+    if (q.lit >= r.lo && q.lit - r.lo + q.ll <= r.cnt) {  // the literals are staged: stores only
+      const uint8_t* w = win + (q.lit - r.lo);
+      for (uint32_t i = (uint32_t)lane; i < q.ll; i += 64) o[at + i] = w[i];
+    } else {
+      wave_copy(o + at, s + q.lit, q.ll, lane);
+    }
+    if (q.ml == 0) break;
+    const uint32_t wop = at + q.ll, src = wop - q.off;
+    const uint32_t span = q.ml < q.off ? q.ml : q.off;
+    if (src + span > fenced) {
+      __syncthreads();  // (uniform) earlier stores before the match loads
+      fenced = wop;
+    }
+    if (q.off >= q.ml) wave_copy(o + wop, o + src, q.ml, lane);
+    else wave_pattern(o + wop, q.off, q.ml, lane);
+  }
+  return op == out_n ? kOk : kErrOutput;
+}
+
+// One zstd frame s[0 .. n) -> o[0 .. out_n) by the wave; returns a status (the same in every lane)
+__device__ __forceinline__ int zstd_wave(WaveLds& sh, const uint8_t* s, uint32_t n, uint8_t* o, uint32_t out_n, int lane) {
+  Tables& t = sh.t;
+  Seq* batch = sh.batch;
+  Streams& ss = sh.ss;
+  int32_t &sh_st = sh.sh_st, &sh_cnt = sh.sh_cnt;
+  int32_t* sh_lst = sh.sh_lst;
+  uint32_t *sh_u = sh.sh_u, *sh_blo = sh.sh_blo;
+  uint8_t(*lbuf)[kLitWin] = sh.lbuf;
   SeqState q;  // lane 0's sequence decoder (its repeat offsets live for the frame)
   if (lane == 0) {
     FrameHdr fh;
@@ -362,9 +435,64 @@ __global__ void __launch_bounds__(kDecThreads) k_zdec(DecArgs a) {
   }
   if (!st && op != out_n) st = kErrOutput;
   if (!st && ip != n) st = kErrTruncated;
-  if (!st && shuf) {
-    __syncthreads();
-    wave_unshuffle(d, o, out_n, lane);
+  return st;
+}
+
+__global__ void __launch_bounds__(kDecThreads) k_zdec(DecArgs a) {
+  __shared__ WaveLds sh;
+  const int lane = threadIdx.x;
+  const DecTask k = a.tasks[blockIdx.x];
+  const uint32_t kind = k.kind & kTaskKindMask;
+  const bool split = (k.kind & kTaskSplit) != 0, bits = (k.kind & kTaskBitshuffle) != 0;
+  const bool shuf = !bits && (k.kind & kTaskShuffle) != 0;
+  const uint32_t out_n = k.dst_len, n = k.src_len;
+  if (k.dst > a.out_bytes || out_n > a.out_bytes - k.dst ||
+      (kind != kTaskFill && (k.src > a.packed_bytes || n > a.packed_bytes - k.src))) {
+    if (lane == 0) a.status[blockIdx.x] = kErrOutput;
+    return;
+  }
+  uint8_t* d = a.out + k.dst;
+  if (kind == kTaskFill) {
+    for (uint32_t i = (uint32_t)lane; i < out_n; i += 64) d[i] = (uint8_t)(k.src >> (8 * (i & 1)));
+    if (lane == 0) a.status[blockIdx.x] = kOk;
+    return;
+  }
+  const uint8_t* s = a.packed + k.src;
+  const bool plain = !split && (kind == kTaskCopy || kind == kTaskStored);  // the bytes are there: un-shuffle or copy
+  if (!plain && kind != kTaskZstd && kind != kTaskLz4) {
+    if (lane == 0) a.status[blockIdx.x] = kErrReserved;
+    return;
+  }
+  uint8_t* o = (shuf || bits) ? a.scratch + k.dst : d;
+  // the streams of the block one after the other, each into its share of the block: a split block holds a low-byte
+  // and a high-byte stream behind an int32 length each (a length of the whole share: stored), any other block is
+  // its one stream
+  const uint32_t nstreams = split ? kSplitStreams : 1u;
+  const uint32_t ne = out_n / nstreams;
+  int st = out_n % nstreams ? kErrOutput : kOk;
+  if (plain && n != out_n) st = kErrOutput;
+  uint32_t pos = 0;
+  for (uint32_t j = 0; j < nstreams && !st && !plain; ++j) {
+    uint32_t at = 0, len = n;
+    if (split) {
+      st = split_stream(s, n, &pos, &at, &len);
+      if (st) break;
+      __syncthreads();  // the LDS of the stream before
+    }
+    if (split && len == ne) wave_copy(o + j * ne, s + at, ne, lane);  // stored
+    else if (kind == kTaskZstd) st = zstd_wave(sh, s + at, len, o + j * ne, ne, lane);
+    else st = lz4_wave(&sh.lbuf[0][0], s + at, len, o + j * ne, ne, lane);
+  }
+  if (split && !st && pos != n) st = kErrTruncated;
+  if (!st) {
+    const uint8_t* from = plain ? s : o;
+    if (shuf || bits) {
+      __syncthreads();  // the decoded bytes are visible to the wave
+      if (bits) wave_unbitshuffle(d, from, out_n, lane);
+      else wave_unshuffle(d, from, out_n, lane);
+    } else if (plain) {
+      wave_copy(d, s, n, lane);
+    }
   }
   if (lane == 0) a.status[blockIdx.x] = st;
 }

@@ -23,8 +23,9 @@ STAGE_APPROX, STAGE_DETAIL = 0, 1
 STREAM_COMPUTE, STREAM_UPLOAD, STREAM_DOWNLOAD = 0, 1, 2
 
 # Blosc block tasks of the device decoder (csrc/dsx_zstd_dec.h DecTask): kinds, the un-shuffle flag, routes per chunk
-TASK_FILL, TASK_COPY, TASK_STORED, TASK_ZSTD = 0, 1, 2, 3
-TASK_SHUFFLE = 0x100
+TASK_FILL, TASK_COPY, TASK_STORED, TASK_ZSTD, TASK_LZ4 = 0, 1, 2, 3, 4
+TASK_SHUFFLE, TASK_SPLIT, TASK_BITSHUFFLE = 0x100, 0x200, 0x400  # (csrc/dsx_lz4_dec.h: split streams, bit un-shuffle)
+ZDEC_ZSTD, ZDEC_ANY = 0, 1  # DSX_ZDEC_*: what dsx_io_read_frames_ex routes to the device
 ROUTE_DEVICE, ROUTE_HOST, ROUTE_FILL = 0, 1, 2
 TASK_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<u4"), ("dst_len", "<u4"), ("kind", "<u4"),
                        ("chunk", "<u4")])  # fmt: skip
@@ -48,7 +49,7 @@ EXPORTED_SYMBOLS = [
     "dsx_io_read_chunks", "dsx_io_write_chunks", "dsx_io_write_chunks_blosc", "dsx_blosc_decode", "dsx_blosc_encode",
     "dsx_png_unfilter", "dsx_plan_streaks", "dsx_get_streaks_threshold",
     "dsx_blosc_encode_device", "dsx_blosc_encode_ref", "dsx_blosc_encode_device_ex", "dsx_blosc_encode_ref_ex",
-    "dsx_io_read_frames", "dsx_blosc_decode_device", "dsx_blosc_decode_ref",
+    "dsx_io_read_frames", "dsx_io_read_frames_ex", "dsx_blosc_decode_device", "dsx_blosc_decode_ref",
     "dsx_pyramid_work_bytes", "dsx_pyramid_block_u16", "dsx_pyramid_block_ref",
 ]  # fmt: skip
 
@@ -203,6 +204,7 @@ def load_library(path=None):
     lib.dsx_io_read_frames.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), i32, ctypes.c_size_t, i32, ctypes.c_uint16,
                                        vp, ctypes.c_size_t, vp, i32, ctypes.POINTER(ctypes.c_size_t),
                                        ctypes.POINTER(i32), vp]  # fmt: skip
+    lib.dsx_io_read_frames_ex.argtypes = lib.dsx_io_read_frames.argtypes + [i32]
     lib.dsx_blosc_decode_device.argtypes = [vp, vp, ctypes.c_size_t, vp, i32, vp, ctypes.c_size_t, vp]
     lib.dsx_blosc_decode_ref.argtypes = [vp, ctypes.c_size_t, vp, i32, vp, ctypes.c_size_t, vp]
     lib.dsx_pyramid_work_bytes.argtypes = [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
@@ -569,13 +571,14 @@ class DestripeEngine:
             return
         self._check(self._lib.dsx_io_write_chunks(self._ctx, cp, dp, nb, n, int(threads), int(zlib_level)))
 
-    def io_read_frames(self, paths, chunk_bytes, packed, tasks, threads=16, fill_value=0, routes=None):
+    def io_read_frames(self, paths, chunk_bytes, packed, tasks, threads=16, fill_value=0, routes=None, mode=0):
         """Chunk files ``paths[i]`` (Blosc) -> frames packed into the uint8 array ``packed`` and Blosc block tasks
         into the ``TASK_DTYPE`` array ``tasks`` (``dsx_io_read_frames``); chunk i decodes to bytes
         ``[i * chunk_bytes, (i + 1) * chunk_bytes)``.  ``routes``: optional uint8 array of ``len(paths)`` (``ROUTE_*``).
-        Returns ``(packed_bytes, n_tasks)``."""
+        ``mode``: ``ZDEC_ZSTD`` (0: unsplit zstd streams go to the device) or ``ZDEC_ANY`` (1: LZ4, split streams and
+        bit shuffle too, ``dsx_io_read_frames_ex``).  Returns ``(packed_bytes, n_tasks)``."""
         return _io_read_frames(self._lib, self._ctx, paths, chunk_bytes, packed, tasks, threads, fill_value, routes,
-                               self._check)  # fmt: skip
+                               self._check, mode)  # fmt: skip
 
     def event_record(self, slot, stream):
         self._check(self._lib.dsx_event_record(self._ctx, int(slot), int(stream)))
@@ -807,23 +810,24 @@ def blosc_encode_ref(chunks, clevel=3, mode="literals"):
     return frames[: offsets[-1]].tobytes(), offsets
 
 
-def _io_read_frames(lib, ctx, paths, chunk_bytes, packed, tasks, threads, fill_value, routes, check):
+def _io_read_frames(lib, ctx, paths, chunk_bytes, packed, tasks, threads, fill_value, routes, check, mode=0):
     n = len(paths)
     assert packed.dtype == np.uint8 and packed.flags["C_CONTIGUOUS"] and tasks.dtype == TASK_DTYPE
     if routes is not None:
         assert routes.dtype == np.uint8 and routes.size >= n
     cp = (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths])
     pb, nt = ctypes.c_size_t(0), ctypes.c_int32(0)
-    check(lib.dsx_io_read_frames(ctx, cp, n, int(chunk_bytes), int(threads), int(fill_value),
-                                 packed.ctypes.data_as(ctypes.c_void_p), packed.nbytes,
-                                 tasks.ctypes.data_as(ctypes.c_void_p), int(tasks.size), ctypes.byref(pb),
-                                 ctypes.byref(nt), routes.ctypes.data_as(ctypes.c_void_p) if routes is not None else None))  # fmt: skip
+    check(lib.dsx_io_read_frames_ex(ctx, cp, n, int(chunk_bytes), int(threads), int(fill_value),
+                                    packed.ctypes.data_as(ctypes.c_void_p), packed.nbytes,
+                                    tasks.ctypes.data_as(ctypes.c_void_p), int(tasks.size), ctypes.byref(pb),
+                                    ctypes.byref(nt), routes.ctypes.data_as(ctypes.c_void_p) if routes is not None else None,
+                                    int(mode)))  # fmt: skip
     return int(pb.value), int(nt.value)
 
 
-def io_read_frames(paths, chunk_bytes, threads=4, fill_value=0):
+def io_read_frames(paths, chunk_bytes, threads=4, fill_value=0, mode=0):
     """:meth:`DestripeEngine.io_read_frames` without an engine, into fresh buffers: ``(packed, tasks, routes)`` trimmed
-    to what was read."""
+    to what was read.  ``mode``: ``ZDEC_ZSTD`` or ``ZDEC_ANY``."""
     lib = load_library()
     n = len(paths)
     packed = np.empty(n * (int(chunk_bytes) + 16) + 1, np.uint8)
@@ -834,7 +838,7 @@ def io_read_frames(paths, chunk_bytes, threads=4, fill_value=0):
         if rc != 0:
             raise DsxError(rc, (lib.dsx_last_error(None) or b"io_read_frames failed").decode())
 
-    pb, nt = _io_read_frames(lib, None, paths, chunk_bytes, packed, tasks, threads, fill_value, routes, check)
+    pb, nt = _io_read_frames(lib, None, paths, chunk_bytes, packed, tasks, threads, fill_value, routes, check, mode)
     return packed[:pb], tasks[:nt], routes
 
 

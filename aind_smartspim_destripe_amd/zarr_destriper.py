@@ -304,7 +304,8 @@ class _DeviceBlocks:
         self.out_brick = int(np.prod(self.co))
         in_bytes = int(np.prod(self.gi)) * self.in_brick * 2
         out_bytes = int(np.prod(self.go)) * self.out_brick * 2
-        self.device_decode = bool(device_decode)
+        self.decode_mode = device_decode_mode(device_decode)  # None, "zstd" or "any"
+        self.device_decode = self.decode_mode is not None
         self.h_in, self.stage_in = [], []
         self.h_packed, self.h_tasks, self.h_status, self.d_packed, self.d_tasks, self.d_status = [], [], [], [], [], []
         if self.device_decode:  # packed frames + task table replace the decompressed staging
@@ -320,6 +321,7 @@ class _DeviceBlocks:
             self.packed = [h.array((cap,), np.uint8) for h in self.h_packed]
             self.tasks = [h.array((n_tasks,), engine_mod.TASK_DTYPE) for h in self.h_tasks]
             self.status = [h.array((n_tasks,), np.int32) for h in self.h_status]
+            self.routes = np.zeros(n_in, np.uint8)  # (one read at a time)
             self.read_info = [None] * self.N_BUF  # (packed bytes, tasks, chunk paths) of the block read into buffer k
             # (tasks, chunk of each task, chunk paths) of the block SUBMITTED from buffer k: the read of block b + 2
             # refills the task table and read_info of buffer k before block b's statuses are checked
@@ -389,15 +391,23 @@ class _DeviceBlocks:
         idx = list(itertools.product(range(nbz), range(self.gi[1]), range(self.gi[2])))
         if self.device_decode:
             paths = [self.src._chunk_path(lead + (bz0 + i[0], i[1], i[2])) for i in idx]
+            mode = engine_mod.ZDEC_ANY if self.decode_mode == "any" else engine_mod.ZDEC_ZSTD
             pb, nt = self.eng.io_read_frames(paths, self.in_brick * 2, self.packed[k], self.tasks[k],
-                                             threads=self.io_threads, fill_value=int(self.src.fill_value))  # fmt: skip
+                                             threads=self.io_threads, fill_value=int(self.src.fill_value),
+                                             routes=self.routes, mode=mode)  # fmt: skip
             self.read_info[k] = (pb, nt, paths)
+            seen = np.bincount(self.routes[: len(paths)], minlength=3)
+            for name, r in (("device", engine_mod.ROUTE_DEVICE), ("host", engine_mod.ROUTE_HOST), ("fill", engine_mod.ROUTE_FILL)):
+                self.timing["decode_routes"][name] += int(seen[r])
             self.timing["read_s"] += time.perf_counter() - t0
             return nbz, zoff
         stage = self.stage_in[k]
-        self.eng.io_read_chunks([self.src._chunk_path(lead + (bz0 + i[0], i[1], i[2])) for i in idx],
-                                [stage[i] for i in idx], threads=self.io_threads,
+        paths = [self.src._chunk_path(lead + (bz0 + i[0], i[1], i[2])) for i in idx]
+        self.eng.io_read_chunks(paths, [stage[i] for i in idx], threads=self.io_threads,
                                 codec=self.src.codec, fill_value=int(self.src.fill_value))  # fmt: skip
+        there = sum(os.path.exists(p) for p in paths)  # (what the reader decoded, what it filled)
+        self.timing["decode_routes"]["host"] += there
+        self.timing["decode_routes"]["fill"] += len(paths) - there
         self.timing["read_s"] += time.perf_counter() - t0
         return nbz, zoff
 
@@ -459,7 +469,7 @@ class _DeviceBlocks:
         eng, (_, H, W), Z = self.eng, self.zyx, z1 - z0
         if self.device_decode:
             pb, nt, paths = self.read_info[k]
-            self.decode_info[k] = (nt, self.tasks[k]["chunk"][:nt].copy(), paths)
+            self.decode_info[k] = (nt, self.tasks[k]["chunk"][:nt].copy(), paths, self.tasks[k]["kind"][:nt].copy())
             if pb:
                 eng.copy_h2d_async(self.d_packed[k], self.packed[k][:pb], U)
             if nt:
@@ -558,13 +568,14 @@ class _DeviceBlocks:
         """(device decode; block in buffer k has been computed) A malformed frame raises as the host reader would."""
         if not self.device_decode:
             return
-        nt, chunk, paths = self.decode_info[k]
+        nt, chunk, paths, kinds = self.decode_info[k]
         st = self.status[k][:nt]  # (written on the compute stream: block b + 2 is not submitted yet)
         bad = np.flatnonzero(st)
         if bad.size:
             i = int(bad[0])
-            raise ValueError("blosc: bad zstd stream ({}) [device decode status {}]".format(paths[int(chunk[i])],
-                                                                                             int(st[i])))  # fmt: skip
+            codec = "lz4" if (int(kinds[i]) & 0xFF) == engine_mod.TASK_LZ4 else "zstd"
+            raise ValueError("blosc: bad {} stream ({}) [device decode status {}]".format(codec, paths[int(chunk[i])],
+                                                                                           int(st[i])))  # fmt: skip
 
     def run_range(self, z_start, z_stop):
         """All blocks of ``[z_start, z_stop)`` through the pipeline; returns the number of planes."""
@@ -621,7 +632,8 @@ _BLOCKS = {}  # one set of staging buffers per process: page-locking 2 GB of hos
 
 
 def _new_timing():
-    return {"read_s": 0.0, "write_s": 0.0, "upload_bytes": 0, "download_bytes": 0, "pyramid_download_bytes": 0}
+    return {"read_s": 0.0, "write_s": 0.0, "upload_bytes": 0, "download_bytes": 0, "pyramid_download_bytes": 0,
+            "decode_routes": {"device": 0, "host": 0, "fill": 0}}  # fmt: skip
 
 
 def device_codec_mode(device_codec):
@@ -634,12 +646,23 @@ def device_codec_mode(device_codec):
     return "literals" if device_codec else None
 
 
+def device_decode_mode(device_decode):
+    """What a ``device_decode`` argument selects: ``None`` (off), ``"zstd"`` (any true value that is not a string: the
+    device takes unsplit zstd streams with byte shuffle or none) or ``"any"`` (the string ``"any"``: LZ4, split streams
+    and bit shuffle too).  Any other string: ``ValueError``."""
+    if isinstance(device_decode, str):
+        if device_decode != "any":
+            raise ValueError("device_decode is False, True or \"any\", not {!r}".format(device_decode))
+        return "any"
+    return "zstd" if device_decode else None
+
+
 def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False, pyr=None):
     """Staging buffers for this geometry, reused from the previous tile when nothing but the stores changed
     (a channel is tens of tiles of one shape, ``zarr_destriper.py:1231``)."""
     key = (id(eng), tuple(zyx[1:]), tuple(src.chunks[-3:]), tuple(dst.chunks[-3:]), int(block_z),
            device_codec_mode(device_codec),
-           bool(device_decode), tuple((lv.level, lv.shape[1:], lv.chunks) for lv in (pyr[0] if pyr else ())))  # fmt: skip
+           device_decode_mode(device_decode), tuple((lv.level, lv.shape[1:], lv.chunks) for lv in (pyr[0] if pyr else ())))  # fmt: skip
     cached = _BLOCKS.get("blocks")
     if cached is not None and cached[0] == key and cached[1].eng._ctx is not None:
         blocks = cached[1]
@@ -741,8 +764,13 @@ def destripe_zarr_store(
     ``device_decode``: ``True`` = the input chunks are decoded on the GPU (``dsx_blosc_decode_device``): the I/O
     threads only read the files, the compressed frames cross the host link, and a zstd decoder fills the input bricks.
     Frames the device does not take (other inner codecs, bit shuffle, split streams, zstd checksums) are decoded by the
-    I/O threads as before.  Needs a Blosc uint16 input and the device re-tiling path; anything else raises
-    ``ValueError``.  Off by default; works with ``device_codec`` on or off.
+    I/O threads as before.  ``"any"`` widens the device's share to what ``numcodecs.Blosc()`` writes by default and its
+    common variants: LZ4 / LZ4HC inside, blocks split into a low-byte and a high-byte stream (LZ4 or zstd) and bit
+    shuffle; blosclz, zlib and snappy inside, type sizes other than 2 and zstd checksums stay with the I/O threads.  Any
+    other string raises ``ValueError``; every other value counts by its truth.  ``LAST_RUN["decode_routes"]`` counts the
+    chunks read over the z range by where they were decoded: ``{"device": n, "host": n, "fill": n}`` (``fill``: a
+    missing file).  Needs a Blosc uint16 input and the device re-tiling path; anything else raises ``ValueError``.  Off
+    by default; works with ``device_codec`` on or off.
 
     ``pyramid_group`` / ``n_levels`` (what ``destripe_zarr(fused_pyramid=True)`` is implemented with): with a group
     folder and ``n_levels > 1`` the pyramid levels ``1 .. n_levels - 1`` are written to ``<pyramid_group>/<i>`` in the
@@ -759,6 +787,7 @@ def destripe_zarr_store(
     logger = logger or logging.getLogger("dsx.zarr")
     codec_mode = device_codec_mode(device_codec)
     device_codec = codec_mode is not None
+    decode_mode = device_decode_mode(device_decode)
     if io_threads is None:
         io_threads = default_io_threads(world_size)
     src = MiniZarrArray.open(dataset_path)
@@ -823,19 +852,22 @@ def destripe_zarr_store(
                              "output-chunk-aligned z blocks)")  # fmt: skip
         pyramid.fused_check_blocks(levels, block_z)
     LAST_RUN.update(device_codec=device_codec, device_codec_mode=codec_mode, device_decode=bool(device_decode),
-                    fused_pyramid=bool(levels), pyramid_levels=[lv.level for lv in levels])  # fmt: skip
+                    device_decode_mode=decode_mode, decode_routes=None, fused_pyramid=bool(levels), pyramid_levels=[lv.level for lv in levels])  # fmt: skip
     if can and device_retile is not False:
         flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
         eng = fl.get_engine(zyx[1:], cells_config, no_cells_config, 2500, flatfield, darkfield,
                             max_batch=min(block_z, 64), device=dev)  # fmt: skip
         blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, "runs" if codec_mode == "runs" else device_codec,
                                 device_decode, (levels, pyr_arrays) if levels else None)  # fmt: skip
-        n_planes = blocks.run_range(z0, z1)
+        try:
+            n_planes = blocks.run_range(z0, z1)
+        finally:
+            LAST_RUN["decode_routes"] = dict(blocks.timing["decode_routes"])
         eng.sync()
         dt = time.perf_counter() - t0
         logger.info("rank %d: %d planes z[%d:%d) in %.2f s (device re-tiling%s, overlapped; read %.2f s, write %.2f s)",
                     rank, n_planes, z0, z1, dt, (", device codec" + (" (runs)" if codec_mode == "runs" else "") if device_codec else "")
-                    + (", device decode" if device_decode else "")
+                    + (", device decode ({})".format(decode_mode) if device_decode else "")
                     + (", pyramid levels 1..{} fused".format(len(levels)) if levels else ""), blocks.timing["read_s"],
                     blocks.timing["write_s"])  # fmt: skip
         return n_planes, dt
@@ -1020,6 +1052,7 @@ def destripe_zarr(
     Returns ``(planes processed by this rank, seconds)``.
     """
     device_codec_mode(device_codec)  # (a wrong string fails before anything is written)
+    device_decode_mode(device_decode)
     no_cells_config = parameters["no_cells_config"]
     cells_config = parameters["cells_config"]
     co_cpus = _cpu_limit()
@@ -1165,6 +1198,7 @@ def destripe_channel(
     if world_size > 1 and group is None:
         raise ValueError("destripe_channel with world_size > 1 needs a group to order the pyramid after all ranks")
     device_codec_mode(device_codec)  # (a wrong string fails before anything is written)
+    device_decode_mode(device_decode)
     logger = logger or logging.getLogger("dsx.zarr")
     zarr_dataset_path, results_folder = Path(zarr_dataset_path), Path(results_folder)
     channel_dataset = zarr_dataset_path.joinpath(channel_name)

@@ -253,7 +253,7 @@ int dsx_blosc_encode_device_ex(dsx_ctx* ctx, const void* d_src, int n_chunks, si
 int dsx_blosc_encode_ref_ex(const void* src, int n_chunks, size_t chunk_bytes, int typesize, int clevel, void* frames,
                             int64_t* offsets, int mode);
 
-/* Blosc-zstd chunks decoded on the device (csrc/dsx_zstd_dec.h, csrc/dsx_zdec_kernels.h).
+/* Blosc chunks decoded on the device (csrc/dsx_zstd_dec.h, csrc/dsx_lz4_dec.h, csrc/dsx_zdec_kernels.h).
  * dsx_io_read_frames: n chunk files -> their frames packed back to back into `packed` (host memory, capacity
  * n * (chunk_bytes + 16)) and one 32-byte task per Blosc block into `tasks` (capacity n * (chunk_bytes / 8192 + 1)):
  * {uint64 src, uint64 dst, uint32 src_len, uint32 dst_len, uint32 kind, uint32 chunk}; chunk i decodes to bytes
@@ -265,7 +265,21 @@ int dsx_blosc_encode_ref_ex(const void* src, int n_chunks, size_t chunk_bytes, i
  * dsx_blosc_decode_device: the tasks into d_out (out_bytes), asynchronous on the context stream; d_status receives
  * one int32 per task (0, or a dsx_zstd_dec.h Status for a malformed frame).  The context keeps a work buffer of
  * out_bytes.
- * dsx_blosc_decode_ref: the host build of the same decoder, byte-identical output (host pointers, synchronous). */
+ * dsx_blosc_decode_ref: the host build of the same decoder, byte-identical output (host pointers, synchronous).
+ * dsx_io_read_frames_ex takes a mode.  DSX_ZDEC_ZSTD: the routes above, byte for byte.  DSX_ZDEC_ANY: the device also
+ * takes (csrc/dsx_lz4_dec.h), still for typesize 2 and at most chunk_bytes / 8192 + 1 Blosc blocks:
+ *     inner codec    zstd (no checksum), lz4, lz4hc            -> device     blosclz, zlib, snappy -> host
+ *     shuffle        none, byte shuffle, bit shuffle           -> device
+ *     block streams  unsplit, or split into 2 (low / high bytes; each stored or coded) -> device
+ *     typesize != 2, zstd checksums, blocks under 8 KiB        -> host
+ * `kind` of a task: 0 fill, 1 copy, 2 stored, 3 zstd, 4 lz4; | 0x100 byte un-shuffle, | 0x200 split (src is the int32
+ * length word of the first of two streams, src_len spans both), | 0x400 bit un-shuffle.  One task per Blosc block in
+ * either mode.  Any other mode: DSX_EINVAL.  dsx_blosc_decode_device / _ref run the tasks of both modes. */
+#define DSX_ZDEC_ZSTD 0
+#define DSX_ZDEC_ANY 1
+int dsx_io_read_frames_ex(dsx_ctx* ctx, const char* const* paths, int n, size_t chunk_bytes, int threads,
+                          uint16_t fill_value, void* packed, size_t packed_capacity, void* tasks, int task_capacity,
+                          size_t* packed_bytes, int* n_tasks, uint8_t* routes, int mode);
 int dsx_io_read_frames(dsx_ctx* ctx, const char* const* paths, int n, size_t chunk_bytes, int threads,
                        uint16_t fill_value, void* packed, size_t packed_capacity, void* tasks, int task_capacity,
                        size_t* packed_bytes, int* n_tasks, uint8_t* routes);

@@ -4,12 +4,18 @@
 download) into another store.  Prints one JSON line; the roofline of this path is the host link
 (PCIe Gen5 x16, 63 GB/s spec: 16.8 MB per plane both ways -> <= 3.7 k planes/s), not HBM.
 
-    bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode] [pyramid|fused-pyramid]
+    bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode|device-decode-any] [lz4]
+                  [pyramid|fused-pyramid]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
 line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
 `device-codec-runs`: the same with runs of equal bytes written as matches (device_codec="runs").
 `device-decode` (Blosc only): the input chunks are decoded on the GPU (destripe_zarr_store(device_decode=True)).
+`device-decode-any`: the same with device_decode="any" (LZ4, split streams and bit shuffle go to the device too).
+`lz4` (Blosc only, N a multiple of 64): the INPUT store is what numcodecs.Blosc() writes by default -- LZ4, byte
+shuffle, 256 KiB blocks split into a low-byte and a high-byte stream (the test suite's LZ4 encoder,
+tests/blosc_any_frames.py; every 64-plane block holds the same planes, as in the other variants); the output stays
+Blosc-zstd.  The line then reports the input store's bytes and the chunks decoded on the device / host / filled.
 `pyramid`: after the timed level-0 pass, compute_multiscale(n_levels=3) on the store is timed too (the two-pass route);
 `fused-pyramid`: level 0 and levels 1-2 in one destripe_zarr_store call (pyramid_group / n_levels).  Both add level-0,
 pyramid and total seconds, the levels' bytes on disk (with the host writer's frames of each level's first chunk row for
@@ -26,16 +32,38 @@ logging.basicConfig(level=logging.INFO, stream=sys.stderr)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 codec = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2] != "raw" else None  # None (raw chunks), "zlib" or "blosc" (Blosc-zstd)
 device_codec = "runs" if "device-codec-runs" in sys.argv[3:] else "device-codec" in sys.argv[3:]
-device_decode = "device-decode" in sys.argv[3:]
+device_decode = "any" if "device-decode-any" in sys.argv[3:] else "device-decode" in sys.argv[3:]
+lz4_input = "lz4" in sys.argv[3:]
 two_pass, fused = "pyramid" in sys.argv[3:], "fused-pyramid" in sys.argv[3:]
 H = W = 2048
 root = tempfile.mkdtemp(prefix="dsx_zarr_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
     t0 = time.perf_counter()
-    src = MiniZarrArray.create(os.path.join(root, "in.zarr"), (1, 1, n, H, W), (1, 1, 64, 128, 128), np.uint16, compressor=codec)
     bank = synth.synthetic_bank(8, H, W)
-    for z in range(0, n, 64):
-        src[0, 0, z : z + 64] = synth.synthetic_stack(min(64, n - z), H, W, bank=bank)
+    if lz4_input:
+        if codec != "blosc" or n % 64:
+            sys.exit("lz4: a Blosc store of a multiple of 64 planes")
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import multiprocessing
+        import blosc_any_frames as baf
+        src = MiniZarrArray.create(os.path.join(root, "in.zarr"), (1, 1, n, H, W), (1, 1, 64, 128, 128), np.uint16,
+                                   compressor={"id": "blosc", "cname": "lz4", "clevel": 5, "shuffle": 1, "blocksize": 0})
+        stack = synth.synthetic_stack(64, H, W, bank=bank)
+        yx = [(y, x) for y in range(H // 128) for x in range(W // 128)]
+        raws = [np.ascontiguousarray(stack[:, 128 * y : 128 * y + 128, 128 * x : 128 * x + 128]).tobytes() for y, x in yx]
+        with multiprocessing.Pool(16) as pool:  # (before anything touches the GPU)
+            frames = pool.starmap(baf.blosc_frame, [(r, 256 * 1024, baf.LZ4, baf.SHUFFLE, True) for r in raws])
+        for zb in range(n // 64):
+            for (y, x), f in zip(yx, frames):
+                p = src._chunk_path((0, 0, zb, y, x))
+                os.makedirs(os.path.dirname(p), exist_ok=True)
+                with open(p, "wb") as fh:
+                    fh.write(f)
+        del stack, raws
+    else:
+        src = MiniZarrArray.create(os.path.join(root, "in.zarr"), (1, 1, n, H, W), (1, 1, 64, 128, 128), np.uint16, compressor=codec)
+        for z in range(0, n, 64):
+            src[0, 0, z : z + 64] = synth.synthetic_stack(min(64, n - z), H, W, bank=bank)
     t_make = time.perf_counter() - t0
     res = {}
     group = os.path.join(root, "out.zarr")
@@ -49,6 +77,11 @@ try:
                                           device_codec=device_codec, device_decode=device_decode, **kw)
             res[name] = {"planes": planes, "seconds": round(time.perf_counter() - t0, 3)}
     timing = dict(zd._BLOCKS["blocks"][1].timing)  # the timed (second) pass
+    decode = {"decode_routes": zd.LAST_RUN.get("decode_routes")}
+    if lz4_input:
+        decode["input_store_bytes"] = sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(src.path)
+                                          for f in fs if not f.startswith("."))
+        decode["input_ratio_to_raw"] = round(decode["input_store_bytes"] / (n * H * W * 2), 4)
     secs = res["overlapped"]["seconds"]
     pyr = {}
     if two_pass or fused:
@@ -120,13 +153,13 @@ try:
                 except AssertionError as e:
                     verified = False
                     print("oracle mismatch", e, file=sys.stderr)
-    label = (codec or "raw") + (", encoded on the device" + (" with run matches" if device_codec == "runs" else "") if device_codec else "") + (", decoded on the device" if device_decode else "")
+    label = (codec or "raw") + (", LZ4 input" if lz4_input else "") + (", encoded on the device" + (" with run matches" if device_codec == "runs" else "") if device_codec else "") + (", decoded on the device" + (" (any)" if device_decode == "any" else "") if device_decode else "")
     label += ", pyramid fused" if fused else ""
     print(json.dumps({"metric": "2048x2048 uint16 slices/s, Zarr store to Zarr store ({} chunks, tmpfs)".format(label), "value": round(v, 1),
                       "planes": n, "seconds": res["overlapped"]["seconds"], "store_make_s": round(t_make, 1),
                       "roofline": {"bound": "host link", "peak_planes_per_s": 3750, "frac": round(v / 3750.0, 3)},
                       "read_s": round(timing["read_s"], 3), "write_s": round(timing["write_s"], 3), "host_link": link,
-                      "plane0_checksum": chk, "verified": verified, **sizes, **({"pyramid": pyr} if pyr else {}),
+                      "plane0_checksum": chk, "verified": verified, **decode, **sizes, **({"pyramid": pyr} if pyr else {}),
                       "verification": {"planes_bit_identical_to_single_plane_runs": checked,
                                        "planes_against_the_cpu_oracle": oracle_checked, "blocks": blocks}}))
     if not verified or not pyr.get("verified", True):
