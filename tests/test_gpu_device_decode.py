@@ -1,6 +1,7 @@
 """Blosc-zstd input chunks decoded on the device (``dsx_blosc_decode_device``, ``csrc/dsx_zdec_kernels.h``): the same
 bytes as the host build of the decoder (``dsx_blosc_decode_ref``, held to libzstd by tests/test_zstd_decoder_host.py)
-and as the host reader, and ``destripe_zarr_store(device_decode=True)`` writes the stores of the host-decode run."""
+and as the host reader, and ``destripe_zarr_store(device_decode=True)`` writes the stores of the host-decode run.  The
+kernel itself is held to libzstd's input too, on every zstd mode and task layout: tests/test_gpu_zdec_cases.py."""
 
 import os
 import struct
