@@ -1846,9 +1846,10 @@ int dsx_pyramid_block_ref(const void* planes, int Z, int H, int W, int n_levels,
   return DSX_OK;
 }
 
-int dsx_pyramid_block_u16(dsx_ctx* ctx, const void* d_planes, int Z, int H, int W, int n_levels,
-                          const dsx_pyramid_level* levels, void* const* d_bricks, void* d_work, size_t work_bytes) {
-  if (!ctx || !d_planes) return DSX_EINVAL;
+namespace {
+// bs == nullptr: d_src is the dense block (k_pyramid_block); otherwise the block in chunk order (k_pyramid_bricks).
+int pyramid_run(dsx_ctx* ctx, const void* d_src, const dsx::pyr::BrickSrc* bs, int Z, int H, int W, int n_levels,
+                const dsx_pyramid_level* levels, void* const* d_bricks, void* d_work, size_t work_bytes) {
   namespace p = dsx::pyr;
   p::Level lv[p::kMaxLevels] = {};
   int n = 0;
@@ -1863,17 +1864,24 @@ int dsx_pyramid_block_u16(dsx_ctx* ctx, const void* d_planes, int Z, int H, int 
   for (int l = 1; l <= n; ++l)
     if (levels[l - 1].zero)
       DSX_HIP(hipMemsetAsync(lv[l - 1].bricks, 0, (size_t)levels[l - 1].rows * p::row_elems(lv[l - 1]) * 2, s));
-  dsx::PyrBlockArgs a = {};
-  a.src = (const uint16_t*)d_planes; a.Z = Z; a.H = H; a.W = W;
-  a.l1 = lv[0];
-  if (n >= 2) a.l2 = lv[1];
+  p::Level l1 = lv[0], l2 = {};
+  if (n >= 2) l2 = lv[1];
   uint8_t* work = (uint8_t*)d_work;
-  if (n > 2) a.dense2 = (uint16_t*)work;
-  const bool vec = W % 8 == 0 && a.l1.cx % 4 == 0 && (n < 2 || a.l2.cx % 2 == 0) && (uintptr_t)d_planes % 16 == 0 &&
-                   (uintptr_t)a.l1.bricks % 8 == 0 && (uintptr_t)a.l2.bricks % 4 == 0;
-  const dim3 grid(((a.l1.W + 3) / 4 + 255) / 256, (a.l1.H + 1) / 2, (a.l1.Z + 1) / 2);
-  if (vec) hipLaunchKernelGGL(dsx::k_pyramid_block<true>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(dsx::k_pyramid_block<false>, grid, dim3(256), 0, s, a);
+  uint16_t* dense2 = n > 2 ? (uint16_t*)work : nullptr;
+  const bool vec = W % 8 == 0 && l1.cx % 4 == 0 && (n < 2 || l2.cx % 2 == 0) && (uintptr_t)d_src % 16 == 0 &&
+                   (uintptr_t)l1.bricks % 8 == 0 && (uintptr_t)l2.bricks % 4 == 0;
+  const dim3 grid(((l1.W + 3) / 4 + 255) / 256, (l1.H + 1) / 2, (l1.Z + 1) / 2);
+  if (bs) {
+    dsx::PyrBricksArgs a = {};
+    a.src = *bs; a.Z = Z; a.H = H; a.W = W; a.l1 = l1; a.l2 = l2; a.dense2 = dense2;
+    if (vec && bs->cx % 8 == 0) hipLaunchKernelGGL(dsx::k_pyramid_bricks<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(dsx::k_pyramid_bricks<false>, grid, dim3(256), 0, s, a);
+  } else {
+    dsx::PyrBlockArgs a = {};
+    a.src = (const uint16_t*)d_src; a.Z = Z; a.H = H; a.W = W; a.l1 = l1; a.l2 = l2; a.dense2 = dense2;
+    if (vec) hipLaunchKernelGGL(dsx::k_pyramid_block<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(dsx::k_pyramid_block<false>, grid, dim3(256), 0, s, a);
+  }
   DSX_HIP(hipGetLastError());
   for (int l = 3; l <= n; ++l) {  // dense level l - 1 (in the work buffer) -> level l
     dsx::PyrLevelArgs b = {};
@@ -1886,6 +1894,44 @@ int dsx_pyramid_block_u16(dsx_ctx* ctx, const void* d_planes, int Z, int H, int 
     hipLaunchKernelGGL(dsx::k_pyramid_level, g, dim3(256), 0, s, b);
     DSX_HIP(hipGetLastError());
   }
+  return DSX_OK;
+}
+
+const char* brick_src(const void* bricks, int H, int W, int cz, int cy, int cx, dsx::pyr::BrickSrc* out) {
+  if (cz <= 0 || cy <= 0 || cx <= 0) return "pyramid: the source chunk shape must be positive";
+  out->bricks = (const uint16_t*)bricks;
+  out->cz = cz; out->cy = cy; out->cx = cx;
+  out->nby = (H + cy - 1) / cy; out->nbx = (W + cx - 1) / cx;
+  return nullptr;
+}
+}  // namespace
+
+int dsx_pyramid_block_u16(dsx_ctx* ctx, const void* d_planes, int Z, int H, int W, int n_levels,
+                          const dsx_pyramid_level* levels, void* const* d_bricks, void* d_work, size_t work_bytes) {
+  if (!ctx || !d_planes) return DSX_EINVAL;
+  return pyramid_run(ctx, d_planes, nullptr, Z, H, W, n_levels, levels, d_bricks, d_work, work_bytes);
+}
+
+int dsx_pyramid_bricks_u16(dsx_ctx* ctx, const void* d_src_bricks, int Z, int H, int W, int src_cz, int src_cy,
+                           int src_cx, int n_levels, const dsx_pyramid_level* levels, void* const* d_bricks,
+                           void* d_work, size_t work_bytes) {
+  if (!ctx || !d_src_bricks) return DSX_EINVAL;
+  dsx::pyr::BrickSrc bs = {};
+  if (const char* e = brick_src(d_src_bricks, H, W, src_cz, src_cy, src_cx, &bs)) return fail(ctx, DSX_EINVAL, e);
+  return pyramid_run(ctx, d_src_bricks, &bs, Z, H, W, n_levels, levels, d_bricks, d_work, work_bytes);
+}
+
+int dsx_pyramid_bricks_ref(const void* src_bricks, int Z, int H, int W, int src_cz, int src_cy, int src_cx,
+                           int n_levels, const dsx_pyramid_level* levels, void* const* bricks) {
+  if (!src_bricks) return DSX_EINVAL;
+  dsx::pyr::BrickSrc bs = {};
+  if (const char* e = brick_src(src_bricks, H, W, src_cz, src_cy, src_cx, &bs)) return fail(nullptr, DSX_EINVAL, e);
+  dsx::pyr::Level lv[dsx::pyr::kMaxLevels] = {};
+  int n = 0;
+  if (const char* e = pyramid_levels(Z, H, W, n_levels, levels, bricks, lv, &n)) return fail(nullptr, DSX_EINVAL, e);
+  for (int l = 1; l <= n; ++l)
+    if (levels[l - 1].zero) memset(lv[l - 1].bricks, 0, (size_t)levels[l - 1].rows * dsx::pyr::row_elems(lv[l - 1]) * 2);
+  dsx::pyr::pyramid_bricks_host(bs, Z, H, W, n + 1, lv);
   return DSX_OK;
 }
 

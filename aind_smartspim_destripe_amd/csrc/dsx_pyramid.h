@@ -5,6 +5,8 @@
 //       chunk ("brick") order at a z offset inside each level's chunk row -- k_downsample2 twice plus
 //       k_planes_to_bricks twice, without the intermediate volumes.  Level 2 is the mean of the TRUNCATED level-1
 //       values, which a thread holds in registers.  On request level 2 is also left dense for the levels below.
+//   k_pyramid_bricks : the same from a block that is still in the chunk order it was stored in (the stand-alone pyramid
+//       of a finished store: a decoded level-0 block), without k_bricks_to_planes in front.
 //   k_pyramid_level : one further level (>= 3; under 0.2 % of the bytes) from the dense previous one: 2 x 2 x 2 mean,
 //       brick-order store, dense copy for the next level.
 //
@@ -90,6 +92,93 @@ __global__ __launch_bounds__(256) void k_pyramid_block(PyrBlockArgs a) {
   } else {
     const uint32_t o[2] = {o0, o1};
     for (int i = 0; i < 2 && x2 + i < a.l2.W; ++i) {
+      if (a.l2.bricks) a.l2.bricks[pyr::brick_offset(a.l2, a.l2.z0 + z2, y2, x2 + i)] = (uint16_t)o[i];
+      if (a.dense2) a.dense2[((size_t)z2 * a.l2.H + y2) * a.l2.W + x2 + i] = (uint16_t)o[i];
+    }
+  }
+}
+
+struct PyrBricksArgs {
+  pyr::BrickSrc src;  // the block in the chunk order of the array it was read from
+  int Z, H, W;        // its extent (level 0): nothing outside it is read
+  pyr::Level l1, l2;  // as PyrBlockArgs
+  uint16_t* dense2;
+};
+
+// k_pyramid_block for a block that is still in chunk order (a decoded level-0 block of the stand-alone pyramid): same
+// grid, same arithmetic, same stores; only the 4 planes x 4 rows x 8 columns of a thread come out of source bricks.
+// The offset of a voxel is a plane part + a row part + a column part (dsx_pyramid_geom.h): the column is split once per
+// thread, the 4 rows once per thread (from blockIdx.y: scalar registers), the 2 planes of a z pair once per pair.
+// VEC == true needs what k_pyramid_block<true> needs and src.cx % 8 == 0: the 8 columns of a thread then lie in one
+// brick, 16-byte aligned, and inside [Z, H, W] (W % 8 == 0).  Otherwise scalar accesses with per-voxel bounds.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_pyramid_bricks(PyrBricksArgs a) {
+  const int xq = blockIdx.x * 256 + threadIdx.x;
+  const int x1 = xq * 4;
+  if (x1 >= a.l1.W) return;
+  const int y2 = blockIdx.y, z2 = blockIdx.z;
+  const int n1 = VEC ? 4 : min(4, a.l1.W - x1);
+  const uint16_t* base = a.src.bricks + (VEC ? pyr::src_col(a.src, 2 * x1) : 0);
+  size_t rows[4];  // rows 4 * y2 .. + 3 (those past 2 * l1.H are not used)
+#pragma unroll
+  for (int r = 0; r < 4; ++r) rows[r] = pyr::src_row(a.src, 4 * y2 + r);
+  uint32_t acc[2] = {0, 0};  // sums of the 8 truncated level-1 values under each level-2 voxel
+#pragma unroll 1
+  for (int dz = 0; dz < 2; ++dz) {
+    const int z1 = 2 * z2 + dz;
+    if (z1 >= a.l1.Z) break;
+    const size_t planes[2] = {pyr::src_plane(a.src, 2 * z1), pyr::src_plane(a.src, 2 * z1 + 1)};
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+      const int y1 = 2 * y2 + dy;
+      if (y1 >= a.l1.H) continue;
+      uint32_t s[4] = {0, 0, 0, 0};
+      if (VEC) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint16_t* p = base + planes[k >> 1] + rows[2 * dy + (k & 1)];
+          const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+          s[0] += pair_sum(v.x); s[1] += pair_sum(v.y); s[2] += pair_sum(v.z); s[3] += pair_sum(v.w);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] = pyr::mean8(s[i]);
+        u32x2 o;
+        o.x = s[0] | (s[1] << 16);
+        o.y = s[2] | (s[3] << 16);
+        __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(a.l1.bricks + pyr::brick_offset(a.l1, a.l1.z0 + z1, y1, x1)));
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (i >= n1) break;
+          const size_t c0 = pyr::src_col(a.src, 2 * (x1 + i)), c1 = pyr::src_col(a.src, 2 * (x1 + i) + 1);
+          uint32_t t = 0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const uint16_t* q = base + planes[k >> 1] + rows[2 * dy + (k & 1)];
+            t += (uint32_t)q[c0] + q[c1];
+          }
+          s[i] = pyr::mean8(t);
+          a.l1.bricks[pyr::brick_offset(a.l1, a.l1.z0 + z1, y1, x1 + i)] = (uint16_t)s[i];
+        }
+      }
+      acc[0] += s[0] + s[1];
+      acc[1] += s[2] + s[3];
+    }
+  }
+  if (z2 >= a.l2.Z || y2 >= a.l2.H) return;
+  const int x2 = xq * 2;
+  const uint32_t o0 = pyr::mean8(acc[0]), o1 = pyr::mean8(acc[1]);
+  if (VEC) {
+    const uint32_t o = o0 | (o1 << 16);
+    if (a.l2.bricks)
+      __builtin_nontemporal_store(o, reinterpret_cast<uint32_t*>(a.l2.bricks + pyr::brick_offset(a.l2, a.l2.z0 + z2, y2, x2)));
+    if (a.dense2)
+      __builtin_nontemporal_store(o, reinterpret_cast<uint32_t*>(a.dense2 + ((size_t)z2 * a.l2.H + y2) * a.l2.W + x2));
+  } else {
+    const uint32_t o[2] = {o0, o1};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      if (x2 + i >= a.l2.W) break;
       if (a.l2.bricks) a.l2.bricks[pyr::brick_offset(a.l2, a.l2.z0 + z2, y2, x2 + i)] = (uint16_t)o[i];
       if (a.dense2) a.dense2[((size_t)z2 * a.l2.H + y2) * a.l2.W + x2 + i] = (uint16_t)o[i];
     }

@@ -46,6 +46,33 @@ DSX_PHD inline size_t brick_offset(const Level& g, int z, int y, int x) {
   return ((brick * g.cz + iz) * g.cy + iy) * (size_t)g.cx + ix;
 }
 
+// A block that is still in the chunk order it was stored in: [nbz][nby][nbx][cz][cy][cx], every brick full-sized, plane
+// 0 of the block at plane 0 of the brick grid (the block starts on a source chunk boundary).  Bricks that stick out of
+// the block hold whatever the store held there: positions outside [Z, H, W] are never read.
+struct BrickSrc {
+  const uint16_t* bricks;
+  int cz, cy, cx;  // chunk shape of the source array
+  int nby, nbx;    // bricks per axis (ceil)
+};
+
+// The offset of voxel (z, y, x) inside a BrickSrc is the sum of a plane, a row and a column part, so a kernel thread
+// splits each of its planes, rows and columns once: src_offset below, and k_pyramid_bricks (dsx_pyramid.h).
+DSX_PHD inline size_t src_plane(const BrickSrc& s, int z) {
+  const int bz = z / s.cz, iz = z - bz * s.cz;
+  return ((size_t)bz * s.nby * s.nbx * s.cz + iz) * s.cy * (size_t)s.cx;
+}
+DSX_PHD inline size_t src_row(const BrickSrc& s, int y) {
+  const int by = y / s.cy, iy = y - by * s.cy;
+  return ((size_t)by * s.nbx * s.cz * s.cy + iy) * (size_t)s.cx;
+}
+DSX_PHD inline size_t src_col(const BrickSrc& s, int x) {
+  const int bx = x / s.cx, ix = x - bx * s.cx;
+  return (size_t)bx * s.cz * s.cy * s.cx + ix;
+}
+DSX_PHD inline size_t src_offset(const BrickSrc& s, int z, int y, int x) {
+  return src_plane(s, z) + src_row(s, y) + src_col(s, x);
+}
+
 inline size_t row_elems(const Level& g) { return (size_t)g.nby * g.nbx * g.cz * g.cy * g.cx; }
 
 // Dense levels 2 .. n_levels - 2 of a block (what the levels >= 3 are computed from), each padded to 16 bytes.
@@ -84,6 +111,18 @@ inline void pyramid_block_host(const uint16_t* planes, int H, int W, int n_level
     src = prev.data();
     sy = g.H; sx = g.W;
   }
+}
+
+// The host build from a block in chunk order: the voxels inside [Z, H, W] gathered dense, then the build above.
+inline void pyramid_bricks_host(const BrickSrc& s, int Z, int H, int W, int n_levels, const Level* levels) {
+  std::vector<uint16_t> planes((size_t)Z * H * W);
+  for (int z = 0; z < Z; ++z)
+    for (int y = 0; y < H; ++y) {
+      const size_t zy = src_plane(s, z) + src_row(s, y);
+      uint16_t* d = planes.data() + ((size_t)z * H + y) * W;
+      for (int x = 0; x < W; ++x) d[x] = s.bricks[zy + src_col(s, x)];
+    }
+  pyramid_block_host(planes.data(), H, W, n_levels, levels);
 }
 
 }  // namespace pyr

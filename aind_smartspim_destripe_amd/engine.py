@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "dsx_blosc_encode_device", "dsx_blosc_encode_ref", "dsx_blosc_encode_device_ex", "dsx_blosc_encode_ref_ex",
     "dsx_io_read_frames", "dsx_io_read_frames_ex", "dsx_blosc_decode_device", "dsx_blosc_decode_ref",
     "dsx_pyramid_work_bytes", "dsx_pyramid_block_u16", "dsx_pyramid_block_ref",
+    "dsx_pyramid_bricks_u16", "dsx_pyramid_bricks_ref",
 ]  # fmt: skip
 
 
@@ -211,6 +212,9 @@ def load_library(path=None):
     lib.dsx_pyramid_block_u16.argtypes = [vp, vp, i32, i32, i32, i32, ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp),
                                           vp, ctypes.c_size_t]  # fmt: skip
     lib.dsx_pyramid_block_ref.argtypes = [vp, i32, i32, i32, i32, ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp)]
+    lib.dsx_pyramid_bricks_u16.argtypes = [vp, vp] + [i32] * 7 + [ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp), vp,
+                                                                  ctypes.c_size_t]  # fmt: skip
+    lib.dsx_pyramid_bricks_ref.argtypes = [vp] + [i32] * 7 + [ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp)]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("dsx_destroy", "dsx_last_error"):
@@ -641,6 +645,25 @@ class DestripeEngine:
             raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
         self._check(rc)
 
+    def pyramid_bricks(self, d_src, zyx, src_chunk, chunks, d_bricks, z0s=None, zero=None, rows=None, d_work=None):
+        """:meth:`pyramid_block` for a block that is still in chunk order (``dsx_pyramid_bricks_u16``;
+        ``zarr_destriper.py:365-407, 746-782``): ``d_src`` holds the uint16 bricks ``[nbz, nby, nbx] + src_chunk`` of
+        the block ``zyx``, which starts on a source chunk boundary; positions outside ``zyx`` are never read.  Every
+        other argument as in :meth:`pyramid_block`.  Asynchronous on the engine stream."""
+        table = _pyramid_table(zyx, chunks, z0s, zero, rows)
+        n = len(chunks)
+        assert d_src.nbytes >= src_brick_elems(zyx, src_chunk) * 2, "pyramid source brick buffer too small"
+        for lv, g, b in zip(range(1, n + 1), table, d_bricks):
+            assert b.nbytes >= pyramid_level_elems(zyx, lv, (g.cz, g.cy, g.cx), g.rows) * 2, "pyramid brick buffer too small"
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[b.ptr for b in d_bricks])
+        rc = self._lib.dsx_pyramid_bricks_u16(self._ctx, ctypes.c_void_p(d_src.ptr), *map(int, zyx), *map(int, src_chunk),
+                                              n + 1, table, ptrs,
+                                              ctypes.c_void_p(d_work.ptr) if d_work is not None else None,
+                                              d_work.nbytes if d_work is not None else 0)  # fmt: skip
+        if rc == -1:
+            raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
+        self._check(rc)
+
     def foreground_background(self, image, cutoff, want_mask=True):
         """``(fore_mean, back_mean, mask uint8)`` of a host image (uint16 / float32, any shape)."""
         a = np.ascontiguousarray(image)
@@ -740,6 +763,14 @@ def pyramid_level_elems(zyx, level, chunk, rows=1):
     return int(rows) * nby * nbx * int(chunk[0]) * int(chunk[1]) * int(chunk[2])
 
 
+def src_brick_elems(zyx, src_chunk):
+    """uint16 elements of the block ``zyx`` in the chunk order of an array with chunks ``src_chunk`` (whole bricks)."""
+    n = 1
+    for e, c in zip(zyx, src_chunk):
+        n *= -(-int(e) // int(c)) * int(c)
+    return n
+
+
 def pyramid_work_bytes(zyx, n_levels):
     """Bytes of the work buffer :meth:`DestripeEngine.pyramid_block` needs for ``n_levels`` levels (level 0 counted)."""
     lib = load_library()
@@ -775,6 +806,40 @@ def pyramid_block_ref(planes, chunks, z0s=None, bricks=None, rows=None):
     rc = lib.dsx_pyramid_block_ref(a.ctypes.data_as(ctypes.c_void_p), *a.shape, n + 1, table, ptrs)
     if rc != 0:
         raise ValueError((lib.dsx_last_error(None) or b"pyramid_block_ref failed").decode())
+    return out
+
+
+def pyramid_bricks_ref(bricks, zyx, src_chunk, chunks, z0s=None, bricks_out=None, rows=None):
+    """Host build of :meth:`DestripeEngine.pyramid_bricks` (``dsx_pyramid_bricks_ref``): ``bricks`` uint16
+    ``[nbz, nby, nbx] + src_chunk`` holding the block ``zyx`` -> one uint16 array ``[rows, nby, nbx, cz, cy, cx]`` per
+    level ``1 .. len(chunks)``, the bytes :func:`pyramid_block_ref` gives for the dense block.  ``bricks_out``: arrays of
+    an earlier call to write into; fresh zeroed ones otherwise."""
+    lib = load_library()
+    a = np.ascontiguousarray(bricks)
+    zyx, src_chunk = tuple(int(v) for v in zyx), tuple(int(v) for v in src_chunk)
+    if a.dtype != np.uint16 or len(zyx) != 3 or len(src_chunk) != 3 or min(src_chunk) <= 0:
+        raise ValueError("the pyramid kernels take uint16 [Z, H, W] blocks")
+    if a.size != src_brick_elems(zyx, src_chunk):
+        raise ValueError("a {} block in chunks {} has {} voxels, not {}".format(zyx, src_chunk,
+                                                                               src_brick_elems(zyx, src_chunk), a.size))  # fmt: skip
+    table = _pyramid_table(zyx, chunks, z0s, [bricks_out is None] * len(chunks), rows)
+    out = []
+    for i, ck in enumerate(chunks):
+        g = table[i]
+        shape = (g.rows, -(-(zyx[1] >> (i + 1)) // g.cy) if zyx[1] >> (i + 1) else 0,
+                 -(-(zyx[2] >> (i + 1)) // g.cx) if zyx[2] >> (i + 1) else 0, g.cz, g.cy, g.cx)  # fmt: skip
+        if bricks_out is None:
+            out.append(np.zeros(shape, np.uint16))
+        else:
+            b = bricks_out[i]
+            if b.dtype != np.uint16 or b.shape != shape or not b.flags["C_CONTIGUOUS"]:
+                raise ValueError("level {}: bricks must be C-contiguous uint16 {}".format(i + 1, shape))
+            out.append(b)
+    n = len(chunks)
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[o.ctypes.data for o in out])
+    rc = lib.dsx_pyramid_bricks_ref(a.ctypes.data_as(ctypes.c_void_p), *zyx, *src_chunk, n + 1, table, ptrs)
+    if rc != 0:
+        raise ValueError((lib.dsx_last_error(None) or b"pyramid_bricks_ref failed").decode())
     return out
 
 

@@ -8,7 +8,11 @@ is the 2 x 2 x 2 windowed mean of the previous one, truncated back to uint16 -- 
 between levels.  No CPU fallback.
 """
 
+import itertools
+import os
+import time
 from collections import namedtuple
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -86,6 +90,25 @@ def fused_schedule(levels, z_start, z_stop, block_z):
     return out
 
 
+def pipelined_block_z(src_cz, levels):
+    """z block of the pipelined stand-alone pyramid: the smallest multiple of the source z chunk ``src_cz`` (blocks are
+    whole source chunks) that :func:`fused_check_blocks` accepts.  The first condition there holds from
+    ``lcm(src_cz, 2^levels) <= src_cz << levels`` on, and a block the chunk rows refuse has no multiple they accept, so
+    the search is bounded; ``ValueError`` when it finds nothing."""
+    src_cz = int(src_cz)
+    if src_cz <= 0:
+        raise ValueError("the source z chunk must be positive, not {}".format(src_cz))
+    for m in range(1, (1 << len(levels)) + 1):
+        try:
+            fused_check_blocks(levels, m * src_cz)
+        except ValueError:
+            continue
+        return m * src_cz
+    raise ValueError("pipelined pyramid: no z block of whole source chunks ({} planes each) holds whole 2 x 2 x 2 windows "
+                     "of {} levels and fills whole chunk rows of every level (z chunks {})".format(
+                         src_cz, len(levels), [lv.chunks[0] for lv in levels]))  # fmt: skip
+
+
 def compute_pyramid(data, n_lvls, scale_axis, chunks="auto", device=0, engine=None):
     """``zarr_destriper.py:365-407``: ``[level 0 (the input), level 1, ...]``, ``n_lvls`` entries.
 
@@ -125,7 +148,8 @@ def compute_pyramid(data, n_lvls, scale_axis, chunks="auto", device=0, engine=No
 
 
 def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_levels=3, chunks=(1, 1, 64, 128, 128),
-                       compressor="blosc", device=0, slab_planes=None):  # fmt: skip
+                       compressor="blosc", device=0, slab_planes=None, pipelined=False, device_codec=False,
+                       device_decode=False, io_threads=None):  # fmt: skip
     """Level loop of ``compute_multiscale`` (``zarr_destriper.py:746-782``) over Zarr-v2 directory stores
     (``zarr_destriper.compute_multiscale`` is the entry point with the reference's signature and calls this):
     writes ``<group_path>/<i>`` for ``i = 1 .. n_levels - 1`` (uint16, ``"/"`` separator), every level from the
@@ -135,10 +159,24 @@ def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_leve
     a slab of ``2 * output z-chunk`` source planes is read, reduced by one ``dsx_downsample2_u16`` launch
     and written as whole output chunks; the 2 x 2 x 2 windows never straddle a slab because slabs start
     at even planes.
-    """
-    import os
 
+    ``pipelined=True``: the same arrays, chunk files and voxels from ONE software-pipelined pass over level 0
+    (:class:`_PipelinedPyramid`): level 0 is read block by block on ``io_threads`` native threads straight into pinned
+    staging, every level is computed from the block where it lies in chunk order (``dsx_pyramid_bricks_u16``) and the
+    finished chunk rows leave through the I/O threads; no level is read back.  ``device_decode`` / ``device_codec``
+    (``False``, ``True``, ``"any"`` / ``"runs"``: ``zarr_destriper.device_decode_mode`` / ``device_codec_mode``) move the
+    Blosc decode of level 0 and the Blosc-zstd encode of the levels to the GPU; they need a Blosc uint16 input / a
+    Blosc-zstd uint16 output with byte shuffle, and ``pipelined``.  ``slab_planes`` is ignored then.
+    :data:`LAST_PYRAMID` holds what the call did.
+    """
     _check_scale((1,) * 2 + tuple(scale_factor))
+    if pipelined:
+        return _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, device, device_codec, device_decode,
+                                io_threads)  # fmt: skip
+    if device_codec is not False or device_decode is not False:
+        raise ValueError("device_codec / device_decode need pipelined=True: the slab route of write_pyramid_levels has no "
+                         "device codecs")  # fmt: skip
+    t_start = time.perf_counter()
     eng = _engine.DestripeEngine(device)
     shapes = []
     try:
@@ -175,4 +213,337 @@ def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_leve
             src_path = os.path.join(group_path, str(i))
     finally:
         eng.close()
+    LAST_PYRAMID.clear()
+    LAST_PYRAMID.update(route="slabs", block_z=None, levels=list(range(1, len(shapes) + 1)), decode_routes=None, read_s=None,
+                        write_s=None, upload_bytes=None, download_bytes=None, seconds=time.perf_counter() - t_start)  # fmt: skip
+    return shapes
+
+
+# ---- the stand-alone pyramid in one pipelined pass (write_pyramid_levels(pipelined=True)) ----------------------------
+# What the last write_pyramid_levels call of this process did: route ("pipelined" / "slabs"), block_z, levels,
+# decode_routes ({"device", "host", "fill"}: level-0 chunks by where they were decoded), read_s / write_s (time inside
+# the I/O stages), upload_bytes / download_bytes over the host link, seconds.  The slab route fills route, levels, seconds.
+LAST_PYRAMID = {}
+
+
+class _PipelinedPyramid:
+    """One pass over a finished level 0 that writes every pyramid level, software-pipelined like the level-0 pass
+    (``zarr_destriper._DeviceBlocks``: three streams, two sets of buffers, the two rules of its docstring) but without a
+    filter and without a level-0 output.
+
+    A block is ``block_z`` planes = whole source chunk rows (:func:`pipelined_block_z`), so it starts on a source chunk
+    boundary and goes to the device as it lies in the store.  While block ``b`` is reduced on the compute stream
+    (``dsx_pyramid_bricks_u16`` into each level's current device chunk row, at the block's z offset,
+    :func:`fused_schedule`), the chunks of block ``b + 1`` are read by the I/O threads into pinned staging and uploaded,
+    and the chunk rows that block ``b - 1`` completed are downloaded and written.
+
+    Ordering: upload(b) -> compute(b) -> download(b); upload(b + 2) after compute(b) (it refills the same device
+    buffer: ``stream_wait(upload, compute)`` right after compute(b) has been given its upload); a compute that refills
+    a device row waits for the downloads enqueued so far (``stream_wait(compute, download)`` in front of the kernel: a
+    level's rows alternate between two buffers and a level flushes at most once per block, so the row that used the
+    buffer left two flushes ago, and with ``device_codec`` its frame fetch was enqueued a block ago).  The host touches
+    a pinned buffer only behind its event slot: slot ``k`` = upload of input buffer ``k``, slot ``2 + k`` = downloads of
+    the block in slot ``k``; a pinned row goes to the writers after that event and is downloaded into again only after
+    ``writes[b - 2]`` has returned.
+
+    ``decode_mode`` (``device_decode``): the I/O threads read the files and pack the Blosc frames with one task per Blosc
+    block (``dsx_io_read_frames``), ``dsx_blosc_decode_device`` fills the device bricks, and the per-task statuses come
+    back on the compute stream and are checked before anything of the block reaches the writers.  ``codec_mode``
+    (``device_codec``): a finished row is encoded on the compute stream (``dsx_blosc_encode_device``), its offsets come
+    back first, then exactly the packed frames, and the I/O threads write the byte ranges.
+    """
+
+    N_BUF = 2
+
+    def __init__(self, eng, src, levels, arrays, block_z, io_threads, codec_mode=None, decode_mode=None):
+        self.eng, self.src, self.levels, self.arrays, self.block_z = eng, src, levels, arrays, int(block_z)
+        self.codec_mode, self.decode_mode, self.io_threads = codec_mode, decode_mode, int(io_threads)
+        self.zyx = tuple(int(n) for n in src.shape[-3:])
+        self.ci = tuple(int(c) for c in src.chunks[-3:])
+        _, H, W = self.zyx
+        self.gi = (self.block_z // self.ci[0], -(-H // self.ci[1]), -(-W // self.ci[2]))
+        self.in_brick = int(np.prod(self.ci))
+        n_in = int(np.prod(self.gi))
+        in_bytes = n_in * self.in_brick * 2
+        self.bufs = []
+        R = range(self.N_BUF)
+        self.d_src = [self._dev(in_bytes) for _ in R]
+        if decode_mode is not None:  # packed frames + task table replace the decompressed staging
+            cap = n_in * (self.in_brick * 2 + 16)
+            n_tasks = n_in * _engine.frame_tasks_per_chunk(self.in_brick * 2)
+            task_bytes = n_tasks * _engine.TASK_DTYPE.itemsize
+            self.packed = [self._host(cap).array((cap,), np.uint8) for _ in R]
+            self.tasks = [self._host(task_bytes).array((n_tasks,), _engine.TASK_DTYPE) for _ in R]
+            self.status = [self._host(4 * n_tasks).array((n_tasks,), np.int32) for _ in R]
+            self.d_packed = [self._dev(cap) for _ in R]
+            self.d_tasks = [self._dev(task_bytes) for _ in R]
+            self.d_status = [self._dev(4 * n_tasks) for _ in R]
+            self.routes = np.zeros(n_in, np.uint8)  # (one read at a time)
+            self.read_info = [None] * self.N_BUF  # (packed bytes, tasks, chunk paths) of the block read into buffer k
+            self.decode_info = [None] * self.N_BUF  # the same of the block SUBMITTED from buffer k (plus chunk / kind)
+        else:
+            self.stage_in = [self._host(in_bytes).array(self.gi + (self.in_brick,), np.uint16) for _ in R]
+        # per level: two device chunk rows in brick order + what carries a finished row to the host
+        self.grid, self.d_row, self.stage_row = [], [], []
+        self.d_frames, self.d_offsets, self.frames, self.offsets = [], [], [], []
+        for lv in levels:
+            ny, nx = -(-lv.shape[1] // lv.chunks[1]), -(-lv.shape[2] // lv.chunks[2])
+            brick = int(np.prod(lv.chunks))
+            self.grid.append((ny, nx, brick))
+            self.d_row.append([self._dev(ny * nx * brick * 2) for _ in R])
+            if codec_mode is not None:
+                cap = ny * nx * (brick * 2 + 16)
+                self.d_frames.append([self._dev(cap) for _ in R])
+                self.d_offsets.append([self._dev(8 * (ny * nx + 1)) for _ in R])
+                self.frames.append([self._host(cap).array((cap,), np.uint8) for _ in R])
+                self.offsets.append([self._host(8 * (ny * nx + 1)).array((ny * nx + 1,), np.int64) for _ in R])
+            else:
+                self.stage_row.append([self._host(ny * nx * brick * 2).array((ny, nx, brick), np.uint16) for _ in R])
+        work = _engine.pyramid_work_bytes((self.block_z, H, W), len(levels) + 1)
+        self.d_work = self._dev(work) if work else None
+        self.cur, self.flushes = [0] * len(levels), [[] for _ in R]
+        self.timing = {"read_s": 0.0, "write_s": 0.0, "upload_bytes": 0, "download_bytes": 0,
+                       "decode_routes": {"device": 0, "host": 0, "fill": 0}}  # fmt: skip
+
+    def _dev(self, nbytes):
+        self.bufs.append(self.eng.alloc(max(int(nbytes), 16)))
+        return self.bufs[-1]
+
+    def _host(self, nbytes):
+        self.bufs.append(self.eng.alloc_host(max(int(nbytes), 16)))
+        return self.bufs[-1]
+
+    def close(self):
+        for b in self.bufs:
+            b.free()
+        self.bufs = []
+
+    # -- host stages (I/O threads) -------------------------------------------------------------
+    def _read(self, z0, z1, k):
+        """The level-0 chunks of planes ``[z0, z1)`` into pinned buffer ``k`` (decoded, or as packed frames + tasks)."""
+        t0 = time.perf_counter()
+        lead = (0,) * (self.src.ndim - 3)
+        bz0, nbz = z0 // self.ci[0], -(-(z1 - z0) // self.ci[0])
+        idx = list(itertools.product(range(nbz), range(self.gi[1]), range(self.gi[2])))
+        paths = [self.src._chunk_path(lead + (bz0 + i[0], i[1], i[2])) for i in idx]
+        routes = self.timing["decode_routes"]
+        try:
+            if self.decode_mode is not None:
+                mode = _engine.ZDEC_ANY if self.decode_mode == "any" else _engine.ZDEC_ZSTD
+                pb, nt = self.eng.io_read_frames(paths, self.in_brick * 2, self.packed[k], self.tasks[k],
+                                                 threads=self.io_threads, fill_value=int(self.src.fill_value),
+                                                 routes=self.routes, mode=mode)  # fmt: skip
+                self.read_info[k] = (pb, nt, paths)
+                seen = np.bincount(self.routes[: len(paths)], minlength=3)
+                for name, r in (("device", _engine.ROUTE_DEVICE), ("host", _engine.ROUTE_HOST), ("fill", _engine.ROUTE_FILL)):
+                    routes[name] += int(seen[r])
+            else:
+                stage = self.stage_in[k]
+                self.eng.io_read_chunks(paths, [stage[i] for i in idx], threads=self.io_threads, codec=self.src.codec,
+                                        fill_value=int(self.src.fill_value))  # fmt: skip
+                there = sum(os.path.exists(p) for p in paths)
+                routes["host"] += there
+                routes["fill"] += len(paths) - there
+        except _engine.DsxError as e:
+            if e.message.startswith("blosc:"):  # a malformed frame the reader itself refused: "blosc: ... (<chunk file>)"
+                raise ValueError(e.message) from None
+            raise
+        finally:
+            self.timing["read_s"] += time.perf_counter() - t0
+        return nbz
+
+    def _write(self, flushes):
+        """The chunk rows that left with a block: ``(level index, buffer, chunk row)`` each."""
+        t0 = time.perf_counter()
+        try:
+            for i, j, row in flushes:
+                arr, (ny, nx, _) = self.arrays[i], self.grid[i]
+                lead = (0,) * (arr.ndim - 3)
+                idx = list(itertools.product(range(ny), range(nx)))
+                paths = [arr._chunk_path(lead + (row, y, x)) for y, x in idx]
+                if self.codec_mode is not None:  # finished frames: chunk c is bytes [offsets[c], offsets[c + 1])
+                    frames, offs = self.frames[i][j], self.offsets[i][j]
+                    self.eng.io_write_chunks(paths, [frames[offs[c] : offs[c + 1]] for c in range(len(idx))],
+                                             threads=self.io_threads, zlib_level=-1)  # fmt: skip
+                    continue
+                comp = arr.compressor
+                self.eng.io_write_chunks(paths, [self.stage_row[i][j][y, x] for y, x in idx], threads=self.io_threads,
+                                         zlib_level=-1 if comp is None else int(comp[1]),
+                                         blosc=arr.blosc_write_params() if comp and comp[0] == "blosc" else None)  # fmt: skip
+        finally:
+            self.timing["write_s"] += time.perf_counter() - t0
+
+    # -- device stages (asynchronous) ----------------------------------------------------------
+    def _submit_in(self, k, nbz):
+        """Upload(b), and with ``device_decode`` the decode: nothing here touches a device row."""
+        from .engine import STREAM_COMPUTE as C, STREAM_UPLOAD as U
+
+        eng = self.eng
+        if self.decode_mode is not None:
+            pb, nt, paths = self.read_info[k]
+            self.decode_info[k] = (nt, self.tasks[k]["chunk"][:nt].copy(), paths, self.tasks[k]["kind"][:nt].copy())
+            if pb:
+                eng.copy_h2d_async(self.d_packed[k], self.packed[k][:pb], U)
+            if nt:
+                eng.copy_h2d_async(self.d_tasks[k], self.tasks[k][:nt], U)
+            self.timing["upload_bytes"] += pb + nt * _engine.TASK_DTYPE.itemsize
+        else:
+            eng.copy_h2d_async(self.d_src[k], self.stage_in[k][:nbz], U)
+            self.timing["upload_bytes"] += self.stage_in[k][:nbz].nbytes
+        eng.event_record(k, U)  # pinned input buffer k may be refilled once this has passed
+        eng.stream_wait(C, U)   # compute(b) after upload(b)
+        eng.stream_wait(U, C)   # uploads from now on after compute(b - 1): they refill its buffer
+        if self.decode_mode is not None:  # the bricks from the frames; the statuses come back in stream order
+            eng.blosc_decode_device(self.d_packed[k], pb, self.d_tasks[k], nt, self.d_src[k], self.d_status[k])
+            if nt:
+                eng.copy_d2h_async(self.status[k][:nt], self.d_status[k], C)
+
+    def _submit_out(self, z0, z1, k, shares):
+        """Compute(b) and download(b): once the pinned rows of block b - 2 have been written out."""
+        from .engine import STREAM_COMPUTE as C, STREAM_DOWNLOAD as D
+
+        eng, (_, H, W), cur = self.eng, self.zyx, self.cur
+        eng.stream_wait(C, D)  # (lands before the kernel:) after the downloads enqueued so far
+        eng.pyramid_bricks(self.d_src[k], (z1 - z0, H, W), self.ci, [lv.chunks for lv in self.levels],
+                           [self.d_row[i][cur[i]] for i in range(len(shares))], z0s=[s.offset for s in shares],
+                           zero=[s.first for s in shares], rows=[1] * len(shares), d_work=self.d_work)  # fmt: skip
+        flushes = []
+        for i, s in enumerate(shares):
+            if not s.flush:
+                continue
+            j = cur[i]
+            if self.codec_mode is not None:
+                ny, nx, brick = self.grid[i]
+                eng.blosc_encode_device(self.d_row[i][j], ny * nx, brick * 2, self.d_frames[i][j], self.d_offsets[i][j],
+                                        typesize=2, clevel=int(self.arrays[i].compressor[1]), mode=self.codec_mode)  # fmt: skip
+            flushes.append((i, j, s.row))
+            cur[i] = (j + 1) % self.N_BUF
+        self.flushes[k] = flushes
+        eng.stream_wait(D, C)  # download(b) after compute(b)
+        for i, j, _ in flushes:
+            if self.codec_mode is not None:
+                eng.copy_d2h_async(self.offsets[i][j], self.d_offsets[i][j], D)
+            else:
+                eng.copy_d2h_async(self.stage_row[i][j], self.d_row[i][j], D)
+                self.timing["download_bytes"] += self.stage_row[i][j].nbytes
+        eng.event_record(self.N_BUF + k, D)  # the rows (or their frame offsets) and the statuses of block b are here
+
+    def _fetch_frames(self, k):
+        """(device codec; the offsets of the rows of the block in slot k are on the host) Download exactly their frames."""
+        from .engine import STREAM_DOWNLOAD as D
+
+        for i, j, _ in self.flushes[k]:
+            offs = self.offsets[i][j]
+            total = int(offs[-1])
+            self.timing["download_bytes"] += total + offs.nbytes
+            if total:
+                self.eng.copy_d2h_async(self.frames[i][j][:total], self.d_frames[i][j], D)
+        self.eng.event_record(self.N_BUF + k, D)
+        self.eng.event_sync(self.N_BUF + k)
+
+    def _check_decode(self, k):
+        """(device decode; the block in slot k has been computed) A malformed frame raises as the level-0 pass does."""
+        if self.decode_mode is None:
+            return
+        nt, chunk, paths, kinds = self.decode_info[k]
+        st = self.status[k][:nt]
+        bad = np.flatnonzero(st)
+        if bad.size:
+            i = int(bad[0])
+            codec = "lz4" if (int(kinds[i]) & 0xFF) == _engine.TASK_LZ4 else "zstd"
+            raise ValueError("blosc: bad {} stream ({}) [device decode status {}]".format(codec, paths[int(chunk[i])],
+                                                                                           int(st[i])))  # fmt: skip
+
+    def _finish(self, k, writer, writes):
+        """Block in slot k: wait for its downloads, check its statuses, then hand its rows to the writers."""
+        self.eng.event_sync(self.N_BUF + k)
+        self._check_decode(k)
+        if self.codec_mode is not None:
+            self._fetch_frames(k)
+        writes.append(writer.submit(self._write, list(self.flushes[k])))
+
+    def run(self):
+        """All blocks of level 0 through the pipeline; returns the number of blocks."""
+        sched = fused_schedule(self.levels, 0, self.zyx[0], self.block_z)
+        nb, N = len(sched), self.N_BUF
+        self.cur = [0] * len(self.levels)
+        reader = ThreadPoolExecutor(max_workers=1)  # stage drivers: one read and one write in flight,
+        writer = ThreadPoolExecutor(max_workers=1)  # each fanning its chunks out over the I/O pool
+        try:
+            reads = {b: reader.submit(self._read, *sched[b][0], b % N) for b in range(min(N, nb))}
+            writes = []
+            for b in range(nb):
+                k = b % N
+                (z0, z1), shares = sched[b]
+                nbz = reads.pop(b).result()
+                self._submit_in(k, nbz)
+                if b >= N:
+                    writes[b - N].result()  # the pinned rows of slot k have been written out
+                self._submit_out(z0, z1, k, shares)
+                if b + N < nb:
+                    self.eng.event_sync(k)  # upload(b) has left pinned input buffer k
+                    reads[b + N] = reader.submit(self._read, *sched[b + N][0], k)
+                if b >= 1:
+                    self._finish((b - 1) % N, writer, writes)
+            if nb:
+                self._finish((nb - 1) % N, writer, writes)
+            for w in writes:
+                w.result()
+        finally:
+            reader.shutdown()
+            writer.shutdown()
+        return nb
+
+
+def _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, device, device_codec, device_decode, io_threads):
+    from . import zarr_destriper as zd
+
+    t_start = time.perf_counter()
+    codec_mode = zd.device_codec_mode(device_codec)
+    decode_mode = zd.device_decode_mode(device_decode)
+    src = MiniZarrArray.open(level0_path)
+    if src.dtype != np.uint16 or any(n != 1 for n in src.shape[:-3]):
+        raise ValueError("the pyramid kernel takes uint16 volumes with singleton leading axes")
+    if decode_mode is not None and (src.compressor is None or src.compressor[0] != "blosc"):
+        raise ValueError("device_decode needs a Blosc uint16 input, not {!r} {}".format(src.compressor, src.dtype))
+    zyx, lead = tuple(src.shape[-3:]), tuple(src.shape[:-3])
+    levels = fused_levels(zyx, chunks, n_levels)
+    block_z = pipelined_block_z(src.chunks[-3], levels) if levels else None
+    arrays, shapes = [], []
+    for lv in levels:  # created as the slab route creates them
+        out_shape = lead + lv.shape
+        ck = tuple(min(c, n) for c, n in zip(tuple(chunks)[-len(out_shape):], out_shape))
+        if len(ck) != len(out_shape) or ck[-3:] != lv.chunks:
+            raise ValueError("chunks {} do not cover the axes of a level of shape {}".format(tuple(chunks), out_shape))
+        arrays.append(MiniZarrArray.create(os.path.join(group_path, str(lv.level)), out_shape, ck, np.uint16,
+                                           compressor=compressor, dimension_separator="/"))  # fmt: skip
+        shapes.append(out_shape)
+    if codec_mode is not None and arrays:
+        comp = arrays[0].compressor
+        if comp is None or comp[0] != "blosc" or comp[2] != "zstd" or comp[3] != 1:
+            raise ValueError("device_codec needs a Blosc-zstd uint16 output with byte shuffle, not {!r}".format(comp))
+    if io_threads is None:
+        io_threads = zd.default_io_threads(1)
+    LAST_PYRAMID.clear()
+    LAST_PYRAMID.update(route="pipelined", block_z=block_z, levels=[lv.level for lv in levels], decode_routes=None,
+                        read_s=0.0, write_s=0.0, upload_bytes=0, download_bytes=0, seconds=None)  # fmt: skip
+    if levels:
+        eng = _engine.DestripeEngine(device)
+        pipe = None
+        try:
+            pipe = _PipelinedPyramid(eng, src, levels, arrays, block_z, io_threads, codec_mode, decode_mode)
+            try:
+                pipe.run()
+            finally:
+                LAST_PYRAMID.update({k: (dict(v) if isinstance(v, dict) else v) for k, v in pipe.timing.items()})
+            eng.sync()
+        finally:
+            if pipe is not None:
+                try:
+                    eng.sync()  # nothing in flight reads or writes a buffer that is about to be freed
+                except Exception:  # noqa: BLE001 - the error that brought us here is the one to report
+                    pass
+                pipe.close()
+            eng.close()
+    LAST_PYRAMID["seconds"] = time.perf_counter() - t_start
     return shapes

@@ -974,6 +974,10 @@ def compute_multiscale(
     compressor="blosc",
     device=0,
     slab_planes=None,
+    pipelined=False,
+    device_codec=False,
+    device_decode=False,
+    io_threads=None,
 ):
     """``compute_multiscale`` of the reference (``zarr_destriper.py:677-794``) with its signature.
 
@@ -982,6 +986,13 @@ def compute_multiscale(
     ``threads_per_worker`` sized the reference's dask ``LocalCluster`` (``:689-697``) and ``voxel_size`` /
     ``image_name`` feed its OME-NGFF metadata (``:728-742``): accepted, not used -- one HIP kernel per level replaces the
     cluster, the metadata is out of scope.  Returns the shapes of the written levels.
+
+    ``pipelined=True``: the same stores from one software-pipelined pass over level 0 -- level 0 is read by ``io_threads``
+    native threads into pinned staging, every level comes from the block where it lies in chunk order
+    (``dsx_pyramid_bricks_u16``), no level is read back (``pyramid.write_pyramid_levels``; ``slab_planes`` is ignored).
+    ``device_decode`` / ``device_codec`` (as in :func:`destripe_zarr_store`: ``False``, ``True``, ``"any"`` / ``"runs"``)
+    then decode level 0 and encode the levels on the GPU; without ``pipelined`` they raise ``ValueError``.
+    ``pyramid.LAST_PYRAMID`` holds what the call did.
     """
     from . import pyramid
 
@@ -989,7 +1000,9 @@ def compute_multiscale(
     level0 = getattr(output_zarr, "path", output_zarr)
     group_path = getattr(zarr_group, "path", zarr_group)
     return pyramid.write_pyramid_levels(str(level0), str(group_path), scale_factor=tuple(scale_factor), n_levels=n_levels,
-                                        chunks=chunks, compressor=compressor, device=device, slab_planes=slab_planes)  # fmt: skip
+                                        chunks=chunks, compressor=compressor, device=device, slab_planes=slab_planes,
+                                        pipelined=pipelined, device_codec=device_codec, device_decode=device_decode,
+                                        io_threads=io_threads)  # fmt: skip
 
 
 def destripe_zarr(
@@ -1021,6 +1034,7 @@ def destripe_zarr(
     device_codec=False,
     device_decode=False,
     fused_pyramid=False,
+    pipelined_pyramid=False,
 ):
     """``destripe_zarr`` of the reference (``zarr_destriper.py:909-1211``) with its 14 parameters, on the GPU chunk map.
 
@@ -1048,11 +1062,16 @@ def destripe_zarr(
     ``compressor`` / ``output_chunks`` of the output, ``n_levels``, ``device_retile``, ``io_threads``, ``device_codec``, ``device_decode``
     (level 0 encoded / decoded on the GPU, :func:`destripe_zarr_store`; ``device_codec="runs"`` = with run matches), ``fused_pyramid`` (levels ``1 .. n_levels - 1``
     are written by every rank in the level-0 pass, from the filtered planes in device memory, instead of by
-    :func:`compute_multiscale` on rank 0 afterwards; same stores; z shards of ``output z chunk << (levels - 1)`` planes).
+    :func:`compute_multiscale` on rank 0 afterwards; same stores; z shards of ``output z chunk << (levels - 1)`` planes),
+    ``pipelined_pyramid`` (rank 0's :func:`compute_multiscale` call runs with ``pipelined=True``, this call's
+    ``device_codec`` and ``io_threads``, and this call's ``device_decode`` when the output is Blosc -- level 0 is this
+    run's own output; same stores; ``ValueError`` together with ``fused_pyramid``).
     Returns ``(planes processed by this rank, seconds)``.
     """
     device_codec_mode(device_codec)  # (a wrong string fails before anything is written)
     device_decode_mode(device_decode)
+    if fused_pyramid and pipelined_pyramid:
+        raise ValueError("fused_pyramid and pipelined_pyramid are two routes to the same pyramid: choose one")
     no_cells_config = parameters["no_cells_config"]
     cells_config = parameters["cells_config"]
     co_cpus = _cpu_limit()
@@ -1134,6 +1153,11 @@ def destripe_zarr(
         group.barrier()  # level 0 of this tile is complete on every rank: the pyramid may read it
     if rank == 0 and n_levels > 1 and not fused_pyramid:
         dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device
+        pipelined_kw = {}
+        if pipelined_pyramid:
+            out_is_blosc = (MiniZarrArray._compressor_meta(compressor) or {}).get("id") == "blosc"  # level 0 = our output
+            pipelined_kw = dict(pipelined=True, device_codec=device_codec, io_threads=io_threads,
+                                device_decode=device_decode if out_is_blosc else False)  # fmt: skip
         t0 = time.perf_counter()
         compute_multiscale(
             output_zarr=str(level0),
@@ -1147,6 +1171,7 @@ def destripe_zarr(
             chunks=output_chunks,
             compressor=compressor,
             device=dev,
+            **pipelined_kw,
         )
         logger.info(f"Processing multiscale time: {time.perf_counter() - t0} seconds")
     logger.info(f"Processing destripe flatfield time: {seconds} seconds")
@@ -1178,6 +1203,7 @@ def destripe_channel(
     device_codec=False,
     device_decode=False,
     fused_pyramid=False,
+    pipelined_pyramid=False,
 ):
     """``destripe_channel`` of the reference (``zarr_destriper.py:1214-1267``), same eight parameters (the reference's
     caller passes them by keyword, ``run_capsule.py:394-403``), wired to the GPU chunk map.
@@ -1191,7 +1217,7 @@ def destripe_channel(
 
     Keyword-only extras: ``rank`` / ``world_size`` / ``group`` / ``device`` (one process per GPU), output codec and
     chunks, ``multiscale`` (the reference hard-codes ``"0"``), ``prediction_chunksize`` (the reference hard-codes the
-    production tile, ``(64, 1600, 2000)``), ``io_threads``, ``device_retile``, ``device_codec``, ``device_decode``, ``fused_pyramid`` (:func:`destripe_zarr`).  ``world_size > 1`` needs ``group`` (anything with
+    production tile, ``(64, 1600, 2000)``), ``io_threads``, ``device_retile``, ``device_codec``, ``device_decode``, ``fused_pyramid``, ``pipelined_pyramid`` (:func:`destripe_zarr`).  ``world_size > 1`` needs ``group`` (anything with
     ``barrier()``): the pyramid of a tile may only be computed once EVERY rank has written its z-range.  With a
     ``distributed.RankGroup`` rank 0 alone reads the flat and dark planes of a tile and broadcasts them (RCCL).
     """
@@ -1199,6 +1225,8 @@ def destripe_channel(
         raise ValueError("destripe_channel with world_size > 1 needs a group to order the pyramid after all ranks")
     device_codec_mode(device_codec)  # (a wrong string fails before anything is written)
     device_decode_mode(device_decode)
+    if fused_pyramid and pipelined_pyramid:
+        raise ValueError("fused_pyramid and pipelined_pyramid are two routes to the same pyramid: choose one")
     logger = logger or logging.getLogger("dsx.zarr")
     zarr_dataset_path, results_folder = Path(zarr_dataset_path), Path(results_folder)
     channel_dataset = zarr_dataset_path.joinpath(channel_name)
@@ -1245,6 +1273,7 @@ def destripe_channel(
             device_codec=device_codec,
             device_decode=device_decode,
             fused_pyramid=fused_pyramid,
+            pipelined_pyramid=pipelined_pyramid,
         )
         done[tile_path.name] = n
     return done

@@ -199,6 +199,19 @@ int dsx_pyramid_block_u16(dsx_ctx* ctx, const void* d_planes, int Z, int H, int 
                           const dsx_pyramid_level* levels, void* const* d_bricks, void* d_work, size_t work_bytes);
 int dsx_pyramid_block_ref(const void* planes, int Z, int H, int W, int n_levels, const dsx_pyramid_level* levels,
                           void* const* bricks);
+/* The same levels from a block that is still in the chunk order it was stored in -- a decoded level-0 block of a
+ * finished store, for the stand-alone pyramid (compute_pyramid, zarr_destriper.py:365-407; level loop of
+ * compute_multiscale, :746-782) -- without dsx_bricks_to_planes_u16 in front.  d_src_bricks:
+ * [nbz][nby][nbx][src_cz][src_cy][src_cx] uint16, every brick full-sized, nb* = ceil((Z, H, W) / src_c*); plane 0 of
+ * the block is plane 0 of the brick grid (the block starts on a source chunk boundary).  Bricks that stick out of
+ * [Z, H, W] hold whatever the store held there: those positions are never read.  levels / d_bricks / d_work, `zero`,
+ * `rows`, `z0`, the outputs and the refusals are dsx_pyramid_block_u16's.  Asynchronous on the context stream.
+ * dsx_pyramid_bricks_ref: the host build (host pointers, synchronous, identical output). */
+int dsx_pyramid_bricks_u16(dsx_ctx* ctx, const void* d_src_bricks, int Z, int H, int W, int src_cz, int src_cy,
+                           int src_cx, int n_levels, const dsx_pyramid_level* levels, void* const* d_bricks,
+                           void* d_work, size_t work_bytes);
+int dsx_pyramid_bricks_ref(const void* src_bricks, int Z, int H, int W, int src_cz, int src_cy, int src_cx,
+                           int n_levels, const dsx_pyramid_level* levels, void* const* bricks);
 
 /* Host side of the chunk map: n Zarr chunk files <-> memory (normally the pinned staging buffers) on
  * `threads` native threads -- what zarr / numcodecs do under the reference's worker processes

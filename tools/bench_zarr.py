@@ -5,7 +5,7 @@ download) into another store.  Prints one JSON line; the roofline of this path i
 (PCIe Gen5 x16, 63 GB/s spec: 16.8 MB per plane both ways -> <= 3.7 k planes/s), not HBM.
 
     bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode|device-decode-any] [lz4]
-                  [pyramid|fused-pyramid]
+                  [pyramid|fused-pyramid|pipelined-pyramid]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
 line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
@@ -17,7 +17,9 @@ shuffle, 256 KiB blocks split into a low-byte and a high-byte stream (the test s
 tests/blosc_any_frames.py; every 64-plane block holds the same planes, as in the other variants); the output stays
 Blosc-zstd.  The line then reports the input store's bytes and the chunks decoded on the device / host / filled.
 `pyramid`: after the timed level-0 pass, compute_multiscale(n_levels=3) on the store is timed too (the two-pass route);
-`fused-pyramid`: level 0 and levels 1-2 in one destripe_zarr_store call (pyramid_group / n_levels).  Both add level-0,
+`fused-pyramid`: level 0 and levels 1-2 in one destripe_zarr_store call (pyramid_group / n_levels);
+`pipelined-pyramid`: level 0 is timed as without a pyramid word, then compute_multiscale(pipelined=True, n_levels=3) with the
+codec words given (device-decode only on a Blosc store) -- its line carries pyramid.LAST_PYRAMID as "pipelined".  All add level-0,
 pyramid and total seconds, the levels' bytes on disk (with the host writer's frames of each level's first chunk row for
 comparison) and a check of the first level-1 / level-2 planes against the NumPy oracle.
 Every line reports the read / write stage times of the timed pass (I/O threads, summed per block), the bytes that
@@ -34,7 +36,7 @@ codec = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2] != "raw" else None  # N
 device_codec = "runs" if "device-codec-runs" in sys.argv[3:] else "device-codec" in sys.argv[3:]
 device_decode = "any" if "device-decode-any" in sys.argv[3:] else "device-decode" in sys.argv[3:]
 lz4_input = "lz4" in sys.argv[3:]
-two_pass, fused = "pyramid" in sys.argv[3:], "fused-pyramid" in sys.argv[3:]
+two_pass, fused, pipelined = ("pyramid" in sys.argv[3:], "fused-pyramid" in sys.argv[3:], "pipelined-pyramid" in sys.argv[3:])
 H = W = 2048
 root = tempfile.mkdtemp(prefix="dsx_zarr_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
@@ -67,7 +69,7 @@ try:
     t_make = time.perf_counter() - t0
     res = {}
     group = os.path.join(root, "out.zarr")
-    level0 = os.path.join(group, "0") if two_pass or fused else group
+    level0 = os.path.join(group, "0") if two_pass or fused or pipelined else group
     for name, kw in (("overlapped", {"pyramid_group": group, "n_levels": 3} if fused else {}),):
         for rep in range(2):  # second pass: plan + pinned buffers exist, page cache warm
             t0 = time.perf_counter()
@@ -84,13 +86,21 @@ try:
         decode["input_ratio_to_raw"] = round(decode["input_store_bytes"] / (n * H * W * 2), 4)
     secs = res["overlapped"]["seconds"]
     pyr = {}
-    if two_pass or fused:
+    if two_pass or fused or pipelined:
         pyramid_s = 0.0
+        if pipelined:  # one pipelined device pass over the finished level 0 (compute_multiscale(pipelined=True))
+            from aind_smartspim_destripe_amd import pyramid
+            t0 = time.perf_counter()
+            zd.compute_multiscale(level0, group, [2, 2, 2], 1, None, "bench", n_levels=3, compressor=codec, device=0,
+                                  pipelined=True, device_codec=device_codec, io_threads=16,
+                                  device_decode=device_decode if codec == "blosc" else False)
+            pyramid_s = time.perf_counter() - t0
+            pyr["pipelined"] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in pyramid.LAST_PYRAMID.items()}
         if two_pass:  # the route destripe_zarr takes by default: rank 0 reads level 0 back and writes the levels
             t0 = time.perf_counter()
             zd.compute_multiscale(level0, group, [2, 2, 2], 1, None, "bench", n_levels=3, compressor=codec, device=0)
             pyramid_s = time.perf_counter() - t0
-        pyr = {"route": "fused" if fused else "two-pass", "level0_s": round(secs, 3), "pyramid_s": round(pyramid_s, 3),
+        pyr = {**pyr, "route": "fused" if fused else ("pipelined" if pipelined else "two-pass"), "level0_s": round(secs, 3), "pyramid_s": round(pyramid_s, 3),
                "total_s": round(secs + pyramid_s, 3), "pyramid_download_bytes": int(timing["pyramid_download_bytes"])}
     up, down = int(timing["upload_bytes"]), int(timing["download_bytes"])
     link = {"upload_bytes": up, "download_bytes": down,
@@ -154,7 +164,7 @@ try:
                     verified = False
                     print("oracle mismatch", e, file=sys.stderr)
     label = (codec or "raw") + (", LZ4 input" if lz4_input else "") + (", encoded on the device" + (" with run matches" if device_codec == "runs" else "") if device_codec else "") + (", decoded on the device" + (" (any)" if device_decode == "any" else "") if device_decode else "")
-    label += ", pyramid fused" if fused else ""
+    label += ", pyramid fused" if fused else ""  # (a stand-alone pyramid, slab or pipelined, is not part of the metric)
     print(json.dumps({"metric": "2048x2048 uint16 slices/s, Zarr store to Zarr store ({} chunks, tmpfs)".format(label), "value": round(v, 1),
                       "planes": n, "seconds": res["overlapped"]["seconds"], "store_make_s": round(t_make, 1),
                       "roofline": {"bound": "host link", "peak_planes_per_s": 3750, "frac": round(v / 3750.0, 3)},
