@@ -2229,7 +2229,7 @@ int dsx_io_read_frames_ex(dsx_ctx* ctx, const char* const* paths, int n, size_t 
                           size_t* packed_bytes, int* n_tasks, uint8_t* routes, int mode) {
   if (n < 0 || (n > 0 && (!paths || !packed || !tasks)) || !packed_bytes || !n_tasks || task_capacity < 0)
     return DSX_EINVAL;
-  if (mode != DSX_ZDEC_ZSTD && mode != DSX_ZDEC_ANY) return DSX_EINVAL;
+  if (mode != DSX_ZDEC_ZSTD && mode != DSX_ZDEC_ANY && mode != DSX_ZDEC_ALL) return DSX_EINVAL;
   const std::string e = dsx::io_read_frames(paths, n, chunk_bytes, threads, fill_value, (unsigned char*)packed,
                                             packed_capacity, (dsx::zdec::DecTask*)tasks, (size_t)task_capacity,
                                             packed_bytes, n_tasks, routes, mode);
@@ -2244,13 +2244,25 @@ int dsx_io_read_frames(dsx_ctx* ctx, const char* const* paths, int n, size_t chu
                                task_capacity, packed_bytes, n_tasks, routes, DSX_ZDEC_ZSTD);
 }
 
+int dsx_io_read_zlib_chunks(dsx_ctx* ctx, const char* const* paths, int n, size_t chunk_bytes, int threads,
+                            uint16_t fill_value, void* packed, size_t packed_capacity, void* tasks, int task_capacity,
+                            size_t* packed_bytes, int* n_tasks, uint8_t* routes) {
+  if (n < 0 || (n > 0 && (!paths || !packed || !tasks)) || !packed_bytes || !n_tasks || task_capacity < 0)
+    return DSX_EINVAL;
+  const std::string e = dsx::io_read_zlib_chunks(paths, n, chunk_bytes, threads, fill_value, (unsigned char*)packed,
+                                                 packed_capacity, (dsx::zdec::DecTask*)tasks, (size_t)task_capacity,
+                                                 packed_bytes, n_tasks, routes);
+  if (!e.empty()) return fail(ctx, DSX_EIO, e);
+  return DSX_OK;
+}
+
 int dsx_blosc_decode_ref(const void* packed, size_t packed_bytes, const void* tasks, int n_tasks, void* out,
                          size_t out_bytes, int32_t* status) {
   if ((!packed && packed_bytes) || (!tasks && n_tasks) || n_tasks < 0 || (!out && out_bytes) || (!status && n_tasks))
     return DSX_EINVAL;
   namespace z = dsx::zdec;
   const z::DecTask* t = (const z::DecTask*)tasks;
-  z::Tables* work = new z::Tables;
+  z::DecWork* work = new z::DecWork;
   std::vector<uint8_t> tmp;
   for (int i = 0; i < n_tasks; ++i) {
     const z::DecTask& k = t[i];
@@ -2260,7 +2272,7 @@ int dsx_blosc_decode_ref(const void* packed, size_t packed_bytes, const void* ta
       continue;
     }
     tmp.resize(k.dst_len);
-    status[i] = z::run_task_host_any(*work, k, (const uint8_t*)packed, (uint8_t*)out, tmp.data());
+    status[i] = z::run_task_host_all(*work, k, (const uint8_t*)packed, (uint8_t*)out, tmp.data());
   }
   delete work;
   return DSX_OK;
@@ -2281,10 +2293,14 @@ int dsx_blosc_decode_device(dsx_ctx* ctx, const void* d_packed, size_t packed_by
       return fail(ctx, DSX_ENOMEM, "blosc_decode: cannot allocate the work buffer");
     ctx->zdec_bytes = out_bytes;
   }
-  if (n_tasks > 0)
-    hipLaunchKernelGGL(z::k_zdec, dim3((unsigned)n_tasks), dim3(z::kDecThreads), 0, s,
-                       z::DecArgs{(const uint8_t*)d_packed, (const z::DecTask*)d_tasks, (uint8_t*)d_out,
-                                  ctx->zdec_scratch, d_status, (uint64_t)packed_bytes, (uint64_t)out_bytes});
+  if (n_tasks > 0) {
+    const z::DecArgs da{(const uint8_t*)d_packed, (const z::DecTask*)d_tasks, (uint8_t*)d_out,
+                        ctx->zdec_scratch, d_status, (uint64_t)packed_bytes, (uint64_t)out_bytes};
+    hipLaunchKernelGGL(z::k_zdec, dim3((unsigned)n_tasks), dim3(z::kDecThreads), 0, s, da);
+    // the zlib and blosclz tasks (DSX_ZDEC_ALL); the table is on the device, so the launch does not know whether it
+    // holds any: a wave of either kernel leaves at once when the task is the other's
+    hipLaunchKernelGGL(z::k_zdec_all, dim3((unsigned)n_tasks), dim3(z::kDecThreads), 0, s, da);
+  }
   DSX_HIP(hipGetLastError());
   return DSX_OK;
 }

@@ -31,6 +31,7 @@
 #include <unistd.h>
 #include <zlib.h>
 
+#include "dsx_inflate.h"
 #include "dsx_lz4_dec.h"
 #include "dsx_zstd_dec.h"
 
@@ -500,7 +501,9 @@ inline std::string io_read_chunks(const char* const* paths, void* const* dst, co
 // shuffle, and split blocks (zstd or LZ4) -- one task per Blosc block still: a split task's src is the length word of
 // its first stream and its src_len spans both streams.  Type sizes other than 2, blosclz / zlib / snappy, zstd
 // checksums and chunks of more than frame_tasks_per_chunk blocks stay on the host.
-constexpr int kZdecZstd = 0, kZdecAny = 1;
+// mode kZdecAll (DSX_ZDEC_ALL) is kZdecAny plus what dsx_inflate.h decodes: blosclz and zlib inside, in the same
+// layouts (split or not, no / byte / bit shuffle).  Snappy stays on the host.
+constexpr int kZdecZstd = 0, kZdecAny = 1, kZdecAll = 3;  // (2 is refused, as before)
 inline size_t frame_tasks_per_chunk(size_t chunk_bytes) { return chunk_bytes / 8192 + 1; }
 enum FrameRoute { kRouteDevice = 0, kRouteHost = 1, kRouteFill = 2 };
 
@@ -520,12 +523,15 @@ inline bool blosc_device_route(const unsigned char* src, size_t n, size_t want, 
     return true;
   }
   const int inner = (flags >> 5) & 7;
-  const bool any = mode == kZdecAny;
-  if (typesize != 2 || (inner != kInnerZstd && !(any && inner == kInnerLz4))) return false;
+  const bool all = mode == kZdecAll, any = mode == kZdecAny || all;
+  if (typesize != 2 || (inner != kInnerZstd && !(any && inner == kInnerLz4) &&
+                        !(all && (inner == kInnerBlosclz || inner == kInnerZlib)))) return false;
   if ((flags & kBloscBitshuffle) && !any) return false;
   const uint32_t shuf = (flags & kBloscBitshuffle) ? zdec::kTaskBitshuffle
                                                    : ((flags & kBloscShuffle) ? zdec::kTaskShuffle : 0u);
-  const uint32_t coded = inner == kInnerZstd ? (uint32_t)zdec::kTaskZstd : zdec::kTaskLz4;
+  const uint32_t coded = inner == kInnerZstd ? (uint32_t)zdec::kTaskZstd
+                         : inner == kInnerLz4 ? zdec::kTaskLz4
+                         : inner == kInnerZlib ? zdec::kTaskZlib : zdec::kTaskBlosclz;
   const bool dont_split = (flags & kBloscDontSplit) != 0;
   if (blocksize == 0 || blocksize > nbytes) return false;
   const size_t nblocks = (nbytes + blocksize - 1) / blocksize;
@@ -606,6 +612,54 @@ inline std::string io_read_frames(const char* const* paths, int n, size_t chunk_
     const size_t off = at.fetch_add(chunk_bytes);
     const std::string e = blosc_decode(raw.data(), raw.size(), packed + off, chunk_bytes);
     if (!e.empty()) return e + " (" + paths[i] + ")";
+    tasks[nt.fetch_add(1)] = zdec::DecTask{off, dst, (uint32_t)chunk_bytes, (uint32_t)chunk_bytes, zdec::kTaskCopy,
+                                           (uint32_t)i};
+    if (routes) routes[i] = kRouteHost;
+    return "";
+  });
+  *packed_bytes = at.load();
+  *n_tasks = (int)nt.load();
+  return err;
+}
+
+// The chunk files of a store whose compressor is plain zlib, for the device decoder: as io_read_frames, with one task
+// of kind kTaskZlib per chunk (the whole file is the stream, dst_len = chunk_bytes, no shuffle).  A file that does not
+// fit the chunk's share of `packed` (chunk_bytes + 16: zlib found nothing to gain) is inflated here and shipped as a
+// copy task.
+inline std::string io_read_zlib_chunks(const char* const* paths, int n, size_t chunk_bytes, int threads, uint16_t fill,
+                                       unsigned char* packed, size_t packed_cap, zdec::DecTask* tasks, size_t task_cap,
+                                       size_t* packed_bytes, int* n_tasks, unsigned char* routes) {
+  if (chunk_bytes > 0x7FFFFFEFu) return "io_read_zlib_chunks: chunk larger than a task can hold";
+  if (packed_cap < (size_t)n * (chunk_bytes + kBloscHeader) || task_cap < (size_t)n)
+    return "io_read_zlib_chunks: packed buffer or task table too small";
+  std::atomic<size_t> at(0), nt(0);
+  const std::string err = io_parallel(n, threads, [&](int i) -> std::string {
+    const uint64_t dst = (uint64_t)i * chunk_bytes;
+    struct stat st;
+    if (stat(paths[i], &st) != 0) {
+      if (errno != ENOENT) return std::string("cannot stat chunk ") + paths[i];
+      tasks[nt.fetch_add(1)] = zdec::DecTask{fill, dst, 0, (uint32_t)chunk_bytes, zdec::kTaskFill, (uint32_t)i};
+      if (routes) routes[i] = kRouteFill;
+      return "";
+    }
+    const size_t fbytes = (size_t)st.st_size;
+    if (fbytes <= chunk_bytes + kBloscHeader) {
+      const size_t off = at.fetch_add(fbytes);
+      if (io_read_file(paths[i], packed + off, fbytes) != (long long)fbytes)
+        return std::string("short or failed read of chunk ") + paths[i];
+      tasks[nt.fetch_add(1)] = zdec::DecTask{off, dst, (uint32_t)fbytes, (uint32_t)chunk_bytes, zdec::kTaskZlib,
+                                             (uint32_t)i};
+      if (routes) routes[i] = kRouteDevice;
+      return "";
+    }
+    static thread_local std::vector<unsigned char> raw;
+    raw.resize(fbytes);
+    if (io_read_file(paths[i], raw.data(), fbytes) != (long long)fbytes)
+      return std::string("short or failed read of chunk ") + paths[i];
+    const size_t off = at.fetch_add(chunk_bytes);
+    uLongf out_len = (uLongf)chunk_bytes;
+    if (uncompress(packed + off, &out_len, raw.data(), (uLong)fbytes) != Z_OK || out_len != chunk_bytes)
+      return std::string("zlib: bad chunk ") + paths[i];
     tasks[nt.fetch_add(1)] = zdec::DecTask{off, dst, (uint32_t)chunk_bytes, (uint32_t)chunk_bytes, zdec::kTaskCopy,
                                            (uint32_t)i};
     if (routes) routes[i] = kRouteHost;

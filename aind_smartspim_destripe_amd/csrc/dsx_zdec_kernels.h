@@ -1,7 +1,8 @@
 // dsx_zdec_kernels.h -- Blosc blocks decoded on the device (dsx_blosc_decode_device): one wave per task of
 // dsx_io_read_frames (dsx_zstd_dec.h DecTask).
 //
-//   k_zdec   grid = tasks, 64 threads.  Fill / copy / stored tasks are wide copies (with the 2-byte un-shuffle where
+//   k_zdec, k_zdec_all   grid = tasks, 64 threads each; every task belongs to one of the two (k_zdec_all: the kinds of
+//            dsx_inflate.h) and the other kernel's wave leaves at once.  Fill / copy / stored tasks are wide copies (with the 2-byte un-shuffle where
 //            the frame is shuffled).  A zstd task runs the decoder core of dsx_zstd_dec.h: lane 0 parses the headers
 //            and builds the Huffman and FSE tables in LDS; the four literal streams are decoded by lanes 0 .. 3 into
 //            the end of the task's output, reading their bits from LDS, where the wave stages kLitWin bytes of each
@@ -18,11 +19,18 @@
 //            length each (stored, zstd or LZ4): the wave decodes them one after the other into the two halves of
 //            the block and un-shuffles after both.  A bit-shuffled task is un-shuffled by 8 x 8 bit transposes, 8
 //            elements per lane and round.
+//            A zlib task (dsx_inflate.h) has literals and matches interleaved in one bit stream: every lane runs the
+//            same parse (inf_step) over the staged window of the stream -- lane 0 alone stores the code tables, which
+//            share the LDS of the zstd tables -- into a batch of up to kSeqBatch sequences and a literal window in
+//            LDS, then the wave executes the batch as it does the zstd sequences; a stored block is one wide copy.
+//            The Adler-32 of the stream is checked against the bytes the wave made.  A blosclz task is an LZ4 task
+//            with another generator (blosclz_next).
 #ifndef DSX_ZDEC_KERNELS_H
 #define DSX_ZDEC_KERNELS_H
 
 #include <hip/hip_runtime.h>
 
+#include "dsx_inflate.h"
 #include "dsx_lz4_dec.h"
 #include "dsx_zstd_dec.h"
 
@@ -127,9 +135,13 @@ __device__ __forceinline__ void wave_unbitshuffle(uint8_t* d, const uint8_t* s, 
   if ((n & 1u) && lane == 0) d[n - 1] = s[n - 1];
 }
 
-// LDS of one wave: the tables and staging of the zstd decoder; an LZ4 stream stages its window in lbuf
+// LDS of one wave: the tables and staging of the zstd decoder; an LZ4 or blosclz stream stages its window in lbuf; a
+// zlib stream has its tables in the place of the zstd tables, its window in lbuf[0] and its literals in lbuf[2 .. 3]
 struct WaveLds {
-  Tables t;
+  union {
+    Tables t;
+    InfTables inf;
+  };
   Seq batch[kSeqBatch];
   Streams ss;
   int32_t sh_st, sh_cnt, sh_lst[4];
@@ -139,6 +151,9 @@ struct WaveLds {
 };
 
 constexpr uint32_t kLz4Win = 2048;  // bytes of an LZ4 stream staged in LDS (within WaveLds::lbuf)
+constexpr uint32_t kInfLitWin = 4096;  // literals of a batch of a zlib stream (WaveLds::lbuf[2 .. 3])
+static_assert(kLz4Win <= kLitWin && kInfLitWin <= 2 * kLitWin, "the windows lie in WaveLds::lbuf");
+static_assert(sizeof(WaveLds::batch) >= 2 * 64 * sizeof(uint32_t), "wave_adler32 reduces in WaveLds::batch");
 
 // The bytes of an LZ4 stream for lz4_next, read by every lane alike: a window [lo, lo + cnt) of the stream in LDS
 // that the wave refills together (uniform control flow) at the first byte asked for outside it.
@@ -148,7 +163,7 @@ struct Lz4Window {
   uint8_t* win;
   uint32_t lo, cnt;
   int lane;
-  __device__ uint8_t at(uint32_t p) {  // p < n
+  __device__ __forceinline__ uint8_t at(uint32_t p) {  // p < n
     if (p - lo >= cnt) {
       __syncthreads();  // the reads of the window so far
       lo = p;
@@ -195,6 +210,125 @@ __device__ __forceinline__ int lz4_wave(uint8_t* win, const uint8_t* s, uint32_t
     else wave_pattern(o + wop, q.off, q.ml, lane);
   }
   return op == out_n ? kOk : kErrOutput;
+}
+
+// One blosclz stream s[0 .. n) -> o[0 .. out_n) by the wave: lz4_wave over blosclz_next, whose instructions are a
+// literal run or a match each; returns a status (the same in every lane)
+__device__ __forceinline__ int blosclz_wave(uint8_t* win, const uint8_t* s, uint32_t n, uint8_t* o, uint32_t out_n, int lane) {
+  Lz4Window r{s, n, win, 0, 0, lane};
+  uint32_t ip = 0, op = 0, fenced = 0;
+  while (ip < n) {
+    Lz4Seq q;
+    const uint32_t at = op;
+    const int st = blosclz_next(r, n, out_n, ip, op, q);
+    if (st) return st;
+    if (q.ml == 0) {
+      if (q.lit >= r.lo && q.lit - r.lo + q.ll <= r.cnt) {  // the literals are staged: stores only
+        const uint8_t* w = win + (q.lit - r.lo);
+        for (uint32_t i = (uint32_t)lane; i < q.ll; i += 64) o[at + i] = w[i];
+      } else {
+        wave_copy(o + at, s + q.lit, q.ll, lane);
+      }
+      continue;
+    }
+    const uint32_t src = at - q.off;
+    const uint32_t span = q.ml < q.off ? q.ml : q.off;
+    if (src + span > fenced) {
+      __syncthreads();  // (uniform) earlier stores before the match loads
+      fenced = at;
+    }
+    if (q.off >= q.ml) wave_copy(o + at, o + src, q.ml, lane);
+    else wave_pattern(o + at, q.off, q.ml, lane);
+  }
+  return op == out_n ? kOk : kErrOutput;
+}
+
+// Adler-32 of p[0 .. n), bytes the wave stored before the last barrier: lane l sums the bytes l, l + 64, ... with
+// their weights n - i (mod 65521, kept by stepping), the wave adds up through red (2 x 64 words of LDS)
+__device__ inline uint32_t wave_adler32(uint32_t* red, const uint8_t* p, uint32_t n, int lane) {
+  uint64_t a = 0, b = 0;
+  uint32_t wgt = (uint32_t)lane < n ? (n - (uint32_t)lane) % kAdlerMod : 0u;
+  for (uint32_t i = (uint32_t)lane; i < n; i += 64) {
+    const uint32_t v = p[i];
+    a += v;
+    b += (uint64_t)wgt * v;
+    wgt = wgt >= 64 ? wgt - 64 : wgt + kAdlerMod - 64;
+  }
+  red[lane] = (uint32_t)(a % kAdlerMod);
+  red[64 + lane] = (uint32_t)(b % kAdlerMod);
+  __syncthreads();
+  uint32_t sa = 1, sb = n % kAdlerMod;
+  for (int l = 0; l < 64; ++l) {
+    sa += red[l];       // (64 terms below 2^16: no overflow)
+    sb += red[64 + l];
+  }
+  __syncthreads();  // red may be written again
+  return ((sb % kAdlerMod) << 16) | (sa % kAdlerMod);
+}
+
+// One zlib stream s[0 .. n) -> o[0 .. out_n) by the wave; returns a status (the same in every lane)
+__device__ __forceinline__ int inflate_wave(WaveLds& sh, const uint8_t* s, uint32_t n, uint8_t* o, uint32_t out_n, int lane) {
+  Lz4Window r{s, n, &sh.lbuf[0][0], 0, 0, lane};
+  InfBits<Lz4Window> b{r, n, 0, 0, 0};
+  InfState st{0, 0, false};
+  uint8_t* lw = &sh.lbuf[2][0];
+  Seq* batch = sh.batch;
+  const bool w = lane == 0;
+  int e = inf_start(b);
+  if (e) return e;
+  uint32_t wop = 0, fenced = 0, adler = 0;
+  for (;;) {
+    // every lane parses the same events: matches into the batch with the literals before them, until the batch or the
+    // literal window is full or an event is none of the two
+    uint32_t c = 0, nl = 0, ll = 0;
+    InfEv ev;
+    ev.type = kInfLit;
+    while (c < (uint32_t)kSeqBatch && nl < kInfLitWin) {
+      e = inf_step(b, sh.inf, st, out_n, ev, w);
+      if (e) return e;  // (uniform)
+      if (ev.type == kInfLit) {
+        if (w) lw[nl] = (uint8_t)ev.a;
+        ++nl;
+        ++ll;
+      } else if (ev.type == kInfMatch) {
+        if (w) batch[c] = Seq{ll, ev.a, ev.b};
+        ++c;
+        ll = 0;
+      } else {
+        break;
+      }
+    }
+    __syncthreads();  // the batch and its literals
+    uint32_t lp = 0;
+    for (uint32_t j = 0; j < c; ++j) {
+      const Seq q = batch[j];
+      for (uint32_t i = (uint32_t)lane; i < q.ll; i += 64) o[wop + i] = lw[lp + i];
+      wop += q.ll;
+      lp += q.ll;
+      const uint32_t src = wop - q.off;
+      const uint32_t span = q.ml < q.off ? q.ml : q.off;
+      if (src + span > fenced) {
+        __syncthreads();  // (uniform) earlier stores before the match loads
+        fenced = wop;
+      }
+      if (q.off >= q.ml) wave_copy(o + wop, o + src, q.ml, lane);
+      else wave_pattern(o + wop, q.off, q.ml, lane);
+      wop += q.ml;
+    }
+    for (uint32_t i = (uint32_t)lane; i < ll; i += 64) o[wop + i] = lw[lp + i];  // the literals behind the last match
+    wop += ll;
+    if (ev.type == kInfStored) {
+      wave_copy(o + wop, s + ev.a, ev.b, lane);
+      wop += ev.b;
+    }
+    __syncthreads();  // the batch may be refilled; the stores above are visible
+    fenced = wop;
+    if (ev.type == kInfEnd) {
+      adler = ev.a;
+      break;
+    }
+  }
+  return wave_adler32((uint32_t*)sh.batch, o, out_n, lane) == adler ? kOk : kErrChecksum;
 }
 
 // One zstd frame s[0 .. n) -> o[0 .. out_n) by the wave; returns a status (the same in every lane)
@@ -438,11 +572,15 @@ __device__ __forceinline__ int zstd_wave(WaveLds& sh, const uint8_t* s, uint32_t
   return st;
 }
 
-__global__ void __launch_bounds__(kDecThreads) k_zdec(DecArgs a) {
+// One task by one wave.  kAll: the kernel of the kinds of dsx_inflate.h (k_zdec_all); the tasks of the other kernel are
+// left alone, their status too.
+template <bool kAll>
+__device__ __forceinline__ void zdec_task(const DecArgs& a) {
   __shared__ WaveLds sh;
   const int lane = threadIdx.x;
   const DecTask k = a.tasks[blockIdx.x];
   const uint32_t kind = k.kind & kTaskKindMask;
+  if ((kind == kTaskZlib || kind == kTaskBlosclz) != kAll) return;
   const bool split = (k.kind & kTaskSplit) != 0, bits = (k.kind & kTaskBitshuffle) != 0;
   const bool shuf = !bits && (k.kind & kTaskShuffle) != 0;
   const uint32_t out_n = k.dst_len, n = k.src_len;
@@ -459,7 +597,7 @@ __global__ void __launch_bounds__(kDecThreads) k_zdec(DecArgs a) {
   }
   const uint8_t* s = a.packed + k.src;
   const bool plain = !split && (kind == kTaskCopy || kind == kTaskStored);  // the bytes are there: un-shuffle or copy
-  if (!plain && kind != kTaskZstd && kind != kTaskLz4) {
+  if (!kAll && !plain && kind != kTaskZstd && kind != kTaskLz4) {
     if (lane == 0) a.status[blockIdx.x] = kErrReserved;
     return;
   }
@@ -480,8 +618,13 @@ __global__ void __launch_bounds__(kDecThreads) k_zdec(DecArgs a) {
       __syncthreads();  // the LDS of the stream before
     }
     if (split && len == ne) wave_copy(o + j * ne, s + at, ne, lane);  // stored
-    else if (kind == kTaskZstd) st = zstd_wave(sh, s + at, len, o + j * ne, ne, lane);
-    else st = lz4_wave(&sh.lbuf[0][0], s + at, len, o + j * ne, ne, lane);
+    else if constexpr (kAll) {
+      if (kind == kTaskZlib) st = inflate_wave(sh, s + at, len, o + j * ne, ne, lane);
+      else st = blosclz_wave(&sh.lbuf[0][0], s + at, len, o + j * ne, ne, lane);
+    } else {
+      if (kind == kTaskZstd) st = zstd_wave(sh, s + at, len, o + j * ne, ne, lane);
+      else st = lz4_wave(&sh.lbuf[0][0], s + at, len, o + j * ne, ne, lane);
+    }
   }
   if (split && !st && pos != n) st = kErrTruncated;
   if (!st) {
@@ -496,6 +639,9 @@ __global__ void __launch_bounds__(kDecThreads) k_zdec(DecArgs a) {
   }
   if (lane == 0) a.status[blockIdx.x] = st;
 }
+
+__global__ void __launch_bounds__(kDecThreads) k_zdec(DecArgs a) { zdec_task<false>(a); }
+__global__ void __launch_bounds__(kDecThreads) k_zdec_all(DecArgs a) { zdec_task<true>(a); }
 
 }  // namespace zdec
 }  // namespace dsx

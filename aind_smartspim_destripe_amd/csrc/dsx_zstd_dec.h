@@ -46,6 +46,12 @@ enum Status {
   kErrOffset = 11,       // a match offset reaches before the start of the output
   kErrOutput = 12,       // output longer or shorter than expected
   kErrSequences = 13,    // a sequence takes more literals than the block has, or a bad code
+  // dsx_inflate.h (zlib streams)
+  kErrChecksum = 14,     // the Adler-32 of the stream is not that of the bytes produced
+  kErrCodes = 15,        // a Huffman code set is over-subscribed, incomplete or lacks the end-of-block code; a code
+                         // that stands for no symbol; a length symbol above 285 or a distance symbol above 29
+  kErrStored = 16,       // LEN and NLEN of a stored block are not complements
+  kErrHeader = 17,       // zlib header: method, window, FCHECK, or a preset dictionary
 };
 
 constexpr uint32_t kMagic = 0xFD2FB528u;

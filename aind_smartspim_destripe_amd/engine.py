@@ -24,8 +24,9 @@ STREAM_COMPUTE, STREAM_UPLOAD, STREAM_DOWNLOAD = 0, 1, 2
 
 # Blosc block tasks of the device decoder (csrc/dsx_zstd_dec.h DecTask): kinds, the un-shuffle flag, routes per chunk
 TASK_FILL, TASK_COPY, TASK_STORED, TASK_ZSTD, TASK_LZ4 = 0, 1, 2, 3, 4
+TASK_ZLIB, TASK_BLOSCLZ = 5, 6  # (csrc/dsx_inflate.h: one zlib stream, one blosclz stream)
 TASK_SHUFFLE, TASK_SPLIT, TASK_BITSHUFFLE = 0x100, 0x200, 0x400  # (csrc/dsx_lz4_dec.h: split streams, bit un-shuffle)
-ZDEC_ZSTD, ZDEC_ANY = 0, 1  # DSX_ZDEC_*: what dsx_io_read_frames_ex routes to the device
+ZDEC_ZSTD, ZDEC_ANY, ZDEC_ALL = 0, 1, 3  # (2 stays refused) DSX_ZDEC_*: what dsx_io_read_frames_ex routes to the device
 ROUTE_DEVICE, ROUTE_HOST, ROUTE_FILL = 0, 1, 2
 TASK_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<u4"), ("dst_len", "<u4"), ("kind", "<u4"),
                        ("chunk", "<u4")])  # fmt: skip
@@ -50,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "dsx_png_unfilter", "dsx_plan_streaks", "dsx_get_streaks_threshold",
     "dsx_blosc_encode_device", "dsx_blosc_encode_ref", "dsx_blosc_encode_device_ex", "dsx_blosc_encode_ref_ex",
     "dsx_io_read_frames", "dsx_io_read_frames_ex", "dsx_blosc_decode_device", "dsx_blosc_decode_ref",
+    "dsx_io_read_zlib_chunks",
     "dsx_pyramid_work_bytes", "dsx_pyramid_block_u16", "dsx_pyramid_block_ref",
     "dsx_pyramid_bricks_u16", "dsx_pyramid_bricks_ref",
 ]  # fmt: skip
@@ -206,6 +208,7 @@ def load_library(path=None):
                                        vp, ctypes.c_size_t, vp, i32, ctypes.POINTER(ctypes.c_size_t),
                                        ctypes.POINTER(i32), vp]  # fmt: skip
     lib.dsx_io_read_frames_ex.argtypes = lib.dsx_io_read_frames.argtypes + [i32]
+    lib.dsx_io_read_zlib_chunks.argtypes = lib.dsx_io_read_frames.argtypes
     lib.dsx_blosc_decode_device.argtypes = [vp, vp, ctypes.c_size_t, vp, i32, vp, ctypes.c_size_t, vp]
     lib.dsx_blosc_decode_ref.argtypes = [vp, ctypes.c_size_t, vp, i32, vp, ctypes.c_size_t, vp]
     lib.dsx_pyramid_work_bytes.argtypes = [i32, i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
@@ -575,14 +578,17 @@ class DestripeEngine:
             return
         self._check(self._lib.dsx_io_write_chunks(self._ctx, cp, dp, nb, n, int(threads), int(zlib_level)))
 
-    def io_read_frames(self, paths, chunk_bytes, packed, tasks, threads=16, fill_value=0, routes=None, mode=0):
+    def io_read_frames(self, paths, chunk_bytes, packed, tasks, threads=16, fill_value=0, routes=None, mode=0,
+                       zlib_chunks=False):
         """Chunk files ``paths[i]`` (Blosc) -> frames packed into the uint8 array ``packed`` and Blosc block tasks
         into the ``TASK_DTYPE`` array ``tasks`` (``dsx_io_read_frames``); chunk i decodes to bytes
         ``[i * chunk_bytes, (i + 1) * chunk_bytes)``.  ``routes``: optional uint8 array of ``len(paths)`` (``ROUTE_*``).
         ``mode``: ``ZDEC_ZSTD`` (0: unsplit zstd streams go to the device) or ``ZDEC_ANY`` (1: LZ4, split streams and
-        bit shuffle too, ``dsx_io_read_frames_ex``).  Returns ``(packed_bytes, n_tasks)``."""
+        bit shuffle too, ``dsx_io_read_frames_ex``) or ``ZDEC_ALL`` (3: blosclz and zlib inside too).
+        ``zlib_chunks``: the files are the chunks of a plain-zlib store, one ``TASK_ZLIB`` task each
+        (``dsx_io_read_zlib_chunks``; ``mode`` does not apply).  Returns ``(packed_bytes, n_tasks)``."""
         return _io_read_frames(self._lib, self._ctx, paths, chunk_bytes, packed, tasks, threads, fill_value, routes,
-                               self._check, mode)  # fmt: skip
+                               self._check, mode, zlib_chunks)  # fmt: skip
 
     def event_record(self, slot, stream):
         self._check(self._lib.dsx_event_record(self._ctx, int(slot), int(stream)))
@@ -875,24 +881,24 @@ def blosc_encode_ref(chunks, clevel=3, mode="literals"):
     return frames[: offsets[-1]].tobytes(), offsets
 
 
-def _io_read_frames(lib, ctx, paths, chunk_bytes, packed, tasks, threads, fill_value, routes, check, mode=0):
+def _io_read_frames(lib, ctx, paths, chunk_bytes, packed, tasks, threads, fill_value, routes, check, mode=0,
+                    zlib_chunks=False):
     n = len(paths)
     assert packed.dtype == np.uint8 and packed.flags["C_CONTIGUOUS"] and tasks.dtype == TASK_DTYPE
     if routes is not None:
         assert routes.dtype == np.uint8 and routes.size >= n
     cp = (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths])
     pb, nt = ctypes.c_size_t(0), ctypes.c_int32(0)
-    check(lib.dsx_io_read_frames_ex(ctx, cp, n, int(chunk_bytes), int(threads), int(fill_value),
-                                    packed.ctypes.data_as(ctypes.c_void_p), packed.nbytes,
-                                    tasks.ctypes.data_as(ctypes.c_void_p), int(tasks.size), ctypes.byref(pb),
-                                    ctypes.byref(nt), routes.ctypes.data_as(ctypes.c_void_p) if routes is not None else None,
-                                    int(mode)))  # fmt: skip
+    args = (ctx, cp, n, int(chunk_bytes), int(threads), int(fill_value), packed.ctypes.data_as(ctypes.c_void_p),
+            packed.nbytes, tasks.ctypes.data_as(ctypes.c_void_p), int(tasks.size), ctypes.byref(pb), ctypes.byref(nt),
+            routes.ctypes.data_as(ctypes.c_void_p) if routes is not None else None)  # fmt: skip
+    check(lib.dsx_io_read_zlib_chunks(*args) if zlib_chunks else lib.dsx_io_read_frames_ex(*(args + (int(mode),))))
     return int(pb.value), int(nt.value)
 
 
-def io_read_frames(paths, chunk_bytes, threads=4, fill_value=0, mode=0):
+def io_read_frames(paths, chunk_bytes, threads=4, fill_value=0, mode=0, zlib_chunks=False):
     """:meth:`DestripeEngine.io_read_frames` without an engine, into fresh buffers: ``(packed, tasks, routes)`` trimmed
-    to what was read.  ``mode``: ``ZDEC_ZSTD`` or ``ZDEC_ANY``."""
+    to what was read.  ``mode``: ``ZDEC_ZSTD``, ``ZDEC_ANY`` or ``ZDEC_ALL``; ``zlib_chunks``: plain-zlib chunk files."""
     lib = load_library()
     n = len(paths)
     packed = np.empty(n * (int(chunk_bytes) + 16) + 1, np.uint8)
@@ -903,7 +909,8 @@ def io_read_frames(paths, chunk_bytes, threads=4, fill_value=0, mode=0):
         if rc != 0:
             raise DsxError(rc, (lib.dsx_last_error(None) or b"io_read_frames failed").decode())
 
-    pb, nt = _io_read_frames(lib, None, paths, chunk_bytes, packed, tasks, threads, fill_value, routes, check, mode)
+    pb, nt = _io_read_frames(lib, None, paths, chunk_bytes, packed, tasks, threads, fill_value, routes, check, mode,
+                             zlib_chunks)  # fmt: skip
     return packed[:pb], tasks[:nt], routes
 
 

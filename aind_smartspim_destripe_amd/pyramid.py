@@ -164,7 +164,7 @@ def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_leve
     (:class:`_PipelinedPyramid`): level 0 is read block by block on ``io_threads`` native threads straight into pinned
     staging, every level is computed from the block where it lies in chunk order (``dsx_pyramid_bricks_u16``) and the
     finished chunk rows leave through the I/O threads; no level is read back.  ``device_decode`` / ``device_codec``
-    (``False``, ``True``, ``"any"`` / ``"runs"``: ``zarr_destriper.device_decode_mode`` / ``device_codec_mode``) move the
+    (``False``, ``True``, ``"any"``, ``"full"`` / ``"runs"``: ``zarr_destriper.device_decode_mode`` / ``device_codec_mode``) move the
     Blosc decode of level 0 and the Blosc-zstd encode of the levels to the GPU; they need a Blosc uint16 input / a
     Blosc-zstd uint16 output with byte shuffle, and ``pipelined``.  ``slab_planes`` is ignored then.
     :data:`LAST_PYRAMID` holds what the call did.
@@ -329,10 +329,12 @@ class _PipelinedPyramid:
         routes = self.timing["decode_routes"]
         try:
             if self.decode_mode is not None:
-                mode = _engine.ZDEC_ANY if self.decode_mode == "any" else _engine.ZDEC_ZSTD
+                from . import zarr_destriper as zd
+
                 pb, nt = self.eng.io_read_frames(paths, self.in_brick * 2, self.packed[k], self.tasks[k],
                                                  threads=self.io_threads, fill_value=int(self.src.fill_value),
-                                                 routes=self.routes, mode=mode)  # fmt: skip
+                                                 routes=self.routes, mode=zd.ZDEC_MODES[self.decode_mode],
+                                                 zlib_chunks=self.src.compressor[0] == "zlib")  # fmt: skip
                 self.read_info[k] = (pb, nt, paths)
                 seen = np.bincount(self.routes[: len(paths)], minlength=3)
                 for name, r in (("device", _engine.ROUTE_DEVICE), ("host", _engine.ROUTE_HOST), ("fill", _engine.ROUTE_FILL)):
@@ -345,7 +347,7 @@ class _PipelinedPyramid:
                 routes["host"] += there
                 routes["fill"] += len(paths) - there
         except _engine.DsxError as e:
-            if e.message.startswith("blosc:"):  # a malformed frame the reader itself refused: "blosc: ... (<chunk file>)"
+            if e.message.startswith(("blosc:", "zlib:")):  # a malformed chunk the reader itself refused: "blosc: ... (<chunk file>)"
                 raise ValueError(e.message) from None
             raise
         finally:
@@ -449,10 +451,11 @@ class _PipelinedPyramid:
         st = self.status[k][:nt]
         bad = np.flatnonzero(st)
         if bad.size:
+            from . import zarr_destriper as zd
+
             i = int(bad[0])
-            codec = "lz4" if (int(kinds[i]) & 0xFF) == _engine.TASK_LZ4 else "zstd"
-            raise ValueError("blosc: bad {} stream ({}) [device decode status {}]".format(codec, paths[int(chunk[i])],
-                                                                                           int(st[i])))  # fmt: skip
+            raise ValueError(zd.bad_stream_message(int(kinds[i]), paths[int(chunk[i])], int(st[i]),
+                                                   self.src.compressor[0] == "zlib"))  # fmt: skip
 
     def _finish(self, k, writer, writes):
         """Block in slot k: wait for its downloads, check its statuses, then hand its rows to the writers."""
@@ -504,7 +507,7 @@ def _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, devi
     src = MiniZarrArray.open(level0_path)
     if src.dtype != np.uint16 or any(n != 1 for n in src.shape[:-3]):
         raise ValueError("the pyramid kernel takes uint16 volumes with singleton leading axes")
-    if decode_mode is not None and (src.compressor is None or src.compressor[0] != "blosc"):
+    if decode_mode is not None and not zd.device_decode_input_ok(src, decode_mode):
         raise ValueError("device_decode needs a Blosc uint16 input, not {!r} {}".format(src.compressor, src.dtype))
     zyx, lead = tuple(src.shape[-3:]), tuple(src.shape[:-3])
     levels = fused_levels(zyx, chunks, n_levels)

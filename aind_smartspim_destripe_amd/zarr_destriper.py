@@ -304,7 +304,7 @@ class _DeviceBlocks:
         self.out_brick = int(np.prod(self.co))
         in_bytes = int(np.prod(self.gi)) * self.in_brick * 2
         out_bytes = int(np.prod(self.go)) * self.out_brick * 2
-        self.decode_mode = device_decode_mode(device_decode)  # None, "zstd" or "any"
+        self.decode_mode = device_decode_mode(device_decode)  # None, "zstd", "any" or "full"
         self.device_decode = self.decode_mode is not None
         self.h_in, self.stage_in = [], []
         self.h_packed, self.h_tasks, self.h_status, self.d_packed, self.d_tasks, self.d_status = [], [], [], [], [], []
@@ -391,10 +391,10 @@ class _DeviceBlocks:
         idx = list(itertools.product(range(nbz), range(self.gi[1]), range(self.gi[2])))
         if self.device_decode:
             paths = [self.src._chunk_path(lead + (bz0 + i[0], i[1], i[2])) for i in idx]
-            mode = engine_mod.ZDEC_ANY if self.decode_mode == "any" else engine_mod.ZDEC_ZSTD
             pb, nt = self.eng.io_read_frames(paths, self.in_brick * 2, self.packed[k], self.tasks[k],
                                              threads=self.io_threads, fill_value=int(self.src.fill_value),
-                                             routes=self.routes, mode=mode)  # fmt: skip
+                                             routes=self.routes, mode=ZDEC_MODES[self.decode_mode],
+                                             zlib_chunks=self.src.compressor[0] == "zlib")  # fmt: skip
             self.read_info[k] = (pb, nt, paths)
             seen = np.bincount(self.routes[: len(paths)], minlength=3)
             for name, r in (("device", engine_mod.ROUTE_DEVICE), ("host", engine_mod.ROUTE_HOST), ("fill", engine_mod.ROUTE_FILL)):
@@ -573,9 +573,8 @@ class _DeviceBlocks:
         bad = np.flatnonzero(st)
         if bad.size:
             i = int(bad[0])
-            codec = "lz4" if (int(kinds[i]) & 0xFF) == engine_mod.TASK_LZ4 else "zstd"
-            raise ValueError("blosc: bad {} stream ({}) [device decode status {}]".format(codec, paths[int(chunk[i])],
-                                                                                           int(st[i])))  # fmt: skip
+            raise ValueError(bad_stream_message(int(kinds[i]), paths[int(chunk[i])], int(st[i]),
+                                                self.src.compressor[0] == "zlib"))  # fmt: skip
 
     def run_range(self, z_start, z_stop):
         """All blocks of ``[z_start, z_stop)`` through the pipeline; returns the number of planes."""
@@ -646,14 +645,33 @@ def device_codec_mode(device_codec):
     return "literals" if device_codec else None
 
 
+ZDEC_MODES = {"zstd": engine_mod.ZDEC_ZSTD, "any": engine_mod.ZDEC_ANY, "full": engine_mod.ZDEC_ALL}
+_TASK_CODECS = {engine_mod.TASK_LZ4: "lz4", engine_mod.TASK_ZLIB: "zlib", engine_mod.TASK_BLOSCLZ: "blosclz"}
+
+
+def bad_stream_message(kind, path, status, zlib_chunks=False):
+    """The text of the ``ValueError`` for a task of ``kind`` the device decoder gave ``status``: what the host reader
+    says of such a chunk (``csrc/dsx_io.h``), and the status."""
+    if zlib_chunks:
+        return "zlib: bad chunk {} [device decode status {}]".format(path, status)
+    return "blosc: bad {} stream ({}) [device decode status {}]".format(_TASK_CODECS.get(kind & 0xFF, "zstd"), path, status)
+
+
+def device_decode_input_ok(src, decode_mode):
+    """Can ``device_decode`` read the store ``src``: a Blosc uint16 store, or with ``"full"`` a plain-zlib one."""
+    comp = src.compressor
+    return comp is not None and src.dtype == np.uint16 and (comp[0] == "blosc" or (decode_mode == "full" and comp[0] == "zlib"))
+
+
 def device_decode_mode(device_decode):
     """What a ``device_decode`` argument selects: ``None`` (off), ``"zstd"`` (any true value that is not a string: the
-    device takes unsplit zstd streams with byte shuffle or none) or ``"any"`` (the string ``"any"``: LZ4, split streams
+    device takes unsplit zstd streams with byte shuffle or none), ``"full"`` (the string ``"full"``: what ``"any"`` takes
+    plus blosclz and zlib inside Blosc, and the chunks of a plain-zlib store) or ``"any"`` (the string ``"any"``: LZ4, split streams
     and bit shuffle too).  Any other string: ``ValueError``."""
     if isinstance(device_decode, str):
-        if device_decode != "any":
-            raise ValueError("device_decode is False, True or \"any\", not {!r}".format(device_decode))
-        return "any"
+        if device_decode not in ("any", "full"):
+            raise ValueError("device_decode is False, True or one of \"any\", \"full\", not {!r}".format(device_decode))
+        return device_decode
     return "zstd" if device_decode else None
 
 
@@ -766,7 +784,9 @@ def destripe_zarr_store(
     Frames the device does not take (other inner codecs, bit shuffle, split streams, zstd checksums) are decoded by the
     I/O threads as before.  ``"any"`` widens the device's share to what ``numcodecs.Blosc()`` writes by default and its
     common variants: LZ4 / LZ4HC inside, blocks split into a low-byte and a high-byte stream (LZ4 or zstd) and bit
-    shuffle; blosclz, zlib and snappy inside, type sizes other than 2 and zstd checksums stay with the I/O threads.  Any
+    shuffle; blosclz, zlib and snappy inside, type sizes other than 2 and zstd checksums stay with the I/O threads.
+    ``"full"`` adds blosclz and zlib inside Blosc frames and accepts a uint16 input whose compressor is plain ``zlib``
+    (``csrc/dsx_inflate.h``; one wave inflates a stream serially: opt-in, not measured to be faster).  Any
     other string raises ``ValueError``; every other value counts by its truth.  ``LAST_RUN["decode_routes"]`` counts the
     chunks read over the z range by where they were decoded: ``{"device": n, "host": n, "fill": n}`` (``fill``: a
     missing file).  Needs a Blosc uint16 input and the device re-tiling path; anything else raises ``ValueError``.  Off
@@ -841,7 +861,7 @@ def destripe_zarr_store(
             raise ValueError("device_codec needs the device re-tiling path (a uint16 store, even planes and "
                              "output-chunk-aligned z blocks)")  # fmt: skip
     if device_decode:
-        if src.compressor is None or src.compressor[0] != "blosc" or src.dtype != np.uint16:
+        if not device_decode_input_ok(src, decode_mode):
             raise ValueError("device_decode needs a Blosc uint16 input, not {!r} {}".format(src.compressor, src.dtype))
         if not can or device_retile is False:
             raise ValueError("device_decode needs the device re-tiling path (a uint16 store, even planes and "
@@ -990,7 +1010,7 @@ def compute_multiscale(
     ``pipelined=True``: the same stores from one software-pipelined pass over level 0 -- level 0 is read by ``io_threads``
     native threads into pinned staging, every level comes from the block where it lies in chunk order
     (``dsx_pyramid_bricks_u16``), no level is read back (``pyramid.write_pyramid_levels``; ``slab_planes`` is ignored).
-    ``device_decode`` / ``device_codec`` (as in :func:`destripe_zarr_store`: ``False``, ``True``, ``"any"`` / ``"runs"``)
+    ``device_decode`` / ``device_codec`` (as in :func:`destripe_zarr_store`: ``False``, ``True``, ``"any"``, ``"full"`` / ``"runs"``)
     then decode level 0 and encode the levels on the GPU; without ``pipelined`` they raise ``ValueError``.
     ``pyramid.LAST_PYRAMID`` holds what the call did.
     """

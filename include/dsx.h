@@ -287,15 +287,28 @@ int dsx_blosc_encode_ref_ex(const void* src, int n_chunks, size_t chunk_bytes, i
  *     typesize != 2, zstd checksums, blocks under 8 KiB        -> host
  * `kind` of a task: 0 fill, 1 copy, 2 stored, 3 zstd, 4 lz4; | 0x100 byte un-shuffle, | 0x200 split (src is the int32
  * length word of the first of two streams, src_len spans both), | 0x400 bit un-shuffle.  One task per Blosc block in
- * either mode.  Any other mode: DSX_EINVAL.  dsx_blosc_decode_device / _ref run the tasks of both modes. */
+ * either mode.  dsx_blosc_decode_device / _ref run the tasks of every mode.
+ * DSX_ZDEC_ALL: DSX_ZDEC_ANY plus the last two inner codecs c-blosc 1.21 writes (csrc/dsx_inflate.h), in the same
+ * layouts and under the same limits:
+ *     inner codec    zstd (no checksum), lz4, lz4hc, blosclz, zlib -> device  snappy -> host
+ * `kind` 5: one zlib stream (RFC 1950, its Adler-32 verified), 6: one blosclz stream; both take the 0x100 / 0x200 /
+ * 0x400 bits.  Modes 0 and 1 route as before, byte for byte.  Any other mode, 2 included as before: DSX_EINVAL.
+ * dsx_io_read_zlib_chunks: the chunk files of a store whose compressor is plain zlib (the whole file is one zlib
+ * stream) packed like frames: one task of kind 5 per chunk with dst_len = chunk_bytes and no shuffle (capacities:
+ * n * (chunk_bytes + 16) bytes, n tasks); a missing file is a fill task; a file longer than chunk_bytes + 16 is
+ * inflated on the I/O threads and shipped as a copy (route 1). */
 #define DSX_ZDEC_ZSTD 0
 #define DSX_ZDEC_ANY 1
+#define DSX_ZDEC_ALL 3
 int dsx_io_read_frames_ex(dsx_ctx* ctx, const char* const* paths, int n, size_t chunk_bytes, int threads,
                           uint16_t fill_value, void* packed, size_t packed_capacity, void* tasks, int task_capacity,
                           size_t* packed_bytes, int* n_tasks, uint8_t* routes, int mode);
 int dsx_io_read_frames(dsx_ctx* ctx, const char* const* paths, int n, size_t chunk_bytes, int threads,
                        uint16_t fill_value, void* packed, size_t packed_capacity, void* tasks, int task_capacity,
                        size_t* packed_bytes, int* n_tasks, uint8_t* routes);
+int dsx_io_read_zlib_chunks(dsx_ctx* ctx, const char* const* paths, int n, size_t chunk_bytes, int threads,
+                            uint16_t fill_value, void* packed, size_t packed_capacity, void* tasks, int task_capacity,
+                            size_t* packed_bytes, int* n_tasks, uint8_t* routes);
 int dsx_blosc_decode_device(dsx_ctx* ctx, const void* d_packed, size_t packed_bytes, const void* d_tasks, int n_tasks,
                             void* d_out, size_t out_bytes, int32_t* d_status);
 int dsx_blosc_decode_ref(const void* packed, size_t packed_bytes, const void* tasks, int n_tasks, void* out,

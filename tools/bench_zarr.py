@@ -4,14 +4,18 @@
 download) into another store.  Prints one JSON line; the roofline of this path is the host link
 (PCIe Gen5 x16, 63 GB/s spec: 16.8 MB per plane both ways -> <= 3.7 k planes/s), not HBM.
 
-    bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode|device-decode-any] [lz4]
-                  [pyramid|fused-pyramid|pipelined-pyramid]
+    bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode|device-decode-any|device-decode-all]
+                  [lz4|blosc-zlib|blosc-blosclz|plain-zlib] [pyramid|fused-pyramid|pipelined-pyramid]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
 line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
 `device-codec-runs`: the same with runs of equal bytes written as matches (device_codec="runs").
 `device-decode` (Blosc only): the input chunks are decoded on the GPU (destripe_zarr_store(device_decode=True)).
 `device-decode-any`: the same with device_decode="any" (LZ4, split streams and bit shuffle go to the device too).
+`device-decode-all`: the same with device_decode="full" (blosclz and zlib inside Blosc, and plain-zlib chunks, too).
+`blosc-zlib`, `blosc-blosclz`, `plain-zlib` (Blosc only, N a multiple of 64): the INPUT store recoded like `lz4` below,
+to Blosc frames with zlib (level 5) or blosclz inside (byte shuffle, 256 KiB blocks split in two streams; the greedy
+blosclz encoder of tests/inflate_cases.py) or to the plain zlib compressor (level 1, one stream per 2 MiB chunk).
 `lz4` (Blosc only, N a multiple of 64): the INPUT store is what numcodecs.Blosc() writes by default -- LZ4, byte
 shuffle, 256 KiB blocks split into a low-byte and a high-byte stream (the test suite's LZ4 encoder,
 tests/blosc_any_frames.py; every 64-plane block holds the same planes, as in the other variants); the output stays
@@ -34,8 +38,10 @@ logging.basicConfig(level=logging.INFO, stream=sys.stderr)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 codec = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2] != "raw" else None  # None (raw chunks), "zlib" or "blosc" (Blosc-zstd)
 device_codec = "runs" if "device-codec-runs" in sys.argv[3:] else "device-codec" in sys.argv[3:]
-device_decode = "any" if "device-decode-any" in sys.argv[3:] else "device-decode" in sys.argv[3:]
-lz4_input = "lz4" in sys.argv[3:]
+device_decode = ("full" if "device-decode-all" in sys.argv[3:] else
+                 "any" if "device-decode-any" in sys.argv[3:] else "device-decode" in sys.argv[3:])
+recode = ([w for w in ("lz4", "blosc-zlib", "blosc-blosclz", "plain-zlib") if w in sys.argv[3:]] + [None])[0]
+lz4_input = recode is not None  # (any recoded input store)
 two_pass, fused, pipelined = ("pyramid" in sys.argv[3:], "fused-pyramid" in sys.argv[3:], "pipelined-pyramid" in sys.argv[3:])
 H = W = 2048
 root = tempfile.mkdtemp(prefix="dsx_zarr_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
@@ -44,17 +50,26 @@ try:
     bank = synth.synthetic_bank(8, H, W)
     if lz4_input:
         if codec != "blosc" or n % 64:
-            sys.exit("lz4: a Blosc store of a multiple of 64 planes")
+            sys.exit(recode + ": a Blosc store of a multiple of 64 planes")
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-        import multiprocessing
+        import multiprocessing, zlib
         import blosc_any_frames as baf
+        import inflate_cases as ic
+        cname = {"lz4": "lz4", "blosc-zlib": "zlib", "blosc-blosclz": "blosclz"}.get(recode)
         src = MiniZarrArray.create(os.path.join(root, "in.zarr"), (1, 1, n, H, W), (1, 1, 64, 128, 128), np.uint16,
-                                   compressor={"id": "blosc", "cname": "lz4", "clevel": 5, "shuffle": 1, "blocksize": 0})
+                                   compressor={"id": "blosc", "cname": cname, "clevel": 5, "shuffle": 1, "blocksize": 0}
+                                   if cname else "zlib")
         stack = synth.synthetic_stack(64, H, W, bank=bank)
         yx = [(y, x) for y in range(H // 128) for x in range(W // 128)]
         raws = [np.ascontiguousarray(stack[:, 128 * y : 128 * y + 128, 128 * x : 128 * x + 128]).tobytes() for y, x in yx]
         with multiprocessing.Pool(16) as pool:  # (before anything touches the GPU)
-            frames = pool.starmap(baf.blosc_frame, [(r, 256 * 1024, baf.LZ4, baf.SHUFFLE, True) for r in raws])
+            if recode == "lz4":
+                frames = pool.starmap(baf.blosc_frame, [(r, 256 * 1024, baf.LZ4, baf.SHUFFLE, True) for r in raws])
+            elif recode == "plain-zlib":
+                frames = pool.starmap(zlib.compress, [(r, 1) for r in raws])
+            else:
+                inner = ic.ZLIB if recode == "blosc-zlib" else baf.BLOSCLZ
+                frames = pool.starmap(ic.blosc_frame, [(r, 256 * 1024, inner, baf.SHUFFLE, True) for r in raws])
         for zb in range(n // 64):
             for (y, x), f in zip(yx, frames):
                 p = src._chunk_path((0, 0, zb, y, x))
@@ -163,7 +178,7 @@ try:
                 except AssertionError as e:
                     verified = False
                     print("oracle mismatch", e, file=sys.stderr)
-    label = (codec or "raw") + (", LZ4 input" if lz4_input else "") + (", encoded on the device" + (" with run matches" if device_codec == "runs" else "") if device_codec else "") + (", decoded on the device" + (" (any)" if device_decode == "any" else "") if device_decode else "")
+    label = (codec or "raw") + (", {} input".format("LZ4" if recode == "lz4" else recode) if lz4_input else "") + (", encoded on the device" + (" with run matches" if device_codec == "runs" else "") if device_codec else "") + (", decoded on the device" + (" ({})".format(device_decode) if isinstance(device_decode, str) else "") if device_decode else "")
     label += ", pyramid fused" if fused else ""  # (a stand-alone pyramid, slab or pipelined, is not part of the metric)
     print(json.dumps({"metric": "2048x2048 uint16 slices/s, Zarr store to Zarr store ({} chunks, tmpfs)".format(label), "value": round(v, 1),
                       "planes": n, "seconds": res["overlapped"]["seconds"], "store_make_s": round(t_make, 1),
