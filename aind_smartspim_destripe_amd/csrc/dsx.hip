@@ -25,6 +25,7 @@
 #include "dsx_io.h"
 #include "dsx_streaks.h"
 #include "dsx_zenc_kernels.h"
+#include "dsx_lz4enc_kernels.h"
 #include "dsx_zdec_kernels.h"
 
 namespace {
@@ -2145,11 +2146,32 @@ int dsx_blosc_encode(const void* src, size_t bytes, int typesize, int clevel, in
   *frame_bytes = out.size();
   return DSX_OK;
 }
+int dsx_blosc_encode_lz4(const void* src, size_t bytes, int clevel, void* frame, size_t frame_capacity,
+                         size_t* frame_bytes) {
+  if ((!src && bytes) || !frame || !frame_bytes) return DSX_EINVAL;
+  if (bytes % 2 || clevel < 0 || clevel > 9) return fail(nullptr, DSX_EINVAL, "bad Blosc-LZ4 parameters (uint16 elements)");
+  const std::string e = dsx::blosc_encode_lz4(src, bytes, clevel, [&](const unsigned char* f, size_t n) {
+    if (n > frame_capacity) return false;
+    memcpy(frame, f, n);
+    *frame_bytes = n;
+    return true;
+  });
+  if (!e.empty()) return fail(nullptr, DSX_EINVAL, e == "sink" ? "frame buffer too small (bytes + 16 always fits)" : e);
+  return DSX_OK;
+}
+int dsx_io_write_chunks_blosc_lz4(dsx_ctx* ctx, const char* const* paths, const void* const* src, const size_t* bytes,
+                                  int n, int threads, int clevel) {
+  if (n < 0 || (n > 0 && (!paths || !src || !bytes))) return DSX_EINVAL;
+  if (clevel < 0 || clevel > 9) return fail(ctx, DSX_EINVAL, "bad Blosc parameters");
+  const std::string e = dsx::io_write_chunks_blosc_lz4(paths, src, bytes, n, threads, clevel);
+  if (!e.empty()) return fail(ctx, DSX_EIO, e);
+  return DSX_OK;
+}
 
 namespace {
 const char* zenc_params(int n_chunks, size_t chunk_bytes, int typesize, int clevel, int mode) {
-  if (mode != DSX_ZENC_LITERALS && mode != DSX_ZENC_RUNS) return "blosc_encode: unknown mode";
-  if (typesize != 2) return "blosc_encode: the zstd encoder supports typesize 2 only";
+  if (mode != DSX_ZENC_LITERALS && mode != DSX_ZENC_RUNS && mode != DSX_ZENC_LZ4) return "blosc_encode: unknown mode";
+  if (typesize != 2) return "blosc_encode: the zstd and LZ4 encoders support typesize 2 only";
   if (n_chunks < 0 || chunk_bytes % 2 || clevel < 0 || clevel > 9) return "blosc_encode: bad parameters";
   if (chunk_bytes > 0x7FFFFFEFu) return "blosc_encode: chunk larger than a frame can hold";
   return nullptr;
@@ -2160,6 +2182,11 @@ int dsx_blosc_encode_ref_ex(const void* src, int n_chunks, size_t chunk_bytes, i
                             int64_t* offsets, int mode) {
   if ((!src && n_chunks > 0 && chunk_bytes) || !frames || !offsets) return DSX_EINVAL;
   if (const char* e = zenc_params(n_chunks, chunk_bytes, typesize, clevel, mode)) return fail(nullptr, DSX_EINVAL, e);
+  if (mode == DSX_ZENC_LZ4) {
+    dsx::lz4enc::blosc_encode_host((const uint16_t*)src, (uint64_t)n_chunks, chunk_bytes, clevel, (uint8_t*)frames,
+                                   offsets);
+    return DSX_OK;
+  }
   dsx::zenc::blosc_encode_host((const uint16_t*)src, (uint64_t)n_chunks, chunk_bytes, clevel, (uint8_t*)frames, offsets,
                                mode);
   return DSX_OK;
@@ -2208,6 +2235,17 @@ int dsx_blosc_encode_device_ex(dsx_ctx* ctx, const void* d_src, int n_chunks, si
     ctx->zenc_lit_blocks = nblocks;
   }
   const z::EncArgs ea{(const uint16_t*)d_src, ctx->zenc_slots, ctx->zenc_sizes, (uint64_t)chunk_bytes, g.nblocks};
+  if (mode == DSX_ZENC_LZ4) {  // one wave per stream; the streams use the slots and sizes of the zstd blocks
+    namespace l = dsx::lz4enc;
+    if (!store && nblocks) hipLaunchKernelGGL(l::k_lz4_stream, dim3((unsigned)nblocks), dim3(64), 0, s, ea);
+    z::PackArgs pa{(const uint16_t*)d_src, ctx->zenc_slots, ctx->zenc_sizes, (uint8_t*)d_frames, d_offsets,
+                   (uint64_t)chunk_bytes, n_chunks, store ? 1 : g.nblocks, store};
+    hipLaunchKernelGGL(l::k_lz4_scan, dim3(1), dim3(256), 0, s, pa);
+    if (n_chunks > 0)
+      hipLaunchKernelGGL(l::k_lz4_copy, dim3((unsigned)(n_chunks * pa.nblocks)), dim3(256), 0, s, pa);
+    DSX_HIP(hipGetLastError());
+    return DSX_OK;
+  }
   if (!store && nblocks) {
     if (mode == DSX_ZENC_RUNS)
       hipLaunchKernelGGL(z::k_zenc_block_runs, dim3((unsigned)nblocks), dim3(z::kEncThreads), 0, s,

@@ -33,10 +33,12 @@
 
 #include "dsx_inflate.h"
 #include "dsx_lz4_dec.h"
+#include "dsx_lz4_enc.h"
 #include "dsx_zstd_dec.h"
 
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -692,6 +694,38 @@ inline std::string io_write_chunks(const char* const* paths, const void* const* 
       return std::string("zlib: cannot compress chunk ") + paths[i];
     if (!io_write_file_atomic(paths[i], z.data(), cap)) return std::string("cannot write chunk ") + paths[i];
     return "";
+  });
+}
+
+// src (n bytes of uint16) -> one Blosc-LZ4 frame (the host build of dsx_lz4_enc.h), handed to sink(frame, bytes);
+// "sink" when the sink refuses it.  The work space is kept per thread.
+template <class Sink>
+inline std::string blosc_encode_lz4(const void* src, size_t n, int clevel, Sink&& sink) {
+  if (n > 0x7FFFFFEFu) return "blosc: buffer larger than a frame can hold";
+  if (n % 2) return "blosc: the LZ4 writer takes 2-byte elements";
+  static thread_local std::unique_ptr<lz4enc::HostWork> work;
+  static thread_local std::vector<unsigned char> frame;
+  static thread_local std::vector<uint16_t> aligned;
+  if (!work) work.reset(new lz4enc::HostWork);
+  frame.resize(n + kBloscHeader);
+  const uint16_t* e = (const uint16_t*)src;
+  if ((uintptr_t)src & 1) {
+    aligned.resize(n / 2);
+    memcpy(aligned.data(), src, n);
+    e = aligned.data();
+  }
+  const uint64_t got = lz4enc::encode_chunk_host(*work, e, n, clevel, frame.data());
+  return sink(frame.data(), (size_t)got) ? "" : "sink";
+}
+// src[i] (bytes[i], uint16) -> chunk file paths[i] as Blosc-LZ4 frames
+inline std::string io_write_chunks_blosc_lz4(const char* const* paths, const void* const* src, const size_t* bytes,
+                                             int n, int threads, int clevel) {
+  return io_parallel(n, threads, [&](int i) -> std::string {
+    const std::string e = blosc_encode_lz4(src[i], bytes[i], clevel, [&](const unsigned char* f, size_t m) {
+      return io_write_file_atomic(paths[i], f, m);
+    });
+    if (e == "sink") return std::string("cannot write chunk ") + paths[i];
+    return e.empty() ? e : e + " (" + paths[i] + ")";
   });
 }
 

@@ -459,7 +459,10 @@ struct PackArgs {
   bool store;        // every chunk is a memcpyed frame (short chunks, clevel <= 0)
 };
 
-__global__ void __launch_bounds__(256) k_zenc_scan(PackArgs a) {
+// The scan of k_zenc_scan and of its LZ4 sibling (dsx_lz4enc_kernels.h), one workgroup of 256: frame_bytes(sizes of
+// the chunk's slots, chunk bytes, store) per chunk and the exclusive scan of these -> offsets.
+template <class FrameBytes>
+__device__ __forceinline__ void scan_frame_bytes(const PackArgs& a, FrameBytes frame_bytes) {
   __shared__ int64_t part[256];
   __shared__ int64_t carry;
   const int tid = threadIdx.x;
@@ -468,7 +471,7 @@ __global__ void __launch_bounds__(256) k_zenc_scan(PackArgs a) {
   const int per = a.nblocks * kZPerBlosc;
   for (int c0 = 0; c0 < a.n_chunks; c0 += 256) {
     const int c = c0 + tid;
-    int64_t v = c < a.n_chunks ? (int64_t)chunk_frame_bytes(a.sizes + (uint64_t)c * per, a.chunk_bytes, a.store) : 0;
+    int64_t v = c < a.n_chunks ? (int64_t)frame_bytes(a.sizes + (uint64_t)c * per, a.chunk_bytes, a.store) : 0;
     part[tid] = v;
     __syncthreads();
     for (int d = 1; d < 256; d <<= 1) {
@@ -482,6 +485,10 @@ __global__ void __launch_bounds__(256) k_zenc_scan(PackArgs a) {
     if (tid == 255) carry += part[255];
     __syncthreads();
   }
+}
+
+__global__ void __launch_bounds__(256) k_zenc_scan(PackArgs a) {
+  scan_frame_bytes(a, [](const uint32_t* ss, uint64_t n, bool store) { return chunk_frame_bytes(ss, n, store); });
 }
 
 __global__ void __launch_bounds__(256) k_zenc_copy(PackArgs a) {

@@ -51,7 +51,7 @@ EXPORTED_SYMBOLS = [
     "dsx_png_unfilter", "dsx_plan_streaks", "dsx_get_streaks_threshold",
     "dsx_blosc_encode_device", "dsx_blosc_encode_ref", "dsx_blosc_encode_device_ex", "dsx_blosc_encode_ref_ex",
     "dsx_io_read_frames", "dsx_io_read_frames_ex", "dsx_blosc_decode_device", "dsx_blosc_decode_ref",
-    "dsx_io_read_zlib_chunks",
+    "dsx_io_read_zlib_chunks", "dsx_io_write_chunks_blosc_lz4", "dsx_blosc_encode_lz4",
     "dsx_pyramid_work_bytes", "dsx_pyramid_block_u16", "dsx_pyramid_block_ref",
     "dsx_pyramid_bricks_u16", "dsx_pyramid_bricks_ref",
 ]  # fmt: skip
@@ -194,6 +194,9 @@ def load_library(path=None):
                                         ctypes.POINTER(ctypes.c_size_t), i32, i32, i32]  # fmt: skip
     lib.dsx_io_write_chunks_blosc.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp),
                                               ctypes.POINTER(ctypes.c_size_t), i32, i32, i32, i32, i32]  # fmt: skip
+    lib.dsx_io_write_chunks_blosc_lz4.argtypes = [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(vp),
+                                                  ctypes.POINTER(ctypes.c_size_t), i32, i32, i32]  # fmt: skip
+    lib.dsx_blosc_encode_lz4.argtypes = [vp, ctypes.c_size_t, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     lib.dsx_png_unfilter.argtypes = [vp, i32, i32, i32]
     lib.dsx_plan_streaks.argtypes = [vp, i32, i32, i32, ctypes.POINTER(_StreaksCfg)]
     lib.dsx_get_streaks_threshold.argtypes = [vp, i32, f32p]
@@ -473,10 +476,11 @@ class DestripeEngine:
 
     def blosc_encode_device(self, d_src, n_chunks, chunk_bytes, d_frames, d_offsets, typesize=2, clevel=3,
                             mode="literals"):
-        """Blosc-zstd frames of ``n_chunks`` chunks of ``chunk_bytes`` (device buffer ``d_src``), encoded on the device
-        into ``d_frames`` (capacity ``n_chunks * (chunk_bytes + 16)``), packed back to back; ``d_offsets`` receives
-        ``n_chunks + 1`` int64 frame offsets.  ``mode``: one of :data:`ZENC_MODES` (``"runs"``: runs of equal bytes
-        become matches).  Asynchronous on the engine stream."""
+        """Blosc frames of ``n_chunks`` chunks of ``chunk_bytes`` (device buffer ``d_src``), encoded on the device into
+        ``d_frames`` (capacity ``n_chunks * (chunk_bytes + 16)``), packed back to back; ``d_offsets`` receives
+        ``n_chunks + 1`` int64 frame offsets.  ``mode``, one of :data:`ZENC_MODES`: ``"literals"`` = Blosc-zstd frames,
+        entropy coding only; ``"runs"`` = Blosc-zstd frames in which runs of equal bytes become matches; ``"lz4"`` =
+        Blosc-LZ4 frames with split streams (``csrc/dsx_lz4_enc.h``).  Asynchronous on the engine stream."""
         self._check(self._lib.dsx_blosc_encode_device_ex(self._ctx, ctypes.c_void_p(d_src.ptr), int(n_chunks),
                                                          int(chunk_bytes), int(typesize), int(clevel),
                                                          ctypes.c_void_p(d_frames.ptr), ctypes.c_void_p(d_offsets.ptr),
@@ -565,12 +569,19 @@ class DestripeEngine:
         self._check(self._lib.dsx_io_read_chunks(self._ctx, cp, dp, nb, n, int(threads), code, int(fill_value)))
 
     def io_write_chunks(self, paths, arrays, threads=16, zlib_level=-1, blosc=None):
-        """``arrays[i]`` -> chunk files ``paths[i]`` (raw, zlib streams for ``zlib_level >= 0``, or Blosc-zstd frames for
-        ``blosc = (clevel, typesize, shuffle)``), atomically."""
+        """``arrays[i]`` -> chunk files ``paths[i]`` (raw, zlib streams for ``zlib_level >= 0``, Blosc-zstd frames for
+        ``blosc = (clevel, typesize, shuffle)``, or Blosc-LZ4 frames of uint16 for ``blosc = (clevel, 2, True, "lz4")``:
+        what ``MiniZarrArray.blosc_write_params`` returns), atomically."""
         n = len(paths)
         cp = (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths])
         dp = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrays])
         nb = (ctypes.c_size_t * n)(*[a.nbytes for a in arrays])
+        if blosc is not None and len(blosc) == 4:
+            clevel, typesize, shuffle, cname = blosc
+            if cname != "lz4" or typesize != 2 or not shuffle:
+                raise ValueError("Blosc-LZ4 chunks are written byte-shuffled at typesize 2, not {!r}".format(blosc))
+            self._check(self._lib.dsx_io_write_chunks_blosc_lz4(self._ctx, cp, dp, nb, n, int(threads), int(clevel)))
+            return
         if blosc is not None:
             clevel, typesize, shuffle = blosc
             self._check(self._lib.dsx_io_write_chunks_blosc(self._ctx, cp, dp, nb, n, int(threads), int(clevel),
@@ -849,8 +860,8 @@ def pyramid_bricks_ref(bricks, zyx, src_chunk, chunks, z0s=None, bricks_out=None
     return out
 
 
-# modes of the device Blosc-zstd encoder (DSX_ZENC_* of include/dsx.h)
-ZENC_MODES = {"literals": 0, "runs": 1}
+# modes of the device Blosc encoder (DSX_ZENC_* of include/dsx.h): two zstd modes, and Blosc-LZ4 frames
+ZENC_MODES = {"literals": 0, "runs": 1, "lz4": 3}
 
 
 def zenc_mode(mode):
@@ -868,7 +879,7 @@ def blosc_encode_ref(chunks, clevel=3, mode="literals"):
     lib = load_library()
     a = np.ascontiguousarray(chunks)
     if a.dtype != np.uint16:
-        raise ValueError("the device Blosc-zstd encoder supports uint16 (typesize 2) only")
+        raise ValueError("the device Blosc encoders support uint16 (typesize 2) only")
     n = a.shape[0] if a.ndim else 0
     chunk_bytes = a.nbytes // n if n else 0
     frames = np.empty(n * (chunk_bytes + 16) + 1, np.uint8)

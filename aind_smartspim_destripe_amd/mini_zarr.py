@@ -7,7 +7,8 @@ production arrays are ``uint16``, chunks ``(1, 1, 64, 128, 128)``, ``Blosc(cname
 ``dimension_separator="/"`` (``zarr_destriper.py:1066-1074``).  Blosc frames are decoded / encoded by the native
 library (``csrc/dsx_io.h``: the c-blosc 1.x container restated from its format description, ``libzstd.so.1`` /
 ``liblz4.so.1`` of the image ``dlopen``ed; frames with zstd, lz4, blosclz or zlib inside, byte- or bit-shuffled, are
-read -- Zarr's own default ``Blosc(lz4, 5, SHUFFLE)`` included -- and zstd frames are written).  Pinned by frames of the
+read -- Zarr's own default ``Blosc(lz4, 5, SHUFFLE)`` included; zstd frames are written, and byte-shuffled LZ4 frames of
+2-byte elements by the library's own LZ4 block encoder, ``csrc/dsx_lz4_enc.h``).  Pinned by frames of the
 real c-blosc 1.21.0 (``tests/golden/blosc_frames.npz``, ``oracle/make_golden_blosc.py``).
 """
 
@@ -41,16 +42,24 @@ def blosc_decode(frame, nbytes):
     return out.raw
 
 
-def blosc_encode(raw, typesize, clevel=3, shuffle=True):
-    """Bytes-like -> one Blosc frame with zstd inside (``dsx_blosc_encode``)."""
+def blosc_encode(raw, typesize, clevel=3, shuffle=True, cname="zstd"):
+    """Bytes-like -> one Blosc frame with zstd inside (``dsx_blosc_encode``), or, for ``cname="lz4"`` (2-byte elements,
+    byte shuffle only), with LZ4 inside and split streams (``dsx_blosc_encode_lz4``)."""
     import ctypes
 
+    if cname not in ("zstd", "lz4"):
+        raise NotImplementedError("Blosc frames are written with zstd or lz4 inside; cname {!r} is read-only".format(cname))
+    if cname == "lz4" and (int(typesize) != 2 or not shuffle):
+        raise NotImplementedError("Blosc-LZ4 frames are written byte-shuffled at typesize 2 only")
     lib = _native()
     raw = bytes(raw)
     out = ctypes.create_string_buffer(len(raw) + 16)
     n = ctypes.c_size_t()
-    rc = lib.dsx_blosc_encode(raw, len(raw), int(typesize), int(clevel), 1 if shuffle else 0, out, len(raw) + 16,
-                              ctypes.byref(n))  # fmt: skip
+    if cname == "lz4":
+        rc = lib.dsx_blosc_encode_lz4(raw, len(raw), int(clevel), out, len(raw) + 16, ctypes.byref(n))
+    else:
+        rc = lib.dsx_blosc_encode(raw, len(raw), int(typesize), int(clevel), 1 if shuffle else 0, out, len(raw) + 16,
+                                  ctypes.byref(n))  # fmt: skip
     if rc != 0:
         raise ValueError((lib.dsx_last_error(None) or b"blosc: encode failed").decode())
     return out.raw[: n.value]
@@ -71,9 +80,10 @@ class MiniZarrArray:
         elif comp.get("id") == "zlib":
             self.compressor = ("zlib", int(comp.get("level", 1)))
         elif comp.get("id") == "blosc":
-            # reading only needs the frames (their headers name the inner codec); writing needs cname zstd
+            # reading only needs the frames (their headers name the inner codec); writing: blosc_write_params
             self.compressor = ("blosc", int(comp.get("clevel", 5)), str(comp.get("cname", "lz4")),
                                int(comp.get("shuffle", 1)))  # fmt: skip
+            self._blosc_blocksize = int(comp.get("blocksize", 0) or 0)
         else:
             raise NotImplementedError(
                 "compressor {!r} is not available (null / zlib / blosc are)".format(comp.get("id"))
@@ -89,10 +99,16 @@ class MiniZarrArray:
         return {None: CODEC_RAW, "zlib": CODEC_ZLIB, "blosc": CODEC_BLOSC}[self.compressor and self.compressor[0]]
 
     def blosc_write_params(self):
-        """``(clevel, typesize, byte shuffle)`` for ``dsx_io_write_chunks_blosc``; raises for what the writer lacks."""
+        """``(clevel, typesize, byte shuffle)`` for ``dsx_io_write_chunks_blosc``, or ``(clevel, 2, True, "lz4")`` for
+        ``dsx_io_write_chunks_blosc_lz4`` (``Engine.io_write_chunks(blosc=...)``); raises for what the writers lack."""
         _, clevel, cname, shuffle = self.compressor
+        if cname == "lz4":
+            if self.dtype.itemsize != 2 or shuffle not in (1, -1) or self._blosc_blocksize:
+                raise NotImplementedError("Blosc-LZ4 frames are written for 2-byte elements with byte shuffle and "
+                                          "blocksize 0 only; this array's compressor is read-only")
+            return clevel, 2, True, "lz4"
         if cname != "zstd":
-            raise NotImplementedError("Blosc frames are written with zstd inside; cname {!r} is read-only".format(cname))
+            raise NotImplementedError("Blosc frames are written with zstd or lz4 inside; cname {!r} is read-only".format(cname))
         if shuffle == 2 or (shuffle == -1 and self.dtype.itemsize == 1):
             raise NotImplementedError("Blosc bit-shuffle is not implemented")
         return clevel, self.dtype.itemsize, shuffle != 0
@@ -109,8 +125,8 @@ class MiniZarrArray:
             return raw
         if self.compressor[0] == "zlib":
             return zlib.compress(raw, self.compressor[1])
-        clevel, typesize, shuffle = self.blosc_write_params()
-        return blosc_encode(raw, typesize, clevel, shuffle)
+        clevel, typesize, shuffle, *cname = self.blosc_write_params()
+        return blosc_encode(raw, typesize, clevel, shuffle, *cname)
 
     # -- construction -------------------------------------------------------------------------
     @staticmethod

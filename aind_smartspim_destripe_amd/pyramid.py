@@ -502,7 +502,7 @@ def _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, devi
     from . import zarr_destriper as zd
 
     t_start = time.perf_counter()
-    codec_mode = zd.device_codec_mode(device_codec)
+    codec_mode = zd.output_codec_mode(device_codec, compressor)  # "lz4" for Blosc-LZ4 levels
     decode_mode = zd.device_decode_mode(device_decode)
     src = MiniZarrArray.open(level0_path)
     if src.dtype != np.uint16 or any(n != 1 for n in src.shape[:-3]):
@@ -522,9 +522,9 @@ def _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, devi
                                            compressor=compressor, dimension_separator="/"))  # fmt: skip
         shapes.append(out_shape)
     if codec_mode is not None and arrays:
-        comp = arrays[0].compressor
-        if comp is None or comp[0] != "blosc" or comp[2] != "zstd" or comp[3] != 1:
-            raise ValueError("device_codec needs a Blosc-zstd uint16 output with byte shuffle, not {!r}".format(comp))
+        if not zd.device_codec_output_ok(arrays[0]):
+            raise ValueError("device_codec needs a Blosc-zstd or Blosc-LZ4 uint16 output with byte shuffle, not {!r}"
+                             .format(arrays[0].compressor))
     if io_threads is None:
         io_threads = zd.default_io_threads(1)
     LAST_PYRAMID.clear()

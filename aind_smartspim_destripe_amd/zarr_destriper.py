@@ -335,7 +335,7 @@ class _DeviceBlocks:
         self.d_bricks_out = [eng.alloc(out_bytes) for _ in range(self.N_BUF)]
         self.d_planes = eng.alloc(block_z * H * W * 2)
         self.d_out = eng.alloc(block_z * H * W * 2)
-        self.codec_mode = device_codec_mode(device_codec)  # None, "literals" or "runs"
+        self.codec_mode = output_codec_mode(device_codec, dst)  # None, "literals", "runs" or "lz4"
         self.device_codec = self.codec_mode is not None
         self.d_frames, self.d_offsets, self.h_frames, self.h_offsets = [], [], [], []
         if self.device_codec:
@@ -645,6 +645,33 @@ def device_codec_mode(device_codec):
     return "literals" if device_codec else None
 
 
+def output_codec_mode(device_codec, output):
+    """:func:`device_codec_mode` for one output: an open array, or the ``compressor`` it will be created with (what
+    ``MiniZarrArray.create`` takes).  A Blosc-LZ4 output is encoded by the device LZ4 encoder: ``"lz4"`` for a true
+    ``device_codec``; ``"runs"`` writes zstd sequences and is a ``ValueError`` there."""
+    mode = device_codec_mode(device_codec)
+    meta = output.compressor_meta if isinstance(output, MiniZarrArray) else MiniZarrArray._compressor_meta(output)
+    if mode is None or not (isinstance(meta, dict) and meta.get("id") == "blosc" and meta.get("cname", "lz4") == "lz4"):
+        return mode
+    if mode == "runs":
+        raise ValueError("device_codec=\"runs\" writes zstd sequences; a Blosc-LZ4 output takes device_codec=True")
+    return "lz4"
+
+
+def device_codec_output_ok(dst):
+    """Can ``device_codec`` write the array ``dst``: uint16, Blosc with zstd (byte shuffle) or what the LZ4 writer takes."""
+    comp = dst.compressor
+    if comp is None or comp[0] != "blosc" or dst.dtype != np.uint16:
+        return False
+    if comp[2] == "lz4":
+        try:
+            dst.blosc_write_params()
+        except NotImplementedError:
+            return False
+        return True
+    return comp[2] == "zstd" and comp[3] == 1
+
+
 ZDEC_MODES = {"zstd": engine_mod.ZDEC_ZSTD, "any": engine_mod.ZDEC_ANY, "full": engine_mod.ZDEC_ALL}
 _TASK_CODECS = {engine_mod.TASK_LZ4: "lz4", engine_mod.TASK_ZLIB: "zlib", engine_mod.TASK_BLOSCLZ: "blosclz"}
 
@@ -679,7 +706,7 @@ def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False, 
     """Staging buffers for this geometry, reused from the previous tile when nothing but the stores changed
     (a channel is tens of tiles of one shape, ``zarr_destriper.py:1231``)."""
     key = (id(eng), tuple(zyx[1:]), tuple(src.chunks[-3:]), tuple(dst.chunks[-3:]), int(block_z),
-           device_codec_mode(device_codec),
+           output_codec_mode(device_codec, dst),  # (a zstd and an LZ4 output of one geometry differ here only)
            device_decode_mode(device_decode), tuple((lv.level, lv.shape[1:], lv.chunks) for lv in (pyr[0] if pyr else ())))  # fmt: skip
     cached = _BLOCKS.get("blocks")
     if cached is not None and cached[0] == key and cached[1].eng._ctx is not None:
@@ -778,6 +805,10 @@ def destripe_zarr_store(
     per voxel, and a chunk is never larger than with ``True``; the pyramid rows of ``pyramid_group`` use the same mode.
     Any other string raises ``ValueError``; every other value counts by its truth.  Needs a Blosc-zstd output with byte
     shuffle and the device re-tiling path; anything else raises ``ValueError``.  Off by default.
+    A Blosc-LZ4 output (``compressor`` a numcodecs config with ``cname`` ``"lz4"``: 2-byte elements, byte shuffle,
+    ``blocksize`` 0) is written by the library's LZ4 encoder on either route: the I/O threads run its host build, and a
+    true ``device_codec`` runs it on the GPU (``DSX_ZENC_LZ4``, ``LAST_RUN["device_codec_mode"] == "lz4"``) -- the same
+    files.  ``"runs"`` on such an output raises ``ValueError`` before anything is created.
 
     ``device_decode``: ``True`` = the input chunks are decoded on the GPU (``dsx_blosc_decode_device``): the I/O
     threads only read the files, the compressed frames cross the host link, and a zstd decoder fills the input bricks.
@@ -805,7 +836,7 @@ def destripe_zarr_store(
     from . import pyramid
 
     logger = logger or logging.getLogger("dsx.zarr")
-    codec_mode = device_codec_mode(device_codec)
+    codec_mode = output_codec_mode(device_codec, compressor)  # (a wrong mode fails before anything is created)
     device_codec = codec_mode is not None
     decode_mode = device_decode_mode(device_decode)
     if io_threads is None:
@@ -854,9 +885,9 @@ def destripe_zarr_store(
     if device_retile and not can:
         raise ValueError("device_retile needs a uint16 store, even planes and output-chunk-aligned z blocks")
     if device_codec:
-        comp = dst.compressor
-        if comp is None or comp[0] != "blosc" or comp[2] != "zstd" or comp[3] != 1 or dst.dtype != np.uint16:
-            raise ValueError("device_codec needs a Blosc-zstd uint16 output with byte shuffle, not {!r}".format(comp))
+        if not device_codec_output_ok(dst):
+            raise ValueError("device_codec needs a Blosc-zstd or Blosc-LZ4 uint16 output with byte shuffle, not {!r}"
+                             .format(dst.compressor))
         if not can or device_retile is False:
             raise ValueError("device_codec needs the device re-tiling path (a uint16 store, even planes and "
                              "output-chunk-aligned z blocks)")  # fmt: skip
@@ -886,7 +917,7 @@ def destripe_zarr_store(
         eng.sync()
         dt = time.perf_counter() - t0
         logger.info("rank %d: %d planes z[%d:%d) in %.2f s (device re-tiling%s, overlapped; read %.2f s, write %.2f s)",
-                    rank, n_planes, z0, z1, dt, (", device codec" + (" (runs)" if codec_mode == "runs" else "") if device_codec else "")
+                    rank, n_planes, z0, z1, dt, (", device codec" + (" ({})".format(codec_mode) if codec_mode in ("runs", "lz4") else "") if device_codec else "")
                     + (", device decode ({})".format(decode_mode) if device_decode else "")
                     + (", pyramid levels 1..{} fused".format(len(levels)) if levels else ""), blocks.timing["read_s"],
                     blocks.timing["write_s"])  # fmt: skip
@@ -1088,7 +1119,7 @@ def destripe_zarr(
     run's own output; same stores; ``ValueError`` together with ``fused_pyramid``).
     Returns ``(planes processed by this rank, seconds)``.
     """
-    device_codec_mode(device_codec)  # (a wrong string fails before anything is written)
+    output_codec_mode(device_codec, compressor)  # (a wrong string or mode fails before anything is written)
     device_decode_mode(device_decode)
     if fused_pyramid and pipelined_pyramid:
         raise ValueError("fused_pyramid and pipelined_pyramid are two routes to the same pyramid: choose one")
@@ -1243,7 +1274,7 @@ def destripe_channel(
     """
     if world_size > 1 and group is None:
         raise ValueError("destripe_channel with world_size > 1 needs a group to order the pyramid after all ranks")
-    device_codec_mode(device_codec)  # (a wrong string fails before anything is written)
+    output_codec_mode(device_codec, compressor)  # (a wrong string or mode fails before anything is written)
     device_decode_mode(device_decode)
     if fused_pyramid and pipelined_pyramid:
         raise ValueError("fused_pyramid and pipelined_pyramid are two routes to the same pyramid: choose one")

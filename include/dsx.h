@@ -239,6 +239,12 @@ int dsx_io_write_chunks_blosc(dsx_ctx* ctx, const char* const* paths, const void
 int dsx_blosc_decode(const void* frame, size_t frame_bytes, void* dst, size_t dst_bytes);
 int dsx_blosc_encode(const void* src, size_t bytes, int typesize, int clevel, int shuffle, void* frame,
                      size_t frame_capacity, size_t* frame_bytes);
+/* The same with LZ4 inside (the host build of csrc/dsx_lz4_enc.h; no liblz4 needed): uint16 elements (bytes even),
+ * byte shuffle, split streams -- the frames of DSX_ZENC_LZ4 below.  clevel 0 stores, 1 ... 9 encode alike. */
+int dsx_io_write_chunks_blosc_lz4(dsx_ctx* ctx, const char* const* paths, const void* const* src,
+                                  const size_t* bytes, int n, int threads, int clevel);
+int dsx_blosc_encode_lz4(const void* src, size_t bytes, int clevel, void* frame, size_t frame_capacity,
+                         size_t* frame_bytes);
 
 /* Blosc-zstd frames of n_chunks uint16 chunks of chunk_bytes each, encoded on the device (csrc/dsx_zstd_enc.h:
  * entropy-only zstd -- Huffman literals, no matches -- in the container dsx_blosc_encode writes: 256 KiB blocks,
@@ -254,9 +260,14 @@ int dsx_blosc_encode(const void* src, size_t bytes, int typesize, int clevel, in
  * the smaller of the two encodings is written, so a frame is never larger than in DSX_ZENC_LITERALS.  On synthetic
  * (64, 128, 128) bricks: 1.00x the bytes of the host writer (zstd level 5) instead of 1.10x
  * (profiles/device_codec_runs_sizes.json).  No general matches, no offsets other than 1, typesize 2 only.  The
- * context keeps a second work buffer of the same size in this mode.  Any other mode: DSX_EINVAL. */
+ * context keeps a second work buffer of the same size in this mode.
+ * DSX_ZENC_LZ4: Blosc-LZ4 frames instead (csrc/dsx_lz4_enc.h: what c-blosc calls LZ4 with byte shuffle -- flags
+ * SHUFFLE | 1 << 5, "don't split" clear: a full 256 KiB block is two LZ4 blocks, the low-byte and the high-byte plane,
+ * each coded or stored on its own; a hash-table match finder, offsets 1 ... 65535), the frames dsx_blosc_encode_lz4
+ * and dsx_io_write_chunks_blosc_lz4 write, byte for byte.  Any other mode: DSX_EINVAL. */
 #define DSX_ZENC_LITERALS 0
 #define DSX_ZENC_RUNS 1
+#define DSX_ZENC_LZ4 3
 int dsx_blosc_encode_device(dsx_ctx* ctx, const void* d_src, int n_chunks, size_t chunk_bytes, int typesize,
                             int clevel, void* d_frames, int64_t* d_offsets);
 int dsx_blosc_encode_ref(const void* src, int n_chunks, size_t chunk_bytes, int typesize, int clevel, void* frames,

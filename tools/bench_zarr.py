@@ -5,7 +5,7 @@ download) into another store.  Prints one JSON line; the roofline of this path i
 (PCIe Gen5 x16, 63 GB/s spec: 16.8 MB per plane both ways -> <= 3.7 k planes/s), not HBM.
 
     bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode|device-decode-any|device-decode-all]
-                  [lz4|blosc-zlib|blosc-blosclz|plain-zlib] [pyramid|fused-pyramid|pipelined-pyramid]
+                  [lz4|blosc-zlib|blosc-blosclz|plain-zlib] [pyramid|fused-pyramid|pipelined-pyramid] [lz4-out] [read-back]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
 line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
@@ -20,6 +20,12 @@ blosclz encoder of tests/inflate_cases.py) or to the plain zlib compressor (leve
 shuffle, 256 KiB blocks split into a low-byte and a high-byte stream (the test suite's LZ4 encoder,
 tests/blosc_any_frames.py; every 64-plane block holds the same planes, as in the other variants); the output stays
 Blosc-zstd.  The line then reports the input store's bytes and the chunks decoded on the device / host / filled.
+`lz4-out` (Blosc only): the OUTPUT store (and the pyramid levels) is Blosc-LZ4 -- what numcodecs.Blosc() writes by default:
+LZ4, clevel 5, byte shuffle, split streams -- written by the host LZ4 writer on the I/O threads, or with `device-codec` by
+the device LZ4 encoder (csrc/dsx_lz4_enc.h; the same files either way).  The host writer's bytes reported for
+comparison are then LZ4 frames too.
+`read-back` (Blosc only): after the timed pass the written store is the input of one more pass with device_decode="any"
+(into a Blosc-zstd store, device_codec="runs"); the line reports its seconds, read stage time and decode routes as "read_back".
 `pyramid`: after the timed level-0 pass, compute_multiscale(n_levels=3) on the store is timed too (the two-pass route);
 `fused-pyramid`: level 0 and levels 1-2 in one destripe_zarr_store call (pyramid_group / n_levels);
 `pipelined-pyramid`: level 0 is timed as without a pyramid word, then compute_multiscale(pipelined=True, n_levels=3) with the
@@ -43,6 +49,11 @@ device_decode = ("full" if "device-decode-all" in sys.argv[3:] else
 recode = ([w for w in ("lz4", "blosc-zlib", "blosc-blosclz", "plain-zlib") if w in sys.argv[3:]] + [None])[0]
 lz4_input = recode is not None  # (any recoded input store)
 two_pass, fused, pipelined = ("pyramid" in sys.argv[3:], "fused-pyramid" in sys.argv[3:], "pipelined-pyramid" in sys.argv[3:])
+lz4_out, read_back = "lz4-out" in sys.argv[3:], "read-back" in sys.argv[3:]
+if (lz4_out or read_back) and codec != "blosc":
+    sys.exit("lz4-out / read-back: a Blosc store")
+out_codec = {"id": "blosc", "cname": "lz4", "clevel": 5, "shuffle": 1, "blocksize": 0} if lz4_out else codec
+host_frame = dict(clevel=5, shuffle=True, cname="lz4") if lz4_out else dict(clevel=3, shuffle=True)
 H = W = 2048
 root = tempfile.mkdtemp(prefix="dsx_zarr_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
@@ -90,7 +101,7 @@ try:
             t0 = time.perf_counter()
             planes, dt = zd.destripe_zarr_store(os.path.join(root, "in.zarr"), level0, synth.CELLS_CONFIG,
                                           synth.NO_CELLS_CONFIG, None, prediction_chunksize=(64, H, W),
-                                          output_chunks=(1, 1, 64, 128, 128), device=0, device_retile=True, io_threads=16, compressor=codec,
+                                          output_chunks=(1, 1, 64, 128, 128), device=0, device_retile=True, io_threads=16, compressor=out_codec,
                                           device_codec=device_codec, device_decode=device_decode, **kw)
             res[name] = {"planes": planes, "seconds": round(time.perf_counter() - t0, 3)}
     timing = dict(zd._BLOCKS["blocks"][1].timing)  # the timed (second) pass
@@ -106,14 +117,14 @@ try:
         if pipelined:  # one pipelined device pass over the finished level 0 (compute_multiscale(pipelined=True))
             from aind_smartspim_destripe_amd import pyramid
             t0 = time.perf_counter()
-            zd.compute_multiscale(level0, group, [2, 2, 2], 1, None, "bench", n_levels=3, compressor=codec, device=0,
+            zd.compute_multiscale(level0, group, [2, 2, 2], 1, None, "bench", n_levels=3, compressor=out_codec, device=0,
                                   pipelined=True, device_codec=device_codec, io_threads=16,
                                   device_decode=device_decode if codec == "blosc" else False)
             pyramid_s = time.perf_counter() - t0
             pyr["pipelined"] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in pyramid.LAST_PYRAMID.items()}
         if two_pass:  # the route destripe_zarr takes by default: rank 0 reads level 0 back and writes the levels
             t0 = time.perf_counter()
-            zd.compute_multiscale(level0, group, [2, 2, 2], 1, None, "bench", n_levels=3, compressor=codec, device=0)
+            zd.compute_multiscale(level0, group, [2, 2, 2], 1, None, "bench", n_levels=3, compressor=out_codec, device=0)
             pyramid_s = time.perf_counter() - t0
         pyr = {**pyr, "route": "fused" if fused else ("pipelined" if pipelined else "two-pass"), "level0_s": round(secs, 3), "pyramid_s": round(pyramid_s, 3),
                "total_s": round(secs + pyramid_s, 3), "pyramid_download_bytes": int(timing["pyramid_download_bytes"])}
@@ -130,10 +141,20 @@ try:
                       for f in fs if not f.startswith("."))
         first = [out._chunk_path((0, 0, 0, y, x)) for y in range(H // 128) for x in range(W // 128)]
         got = sum(os.path.getsize(p) for p in first)
-        host = sum(len(mini_zarr.blosc_encode(out._read_chunk((0, 0, 0, y, x)).tobytes(), 2, clevel=3, shuffle=True))
+        host = sum(len(mini_zarr.blosc_encode(out._read_chunk((0, 0, 0, y, x)).tobytes(), 2, **host_frame))
                    for y in range(H // 128) for x in range(W // 128))
         sizes = {"bytes_written": written, "raw_bytes": n * H * W * 2, "ratio_to_raw": round(written / (n * H * W * 2), 4),
                  "first_block_bytes": got, "first_block_host_writer_bytes": host, "size_ratio_to_host_writer": round(got / host, 4)}
+    if read_back:  # the written store as the input of a pass that decodes it on the device
+        for rep in range(2):  # (second pass: the staging buffers of this geometry exist)
+            t0 = time.perf_counter()
+            zd.destripe_zarr_store(level0, os.path.join(root, "back.zarr"), synth.CELLS_CONFIG, synth.NO_CELLS_CONFIG, None,
+                                   prediction_chunksize=(64, H, W), output_chunks=(1, 1, 64, 128, 128), device=0,
+                                   device_retile=True, io_threads=16, compressor="blosc", device_codec="runs", device_decode="any")
+        sizes["read_back"] = {"seconds": round(time.perf_counter() - t0, 3),
+                              "read_s": round(zd._BLOCKS["blocks"][1].timing["read_s"], 3),
+                              "decode_routes": zd.LAST_RUN.get("decode_routes")}
+        shutil.rmtree(os.path.join(root, "back.zarr"), ignore_errors=True)
     if pyr:
         from oracle import format_oracle as fo
         want = fo.pyramid(out[0, 0, 0:8], 3)
@@ -147,7 +168,7 @@ try:
             if codec == "blosc":  # the level's first chunk row: bytes on disk against the host writer's frames
                 idx = [(0, 0, 0, y, x) for y in range(-(-arr.shape[3] // arr.chunks[3])) for x in range(-(-arr.shape[4] // arr.chunks[4]))]
                 info["first_row_bytes"] = sum(os.path.getsize(arr._chunk_path(i)) for i in idx)
-                info["first_row_host_writer_bytes"] = sum(len(mini_zarr.blosc_encode(arr._read_chunk(i).tobytes(), 2, clevel=3, shuffle=True)) for i in idx)
+                info["first_row_host_writer_bytes"] = sum(len(mini_zarr.blosc_encode(arr._read_chunk(i).tobytes(), 2, **host_frame)) for i in idx)
                 info["size_ratio_to_host_writer"] = round(info["first_row_bytes"] / info["first_row_host_writer_bytes"], 4)
             pyr["levels"][str(lvl)] = info
     v = res["overlapped"]["planes"] / res["overlapped"]["seconds"]
@@ -178,7 +199,7 @@ try:
                 except AssertionError as e:
                     verified = False
                     print("oracle mismatch", e, file=sys.stderr)
-    label = (codec or "raw") + (", {} input".format("LZ4" if recode == "lz4" else recode) if lz4_input else "") + (", encoded on the device" + (" with run matches" if device_codec == "runs" else "") if device_codec else "") + (", decoded on the device" + (" ({})".format(device_decode) if isinstance(device_decode, str) else "") if device_decode else "")
+    label = (codec or "raw") + (", {} input".format("LZ4" if recode == "lz4" else recode) if lz4_input else "") + (", LZ4 output" if lz4_out else "") + (", encoded on the device" + (" with run matches" if device_codec == "runs" else "") if device_codec else "") + (", decoded on the device" + (" ({})".format(device_decode) if isinstance(device_decode, str) else "") if device_decode else "")
     label += ", pyramid fused" if fused else ""  # (a stand-alone pyramid, slab or pipelined, is not part of the metric)
     print(json.dumps({"metric": "2048x2048 uint16 slices/s, Zarr store to Zarr store ({} chunks, tmpfs)".format(label), "value": round(v, 1),
                       "planes": n, "seconds": res["overlapped"]["seconds"], "store_make_s": round(t_make, 1),
