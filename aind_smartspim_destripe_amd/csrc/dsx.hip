@@ -191,6 +191,12 @@ struct dsx_ctx {
   unsigned* st_hist = nullptr;    // [max_batch][kStBins]
   float* st_t = nullptr;          // [max_batch] threshold per plane
   dsx::st::OtsuOut* st_info = nullptr;
+  // march route of the streaks plan (DSX_STREAKS_MARCH): `plan` holds the log-space chain over the virtual band planes
+  // (cfg 0 / 1 = foreground / background band), run_cohort launches neither k_hist nor k_otsu
+  bool st_march = false;
+  int st_vdtype = DSX_U16;        // element type of the virtual planes of uint16 input (float32 input: float32)
+  void* st_vin = nullptr;         // [bands * B][H][W] virtual input planes
+  float* st_vout = nullptr;       // [bands * B][H][W] what the chain writes: band + 2
 };
 
 namespace {
@@ -588,6 +594,7 @@ int run_cohort(dsx_ctx* ctx, const CohortView& v, const void* d_in, int in_dtype
 #endif
   // histograms of levels [l0, l1) in ONE launch (k_hist finds its level from the block index)
   auto hist_levels = [&](int l0, int l1, hipStream_t hs) -> int {
+    if (ctx->st_march) return DSX_OK;  // no mask: thr / cfg come from k_st_chainfill
     dsx::HistArgs a;
     memset(&a, 0, sizeof(a));
     a.ws = v.ws;
@@ -715,7 +722,7 @@ int run_cohort(dsx_ctx* ctx, const CohortView& v, const void* d_in, int in_dtype
   // ---- thresholds -----------------------------------------------------------------------------
   if (int rc = hist_levels(split ? 2 : 0, L, s)) return rc;
   if (split) DSX_HIP(hipStreamWaitEvent(s, v.ev[1], 0));  // histograms of levels 1, 2 (helper stream)
-  if (L > 0) {
+  if (L > 0 && !ctx->st_march) {
     dsx::OtsuArgs a;
     a.stats = v.stats;
     a.npix = (double)p.H * (double)p.W;
@@ -1072,6 +1079,9 @@ void free_streaks(dsx_ctx* c) {
   fr(c->st_hist); c->st_hist = nullptr;
   fr(c->st_t); c->st_t = nullptr;
   fr(c->st_info); c->st_info = nullptr;
+  fr(c->st_vin); c->st_vin = nullptr;
+  fr(c->st_vout); c->st_vout = nullptr;
+  c->st_march = false;
   c->streaks = false;
 }
 
@@ -1090,14 +1100,11 @@ void st_final(hipStream_t s, const dsx::st::StreaksPlan& p, const void* in, cons
                                                                p.bands, t, 1.0f / p.crossover, (TO*)out);
 }
 
-// One cohort (nb <= max_batch planes) of the dual-band filter on stream s.
-int streaks_cohort(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d_out, int out_dtype) {
+// Threshold per plane of a cohort into ctx->st_t (both routes)
+int streaks_threshold(dsx_ctx* ctx, hipStream_t s, const void* d_in, bool u16, int nb) {
   using namespace dsx::st;
   const StreaksPlan& p = ctx->sp;
-  hipStream_t s = use_main(ctx);
   const size_t px = (size_t)p.H * p.W;
-  const bool u16 = in_dtype == DSX_U16;
-  // 1. threshold per plane
   if (p.otsu) {
     k_st_mminit<<<st_blocks(nb), 256, 0, s>>>(ctx->st_mm, nb);
     DSX_HIP(hipMemsetAsync(ctx->st_hist, 0, sizeof(unsigned) * kStBins * nb, s));
@@ -1115,6 +1122,72 @@ int streaks_cohort(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d
   } else {
     k_st_fill<<<st_blocks(nb), 256, 0, s>>>(ctx->st_t, nb, p.threshold);
   }
+  DSX_HIP(hipGetLastError());
+  return DSX_OK;
+}
+
+template <typename TI, typename TV>
+void st_bands(hipStream_t s, dim3 g, bool vec, const void* in, size_t px, int bands, const float* t, void* v,
+              unsigned* sticky) {
+  using namespace dsx::st;
+  if (vec) k_st_bands<TI, TV, 4><<<g, 256, 0, s>>>((const TI*)in, px, bands, t, (TV*)v, sticky);
+  else k_st_bands<TI, TV, 1><<<g, 256, 0, s>>>((const TI*)in, px, bands, t, (TV*)v, sticky);
+}
+template <typename TI, typename TO>
+void st_blend(hipStream_t s, dim3 g, bool vec, const void* in, const float* r, size_t px, int bands, const float* t,
+              float inv_crossover, void* out) {
+  using namespace dsx::st;
+  if (vec) k_st_blend<TI, TO, 4><<<g, 256, 0, s>>>((const TI*)in, r, px, bands, t, inv_crossover, (TO*)out);
+  else k_st_blend<TI, TO, 1><<<g, 256, 0, s>>>((const TI*)in, r, px, bands, t, inv_crossover, (TO*)out);
+}
+
+// One cohort of the march route: threshold, band planes and the row filters' thr / cfg on the context stream, the
+// log-space chain over the virtual planes on the sub-cohort streams (run_cohort_split forks them behind an event of
+// the context stream), the blend on the context stream again, behind the join events (use_main).
+int streaks_cohort_march(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d_out, int out_dtype) {
+  using namespace dsx::st;
+  const StreaksPlan& p = ctx->sp;
+  const bool u16 = in_dtype == DSX_U16;
+  const size_t px = (size_t)p.H * p.W;
+  const int P = p.bands * nb, Lc = std::max(1, ctx->plan.L);
+  const int vdtype = u16 ? ctx->st_vdtype : DSX_F32;
+  // use_main joins the parts of the cohort before (they read the buffers written below) and counts as an operation on
+  // the context stream, so run_cohort_split forks anew instead of queueing its parts behind their predecessors
+  hipStream_t s = use_main(ctx);
+  if (int rc = streaks_threshold(ctx, s, d_in, u16, nb)) return rc;
+  k_st_chainfill<<<st_blocks((size_t)std::max(P * Lc, P)), 256, 0, s>>>(ctx->d_thr, P * Lc, ctx->d_cfg, P, p.bands);
+  const dim3 g((unsigned)std::max<size_t>(1, std::min<size_t>(1024, px / (256 * 4 * 4))), nb);
+  const size_t esz = elem_size(in_dtype);
+  const bool vec_in = ((uintptr_t)d_in % (4 * esz)) == 0;
+  if (!u16) st_bands<float, float>(s, g, vec_in, d_in, px, p.bands, ctx->st_t, ctx->st_vin, ctx->d_sticky);
+  else if (vdtype == DSX_U16) st_bands<uint16_t, uint16_t>(s, g, vec_in, d_in, px, p.bands, ctx->st_t, ctx->st_vin, nullptr);
+  else st_bands<uint16_t, float>(s, g, vec_in, d_in, px, p.bands, ctx->st_t, ctx->st_vin, nullptr);
+  DSX_HIP(hipGetLastError());
+  if (int rc = run_cohort_split(ctx, ctx->st_vin, vdtype, P, ctx->st_vout, DSX_F32, nullptr, px * elem_size(vdtype),
+                                px * sizeof(float)))
+    return rc;
+  s = use_main(ctx);
+  const bool vec = vec_in && ((uintptr_t)d_out % (4 * elem_size(out_dtype))) == 0;
+  const float ic = 1.0f / p.crossover;
+  if (u16 && out_dtype == DSX_U16) st_blend<uint16_t, uint16_t>(s, g, vec, d_in, ctx->st_vout, px, p.bands, ctx->st_t, ic, d_out);
+  else if (u16) st_blend<uint16_t, float>(s, g, vec, d_in, ctx->st_vout, px, p.bands, ctx->st_t, ic, d_out);
+  else if (out_dtype == DSX_U16) st_blend<float, uint16_t>(s, g, vec, d_in, ctx->st_vout, px, p.bands, ctx->st_t, ic, d_out);
+  else st_blend<float, float>(s, g, vec, d_in, ctx->st_vout, px, p.bands, ctx->st_t, ic, d_out);
+  DSX_HIP(hipGetLastError());
+  ctx->last_n = nb;
+  return DSX_OK;
+}
+
+// One cohort (nb <= max_batch planes) of the dual-band filter on stream s.
+int streaks_cohort(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d_out, int out_dtype) {
+  using namespace dsx::st;
+  if (ctx->st_march) return streaks_cohort_march(ctx, d_in, in_dtype, nb, d_out, out_dtype);
+  const StreaksPlan& p = ctx->sp;
+  hipStream_t s = use_main(ctx);
+  const size_t px = (size_t)p.H * p.W;
+  const bool u16 = in_dtype == DSX_U16;
+  // 1. threshold per plane
+  if (int rc = streaks_threshold(ctx, s, d_in, u16, nb)) return rc;
   // 2. log(1 + band) of the padded plane
   float* ws = ctx->st_ws;
   const int P = p.bands * nb;  // workspace planes of this cohort, band-major (v = band * nb + plane)
@@ -1342,6 +1415,14 @@ void dsx_destroy(dsx_ctx* ctx) {
   delete ctx;
 }
 
+namespace {
+// The log-space chain of ctx->cfg[0 / 1] for planes of height x width, max_batch planes per cohort: plan, workspace,
+// control block, constants and shading.  dsx_plan, and the march route of dsx_plan_streaks_ex (whose planes are the
+// virtual band planes).  The context's earlier plan has been freed.
+int plan_chain(dsx_ctx* ctx, int height, int width, int max_batch, bool bank, double microscope_high_int,
+               const float* flat, const float* dark, int dark_h, int dark_w);
+}  // namespace
+
 int dsx_plan(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_cfg* cells_config,
              const dsx_cfg* no_cells_config, double microscope_high_int, const float* flat,
              const float* dark, int dark_h, int dark_w) {
@@ -1368,6 +1449,12 @@ int dsx_plan(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_cfg* 
   }
   const bool bank = src[0]->wavelet == DSX_WAVELET_BANK;
   if (bank && !ctx->wl_set) return fail(ctx, DSX_EINVAL, "DSX_WAVELET_BANK without dsx_set_wavelet");
+  return plan_chain(ctx, height, width, max_batch, bank, microscope_high_int, flat, dark, dark_h, dark_w);
+}
+
+namespace {
+int plan_chain(dsx_ctx* ctx, int height, int width, int max_batch, bool bank, double microscope_high_int,
+               const float* flat, const float* dark, int dark_h, int dark_w) {
   ctx->wl_len = bank ? ctx->wl_bank_len : 0;
   if (bank) {
     memcpy(ctx->wl, ctx->wl_bank, sizeof(ctx->wl));
@@ -1429,6 +1516,7 @@ int dsx_plan(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_cfg* 
   ctx->last_n = 0;
   return DSX_OK;
 }
+}  // namespace
 
 int dsx_set_wavelet(dsx_ctx* ctx, const double* dec_lo, const double* dec_hi, const double* rec_lo,
                     const double* rec_hi, int len) {
@@ -2410,7 +2498,12 @@ int dsx_get_level(dsx_ctx* ctx, int plane, int level, int stage, float* out) {
 }
 
 int dsx_plan_streaks(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_streaks_cfg* cfg) {
+  return dsx_plan_streaks_ex(ctx, height, width, max_batch, cfg, DSX_STREAKS_GENERIC);
+}
+
+int dsx_plan_streaks_ex(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_streaks_cfg* cfg, int route) {
   if (!ctx) return DSX_EINVAL;
+  if (route != DSX_STREAKS_GENERIC && route != DSX_STREAKS_MARCH) return fail(ctx, DSX_EINVAL, "unknown streaks route");
   if (!cfg) return fail(ctx, DSX_EINVAL, "config is NULL");
   if (height < 1 || width < 1) return fail(ctx, DSX_EINVAL, "plane must be at least 1 x 1");
   if (max_batch < 1) return fail(ctx, DSX_EINVAL, "max_batch must be >= 1");
@@ -2423,6 +2516,14 @@ int dsx_plan_streaks(dsx_ctx* ctx, int height, int width, int max_batch, const d
   if (cfg->wavelet == DSX_WAVELET_BANK && !ctx->wl_set)
     return fail(ctx, DSX_EINVAL, "DSX_WAVELET_BANK needs a filter bank (dsx_set_wavelet)");
   if ((size_t)height * width > ((size_t)1 << 30)) return fail(ctx, DSX_ELIMIT, "plane larger than 2^30 pixels");
+  const bool march = route == DSX_STREAKS_MARCH;
+  if (march && cfg->wavelet != DSX_WAVELET_DB3)
+    return fail(ctx, DSX_EINVAL, "the march route of the streaks plan takes the db3 wavelet only");
+  if (march && ((height | width) & 1))
+    return fail(ctx, DSX_EINVAL, "the march route of the streaks plan takes planes of even height and width only");
+  if (march && max_batch > (1 << 29)) return fail(ctx, DSX_EINVAL, "max_batch too large");
+  if (march && cfg->level > std::min(dsx::dwt_max_level(height), dsx::dwt_max_level(width)))
+    return fail(ctx, DSX_EINVAL, "the march route of the streaks plan takes levels up to the maximum level only");
   DSX_HIP(hipSetDevice(ctx->device));
   DSX_HIP(hipStreamSynchronize(use_main(ctx)));
   free_plan_buffers(ctx);
@@ -2455,6 +2556,45 @@ int dsx_plan_streaks(dsx_ctx* ctx, int height, int width, int max_batch, const d
       p.rec.hi[t] = ctx->wl_bank[3][t];
     }
   }
+  auto alloc = [&](void** ptr, size_t bytes) -> int {
+    hipError_t e = hipMalloc(ptr, std::max<size_t>(bytes, 4));
+    if (e != hipSuccess) {
+      *ptr = nullptr;
+      free_streaks(ctx);
+      if (march) free_plan_buffers(ctx);
+      return fail(ctx, DSX_ENOMEM, std::string("hipMalloc (streaks plan): ") + hipGetErrorString(e));
+    }
+    return DSX_OK;
+  };
+  if (march) {
+    // band(z, sigma) = log_space_fft_filtering(z, sigma min(H, W) / H, empty mask) - 2: the two filters differ in the
+    // normalisation of s only (h sigma / H against h sigma / min(H, W)); cfg 0 = foreground (or the single) band
+    const double scale = (double)std::min(height, width) / (double)height;
+    for (int c = 0; c < 2; ++c) {
+      ctx->cfg[c].level = cfg->level == 0 ? -1 : cfg->level;
+      ctx->cfg[c].sigma = (double)(c == 0 ? cfg->sigma_fg : cfg->sigma_bg) * scale;
+      ctx->cfg[c].max_threshold = 0.0;  // not read: k_otsu is not launched
+    }
+    p.Hp = height; p.Wp = width;
+    const int P = p.bands * max_batch;
+    if (int rc = plan_chain(ctx, height, width, P, false, 0.0, nullptr, nullptr, 0, 0)) return rc;
+    p.L = ctx->plan.L;
+    // uint16 planes keep uint16 bands when t is integral: Otsu of a uint16 plane always is, a fixed value may not be
+    const bool integral = p.otsu || (p.threshold >= 0.f && p.threshold <= 65535.f && p.threshold == floorf(p.threshold));
+    ctx->st_vdtype = integral ? DSX_U16 : DSX_F32;
+    const size_t px = (size_t)height * width;
+    ctx->st_march = true;  // (free_streaks clears it again when an allocation fails)
+    if (int rc = alloc(&ctx->st_vin, px * P * sizeof(float))) return rc;  // float32 planes may come with either plan
+    if (int rc = alloc((void**)&ctx->st_vout, px * P * sizeof(float))) return rc;
+    if (int rc = alloc((void**)&ctx->st_mm, sizeof(unsigned) * 2 * max_batch)) return rc;
+    if (int rc = alloc((void**)&ctx->st_hist, sizeof(unsigned) * dsx::st::kStBins * max_batch)) return rc;
+    if (int rc = alloc((void**)&ctx->st_t, sizeof(float) * max_batch)) return rc;
+    if (int rc = alloc((void**)&ctx->st_info, sizeof(dsx::st::OtsuOut) * max_batch)) return rc;
+    ctx->workspace_bytes += 2 * px * P * sizeof(float);
+    ctx->streaks = true;
+    ctx->last_n = 0;
+    return DSX_OK;
+  }
   if (!dsx::st::st_build_plan(p, cfg->level)) return fail(ctx, DSX_ELIMIT, "decomposition level out of range");
   for (int l = 0; l < p.L; ++l)
     if ((size_t)max_batch * p.lv[l].h > (size_t)65535 * dsx::st::kMmT)
@@ -2464,15 +2604,6 @@ int dsx_plan_streaks(dsx_ctx* ctx, int height, int width, int max_batch, const d
     for (int b = 0; b < p.bands; ++b)
       dsx::st::st_notch_factors(p.lv[l].w, (double)p.lv[l].h * p.sigma[b] / p.Hp, p.lv[l].rank[b],
                                 mats.data() + p.lv[l].mat[b], mats.data() + p.lv[l].mat[b] + (size_t)p.lv[l].w * p.lv[l].rank[b]);
-  auto alloc = [&](void** ptr, size_t bytes) -> int {
-    hipError_t e = hipMalloc(ptr, std::max<size_t>(bytes, 4));
-    if (e != hipSuccess) {
-      *ptr = nullptr;
-      free_streaks(ctx);
-      return fail(ctx, DSX_ENOMEM, std::string("hipMalloc (streaks plan): ") + hipGetErrorString(e));
-    }
-    return DSX_OK;
-  };
   if (int rc = alloc((void**)&ctx->st_ws, sizeof(float) * p.ws_floats)) return rc;
   if (int rc = alloc((void**)&ctx->st_mat, sizeof(float) * mats.size())) return rc;
   if (int rc = alloc((void**)&ctx->st_mm, sizeof(unsigned) * 2 * max_batch)) return rc;

@@ -22,6 +22,12 @@
 //                 the low-rank form of irfft(rfft(cH) * g) - cH (only K ~ 6.4 s packed gains differ from 1)
 //   k_st_idwt<A>  one synthesis pass along axis A
 //   k_st_final    exp(r) - 1 per band, sigmoid blend, crop, float32 / uint16 store
+//
+// March route (dsx_plan_streaks_ex, DSX_STREAKS_MARCH): the bands go through the log-space chain of dsx.hip instead of
+// k_st_prep ... k_st_idwt; t comes from the same k_st_minmax / k_st_hist / k_st_otsu / k_st_fill.
+//   k_st_chainfill  what the chain's row filters read per virtual plane: mask threshold +inf on every level, cfg = band
+//   k_st_bands      the virtual input planes max(x, t) (2k) and min(x, t) (2k + 1), or x for a single band
+//   k_st_blend      (F - 2) w + (B - 2) (1 - w) of the chain's float32 planes, float32 / uint16 store
 #ifndef DSX_STREAKS_H
 #define DSX_STREAKS_H
 
@@ -369,6 +375,11 @@ __global__ __launch_bounds__(256) void k_st_rowmat(const float* __restrict__ X, 
   }
 }
 
+// w of the blend: the reference's foreground_fraction(x, t, crossover)
+__device__ __forceinline__ float st_weight(float x, float t, float inv_crossover) {
+  return 1.0f / (1.0f + expf(-(x - t) * inv_crossover));
+}
+
 // out[b][i][j], i < H, j < W: exp(r) - 1 per band (r: [P][Hp][Wp], band-major), blend, store
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void k_st_final(const TI* __restrict__ in, const float* __restrict__ r, int nb, int B,
@@ -386,7 +397,7 @@ __global__ __launch_bounds__(256) void k_st_final(const TI* __restrict__ in, con
     const float bg = expm1f(r[(size_t)b * pp + off]);
     const float fg = expm1f(r[((size_t)B + b) * pp + off]);
     const float x = pix(in, idx);
-    const float wf = 1.0f / (1.0f + expf(-(x - t[b]) * inv_crossover));
+    const float wf = st_weight(x, t[b], inv_crossover);
     res = fg * wf + bg * (1.0f - wf);
   }
   if (sizeof(TO) == 2) {
@@ -394,6 +405,84 @@ __global__ __launch_bounds__(256) void k_st_final(const TI* __restrict__ in, con
     out[idx] = (TO)(unsigned)c;
   } else {
     out[idx] = (TO)res;
+  }
+}
+
+// ---- march route ---------------------------------------------------------------------------------------------------
+// The virtual planes of real plane k are 2k (foreground band, cfg 0) and 2k + 1 (background band, cfg 1); a single band
+// has one virtual plane per real plane (cfg 0).  Planes are H x W with H and W even (no padding), so a plane holds a
+// multiple of 4 pixels: VEC = 4 moves 4 pixels per access where the caller's pointers allow it, VEC = 1 otherwise.
+template <typename T, int N>
+struct alignas(sizeof(T) * N) StVec {
+  T v[N];
+};
+
+__global__ __launch_bounds__(256) void k_st_chainfill(float* thr, int n_thr, int* cfg, int n_cfg, int bands) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_thr) thr[i] = INFINITY;
+  if (i < n_cfg) cfg[i] = bands == 2 ? (i & 1) : 0;
+}
+
+// grid (blocks, planes); v: [bands * planes][px]
+template <typename TI, typename TV, int VEC>
+__global__ __launch_bounds__(256) void k_st_bands(const TI* __restrict__ in, size_t px, int bands, const float* t,
+                                                  TV* __restrict__ v, unsigned* sticky) {
+  const int b = blockIdx.y;
+  const float tb = t[b];
+  const TI* p = in + (size_t)b * px;
+  TV* f = v + (size_t)bands * b * px;
+  TV* g = f + px;
+  const size_t step = (size_t)gridDim.x * blockDim.x * VEC;
+  bool bad = false;
+  for (size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * VEC; i < px; i += step) {
+    const StVec<TI, VEC> x = *(const StVec<TI, VEC>*)(p + i);
+    StVec<TV, VEC> hi, lo;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const float xv = (float)x.v[k];
+      // as k_st_prep: a float32 pixel without a finite log(1 + x) flags the context's host-mapped word
+      if (sizeof(TI) == 4 && !(xv > -1.0f && xv < INFINITY)) bad = true;
+      hi.v[k] = (TV)(bands == 2 ? fmaxf(xv, tb) : xv);
+      lo.v[k] = (TV)fminf(xv, tb);
+    }
+    *(StVec<TV, VEC>*)(f + i) = hi;
+    if (bands == 2) *(StVec<TV, VEC>*)(g + i) = lo;
+  }
+  if (bad && sticky != nullptr) *(volatile unsigned*)sticky = 1u;
+}
+
+// grid (blocks, planes); r: [bands * planes][px], the chain's exp(.) + 1 of every band, i.e. band + 2
+template <typename TI, typename TO, int VEC>
+__global__ __launch_bounds__(256) void k_st_blend(const TI* __restrict__ in, const float* __restrict__ r, size_t px,
+                                                  int bands, const float* t, float inv_crossover,
+                                                  TO* __restrict__ out) {
+  const int b = blockIdx.y;
+  const float tb = t[b];
+  const TI* p = in + (size_t)b * px;
+  const float* f = r + (size_t)bands * b * px;
+  const float* g = f + px;
+  TO* o = out + (size_t)b * px;
+  const size_t step = (size_t)gridDim.x * blockDim.x * VEC;
+  for (size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * VEC; i < px; i += step) {
+    const StVec<float, VEC> fv = *(const StVec<float, VEC>*)(f + i);
+    StVec<float, VEC> gv = fv;
+    StVec<TI, VEC> x = {};
+    if (bands == 2) {
+      gv = *(const StVec<float, VEC>*)(g + i);
+      x = *(const StVec<TI, VEC>*)(p + i);
+    }
+    StVec<TO, VEC> ov;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      float res = fv.v[k] - 2.0f;
+      if (bands == 2) {
+        const float wf = st_weight((float)x.v[k], tb, inv_crossover);
+        res = res * wf + (gv.v[k] - 2.0f) * (1.0f - wf);
+      }
+      if (sizeof(TO) == 2) ov.v[k] = (TO)(unsigned)fminf(fmaxf(res, 0.0f), 65535.0f);
+      else ov.v[k] = (TO)res;
+    }
+    *(StVec<TO, VEC>*)(o + i) = ov;
   }
 }
 

@@ -120,13 +120,19 @@ def read_filter_save(
     compression: Optional[int] = 1,
     output_format: Optional[str] = None,
     output_dtype: Optional[type] = None,
+    streaks: Optional[dict] = None,
 ):
     """One plane: read (3 tries), ``filter_stripes`` on the GPU, ``astype`` to the source dtype (or
-    ``output_dtype``), save (``destriper.py:113-215``)."""
+    ``output_dtype``), save (``destriper.py:113-215``).  ``streaks``: the dict of :func:`batch_filter`."""
+    streaks = _streaks_options(streaks, shadow_correction)
     raw_image = _read_with_retries(output_dir, input_path)
     if raw_image is None:
         return
     dtype = _target_dtype(raw_image.dtype, output_dtype)
+    if streaks is not None:
+        filtered_image = fl.filter_streaks(raw_image, **streaks)
+        _save_with_retries(output_path, filtered_image.astype(dtype), compression, output_format)
+        return
     filtered_image = fl.filter_stripes(
         image=raw_image,
         input_tile_path=input_path,
@@ -135,6 +141,17 @@ def read_filter_save(
         shadow_correction=shadow_correction,
     )
     _save_with_retries(output_path, filtered_image.astype(dtype), compression, output_format)
+
+
+def _streaks_options(streaks, shadow_correction):
+    """The checked ``streaks`` dict (``filtering.streaks_options``) or ``None``; the dual-band filter has no dark / flat
+    step, so it refuses a ``shadow_correction``."""
+    if streaks is None:
+        return None
+    streaks = fl.streaks_options(streaks)
+    if shadow_correction is not None:
+        raise ValueError("streaks: the dual-band filter has no dark / flat step; shadow_correction must be None")
+    return streaks
 
 
 def _read_filter_save(input_dict: dict):
@@ -189,11 +206,19 @@ def batch_filter(
     output_format: Optional[str] = None,
     output_dtype: Optional[type] = None,
     device: int = 0,
+    streaks: Optional[dict] = None,
 ):
     """Filter every image below ``input_path`` into the same tree under ``output_path``
     (``destriper.py:267-378``).  ``workers`` = I/O threads, ``chunks`` = planes per GPU batch
     (the reference's pool size and ``imap`` chunk size).  Returns the number of planes written.
+
+    ``streaks``: a dict ``{"sigma": (fg, bg), "level": 0, "wavelet": "db3", "crossover": 10, "threshold": -1,
+    "route": "auto"}`` (defaults as in ``filtering.filter_streaks``; unknown keys raise ``TypeError``) runs the dual-band
+    filter (``filtering.destripe_streaks_planes``) on every group of planes instead of the stripe filter; the two
+    parameter dicts are not read then and ``shadow_correction`` must be ``None`` (``ValueError``, before anything is
+    created).
     """
+    streaks = _streaks_options(streaks, shadow_correction)
     input_path, output_path = Path(input_path), Path(output_path)
     error_path = os.path.join(output_path, "destripe_log.txt")
     img_paths, outs = _prepare_tree(input_path, output_path)
@@ -221,16 +246,20 @@ def batch_filter(
                 # source dtype: for integer sources that is the clip-free truncation the uint16 epilogue does
                 want = _target_dtype(stack.dtype, output_dtype)
                 as_u16 = shaded or np.dtype(want) == np.uint16
-                res = fl.destripe_planes(
-                    stack,
-                    input_tile_path=str(paths[ks[0]]),
-                    no_cells_config=low_int_filt_params,
-                    cells_config=high_int_filt_params,
-                    shadow_correction=shadow_correction,
-                    out_dtype=np.uint16 if as_u16 else np.float32,
-                    max_batch=min(batch, 64),
-                    device=device,
-                )
+                if streaks is not None:
+                    res = fl.destripe_streaks_planes(stack, out_dtype=np.uint16 if as_u16 else np.float32,
+                                                     max_batch=min(batch, 64), device=device, **streaks)  # fmt: skip
+                else:
+                    res = fl.destripe_planes(
+                        stack,
+                        input_tile_path=str(paths[ks[0]]),
+                        no_cells_config=low_int_filt_params,
+                        cells_config=high_int_filt_params,
+                        shadow_correction=shadow_correction,
+                        out_dtype=np.uint16 if as_u16 else np.float32,
+                        max_batch=min(batch, 64),
+                        device=device,
+                    )
                 for j, k in enumerate(ks):
                     jobs.append((outs[start + k], res[j].astype(want, copy=False)))
             list(pool.map(lambda jo: _save_with_retries(jo[0], jo[1], compression, output_format), jobs))

@@ -6,6 +6,7 @@ constructor raises :class:`DsxError`.
 """
 
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -48,7 +49,7 @@ EXPORTED_SYMBOLS = [
     "dsx_malloc_host", "dsx_free_host", "dsx_memcpy_h2d_async", "dsx_memcpy_d2h_async",
     "dsx_stream_wait", "dsx_stream_sync", "dsx_event_record", "dsx_event_sync",
     "dsx_io_read_chunks", "dsx_io_write_chunks", "dsx_io_write_chunks_blosc", "dsx_blosc_decode", "dsx_blosc_encode",
-    "dsx_png_unfilter", "dsx_plan_streaks", "dsx_get_streaks_threshold",
+    "dsx_png_unfilter", "dsx_plan_streaks", "dsx_plan_streaks_ex", "dsx_get_streaks_threshold",
     "dsx_blosc_encode_device", "dsx_blosc_encode_ref", "dsx_blosc_encode_device_ex", "dsx_blosc_encode_ref_ex",
     "dsx_io_read_frames", "dsx_io_read_frames_ex", "dsx_blosc_decode_device", "dsx_blosc_decode_ref",
     "dsx_io_read_zlib_chunks", "dsx_io_write_chunks_blosc_lz4", "dsx_blosc_encode_lz4",
@@ -199,6 +200,7 @@ def load_library(path=None):
     lib.dsx_blosc_encode_lz4.argtypes = [vp, ctypes.c_size_t, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     lib.dsx_png_unfilter.argtypes = [vp, i32, i32, i32]
     lib.dsx_plan_streaks.argtypes = [vp, i32, i32, i32, ctypes.POINTER(_StreaksCfg)]
+    lib.dsx_plan_streaks_ex.argtypes = [vp, i32, i32, i32, ctypes.POINTER(_StreaksCfg), i32]
     lib.dsx_get_streaks_threshold.argtypes = [vp, i32, f32p]
     lib.dsx_blosc_decode.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t]
     lib.dsx_blosc_encode.argtypes = [vp, ctypes.c_size_t, i32, i32, i32, vp, ctypes.c_size_t,
@@ -228,6 +230,38 @@ def load_library(path=None):
     if path is None:
         _lib = lib
     return lib
+
+
+STREAKS_ROUTES = {"generic": 0, "march": 1}  # DSX_STREAKS_GENERIC, DSX_STREAKS_MARCH
+# What "auto" resolves to where the march route applies.  The march route's rate has not been measured, so "auto" is the
+# generic route everywhere; it becomes "march" here once a same-session record (tools/bench_streaks.py with both
+# routes, README "filter_streaks") shows march ahead.  Elsewhere "auto" is the generic route in any case.
+AUTO_ROUTE = "generic"
+
+
+def _db3_max_level(height, width):
+    def one(n):  # pywt.dwt_max_level(n, 6)
+        return 0 if n < 5 else max(0, int(math.floor(math.log2(n // 5))))
+
+    return min(one(int(height)), one(int(width)))
+
+
+def streaks_route(route, height, width, wavelet="db3", level=0):
+    """The route a streaks plan takes: ``"auto"`` resolved, ``ValueError`` for a name that is none of ``generic`` /
+    ``march`` / ``auto`` and for ``"march"`` where it does not apply (it takes db3, even height and width and a
+    ``level`` up to the maximum level)."""
+    if route not in ("generic", "march", "auto"):
+        raise ValueError("route must be 'generic', 'march' or 'auto', not {!r}".format(route))
+    if route == "generic":
+        return route
+    applies = (_wavelet_key({"wavelet": wavelet}) == "db3" and int(height) % 2 == 0 and int(width) % 2 == 0
+               and int(level or 0) <= _db3_max_level(height, width))  # fmt: skip
+    if route == "march":
+        if not applies:
+            raise ValueError("route 'march' takes the db3 wavelet, planes of even height and width and levels up to "
+                             "the maximum level only")  # fmt: skip
+        return route
+    return AUTO_ROUTE if applies else "generic"
 
 
 def _wavelet_key(cfg):
@@ -321,6 +355,7 @@ class DestripeEngine:
         self._ctx = ctx
         self.device = int(device)
         self.info = None
+        self.streaks_route = None  # route of the current plan when it is a streaks plan
 
     # -- plumbing --------------------------------------------------------------------------------
     def _check(self, rc):
@@ -392,12 +427,17 @@ class DestripeEngine:
             info = call(flat.ctypes.data_as(ctypes.c_void_p), dark.ctypes.data_as(ctypes.c_void_p),
                         dark.shape[0], dark.shape[1])  # fmt: skip
         self.info = info
+        self.streaks_route = None
         return info
 
     def plan_streaks(self, height, width, sigma_fg, sigma_bg, wavelet="db3", level=0, crossover=10.0,
-                     threshold=None, max_batch=32):  # fmt: skip
-        """Plan the dual-band filter (``dsx_plan_streaks``); ``threshold=None``: Otsu per plane.  Replaces any plan of
-        this engine; :meth:`run` / :meth:`run_device` then return ``[n, height, width]``."""
+                     threshold=None, max_batch=32, route="generic"):  # fmt: skip
+        """Plan the dual-band filter (``dsx_plan_streaks_ex``); ``threshold=None``: Otsu per plane.  Replaces any plan
+        of this engine; :meth:`run` / :meth:`run_device` then return ``[n, height, width]``.  ``route``: ``"generic"``
+        (the per-band kernels of the filter, any wavelet and plane), ``"march"`` (the bands run through the log-space
+        db3 chain; db3, even planes and levels up to the maximum only, ``ValueError`` elsewhere) or ``"auto"``
+        (``AUTO_ROUTE`` where march applies -- generic until a measurement shows march ahead -- generic elsewhere)."""
+        route = streaks_route(route, height, width, wavelet, level)
         key = _wavelet_key({"wavelet": wavelet})
         wid = DSX_WAVELET_DB3 if key == "db3" else DSX_WAVELET_BANK
         if wid == DSX_WAVELET_BANK:
@@ -409,7 +449,8 @@ class DestripeEngine:
             self._check(rc)
         cfg = _StreaksCfg(wid, int(level or 0), float(sigma_fg), float(sigma_bg), float(crossover),
                           1 if threshold is None else 0, 0.0 if threshold is None else float(threshold))  # fmt: skip
-        rc = self._lib.dsx_plan_streaks(self._ctx, int(height), int(width), int(max_batch), ctypes.byref(cfg))
+        rc = self._lib.dsx_plan_streaks_ex(self._ctx, int(height), int(width), int(max_batch), ctypes.byref(cfg),
+                                           STREAKS_ROUTES[route])  # fmt: skip
         if rc == -1:
             raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
         self._check(rc)
@@ -417,6 +458,7 @@ class DestripeEngine:
         info.height, info.width, info.out_height, info.out_width = int(height), int(width), int(height), int(width)
         info.max_batch = int(max_batch)
         self.info = info
+        self.streaks_route = route
         return info
 
     def streaks_threshold(self, plane):

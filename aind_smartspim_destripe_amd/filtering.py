@@ -322,10 +322,12 @@ def _streaks_params(sigma, level, wavelet, crossover, threshold):
     return sigma_fg, sigma_bg, 0 if level is None else int(level)
 
 
-def _streaks_engine(shape, sigma_fg, sigma_bg, level, wavelet, crossover, threshold, max_batch, device):
+def _streaks_engine(shape, sigma_fg, sigma_bg, level, wavelet, crossover, threshold, max_batch, device,
+                    route="generic"):  # fmt: skip
+    """Planned streaks engine (cached per process and device); ``route`` is resolved: ``generic`` or ``march``."""
     fixed = None if float(threshold) == -1 else float(threshold)
     key = (device, "streaks", tuple(shape), sigma_fg, sigma_bg, level, _engine._wavelet_key({"wavelet": wavelet}),
-           float(crossover), fixed, int(max_batch))  # fmt: skip
+           float(crossover), fixed, int(max_batch), route)  # fmt: skip
     eng = _ENGINES.get(key)
     if eng is not None:
         _ENGINES.move_to_end(key)
@@ -335,9 +337,32 @@ def _streaks_engine(shape, sigma_fg, sigma_bg, level, wavelet, crossover, thresh
         old[0].close()
     e = _engine.DestripeEngine(device)
     e.plan_streaks(shape[0], shape[1], sigma_fg, sigma_bg, wavelet=wavelet, level=level, crossover=crossover,
-                   threshold=fixed, max_batch=max_batch)  # fmt: skip
+                   threshold=fixed, max_batch=max_batch, route=route)  # fmt: skip
     _ENGINES[key] = (e, None, None)
     return e
+
+
+STREAKS_DEFAULTS = {"sigma": None, "level": 0, "wavelet": "db3", "crossover": 10, "threshold": -1, "route": "auto"}
+
+
+def streaks_options(streaks):
+    """The ``streaks=`` dict of the pipelines (``destripe_zarr_store``, ``destripe_zarr``, ``batch_filter``), checked
+    and completed with the defaults of :func:`filter_streaks` (``route``: ``"auto"``): ``TypeError`` for an unknown key
+    or a missing ``sigma`` pair, ``ValueError`` for a bad value.  No device call."""
+    if not isinstance(streaks, dict):
+        raise TypeError("streaks must be a dict {'sigma': (fg, bg), ...}")
+    unknown = sorted(set(streaks) - set(STREAKS_DEFAULTS))
+    if unknown:
+        raise TypeError("streaks got unexpected keys: {}".format(unknown))
+    opt = dict(STREAKS_DEFAULTS, **streaks)
+    if opt["sigma"] is None:
+        raise TypeError("streaks needs 'sigma': (sigma_fg, sigma_bg)")
+    if opt["route"] not in ("generic", "march", "auto"):
+        raise ValueError("route must be 'generic', 'march' or 'auto', not {!r}".format(opt["route"]))
+    sigma_fg, sigma_bg, opt["level"] = _streaks_params(opt["sigma"], opt["level"], opt["wavelet"], opt["crossover"],
+                                                       opt["threshold"])  # fmt: skip
+    opt["sigma"] = (sigma_fg, sigma_bg)
+    return opt
 
 
 def _warn_streaks_level(shape, level, wavelet):
@@ -349,7 +374,7 @@ def _warn_streaks_level(shape, level, wavelet):
         )
 
 
-def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, threshold=-1, **params):
+def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, threshold=-1, route="generic", **params):
     """The stripe filter under its upstream (pystripe) name, in two forms.
 
     * Scalar ``sigma``: ``log_space_fft_filtering(image, sigma=sigma, level=level, wavelet=wavelet, **params)``,
@@ -359,11 +384,16 @@ def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, thresh
       split into ``min(x, t)`` and ``max(x, t)``, each band goes through log(1 + z), ``wavedec2`` (``level`` 0 / None
       = the maximum depth), a packed-index notch on every cH row (``s = cH.shape[0] * sigma / H'``), ``waverec2`` and
       exp(r) - 1, and the bands are blended with ``foreground_fraction(x, t, crossover)``.  Equal sigmas run one band
-      on the unclipped plane.  Returns float64 ``[H, W]`` (computed in float32 on the device).
+      on the unclipped plane.  Returns float64 ``[H, W]`` (computed in float32 on the device).  ``route``:
+      ``"generic"`` (the default: per-band analysis / synthesis kernels, any wavelet and plane), ``"march"`` (the bands
+      run through the marching db3 kernels and the FFT row filter of the log-space engine -- the same filter, for
+      db3, planes of even height and width and levels up to the maximum; ``ValueError`` elsewhere) or ``"auto"``
+      (``engine.AUTO_ROUTE`` where march applies: the generic route until a same-session measurement shows march
+      ahead; generic elsewhere).
     """
     if not isinstance(sigma, (str, bytes)) and np.ndim(sigma) == 0:
-        if "crossover" in params or crossover != 10 or threshold != -1:
-            raise TypeError("crossover / threshold belong to the dual-band form: pass sigma=(sigma_fg, sigma_bg)")
+        if "crossover" in params or crossover != 10 or threshold != -1 or route != "generic":
+            raise TypeError("crossover / threshold / route belong to the dual-band form: pass sigma=(sigma_fg, sigma_bg)")
         return log_space_fft_filtering(input_image=image, sigma=sigma, level=level, wavelet=wavelet, **params)
     if params:
         raise TypeError("filter_streaks got unexpected arguments: {}".format(sorted(params)))
@@ -372,21 +402,23 @@ def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, thresh
     if image.ndim != 2 or image.size == 0:
         raise ValueError("filter_streaks takes one non-empty 2-D plane; use destripe_streaks_planes for a stack")
     out = destripe_streaks_planes(image[None], (sigma_fg, sigma_bg), level=level, wavelet=wavelet, crossover=crossover,
-                                  threshold=threshold, out_dtype=np.float32, max_batch=1)  # fmt: skip
+                                  threshold=threshold, out_dtype=np.float32, max_batch=1, route=route)  # fmt: skip
     return out[0].astype(np.float64)
 
 
 def destripe_streaks_planes(planes, sigma, level=0, wavelet="db3", crossover=10, threshold=-1, out_dtype=np.uint16,
-                            max_batch=32, device=0, return_threshold=False):  # fmt: skip
+                            max_batch=32, device=0, return_threshold=False, route="generic"):  # fmt: skip
     """Batched dual-band :func:`filter_streaks` over ``planes[n, H, W]`` (uint16 or float32), every plane on its own
     (with ``threshold=-1`` each takes its own Otsu ``t``).  ``out_dtype`` uint16: clip to [0, 65535] and truncate, as
-    the Zarr path stores; float32: the filter's value.  ``return_threshold``: also the per-plane ``t`` (float64)."""
+    the Zarr path stores; float32: the filter's value.  ``return_threshold``: also the per-plane ``t`` (float64).
+    ``route``: as in :func:`filter_streaks`."""
     sigma_fg, sigma_bg, level = _streaks_params(sigma, level, wavelet, crossover, threshold)
     planes = np.asarray(planes)
     if planes.ndim != 3:
         raise ValueError("planes must be [n, H, W]")
     if planes.shape[1] == 0 or planes.shape[2] == 0:
         raise ValueError("planes must not be empty")
+    route = _engine.streaks_route(route, planes.shape[1], planes.shape[2], wavelet, level)
     if planes.dtype != np.uint16 and planes.dtype != np.float32:
         planes = np.stack([_as_plane_dtype(p) for p in planes]) if len(planes) else planes.astype(np.float32)
         if planes.dtype not in (np.uint16, np.float32):
@@ -394,7 +426,8 @@ def destripe_streaks_planes(planes, sigma, level=0, wavelet="db3", crossover=10,
     _warn_streaks_level(planes.shape[1:], level, wavelet)
     n = planes.shape[0]
     max_batch = max(1, min(int(max_batch), max(n, 1)))
-    eng = _streaks_engine(planes.shape[1:], sigma_fg, sigma_bg, level, wavelet, crossover, threshold, max_batch, device)
+    eng = _streaks_engine(planes.shape[1:], sigma_fg, sigma_bg, level, wavelet, crossover, threshold, max_batch, device,
+                          route)  # fmt: skip
     out = np.empty(planes.shape, dtype=out_dtype)
     ts = np.zeros(n, dtype=np.float64)
     for start in range(0, n, max_batch):

@@ -194,8 +194,12 @@ def execute_worker(
     logger: logging.Logger,
     device: int = 0,
     max_batch: int = 64,
+    streaks=None,
 ):
     """``zarr_destriper.py:253-336`` with the plane loop (``:319-327``) as one batched GPU call.
+
+    ``streaks`` (the checked dict of ``fl.streaks_options``, ``route`` resolved): the planes go through the dual-band
+    filter (``fl.destripe_streaks_planes``) instead; the configs and ``shadow_correction`` are not read then.
 
     ``data``: float32 (or uint16) ``[1, Z, Y, X]``; every plane goes through ``filter_stripes`` semantics
     with ``microscope_high_int=2500`` (``:326``); the result is assigned to
@@ -220,17 +224,20 @@ def execute_worker(
 
     input_tile_path = dataset_name.replace(".zarr", "")
     planes = data if data.dtype in (np.uint16, np.float32) else data.astype(np.float32)
-    filtered = fl.destripe_planes(
-        planes,
-        input_tile_path=input_tile_path,
-        no_cells_config=no_cells_config,
-        cells_config=cells_config,
-        shadow_correction=shadow_correction,
-        microscope_high_int=2500,
-        out_dtype=np.uint16,
-        max_batch=max_batch,
-        device=device,
-    )
+    if streaks is not None:
+        filtered = fl.destripe_streaks_planes(planes, out_dtype=np.uint16, max_batch=max_batch, device=device, **streaks)
+    else:
+        filtered = fl.destripe_planes(
+            planes,
+            input_tile_path=input_tile_path,
+            no_cells_config=no_cells_config,
+            cells_config=cells_config,
+            shadow_correction=shadow_correction,
+            microscope_high_int=2500,
+            out_dtype=np.uint16,
+            max_batch=max_batch,
+            device=device,
+        )
     if filtered.shape != data.shape:
         # odd planes grow by one row / column (waverec2); the reference's assignment into
         # np.zeros_like(data) would raise here -- keep the part that maps onto the input grid
@@ -768,6 +775,7 @@ def destripe_zarr_store(
     device_decode=False,
     pyramid_group=None,
     n_levels=1,
+    streaks=None,
 ):
     """Chunk map of ``destripe_zarr`` (``zarr_destriper.py:909-1211``) over a Zarr-v2 directory store -- the engine-level
     form (explicit configs and ``shadow_correction``); :func:`destripe_zarr` is the entry point with the reference's
@@ -832,10 +840,23 @@ def destripe_zarr_store(
     Needs the device re-tiling path and z blocks that hold whole 2 x 2 x 2 windows of every level and fill whole chunk
     rows; anything else raises ``ValueError``.  Works with ``device_codec`` / ``device_decode`` on or off and with raw,
     zlib and Blosc outputs.
+
+    ``streaks``: a dict ``{"sigma": (fg, bg), "level": 0, "wavelet": "db3", "crossover": 10, "threshold": -1,
+    "route": "auto"}`` (defaults as in ``filtering.filter_streaks``; an unknown key raises ``TypeError``) runs the
+    dual-band filter on every plane instead of the stripe filter: the device path plans a streaks engine, the host path
+    (``device_retile=False`` or a geometry that is not chunk-aligned) calls ``filtering.destripe_streaks_planes``;
+    everything around the filter -- re-tiling, codecs, pyramid, ranks -- is the same.  ``cells_config`` /
+    ``no_cells_config`` may be ``None`` then; the dual-band filter has no dark / flat step, so a ``shadow_correction``
+    raises ``ValueError`` before anything is created.  ``LAST_RUN["filter"]`` is ``"stripes"`` or ``"streaks"``,
+    ``LAST_RUN["streaks_route"]`` the route taken (``None`` for the stripe filter).
     """
     from . import pyramid
 
     logger = logger or logging.getLogger("dsx.zarr")
+    if streaks is not None:
+        streaks = fl.streaks_options(streaks)
+        if shadow_correction is not None:
+            raise ValueError("streaks: the dual-band filter has no dark / flat step; shadow_correction must be None")
     codec_mode = output_codec_mode(device_codec, compressor)  # (a wrong mode fails before anything is created)
     device_codec = codec_mode is not None
     decode_mode = device_decode_mode(device_decode)
@@ -845,6 +866,9 @@ def destripe_zarr_store(
     zyx = src.shape[-3:]
     if prediction_chunksize[1] < zyx[1] or prediction_chunksize[2] < zyx[2]:
         raise ValueError("blocks must cover whole planes: the stripe filter is a per-plane operation")
+    if streaks is not None:  # ("march" on an odd plane or another wavelet fails here, before anything is created)
+        streaks["route"] = engine_mod.streaks_route(streaks["route"], zyx[1], zyx[2], streaks["wavelet"],
+                                                    streaks["level"])  # fmt: skip
     out_shape = (1,) * (5 - len(src.shape)) + tuple(src.shape)
     out_chunks = tuple(output_chunks)[-len(out_shape):]
     fused = pyramid_group is not None and int(n_levels) > 1
@@ -876,7 +900,9 @@ def destripe_zarr_store(
     else:
         z0, z1 = z_shard(zyx[0], world_size, rank, z_chunk=output_chunks[-3])
     dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device
-    LAST_RUN.update(rank=rank, world_size=world_size, z_range=(z0, z1), io_threads=int(io_threads), device=dev)
+    LAST_RUN.update(rank=rank, world_size=world_size, z_range=(z0, z1), io_threads=int(io_threads), device=dev,
+                    filter="stripes" if streaks is None else "streaks",
+                    streaks_route=None if streaks is None else streaks["route"])  # fmt: skip
     # dataset_name of the reference = the tile folder (X_..._Y_....zarr), also when level "0" is opened
     name = tile_name or os.path.basename(str(dataset_path).rstrip("/"))
     n_planes, t0 = 0, time.perf_counter()
@@ -905,9 +931,13 @@ def destripe_zarr_store(
     LAST_RUN.update(device_codec=device_codec, device_codec_mode=codec_mode, device_decode=bool(device_decode),
                     device_decode_mode=decode_mode, decode_routes=None, fused_pyramid=bool(levels), pyramid_levels=[lv.level for lv in levels])  # fmt: skip
     if can and device_retile is not False:
-        flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
-        eng = fl.get_engine(zyx[1:], cells_config, no_cells_config, 2500, flatfield, darkfield,
-                            max_batch=min(block_z, 64), device=dev)  # fmt: skip
+        if streaks is not None:
+            eng = fl._streaks_engine(zyx[1:], *streaks["sigma"], streaks["level"], streaks["wavelet"], streaks["crossover"],
+                                     streaks["threshold"], min(block_z, 64), dev, streaks["route"])  # fmt: skip
+        else:
+            flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
+            eng = fl.get_engine(zyx[1:], cells_config, no_cells_config, 2500, flatfield, darkfield,
+                                max_batch=min(block_z, 64), device=dev)  # fmt: skip
         blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, "runs" if codec_mode == "runs" else device_codec,
                                 device_decode, (levels, pyr_arrays) if levels else None)  # fmt: skip
         try:
@@ -927,7 +957,7 @@ def destripe_zarr_store(
         block = src[lead + sc]
         data = block[np.newaxis].astype(np.float32) if block.dtype != np.uint16 else block[np.newaxis]
         execute_worker(data, sc, internal, cells_config, no_cells_config, (0, 0, 0), dst, shadow_correction,
-                       name, logger, device=dev)  # fmt: skip
+                       name, logger, device=dev, streaks=streaks)  # fmt: skip
         n_planes += block.shape[0]
     dt = time.perf_counter() - t0
     logger.info("rank %d: %d planes z[%d:%d) in %.2f s", rank, n_planes, z0, z1, dt)
@@ -1086,6 +1116,7 @@ def destripe_zarr(
     device_decode=False,
     fused_pyramid=False,
     pipelined_pyramid=False,
+    streaks=None,
 ):
     """``destripe_zarr`` of the reference (``zarr_destriper.py:909-1211``) with its 14 parameters, on the GPU chunk map.
 
@@ -1116,15 +1147,25 @@ def destripe_zarr(
     :func:`compute_multiscale` on rank 0 afterwards; same stores; z shards of ``output z chunk << (levels - 1)`` planes),
     ``pipelined_pyramid`` (rank 0's :func:`compute_multiscale` call runs with ``pipelined=True``, this call's
     ``device_codec`` and ``io_threads``, and this call's ``device_decode`` when the output is Blosc -- level 0 is this
-    run's own output; same stores; ``ValueError`` together with ``fused_pyramid``).
+    run's own output; same stores; ``ValueError`` together with ``fused_pyramid``), ``streaks`` (the dict of
+    :func:`destripe_zarr_store`: the dual-band filter instead of the stripe filter; ``parameters`` need no configs then,
+    and a derivatives folder that exists or a ``flatfield`` raises ``ValueError`` before anything is created -- that
+    filter has no dark / flat step).
     Returns ``(planes processed by this rank, seconds)``.
     """
     output_codec_mode(device_codec, compressor)  # (a wrong string or mode fails before anything is written)
     device_decode_mode(device_decode)
     if fused_pyramid and pipelined_pyramid:
         raise ValueError("fused_pyramid and pipelined_pyramid are two routes to the same pyramid: choose one")
-    no_cells_config = parameters["no_cells_config"]
-    cells_config = parameters["cells_config"]
+    if streaks is not None:
+        streaks = fl.streaks_options(streaks)
+        if flatfield is not None or os.path.exists(Path(derivatives_path)):
+            raise ValueError("streaks: the dual-band filter has no dark / flat step; give no flatfield and no "
+                             "derivatives folder")  # fmt: skip
+        no_cells_config, cells_config = parameters.get("no_cells_config"), parameters.get("cells_config")
+    else:
+        no_cells_config = parameters["no_cells_config"]
+        cells_config = parameters["cells_config"]
     co_cpus = _cpu_limit()
     if n_workers > co_cpus:
         raise ValueError(f"Provided workers {n_workers} > current workers {co_cpus}")
@@ -1145,7 +1186,9 @@ def destripe_zarr(
         return {"darkfield": sc["darkfield"], "microscope_flats": None if sc["retrospective"] else sc["flatfield"],
                 "tile_config": sc["tile_config"]}  # fmt: skip
 
-    if _group_broadcasts(group, world_size):
+    if streaks is not None:
+        shadow_correction = {"flatfield": None, "darkfield": None}
+    elif _group_broadcasts(group, world_size):
         tile_config = {}
 
         def read_planes():
@@ -1199,6 +1242,7 @@ def destripe_zarr(
         device_decode=device_decode,
         pyramid_group=str(output_destriped_zarr) if fused_pyramid else None,
         n_levels=n_levels if fused_pyramid else 1,
+        streaks=streaks,
     )
     if group is not None and world_size > 1:
         group.barrier()  # level 0 of this tile is complete on every rank: the pyramid may read it

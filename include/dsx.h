@@ -391,6 +391,18 @@ typedef struct dsx_streaks_cfg {
   float threshold;
 } dsx_streaks_cfg;
 int dsx_plan_streaks(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_streaks_cfg* cfg);
+/* The same plan with a choice of kernels.  DSX_STREAKS_GENERIC: dsx_plan_streaks, byte for byte.  DSX_STREAKS_MARCH:
+ * the bands run through the marching db3 kernels and the FFT row filter of the log-space engine.  With an empty mask
+ * log_space_fft_filtering(z, sigma = s min(H, W) / H) - 2 IS band(z, s), so per cohort: t as above (same kernels,
+ * same t), then one kernel writes the bands max(x, t) / min(x, t) as virtual input planes 2k / 2k + 1 (uint16 where the
+ * planes are uint16 and t is integral, else float32; one plane per real plane for equal sigmas), the log-space chain
+ * of dsx_plan runs over them with cfg = plane index & 1 and every level's mask threshold +inf (no histogram, no Otsu
+ * per level), and one kernel blends (F - 2) w + (B - 2) (1 - w), crops and stores.  For DSX_WAVELET_DB3, even
+ * height and width, a level up to the maximum level, and every geometry dsx_plan accepts; anything else: DSX_EINVAL (DSX_ELIMIT where dsx_plan
+ * says so).  Any other route: DSX_EINVAL. */
+#define DSX_STREAKS_GENERIC 0
+#define DSX_STREAKS_MARCH 1
+int dsx_plan_streaks_ex(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_streaks_cfg* cfg, int route);
 /* t of a plane of the last cohort of the last run (a bin centre for float32 planes, an integer for uint16). */
 int dsx_get_streaks_threshold(dsx_ctx* ctx, int plane, float* threshold);
 

@@ -3,6 +3,7 @@ planes in, uint16 planes out, db3, maximum level, Otsu per plane.  Prints one JS
 16 777 216 bytes per 2048 x 2048 plane (uint16 in + uint16 out, read and written once) against 8 TB/s.
 
     python tools/bench_streaks.py [--planes 256] [--steps 5] [--warmup 2] [--size 2048] [--max-batch 32]
+                                  [--route generic|march|auto]
 """
 
 import argparse
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("--max-batch", type=int, default=32)
     ap.add_argument("--sigma", type=float, nargs=2, default=(64.0, 128.0))
     ap.add_argument("--crossover", type=float, default=10.0)
+    ap.add_argument("--route", default="generic", choices=("generic", "march", "auto"))
     args = ap.parse_args()
     n, S = args.planes, args.size
     rng = np.random.default_rng(0)
@@ -37,7 +39,7 @@ def main():
     block = np.clip(block, 0, 65535).astype(np.uint16)
     eng = engine.DestripeEngine(0)
     eng.plan_streaks(S, S, args.sigma[0], args.sigma[1], wavelet="db3", level=0, crossover=args.crossover,
-                     threshold=None, max_batch=args.max_batch)  # fmt: skip
+                     threshold=None, max_batch=args.max_batch, route=args.route)  # fmt: skip
     plane_bytes = S * S * 2
     d_in = eng.alloc(plane_bytes * n)
     d_out = eng.alloc(plane_bytes * n)
@@ -63,6 +65,7 @@ def main():
                                                                                  args.crossover),
         "value": round(rate, 2),
         "unit": "planes/s",
+        "route": eng.streaks_route,
         "planes": n,
         "max_batch": args.max_batch,
         "step_seconds": [round(t, 6) for t in times],

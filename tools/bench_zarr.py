@@ -6,6 +6,7 @@ download) into another store.  Prints one JSON line; the roofline of this path i
 
     bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode|device-decode-any|device-decode-all]
                   [lz4|blosc-zlib|blosc-blosclz|plain-zlib] [pyramid|fused-pyramid|pipelined-pyramid] [lz4-out] [read-back]
+                  [streaks|streaks-generic|streaks-march]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
 line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
@@ -26,6 +27,10 @@ the device LZ4 encoder (csrc/dsx_lz4_enc.h; the same files either way).  The hos
 comparison are then LZ4 frames too.
 `read-back` (Blosc only): after the timed pass the written store is the input of one more pass with device_decode="any"
 (into a Blosc-zstd store, device_codec="runs"); the line reports its seconds, read stage time and decode routes as "read_back".
+`streaks`: the dual-band filter (destripe_zarr_store(streaks={"sigma": (64, 128), "route": "auto"})) instead of the stripe
+filter ("auto" is the generic route until the march route's rate is on record, engine.AUTO_ROUTE); `streaks-generic` /
+`streaks-march` name the route.  The picked planes are then held to destripe_streaks_planes of
+the same route, bit for bit (no CPU oracle pass).
 `pyramid`: after the timed level-0 pass, compute_multiscale(n_levels=3) on the store is timed too (the two-pass route);
 `fused-pyramid`: level 0 and levels 1-2 in one destripe_zarr_store call (pyramid_group / n_levels);
 `pipelined-pyramid`: level 0 is timed as without a pyramid word, then compute_multiscale(pipelined=True, n_levels=3) with the
@@ -50,6 +55,8 @@ recode = ([w for w in ("lz4", "blosc-zlib", "blosc-blosclz", "plain-zlib") if w 
 lz4_input = recode is not None  # (any recoded input store)
 two_pass, fused, pipelined = ("pyramid" in sys.argv[3:], "fused-pyramid" in sys.argv[3:], "pipelined-pyramid" in sys.argv[3:])
 lz4_out, read_back = "lz4-out" in sys.argv[3:], "read-back" in sys.argv[3:]
+streaks = ([{"sigma": (64.0, 128.0), "route": r} for w, r in (("streaks", "auto"), ("streaks-generic", "generic"),
+                                                               ("streaks-march", "march")) if w in sys.argv[3:]] + [None])[0]
 if (lz4_out or read_back) and codec != "blosc":
     sys.exit("lz4-out / read-back: a Blosc store")
 out_codec = {"id": "blosc", "cname": "lz4", "clevel": 5, "shuffle": 1, "blocksize": 0} if lz4_out else codec
@@ -102,7 +109,7 @@ try:
             planes, dt = zd.destripe_zarr_store(os.path.join(root, "in.zarr"), level0, synth.CELLS_CONFIG,
                                           synth.NO_CELLS_CONFIG, None, prediction_chunksize=(64, H, W),
                                           output_chunks=(1, 1, 64, 128, 128), device=0, device_retile=True, io_threads=16, compressor=out_codec,
-                                          device_codec=device_codec, device_decode=device_decode, **kw)
+                                          device_codec=device_codec, device_decode=device_decode, streaks=streaks, **kw)
             res[name] = {"planes": planes, "seconds": round(time.perf_counter() - t0, 3)}
     timing = dict(zd._BLOCKS["blocks"][1].timing)  # the timed (second) pass
     decode = {"decode_routes": zd.LAST_RUN.get("decode_routes")}
@@ -187,12 +194,16 @@ try:
         for z in stream_part_picks(64, z0, z1):
             plane_in = src[0, 0, z]
             got = out[0, 0, z]
-            alone = fl.destripe_planes(plane_in[None], "t", synth.NO_CELLS_CONFIG, synth.CELLS_CONFIG, None, 2500,
-                                       out_dtype=np.uint16, max_batch=1)[0]
+            if streaks is not None:
+                alone = fl.destripe_streaks_planes(plane_in[None], streaks["sigma"], route=zd.LAST_RUN["streaks_route"],
+                                                   out_dtype=np.uint16, max_batch=1)[0]
+            else:
+                alone = fl.destripe_planes(plane_in[None], "t", synth.NO_CELLS_CONFIG, synth.CELLS_CONFIG, None, 2500,
+                                           out_dtype=np.uint16, max_batch=1)[0]
             if not np.array_equal(alone, got):
                 verified = False
             checked.append(int(z))
-            if b == 0:
+            if b == 0 and streaks is None:
                 try:
                     u16_plane_against_oracle(got, plane_in, "t", None, ("bench_zarr", z))
                     oracle_checked.append(int(z))
@@ -200,12 +211,14 @@ try:
                     verified = False
                     print("oracle mismatch", e, file=sys.stderr)
     label = (codec or "raw") + (", {} input".format("LZ4" if recode == "lz4" else recode) if lz4_input else "") + (", LZ4 output" if lz4_out else "") + (", encoded on the device" + (" with run matches" if device_codec == "runs" else "") if device_codec else "") + (", decoded on the device" + (" ({})".format(device_decode) if isinstance(device_decode, str) else "") if device_decode else "")
+    label += ", dual-band filter ({} route)".format(zd.LAST_RUN["streaks_route"]) if streaks is not None else ""
     label += ", pyramid fused" if fused else ""  # (a stand-alone pyramid, slab or pipelined, is not part of the metric)
     print(json.dumps({"metric": "2048x2048 uint16 slices/s, Zarr store to Zarr store ({} chunks, tmpfs)".format(label), "value": round(v, 1),
                       "planes": n, "seconds": res["overlapped"]["seconds"], "store_make_s": round(t_make, 1),
                       "roofline": {"bound": "host link", "peak_planes_per_s": 3750, "frac": round(v / 3750.0, 3)},
                       "read_s": round(timing["read_s"], 3), "write_s": round(timing["write_s"], 3), "host_link": link,
-                      "plane0_checksum": chk, "verified": verified, **decode, **sizes, **({"pyramid": pyr} if pyr else {}),
+                      "plane0_checksum": chk, "verified": verified,
+                      "filter": zd.LAST_RUN.get("filter"), "streaks_route": zd.LAST_RUN.get("streaks_route"), **decode, **sizes, **({"pyramid": pyr} if pyr else {}),
                       "verification": {"planes_bit_identical_to_single_plane_runs": checked,
                                        "planes_against_the_cpu_oracle": oracle_checked, "blocks": blocks}}))
     if not verified or not pyr.get("verified", True):
