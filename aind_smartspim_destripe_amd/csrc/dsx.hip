@@ -2398,7 +2398,7 @@ int dsx_blosc_decode_ref(const void* packed, size_t packed_bytes, const void* ta
       continue;
     }
     tmp.resize(k.dst_len);
-    status[i] = z::run_task_host_all(*work, k, (const uint8_t*)packed, (uint8_t*)out, tmp.data());
+    status[i] = z::run_task_host(*work, k, (const uint8_t*)packed, (uint8_t*)out, tmp.data());
   }
   delete work;
   return DSX_OK;

@@ -1,8 +1,8 @@
-// dsx_inflate.h -- the last two inner codecs of c-blosc 1.21 for the device decoder (DSX_ZDEC_ALL): zlib streams
-// (DEFLATE, RFC 1950 / 1951; also the chunks of a plain-zlib Zarr store) and blosclz.  Shared by the host reference
-// (dsx_blosc_decode_ref) and the device kernel (dsx_zdec_kernels.h), like dsx_lz4_dec.h: plain C++ with no STL, no
-// allocation and no library call; g++ builds it for the CPU tests (tests/host/inflate_dec_check.cpp, also under ASan /
-// UBSan).
+// dsx_inflate.h -- zlib streams (DEFLATE, RFC 1950 / 1951; also the chunks of a plain-zlib Zarr store) and blosclz
+// streams for the Blosc block decoder (task kinds kTaskZlib and kTaskBlosclz of dsx_zdec_task.h).  Shared by the host
+// reference (dsx_blosc_decode_ref) and the device kernel (dsx_zdec_kernels.h), like dsx_lz4_dec.h: plain C++ with no
+// STL, no allocation and no library call; g++ builds it for the CPU tests (tests/host/zdec_task_check.cpp, also under
+// ASan / UBSan).
 //
 // Both decoders are generators over a byte reader (Lz4Direct on the host, the LDS window of the kernel): inf_step
 // yields the next literal, match, stored run or the end of a zlib stream, blosclz_next the next literal run or match
@@ -31,10 +31,6 @@
 namespace dsx {
 namespace zdec {
 
-// task kinds next to those of dsx_zstd_dec.h (0 .. 3) and dsx_lz4_dec.h (4); they take the same flags
-constexpr uint32_t kTaskZlib = 5;     // one zlib stream (RFC 1950)
-constexpr uint32_t kTaskBlosclz = 6;  // one blosclz stream
-
 // ---- DEFLATE ---------------------------------------------------------------------------------------------------------
 constexpr int kInfFastBits = 10;  // codes up to this length decode by one lookup, longer ones canonically
 constexpr int kInfMaxBits = 15;
@@ -52,12 +48,6 @@ struct InfTables {
   uint16_t offs[kInfMaxBits + 1];
   uint8_t lens[kInfMaxLL + kInfMaxDD];
 };
-// the tables of one task: a zstd frame or a zlib stream (LDS on the device)
-union DecWork {
-  Tables t;
-  InfTables inf;
-};
-static_assert(sizeof(InfTables) <= sizeof(Tables), "the inflate tables live in the space of the zstd tables");
 
 enum InfSet { kInfSetLens = 0, kInfSetLitLen = 1, kInfSetDist = 2 };
 
@@ -389,10 +379,9 @@ inline int inflate_decode(InfTables& t, const uint8_t* s, uint32_t n, uint8_t* o
     if (ev.type == kInfLit) {
       out[at] = (uint8_t)ev.a;
     } else if (ev.type == kInfMatch) {
-      uint8_t* d = out + at;
-      for (uint32_t i = 0; i < ev.a; ++i) d[i] = d[(int64_t)i - (int64_t)ev.b];
+      run_seq_host(out + at, s, 0, ev.a, ev.b);
     } else if (ev.type == kInfStored) {
-      for (uint32_t i = 0; i < ev.b; ++i) out[at + i] = s[ev.a + i];
+      copy_bytes(out + at, s + ev.a, ev.b);
     } else {
       return adler32_host(out, out_n) == ev.a ? kOk : kErrChecksum;
     }
@@ -467,46 +456,9 @@ inline int blosclz_decode(const uint8_t* s, uint32_t n, uint8_t* out, uint32_t o
     const uint32_t at = op;
     const int st = blosclz_next(r, n, out_n, ip, op, q);
     if (st) return st;
-    for (uint32_t i = 0; i < q.ll; ++i) out[at + i] = s[q.lit + i];
-    uint8_t* d = out + at;
-    for (uint32_t i = 0; i < q.ml; ++i) d[i] = d[(int64_t)i - (int64_t)q.off];
+    run_seq_host(out + at, s + q.lit, q.ll, q.ml, q.off);  // (a literal run or a match)
   }
   return op == out_n ? kOk : kErrOutput;
-}
-
-// ---- tasks -------------------------------------------------------------------------------------------------------------
-// One task of any kind on the host; tmp: dst_len bytes of scratch.  Tasks of the kinds of dsx_zstd_dec.h and
-// dsx_lz4_dec.h run through run_task_host_any as before; kTaskZlib and kTaskBlosclz take the same flags (a split
-// task: two streams behind an int32 length each, one as long as its share is stored).  Returns a status.
-inline int run_task_host_all(DecWork& wk, const DecTask& k, const uint8_t* packed, uint8_t* out, uint8_t* tmp) {
-  const uint32_t kind = k.kind & kTaskKindMask;
-  if (kind != kTaskZlib && kind != kTaskBlosclz) return run_task_host_any(wk.t, k, packed, out, tmp);
-  const bool split = (k.kind & kTaskSplit) != 0, bits = (k.kind & kTaskBitshuffle) != 0;
-  const bool shuf = !bits && (k.kind & kTaskShuffle) != 0;
-  const uint8_t* s = packed + k.src;
-  uint8_t* d = out + k.dst;
-  uint8_t* o = (shuf || bits) ? tmp : d;
-  const uint32_t nstreams = split ? kSplitStreams : 1u;
-  if (k.dst_len % nstreams) return kErrOutput;
-  const uint32_t ne = k.dst_len / nstreams;
-  uint32_t pos = 0;
-  for (uint32_t j = 0; j < nstreams; ++j) {
-    uint32_t at = 0, len = k.src_len;
-    if (split) {
-      const int st = split_stream(s, k.src_len, &pos, &at, &len);
-      if (st) return st;
-    }
-    int st;
-    if (split && len == ne) st = run_stream_host(wk.t, kTaskStored, true, s + at, len, o + j * ne, ne);
-    else if (kind == kTaskZlib) st = inflate_decode(wk.inf, s + at, len, o + j * ne, ne);
-    else st = blosclz_decode(s + at, len, o + j * ne, ne);
-    if (st) return st;
-  }
-  if (split && pos != k.src_len) return kErrTruncated;
-  if (bits) unbitshuffle_host(d, o, k.dst_len);
-  else if (shuf)
-    for (uint32_t i = 0; i < k.dst_len; ++i) d[i] = unshuffled_byte(o, k.dst_len, i);
-  return kOk;
 }
 
 }  // namespace zdec

@@ -31,10 +31,8 @@
 #include <unistd.h>
 #include <zlib.h>
 
-#include "dsx_inflate.h"
-#include "dsx_lz4_dec.h"
 #include "dsx_lz4_enc.h"
-#include "dsx_zstd_dec.h"
+#include "dsx_zdec_task.h"
 
 #include <algorithm>
 #include <atomic>
@@ -499,8 +497,8 @@ inline std::string io_read_chunks(const char* const* paths, void* const* dst, co
 // at most frame_tasks_per_chunk blocks -> one task per block (a zstd frame, or a stored stream); memcpyed frames -> one
 // copy task; a missing file -> one fill task.  Any other frame is decoded here by blosc_decode (its error is the
 // error of the read) and shipped as a copy task.
-// mode kZdecAny (DSX_ZDEC_ANY) widens the device's share to what dsx_lz4_dec.h decodes: LZ4 / LZ4HC inside, bit
-// shuffle, and split blocks (zstd or LZ4) -- one task per Blosc block still: a split task's src is the length word of
+// mode kZdecAny (DSX_ZDEC_ANY) widens the device's share to the other kinds and flags of dsx_zdec_task.h: LZ4 / LZ4HC
+// inside, bit shuffle, and split blocks (zstd or LZ4) -- one task per Blosc block still: a split task's src is the length word of
 // its first stream and its src_len spans both streams.  Type sizes other than 2, blosclz / zlib / snappy, zstd
 // checksums and chunks of more than frame_tasks_per_chunk blocks stay on the host.
 // mode kZdecAll (DSX_ZDEC_ALL) is kZdecAny plus what dsx_inflate.h decodes: blosclz and zlib inside, in the same

@@ -1,38 +1,39 @@
 // dsx_zdec_kernels.h -- Blosc blocks decoded on the device (dsx_blosc_decode_device): one wave per task of
-// dsx_io_read_frames (dsx_zstd_dec.h DecTask).
+// dsx_io_read_frames (dsx_zdec_task.h: DecTask, the kinds and flags; run_task_host is the same flow on the host).
 //
-//   k_zdec, k_zdec_all   grid = tasks, 64 threads each; every task belongs to one of the two (k_zdec_all: the kinds of
-//            dsx_inflate.h) and the other kernel's wave leaves at once.  Fill / copy / stored tasks are wide copies (with the 2-byte un-shuffle where
-//            the frame is shuffled).  A zstd task runs the decoder core of dsx_zstd_dec.h: lane 0 parses the headers
-//            and builds the Huffman and FSE tables in LDS; the four literal streams are decoded by lanes 0 .. 3 into
-//            the end of the task's output, reading their bits from LDS, where the wave stages kLitWin bytes of each
-//            stream per round; lane 0 decodes and validates a batch of up to kSeqBatch sequences into LDS
-//            and the wave executes them (literal copy, then the match).  A match may read bytes the wave stored
-//            earlier: the wave keeps a watermark of output made visible by the last barrier (whose workgroup-scope
-//            fence orders the global stores before the loads that follow) and passes another barrier only when the
-//            match source reaches above it.  A shuffled task decodes into scratch and is un-shuffled into the bricks
-//            after one more barrier.  One int32 status per task (dsx_zstd_dec.h Status; 0 = exact output).
-//            An LZ4 task (dsx_lz4_dec.h) has no tables to build: every lane parses the same token from a window of
-//            the stream staged in LDS (the reads are broadcasts, the wave refills the window together when the parse
-//            leaves it), then the wave copies the literals -- out of the window when they lie in it -- and the match
-//            as the zstd sequences do, behind the same watermark.  A split task holds two streams behind an int32
-//            length each (stored, zstd or LZ4): the wave decodes them one after the other into the two halves of
-//            the block and un-shuffles after both.  A bit-shuffled task is un-shuffled by 8 x 8 bit transposes, 8
-//            elements per lane and round.
-//            A zlib task (dsx_inflate.h) has literals and matches interleaved in one bit stream: every lane runs the
-//            same parse (inf_step) over the staged window of the stream -- lane 0 alone stores the code tables, which
-//            share the LDS of the zstd tables -- into a batch of up to kSeqBatch sequences and a literal window in
-//            LDS, then the wave executes the batch as it does the zstd sequences; a stored block is one wide copy.
-//            The Adler-32 of the stream is checked against the bytes the wave made.  A blosclz task is an LZ4 task
-//            with another generator (blosclz_next).
+//   k_zdec, k_zdec_all   grid = tasks, 64 threads each.  Both are zdec_task: k_zdec_all runs the zlib and blosclz
+//            tasks, k_zdec every other kind, and the wave of the other kernel leaves at once (all four decoders in one
+//            kernel need 255 VGPRs and scratch).  One int32 status per task (dsx_zstd_dec.h Status; 0 = exact output).
+//
+//   zdec_task    fill, or copy / stored bytes (wide copies), or the streams of the block one after the other -- a
+//            split block has two, each stored or coded -- into the output, or into scratch when an un-shuffle follows
+//            (2-byte: wave_unshuffle; bit: wave_unbitshuffle, 8 x 8 bit transposes, 8 elements per lane and round).
+//
+//   The four stream drivers parse with the primitives of the codec headers and execute with:
+//     wave_copy / wave_pattern   a copy by the whole wave, 8 loads in flight per lane; a match that overlaps itself.
+//     wave_match     one match behind the watermark: the wave keeps the offset `fenced` below which its output was
+//                    made visible by the last barrier (whose workgroup-scope fence orders the global stores before
+//                    the loads that follow) and passes another barrier only when the match source reaches above it
+//                    (match_needs_fence of dsx_zdec_task.h, which the walker of tests/host/zstd_dec_check.cpp replays).
+//     Lz4Window      the stream bytes of a parser that every lane runs alike: a window of kLz4Win bytes in LDS (the
+//                    reads are broadcasts) that the wave refills together when the parse leaves it.
+//   zstd_wave    lane 0 parses the headers and builds the Huffman and FSE tables in LDS; the four literal streams
+//            are decoded by lanes 0 .. 3 into the end of the stream's output, reading their bits from LDS, where the
+//            wave stages kLitWin bytes of each stream per round; lane 0 decodes and validates a batch of up to kSeqBatch
+//            sequences into LDS and the wave runs it, the literals from the end of the output (or from the frame: raw).
+//   lz_wave      LZ4 (lz4_next) and blosclz (blosclz_next) have no tables: every lane parses the same sequence
+//            through an Lz4Window, then the wave copies the literals -- out of the window when they lie in it -- and
+//            the match.
+//   inflate_wave zlib: literals and matches are interleaved in one bit stream, so every lane runs the same parse
+//            (inf_step) through an Lz4Window -- lane 0 alone stores the code tables, which share the LDS of the zstd
+//            tables -- into a batch of sequences and a literal window in LDS, then the wave runs the batch; a stored
+//            block is one wide copy.  The Adler-32 of the stream is checked against the bytes the wave made.
 #ifndef DSX_ZDEC_KERNELS_H
 #define DSX_ZDEC_KERNELS_H
 
 #include <hip/hip_runtime.h>
 
-#include "dsx_inflate.h"
-#include "dsx_lz4_dec.h"
-#include "dsx_zstd_dec.h"
+#include "dsx_zdec_task.h"
 
 namespace dsx {
 namespace zdec {
@@ -90,6 +91,18 @@ __device__ inline void wave_pattern(uint8_t* dst, uint32_t off, uint32_t ml, int
   }
 }
 
+// The match of ml bytes at o + wop whose source starts `off` bytes back, behind the watermark `fenced` (uniform: every
+// lane runs the same sequence)
+__device__ __forceinline__ void wave_match(uint8_t* o, uint32_t wop, uint32_t off, uint32_t ml, uint32_t& fenced, int lane) {
+  const uint32_t src = wop - off;
+  if (match_needs_fence(src, ml, off, fenced)) {
+    __syncthreads();  // earlier stores before the match loads
+    fenced = wop;
+  }
+  if (off >= ml) wave_copy(o + wop, o + src, ml, lane);
+  else wave_pattern(o + wop, off, ml, lane);  // overlapping: the last `off` bytes repeat
+}
+
 // 2-byte un-shuffle of n bytes s -> d (bytes [0, n/2) are the low bytes; an odd tail byte as is)
 __device__ inline void wave_unshuffle(uint8_t* d, const uint8_t* s, uint32_t n, int lane) {
   const uint32_t ne = n / 2;
@@ -112,7 +125,7 @@ __device__ inline void wave_unshuffle(uint8_t* d, const uint8_t* s, uint32_t n, 
   if ((n & 1u) && lane == 0) d[n - 1] = s[n - 1];
 }
 
-// bit un-shuffle of n bytes s -> d (dsx_lz4_dec.h unbitshuffle8: 8 elements = 16 bytes per lane and round)
+// bit un-shuffle of n bytes s -> d (dsx_zdec_task.h unbitshuffle8: 8 elements = 16 bytes per lane and round)
 __device__ __forceinline__ void wave_unbitshuffle(uint8_t* d, const uint8_t* s, uint32_t n, int lane) {
   if (!bitshuffled(n)) {
     wave_copy(d, s, n, lane);
@@ -153,10 +166,12 @@ struct WaveLds {
 constexpr uint32_t kLz4Win = 2048;  // bytes of an LZ4 stream staged in LDS (within WaveLds::lbuf)
 constexpr uint32_t kInfLitWin = 4096;  // literals of a batch of a zlib stream (WaveLds::lbuf[2 .. 3])
 static_assert(kLz4Win <= kLitWin && kInfLitWin <= 2 * kLitWin, "the windows lie in WaveLds::lbuf");
+static_assert(kLz4Win % 512 == 0 && kLitWin % 512 == 0, "the staging loops store whole rounds of 512 bytes");
 static_assert(sizeof(WaveLds::batch) >= 2 * 64 * sizeof(uint32_t), "wave_adler32 reduces in WaveLds::batch");
 
-// The bytes of an LZ4 stream for lz4_next, read by every lane alike: a window [lo, lo + cnt) of the stream in LDS
-// that the wave refills together (uniform control flow) at the first byte asked for outside it.
+// The bytes of a stream for a parser that every lane runs alike (lz4_next, blosclz_next, inf_step): a window
+// [lo, lo + cnt) of the stream in LDS that the wave refills together (uniform control flow) at the first byte asked
+// for outside it.
 struct Lz4Window {
   const uint8_t* s;
   uint32_t n;
@@ -184,61 +199,33 @@ struct Lz4Window {
   }
 };
 
-// One bare LZ4 block s[0 .. n) -> o[0 .. out_n) by the wave; returns a status (the same in every lane)
-__device__ __forceinline__ int lz4_wave(uint8_t* win, const uint8_t* s, uint32_t n, uint8_t* o, uint32_t out_n, int lane) {
+// One bare LZ4 block (lz4_next: sequences of literals and a match, the last one without a match) or one blosclz stream
+// (kBlosclz, blosclz_next: instructions that are a literal run or a match, until the bytes end) s[0 .. n) ->
+// o[0 .. out_n) by the wave; returns a status (the same in every lane)
+template <bool kBlosclz>
+__device__ __forceinline__ int lz_wave(uint8_t* win, const uint8_t* s, uint32_t n, uint8_t* o, uint32_t out_n, int lane) {
   Lz4Window r{s, n, win, 0, 0, lane};
   uint32_t ip = 0, op = 0, fenced = 0;
-  for (;;) {
+  while (!kBlosclz || ip < n) {
     Lz4Seq q;
     const uint32_t at = op;
-    const int st = lz4_next(r, n, out_n, ip, op, q);
+    int st;
+    if constexpr (kBlosclz) st = blosclz_next(r, n, out_n, ip, op, q);
+    else st = lz4_next(r, n, out_n, ip, op, q);
     if (st) return st;
-    if (q.lit >= r.lo && q.lit - r.lo + q.ll <= r.cnt) {  // the literals are staged: stores only
-      const uint8_t* w = win + (q.lit - r.lo);
-      for (uint32_t i = (uint32_t)lane; i < q.ll; i += 64) o[at + i] = w[i];
-    } else {
-      wave_copy(o + at, s + q.lit, q.ll, lane);
-    }
-    if (q.ml == 0) break;
-    const uint32_t wop = at + q.ll, src = wop - q.off;
-    const uint32_t span = q.ml < q.off ? q.ml : q.off;
-    if (src + span > fenced) {
-      __syncthreads();  // (uniform) earlier stores before the match loads
-      fenced = wop;
-    }
-    if (q.off >= q.ml) wave_copy(o + wop, o + src, q.ml, lane);
-    else wave_pattern(o + wop, q.off, q.ml, lane);
-  }
-  return op == out_n ? kOk : kErrOutput;
-}
-
-// One blosclz stream s[0 .. n) -> o[0 .. out_n) by the wave: lz4_wave over blosclz_next, whose instructions are a
-// literal run or a match each; returns a status (the same in every lane)
-__device__ __forceinline__ int blosclz_wave(uint8_t* win, const uint8_t* s, uint32_t n, uint8_t* o, uint32_t out_n, int lane) {
-  Lz4Window r{s, n, win, 0, 0, lane};
-  uint32_t ip = 0, op = 0, fenced = 0;
-  while (ip < n) {
-    Lz4Seq q;
-    const uint32_t at = op;
-    const int st = blosclz_next(r, n, out_n, ip, op, q);
-    if (st) return st;
-    if (q.ml == 0) {
+    if (!kBlosclz || q.ml == 0) {  // (a blosclz instruction is a literal run or a match)
       if (q.lit >= r.lo && q.lit - r.lo + q.ll <= r.cnt) {  // the literals are staged: stores only
         const uint8_t* w = win + (q.lit - r.lo);
         for (uint32_t i = (uint32_t)lane; i < q.ll; i += 64) o[at + i] = w[i];
       } else {
         wave_copy(o + at, s + q.lit, q.ll, lane);
       }
-      continue;
     }
-    const uint32_t src = at - q.off;
-    const uint32_t span = q.ml < q.off ? q.ml : q.off;
-    if (src + span > fenced) {
-      __syncthreads();  // (uniform) earlier stores before the match loads
-      fenced = at;
+    if (q.ml == 0) {
+      if constexpr (kBlosclz) continue;
+      else break;  // the last sequence of an LZ4 block
     }
-    if (q.off >= q.ml) wave_copy(o + at, o + src, q.ml, lane);
-    else wave_pattern(o + at, q.off, q.ml, lane);
+    wave_match(o, kBlosclz ? at : at + q.ll, q.off, q.ml, fenced, lane);
   }
   return op == out_n ? kOk : kErrOutput;
 }
@@ -305,14 +292,7 @@ __device__ __forceinline__ int inflate_wave(WaveLds& sh, const uint8_t* s, uint3
       for (uint32_t i = (uint32_t)lane; i < q.ll; i += 64) o[wop + i] = lw[lp + i];
       wop += q.ll;
       lp += q.ll;
-      const uint32_t src = wop - q.off;
-      const uint32_t span = q.ml < q.off ? q.ml : q.off;
-      if (src + span > fenced) {
-        __syncthreads();  // (uniform) earlier stores before the match loads
-        fenced = wop;
-      }
-      if (q.off >= q.ml) wave_copy(o + wop, o + src, q.ml, lane);
-      else wave_pattern(o + wop, q.off, q.ml, lane);
+      wave_match(o, wop, q.off, q.ml, fenced, lane);
       wop += q.ml;
     }
     for (uint32_t i = (uint32_t)lane; i < ll; i += 64) o[wop + i] = lw[lp + i];  // the literals behind the last match
@@ -537,14 +517,7 @@ __device__ __forceinline__ int zstd_wave(WaveLds& sh, const uint8_t* s, uint32_t
           wave_copy(o + wop, lit + lp, e1.ll, lane);  // (writes stay below the literals not yet read)
           wop += e1.ll;
           lp += e1.ll;
-          const uint32_t src = wop - e1.off;
-          const uint32_t span = e1.ml < e1.off ? e1.ml : e1.off;
-          if (src + span > fenced) {
-            __syncthreads();  // (uniform: every lane runs the same batch) earlier stores before the match loads
-            fenced = wop;
-          }
-          if (e1.off >= e1.ml) wave_copy(o + wop, o + src, e1.ml, lane);
-          else wave_pattern(o + wop, e1.off, e1.ml, lane);  // overlapping: the last `off` bytes repeat
+          wave_match(o, wop, e1.off, e1.ml, fenced, lane);
           wop += e1.ml;
         }
         done += (uint32_t)c;
@@ -572,8 +545,8 @@ __device__ __forceinline__ int zstd_wave(WaveLds& sh, const uint8_t* s, uint32_t
   return st;
 }
 
-// One task by one wave.  kAll: the kernel of the kinds of dsx_inflate.h (k_zdec_all); the tasks of the other kernel are
-// left alone, their status too.
+// One task by one wave (run_task_host of dsx_zdec_task.h is this flow on the host).  kAll: the kernel of the zlib and
+// blosclz tasks (k_zdec_all); the tasks of the other kernel are left alone, their status too.
 template <bool kAll>
 __device__ __forceinline__ void zdec_task(const DecArgs& a) {
   __shared__ WaveLds sh;
@@ -620,10 +593,10 @@ __device__ __forceinline__ void zdec_task(const DecArgs& a) {
     if (split && len == ne) wave_copy(o + j * ne, s + at, ne, lane);  // stored
     else if constexpr (kAll) {
       if (kind == kTaskZlib) st = inflate_wave(sh, s + at, len, o + j * ne, ne, lane);
-      else st = blosclz_wave(&sh.lbuf[0][0], s + at, len, o + j * ne, ne, lane);
+      else st = lz_wave<true>(&sh.lbuf[0][0], s + at, len, o + j * ne, ne, lane);
     } else {
       if (kind == kTaskZstd) st = zstd_wave(sh, s + at, len, o + j * ne, ne, lane);
-      else st = lz4_wave(&sh.lbuf[0][0], s + at, len, o + j * ne, ne, lane);
+      else st = lz_wave<false>(&sh.lbuf[0][0], s + at, len, o + j * ne, ne, lane);
     }
   }
   if (split && !st && pos != n) st = kErrTruncated;

@@ -1,5 +1,7 @@
 // dsx_zstd_dec.h -- zstd frame decoder (RFC 8878) shared by the host reference (dsx_blosc_decode_ref) and the device
-// kernels (dsx_zdec_kernels.h).  Plain C++ with no STL and no allocation; g++ builds it for the CPU tests
+// kernels (dsx_zdec_kernels.h): the format primitives, which both builds run, and decode_frame, the host decoder of one
+// frame.  The statuses of every codec of the Blosc block decoder are here too; the tasks around a frame are
+// dsx_zdec_task.h.  Plain C++ with no STL and no allocation; g++ builds it for the CPU tests
 // (tests/host/zstd_dec_check.cpp, also under ASan / UBSan).
 //
 // One frame decodes into a caller-given output of exactly the expected size.  Supported: single-segment and window
@@ -90,6 +92,18 @@ DSX_ZHD inline uint32_t le(const uint8_t* p, int n) {
   uint32_t v = 0;
   for (int i = n - 1; i >= 0; --i) v = (v << 8) | p[i];
   return v;
+}
+
+// How every host decoder (decode_frame, lz4_decode, inflate_decode, blosclz_decode) executes what it has validated:
+// ll literals to d, then a match of ml bytes whose source starts `off` bytes back, byte by byte (off < ml: the match
+// overlaps itself and repeats its last `off` bytes)
+inline void copy_bytes(uint8_t* d, const uint8_t* s, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) d[i] = s[i];
+}
+inline void run_seq_host(uint8_t* d, const uint8_t* lit, uint32_t ll, uint32_t ml, uint32_t off) {
+  copy_bytes(d, lit, ll);
+  d += ll;
+  for (uint32_t i = 0; i < ml; ++i) d[i] = d[(int64_t)i - (int64_t)off];
 }
 
 // Backward bit reader over s[0 .. n): bits [0, pos) are unread, reads take the top ones.  Bits below 0 read as 0
@@ -620,7 +634,7 @@ inline int decode_frame(Tables& t, const uint8_t* s, uint32_t n, uint8_t* out, u
     if (type == 0) {
       if (bs > n - ip) return kErrTruncated;
       if (bs > out_n - op) return kErrOutput;
-      for (uint32_t i = 0; i < bs; ++i) out[op + i] = s[ip + i];
+      copy_bytes(out + op, s + ip, bs);
       ip += bs;
       op += bs;
     } else if (type == 1) {
@@ -676,9 +690,7 @@ inline int decode_frame(Tables& t, const uint8_t* s, uint32_t n, uint8_t* out, u
         const uint32_t o0 = q.op, l0 = q.lit_used;
         st = next_seq(t, q, out_n, e);
         if (st) return st;
-        for (uint32_t i = 0; i < e.ll; ++i) out[o0 + i] = lit[l0 + i];
-        uint8_t* d = out + o0 + e.ll;
-        for (uint32_t i = 0; i < e.ml; ++i) d[i] = d[(int64_t)i - (int64_t)e.off];
+        run_seq_host(out + o0, lit + l0, e.ll, e.ml, e.off);
       }
       if (nseq) {
         st = seq_end(q);
@@ -686,7 +698,7 @@ inline int decode_frame(Tables& t, const uint8_t* s, uint32_t n, uint8_t* out, u
       }
       const uint32_t rest = lh.regen - q.lit_used;
       if (rest > out_n - q.op) return kErrOutput;
-      for (uint32_t i = 0; i < rest; ++i) out[q.op + i] = lit[q.lit_used + i];
+      copy_bytes(out + q.op, lit + q.lit_used, rest);  // (from above, when the literals lie at the end of out)
       if (q.op + rest - op > kBlockMax) return kErrBlockSize;
       op = q.op + rest;
       ip += bs;
@@ -695,51 +707,6 @@ inline int decode_frame(Tables& t, const uint8_t* s, uint32_t n, uint8_t* out, u
   }
   if (op != out_n) return kErrOutput;
   if (ip != n) return kErrTruncated;
-  return kOk;
-}
-
-
-// ---- Blosc block tasks: dsx_io_read_frames -> dsx_blosc_decode_device / dsx_blosc_decode_ref --------------------
-enum TaskKind { kTaskFill = 0, kTaskCopy = 1, kTaskStored = 2, kTaskZstd = 3 };
-constexpr uint32_t kTaskKindMask = 0xFF;
-constexpr uint32_t kTaskShuffle = 0x100;  // byte un-shuffle of 2-byte elements after the copy / decode
-struct DecTask {
-  uint64_t src;      // offset of the bytes in the packed buffer (kTaskFill: the 16-bit fill value)
-  uint64_t dst;      // offset in the output
-  uint32_t src_len;  // bytes in the packed buffer
-  uint32_t dst_len;  // bytes of output
-  uint32_t kind;     // TaskKind | kTaskShuffle
-  uint32_t chunk;    // index of the chunk file (error messages)
-};
-
-// byte p of the un-shuffled output from the shuffled block s of n bytes (2-byte elements, the odd tail as is)
-DSX_ZHD inline uint8_t unshuffled_byte(const uint8_t* s, uint32_t n, uint32_t p) {
-  const uint32_t ne = n / 2;
-  return p < 2 * ne ? s[(p & 1) * ne + (p >> 1)] : s[p];
-}
-
-// One task on the host; tmp: dst_len bytes of scratch (shuffled tasks).  Returns a status.
-inline int run_task_host(Tables& t, const DecTask& k, const uint8_t* packed, uint8_t* out, uint8_t* tmp) {
-  uint8_t* d = out + k.dst;
-  const uint32_t kind = k.kind & kTaskKindMask;
-  const bool shuf = (k.kind & kTaskShuffle) != 0;
-  if (kind == kTaskFill) {
-    for (uint32_t i = 0; i < k.dst_len; ++i) d[i] = (uint8_t)(k.src >> (8 * (i & 1)));
-    return kOk;
-  }
-  const uint8_t* s = packed + k.src;
-  if (kind == kTaskZstd) {
-    const int st = decode_frame(t, s, k.src_len, shuf ? tmp : d, k.dst_len);
-    if (st) return st;
-    s = tmp;
-  } else if (k.src_len != k.dst_len) {
-    return kErrOutput;
-  }
-  if (shuf) {
-    for (uint32_t i = 0; i < k.dst_len; ++i) d[i] = unshuffled_byte(s, k.dst_len, i);
-  } else if (kind != kTaskZstd) {
-    for (uint32_t i = 0; i < k.dst_len; ++i) d[i] = s[i];
-  }
   return kOk;
 }
 

@@ -23,10 +23,10 @@ DSX_WAVELET_BANK = 0  # filter bank handed over with dsx_set_wavelet
 STAGE_APPROX, STAGE_DETAIL = 0, 1
 STREAM_COMPUTE, STREAM_UPLOAD, STREAM_DOWNLOAD = 0, 1, 2
 
-# Blosc block tasks of the device decoder (csrc/dsx_zstd_dec.h DecTask): kinds, the un-shuffle flag, routes per chunk
+# Blosc block tasks of the device decoder (csrc/dsx_zdec_task.h DecTask): kinds, the un-shuffle flag, routes per chunk
 TASK_FILL, TASK_COPY, TASK_STORED, TASK_ZSTD, TASK_LZ4 = 0, 1, 2, 3, 4
-TASK_ZLIB, TASK_BLOSCLZ = 5, 6  # (csrc/dsx_inflate.h: one zlib stream, one blosclz stream)
-TASK_SHUFFLE, TASK_SPLIT, TASK_BITSHUFFLE = 0x100, 0x200, 0x400  # (csrc/dsx_lz4_dec.h: split streams, bit un-shuffle)
+TASK_ZLIB, TASK_BLOSCLZ = 5, 6  # (one zlib stream, one blosclz stream)
+TASK_SHUFFLE, TASK_SPLIT, TASK_BITSHUFFLE = 0x100, 0x200, 0x400  # (split streams, bit un-shuffle)
 ZDEC_ZSTD, ZDEC_ANY, ZDEC_ALL = 0, 1, 3  # (2 stays refused) DSX_ZDEC_*: what dsx_io_read_frames_ex routes to the device
 ROUTE_DEVICE, ROUTE_HOST, ROUTE_FILL = 0, 1, 2
 TASK_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<u4"), ("dst_len", "<u4"), ("kind", "<u4"),

@@ -277,7 +277,7 @@ int dsx_blosc_encode_device_ex(dsx_ctx* ctx, const void* d_src, int n_chunks, si
 int dsx_blosc_encode_ref_ex(const void* src, int n_chunks, size_t chunk_bytes, int typesize, int clevel, void* frames,
                             int64_t* offsets, int mode);
 
-/* Blosc chunks decoded on the device (csrc/dsx_zstd_dec.h, csrc/dsx_lz4_dec.h, csrc/dsx_zdec_kernels.h).
+/* Blosc chunks decoded on the device (csrc/dsx_zdec_task.h: the tasks; csrc/dsx_zdec_kernels.h: the kernels).
  * dsx_io_read_frames: n chunk files -> their frames packed back to back into `packed` (host memory, capacity
  * n * (chunk_bytes + 16)) and one 32-byte task per Blosc block into `tasks` (capacity n * (chunk_bytes / 8192 + 1)):
  * {uint64 src, uint64 dst, uint32 src_len, uint32 dst_len, uint32 kind, uint32 chunk}; chunk i decodes to bytes

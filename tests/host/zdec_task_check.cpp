@@ -1,13 +1,13 @@
-// Host build of the Blosc block tasks of the device path with the kinds of csrc/dsx_inflate.h (zlib streams, blosclz;
-// every other kind through csrc/dsx_lz4_dec.h), for tests/test_inflate_decoder_host.py:
-//   inflate_dec_check decode <records> <out>          run every record; <out>: per record int32 status + the bytes
-//   inflate_dec_check mutate <records> <iters> <seed> every truncation of every record, then <iters> seeded single-byte
-//                                                 mutations each; prints "<status> <same bytes> <count>" per
-//                                                 outcome (same bytes: 1 when status 0 came with the original output)
+// Host build of the Blosc block tasks of the device path (csrc/dsx_zdec_task.h: run_task_host over every kind and
+// flag), for the host tests of the decoders (tests/zdec_cases.py build_check_exe):
+//   zdec_task_check decode <records> <out>          run every record; <out>: per record int32 status + the bytes
+//   zdec_task_check mutate <records> <iters> <seed> every truncation of every record, then <iters> seeded single-byte
+//                                                   mutations each; prints "<status> <same bytes> <count>" per
+//                                                   outcome (same bytes: 1 when status 0 came with the original output)
 // <records>: back to back [uint32 task bytes][uint32 output bytes][uint32 kind][task bytes]: one DecTask whose src is
 // the whole record.  The inputs live in buffers of exactly their size, so a sanitizer build sees any read past the
 // task's bytes and any write past its output.
-#include "../../aind_smartspim_destripe_amd/csrc/dsx_inflate.h"
+#include "../../aind_smartspim_destripe_amd/csrc/dsx_zdec_task.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -47,7 +47,7 @@ static int run(z::DecWork& t, const std::vector<uint8_t>& in_, uint32_t want, ui
   uint8_t* tmp = new uint8_t[want ? want : 1];
   memset(o, 0, want ? want : 1);
   const z::DecTask k{0, 0, (uint32_t)in_.size(), want, kind, 0};
-  const int st = z::run_task_host_all(t, k, in, o, tmp);
+  const int st = z::run_task_host(t, k, in, o, tmp);
   out.assign(o, o + want);
   delete[] tmp;
   delete[] o;

@@ -1,4 +1,5 @@
-// Host build of the zstd frame decoder of the device path (csrc/dsx_zstd_dec.h), for tests/test_zstd_decoder_host.py:
+// Host build of the zstd frame decoder of the device path (csrc/dsx_zstd_dec.h; the watermark rule of
+// csrc/dsx_zdec_task.h), for tests/test_zstd_decoder_host.py:
 //   zstd_dec_check decode <records> <out>          decode every record; <out>: per record int32 status + the bytes
 //   zstd_dec_check mutate <records> <iters> <seed> every truncation of every record, then <iters> seeded bit flips and
 //                                                  byte overwrites each; prints "<status> <count>" per outcome
@@ -9,7 +10,7 @@
 // <records>: back to back [uint32 frame bytes][uint32 output bytes][frame].  The inputs live in buffers of exactly
 // their size, so a sanitizer build sees any read past a frame.  A mutated frame must end in an error status or in
 // exactly the expected number of bytes.
-#include "../../aind_smartspim_destripe_amd/csrc/dsx_zstd_dec.h"
+#include "../../aind_smartspim_destripe_amd/csrc/dsx_zdec_task.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -57,7 +58,8 @@ static const char* kStatNames =
 
 // The blocks of a frame as decode_frame takes them, without an output: the literals are only measured, the sequences
 // are decoded and validated by next_seq.  `fenced` is the watermark of zstd_wave: output below it is visible to the
-// wave, a match whose source reaches above it passes a barrier first; the end of a batch of `batch` sequences is one.
+// wave, a match whose source reaches above it (match_needs_fence of csrc/dsx_zdec_task.h, which the kernel runs)
+// passes a barrier first; the end of a batch of `batch` sequences is one.
 static void walk(z::Tables& t, const uint8_t* s, uint32_t n, uint32_t out_n, uint32_t batch, long* c) {
   for (int i = 0; i < kStats; ++i) c[i] = 0;
   z::FrameHdr fh;
@@ -129,11 +131,11 @@ static void walk(z::Tables& t, const uint8_t* s, uint32_t n, uint32_t out_n, uin
         c[kSeqs]++;
         if (ofc <= 1) c[kRepeat]++;  // offset values 1 .. 3: the repeat offsets
         wop += e.ll;
-        const uint32_t src = wop - e.off, span = e.ml < e.off ? e.ml : e.off;
+        const uint32_t src = wop - e.off, span = e.ml < e.off ? e.ml : e.off;  // (the bytes the match loads)
         if (e.off >= e.ml) c[kOffGeMl]++;
         else c[64u % e.off == 0 ? kPatDiv : kPatNoDiv]++;
         if (e.off == 1) c[kOff1]++;
-        if (src + span > fenced) {
+        if (z::match_needs_fence(src, e.ml, e.off, fenced)) {  // the rule wave_match runs
           c[kBarriers]++;
           const bool own = e.ll > 0 && src + span > wop - e.ll;  // the source holds literals of this sequence
           if (own) c[kBarOwnLit]++;

@@ -1,4 +1,4 @@
-"""``k_zdec_all`` (``csrc/dsx_zdec_kernels.h``: ``inflate_wave``, ``blosclz_wave``) held to the tables of
+"""``k_zdec_all`` (``csrc/dsx_zdec_kernels.h``: ``inflate_wave``, ``lz_wave``) held to the tables of
 tests/inflate_cases.py, which tests/test_inflate_decoder_host.py runs through the host build and the sanitizer
 builds: the kernel returns the bytes that were encoded, the status words of the host build, and changes no byte
 outside a task's destination."""

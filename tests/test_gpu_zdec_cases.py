@@ -1,6 +1,6 @@
 """``k_zdec`` (``csrc/dsx_zdec_kernels.h``) held to bytes that no decoder of this project made: the tables of
 tests/zdec_cases.py, which tests/test_zdec_cases_host.py runs through the host build, here through the kernel.  The
-kernel's driver (``zstd_wave``, ``lz4_wave``, the wave copies and un-shuffles) exists only on the device; these tests are
+kernel's driver (``zstd_wave``, ``lz_wave``, the wave copies and un-shuffles) exists only on the device; these tests are
 what holds it to libzstd's input on every zstd mode, at every task layout, and to the host build's status words on
 malformed zstd frames (each of which went through the CPU sanitizer builds in the host file first)."""
 

@@ -1,5 +1,5 @@
 """The zlib and blosclz decoders of the device path (``csrc/dsx_inflate.h``), built on the host: as
-``dsx_blosc_decode_ref`` of the library and with g++ from ``tests/host/inflate_dec_check.cpp`` (also under ASan /
+``dsx_blosc_decode_ref`` of the library and with g++ from ``tests/host/zdec_task_check.cpp`` (also under ASan /
 UBSan, a program of its own).  ``dsx_io_read_frames_ex`` in mode ``DSX_ZDEC_ALL`` routes frames with zlib or blosclz
 inside to the device and modes 0 and 1 keep them on the host; the frames of the real c-blosc 1.21.0 decode to their
 payload; every valid zlib stream is one Python's ``zlib`` decodes to the same bytes; hand-assembled streams cover
@@ -20,7 +20,6 @@ from aind_smartspim_destripe_amd import engine as eng_mod
 from aind_smartspim_destripe_amd import mini_zarr
 from aind_smartspim_destripe_amd import zarr_destriper as zd
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 E = eng_mod
 
 
@@ -234,28 +233,14 @@ def test_plain_zlib_chunk_files(tmp_path):
 
 
 # ---- the g++ build, and malformed input under the sanitizers --------------------------------------------------------
-def _write_records(path, recs):
-    with open(path, "wb") as f:
-        for data, want, kind in recs:
-            f.write(struct.pack("<III", len(data), want, kind))
-            f.write(data)
-
-
-def _build(tmp_path_factory, flags):
-    exe = str(tmp_path_factory.mktemp("infdec") / "inflate_dec_check")
-    subprocess.run(["g++", "-std=c++17", "-Wall"] + flags + ["-o", exe, os.path.join(HERE, "host", "inflate_dec_check.cpp")],
-                   check=True)  # fmt: skip
-    return exe
-
-
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    return _build(tmp_path_factory, ["-O2"])
+    return zc.build_task_exe(tmp_path_factory)
 
 
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    return _build(tmp_path_factory, ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    return zc.build_task_exe(tmp_path_factory, sanitize=True)
 
 
 def _table_records(t):
@@ -264,7 +249,7 @@ def _table_records(t):
 
 def _decode(exe, tmp_path, recs):
     rec, out = str(tmp_path / "rec.bin"), str(tmp_path / "out.bin")
-    _write_records(rec, recs)
+    zc.write_records(rec, recs)
     r = subprocess.run([exe, "decode", rec, out], capture_output=True, text=True,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))  # fmt: skip
     assert r.returncode == 0, r.stderr[-3000:]
@@ -317,7 +302,7 @@ def test_mutations_under_sanitizers(asan_exe, tmp_path):
     recs.append((ic.deflate(raw, 6, zlib.Z_FIXED), len(raw), E.TASK_ZLIB))
     recs.append((ic.deflate(raw, 0), len(raw), E.TASK_ZLIB))
     rec = str(tmp_path / "rec.bin")
-    _write_records(rec, recs)
+    zc.write_records(rec, recs)
     r = subprocess.run([asan_exe, "mutate", rec, "300", "1"], capture_output=True, text=True,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))  # fmt: skip
     assert r.returncode == 0, r.stderr[-3000:]

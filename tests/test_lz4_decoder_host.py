@@ -1,5 +1,6 @@
-"""The device decoder beyond unsplit zstd (``csrc/dsx_lz4_dec.h``: LZ4 blocks, split streams, bit un-shuffle), built on
-the host: as ``dsx_blosc_decode_ref`` of the library and with g++ from ``tests/host/lz4_dec_check.cpp`` (also under
+"""The device decoder beyond unsplit zstd (``csrc/dsx_lz4_dec.h``: LZ4 blocks; ``csrc/dsx_zdec_task.h``: split streams,
+bit un-shuffle), built on
+the host: as ``dsx_blosc_decode_ref`` of the library and with g++ from ``tests/host/zdec_task_check.cpp`` (also under
 ASan / UBSan).  ``dsx_io_read_frames_ex`` in mode ``DSX_ZDEC_ANY`` routes these frames to the device and mode 0 keeps
 them on the host; the frames of the real c-blosc 1.21.0 (``tests/golden/blosc_frames.npz``) decode to their payload;
 hand-assembled blocks cover the corners of the formats; malformed tasks end in a status.  No GPU needed."""
@@ -12,11 +13,10 @@ import numpy as np
 import pytest
 
 import blosc_any_frames as baf
+import zdec_cases as zc
 from aind_smartspim_destripe_amd import engine as eng_mod
 from aind_smartspim_destripe_amd import mini_zarr
 from aind_smartspim_destripe_amd import zarr_destriper as zd
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _read(tmp_path, frame, nbytes, mode, name="chunk"):
@@ -148,34 +148,20 @@ def _records(tmp_path, frames):
     return recs, want
 
 
-def _write_records(path, recs):
-    with open(path, "wb") as f:
-        for data, want, kind in recs:
-            f.write(struct.pack("<III", len(data), want, kind))
-            f.write(data)
-
-
-def _build(tmp_path_factory, flags):
-    exe = str(tmp_path_factory.mktemp("lz4dec") / "lz4_dec_check")
-    subprocess.run(["g++", "-std=c++17", "-Wall"] + flags + ["-o", exe, os.path.join(HERE, "host", "lz4_dec_check.cpp")],
-                   check=True)  # fmt: skip
-    return exe
-
-
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    return _build(tmp_path_factory, ["-O2"])
+    return zc.build_task_exe(tmp_path_factory)
 
 
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    return _build(tmp_path_factory, ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    return zc.build_task_exe(tmp_path_factory, sanitize=True)
 
 
 def test_gxx_build_decodes_the_corpus(check_exe, tmp_path):
     recs, want = _records(tmp_path, baf.hand_frames())
     rec, out = str(tmp_path / "rec.bin"), str(tmp_path / "out.bin")
-    _write_records(rec, recs)
+    zc.write_records(rec, recs)
     subprocess.run([check_exe, "decode", rec, out], check=True)
     blob, at = open(out, "rb").read(), 0
     for (_, n, kind), w in zip(recs, want):
@@ -209,7 +195,7 @@ def test_mutations_under_sanitizers(asan_exe, tmp_path):
     assert {eng_mod.TASK_LZ4, eng_mod.TASK_LZ4 | eng_mod.TASK_SPLIT, eng_mod.TASK_ZSTD | eng_mod.TASK_SPLIT,
             eng_mod.TASK_LZ4 | eng_mod.TASK_SPLIT | eng_mod.TASK_BITSHUFFLE} <= kinds  # fmt: skip
     rec = str(tmp_path / "rec.bin")
-    _write_records(rec, recs)
+    zc.write_records(rec, recs)
     r = subprocess.run([asan_exe, "mutate", rec, "300", "1"], capture_output=True, text=True,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))  # fmt: skip
     assert r.returncode == 0, r.stderr[-3000:]

@@ -14,7 +14,6 @@ import blosc_any_frames as baf
 import test_zstd_decoder_host as zh
 import zdec_cases as zc
 from aind_smartspim_destripe_amd import engine as eng_mod
-from test_lz4_decoder_host import _write_records as write_task_records
 
 
 @pytest.fixture(scope="module")
@@ -34,8 +33,7 @@ def asan_zstd(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def asan_tasks(tmp_path_factory):
-    return zc.build_check_exe(str(tmp_path_factory.mktemp("zc_asan") / "lz4_dec_check"), sanitize=True,
-                              source="lz4_dec_check.cpp")  # fmt: skip
+    return zc.build_task_exe(tmp_path_factory, sanitize=True)
 
 
 # ---- the helpers themselves --------------------------------------------------------------------------------------------
@@ -158,12 +156,12 @@ def test_lz4_window_walk_follows_the_python_decoder():
 
 # ---- C -------------------------------------------------------------------------------------------------------------------
 def test_malformed_tasks_under_sanitizers_first(asan_zstd, asan_tasks, tmp_path):
-    """Every input of section C through the ASan / UBSan builds: as a task (``lz4_dec_check``), and the bare frames
+    """Every input of section C through the ASan / UBSan builds: as a task (``zdec_task_check``), and the bare frames
     through ``zstd_dec_check`` too."""
     cases = zc.malformed_cases()
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
     rec, out = str(tmp_path / "tasks.bin"), str(tmp_path / "tasks.out")
-    write_task_records(rec, [(b, n, kind) for _, b, n, kind, _ in cases])
+    zc.write_records(rec, [(b, n, kind) for _, b, n, kind, _ in cases])
     r = subprocess.run([asan_tasks, "decode", rec, out], capture_output=True, text=True, env=env)
     assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
     blob = open(out, "rb").read()
@@ -173,7 +171,7 @@ def test_malformed_tasks_under_sanitizers_first(asan_zstd, asan_tasks, tmp_path)
         assert st != 0 and (want is None or st == want), (name, st, want)
     bare = [(b, n) for _, b, n, kind, _ in cases if kind == eng_mod.TASK_ZSTD]
     rec = str(tmp_path / "frames.bin")
-    zh._write_records(rec, bare)
+    zc.write_records(rec, bare)
     r = subprocess.run([asan_zstd, "decode", rec, out], capture_output=True, text=True, env=env)
     assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
     assert len(open(out, "rb").read()) == 4 * len(bare)

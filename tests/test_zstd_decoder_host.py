@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import zdec_cases as zc  # (it imports this module in turn: neither uses the other while it loads)
 from aind_smartspim_destripe_amd import engine as eng_mod
 from aind_smartspim_destripe_amd import mini_zarr, synth
 
@@ -122,24 +123,14 @@ def zstd_decode_ref(frame, n):
     return int(status[0]), (out.tobytes() if status[0] == 0 else None)
 
 
-def _write_records(path, items):
-    with open(path, "wb") as f:
-        for frame, want in items:
-            f.write(struct.pack("<II", len(frame), want))
-            f.write(frame)
-
-
 @pytest.fixture(scope="module")
 def check_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("zdec") / "zstd_dec_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-o", exe, os.path.join(HERE, "host", "zstd_dec_check.cpp")],
-                   check=True)  # fmt: skip
-    return exe
+    return zc.build_check_exe(str(tmp_path_factory.mktemp("zdec") / "zstd_dec_check"))
 
 
 def _decode_gxx(exe, tmp_path, items):
     rec, out = str(tmp_path / "rec.bin"), str(tmp_path / "out.bin")
-    _write_records(rec, items)
+    zc.write_records(rec, items)
     subprocess.run([exe, "decode", rec, out], check=True)
     blob = open(out, "rb").read()
     res, at = [], 0
@@ -415,10 +406,7 @@ def test_blosc_corpus_through_reader_and_ref(tmp_path):
 # ---- malformed input: CPU sanitizers ---------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def asan_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("zdec_asan") / "zstd_dec_check")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-o", exe, os.path.join(HERE, "host", "zstd_dec_check.cpp")], check=True)  # fmt: skip
-    return exe
+    return zc.build_check_exe(str(tmp_path_factory.mktemp("zdec_asan") / "zstd_dec_check"), sanitize=True)
 
 
 def test_mutations_under_sanitizers(asan_exe, tmp_path, corpus):
@@ -426,7 +414,7 @@ def test_mutations_under_sanitizers(asan_exe, tmp_path, corpus):
     assert len(pick) == 5
     pick.append(("hand",) + _hand_frame())
     rec = str(tmp_path / "rec.bin")
-    _write_records(rec, [(f, len(d)) for _, f, d in pick])
+    zc.write_records(rec, [(f, len(d)) for _, f, d in pick])
     r = subprocess.run([asan_exe, "mutate", rec, "600", "1"], capture_output=True, text=True,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))  # fmt: skip
     assert r.returncode == 0, r.stderr[-3000:]

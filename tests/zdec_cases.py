@@ -238,15 +238,30 @@ def mode_table(frames, flag):
 
 
 def build_check_exe(path, sanitize=False, source="zstd_dec_check.cpp"):
+    """g++ build of a stand-alone check program of tests/host: ``zstd_dec_check.cpp`` (bare frames, the stats walker) or
+    ``zdec_task_check.cpp`` (tasks of every kind); ``sanitize``: under ASan / UBSan."""
     flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
     subprocess.run(["g++", "-std=c++17", "-Wall"] + flags + ["-o", path, os.path.join(HERE, "host", source)], check=True)
     return path
 
 
+def build_task_exe(tmp_path_factory, sanitize=False):
+    return build_check_exe(str(tmp_path_factory.mktemp("zdec_task") / "zdec_task_check"), sanitize, "zdec_task_check.cpp")
+
+
+def write_records(path, recs):
+    """The records file of a check program: ``(frame, output bytes)`` each for ``zstd_dec_check``, ``(task bytes,
+    output bytes, kind)`` for ``zdec_task_check``."""
+    with open(path, "wb") as f:
+        for data, *words in recs:
+            f.write(struct.pack("<{}I".format(1 + len(words)), len(data), *words))
+            f.write(data)
+
+
 def frame_stats(exe, tmp_path, frames):
     """[{name: count}] per frame from ``zstd_dec_check stats`` (batches of kSeqBatch sequences)."""
     rec = str(tmp_path / "stats_rec.bin")
-    zh._write_records(rec, [(f, len(d)) for _, f, d in frames])
+    write_records(rec, [(f, len(d)) for _, f, d in frames])
     r = subprocess.run([exe, "stats", rec, str(kernel_constants()["kSeqBatch"])], check=True, capture_output=True,
                        text=True)  # fmt: skip
     lines = r.stdout.strip().splitlines()
@@ -420,7 +435,7 @@ def lz4_window_stream():
 
 
 def lz4_window_walk(stream):
-    """The reads of ``lz4_wave`` replayed next to ``baf.lz4_decompress_py``: the window is refilled at the first byte
+    """The reads of ``lz_wave`` replayed next to ``baf.lz4_decompress_py``: the window is refilled at the first byte
     asked for outside it; a literal run is copied out of the window when it lies in it once its sequence is parsed,
     else out of the stream ("crossing": it began in a window and ran over its edge; "outside": any other).  Counts."""
     win = kernel_constants()["kLz4Win"]
@@ -456,7 +471,7 @@ def lz4_window_walk(stream):
             _, ip = length(token & 15, ip + 2)
         lo, hi = state["lo"], state["lo"] + state["cnt"]
         if ll:
-            if lit >= lo and lit + ll <= hi:  # (the test of lz4_wave, after the whole sequence was parsed)
+            if lit >= lo and lit + ll <= hi:  # (the test of lz_wave, after the whole sequence was parsed)
                 c["staged"] += 1
             elif lit < edge < lit + ll:
                 c["crossing"] += 1
@@ -563,6 +578,26 @@ def layout_paths(facts):
     for r in range(4):
         hit("src % 4 = {}".format(r), any(f["src"] % 4 == r and f["kind"] != E.TASK_FILL for f in facts))
     return paths
+
+
+# ---- the status table --------------------------------------------------------------------------------------------------------
+STATUS_TABLE = os.path.join(HERE, "golden", "zdec_task_statuses.npz")
+
+
+def status_table(who):
+    """The table of tools/make_golden_zdec_statuses.py -- every kind 0 .. 7 under the flag words 0, 0x100, 0x200, 0x400,
+    0x300, 0x600, 0x500, 0x800 with a valid, a cut and a raw payload, 32 bytes of output each, and an odd split task per
+    kind -- with the statuses and the bytes on record for ``who`` ("host": ``dsx_blosc_decode_ref``, "device": the
+    kernels on an MI355X), both of the commit before the three host task runners became one."""
+    rec = np.load(STATUS_TABLE)
+    t = Table()
+    t.packed = bytearray(rec["packed"].tobytes())
+    t.rows = [tuple(int(v) for v in r) for r in rec["rows"]]
+    t.names = [str(n) for n in rec["names"]]
+    t.status = [int(s) for s in rec[who + "_status"]]
+    t.expect = [rec[who + "_out"][i, : r[3]].tobytes() if st == 0 else None for i, (r, st) in enumerate(zip(t.rows, t.status))]
+    t.end = max(r[1] + r[3] for r in t.rows)
+    return t
 
 
 # ---- C: malformed zstd tasks ---------------------------------------------------------------------------------------------

@@ -88,6 +88,8 @@ try:
             else:
                 inner = ic.ZLIB if recode == "blosc-zlib" else baf.BLOSCLZ
                 frames = pool.starmap(ic.blosc_frame, [(r, 256 * 1024, inner, baf.SHUFFLE, True) for r in raws])
+            pool.close()  # the workers leave by themselves: under rocprofv3, which handles SIGTERM in every child, the
+            pool.join()   # terminate() of the with-block never saw them exit and the run hung before it reached the GPU
         for zb in range(n // 64):
             for (y, x), f in zip(yx, frames):
                 p = src._chunk_path((0, 0, zb, y, x))
