@@ -1,9 +1,14 @@
 // dsx.hip -- C ABI of the MI355X destripe engine (see include/dsx.h) and the launch pipeline.
 //
 // Pipeline per cohort part (a cohort of <= max_batch planes is split into parts that run on separate
-// HIP streams; no host synchronisation inside):
-//   k_zero3  ->  k_fwd_march x L  ->  k_hist x L  ->  k_otsu  ->  k_rowfilter x L
-//   ->  k_inv_march<pyramid> x (L-1)  ->  k_inv_march<final>
+// HIP streams; no host synchronisation inside) -- run_cohort and its stages; what is fused and every grid, block and
+// LDS size is decided by dsx_chain.h:
+//   k_zero3  ->  k_fwd_march<fused: levels 1 + 2>, k_fwd_march per level from 3  ->  k_hist (one launch per stream)
+//   ->  k_otsu  ->  k_rowfilter (level 2), k_rowfilter_multi (the coarse levels in one launch)
+//   ->  k_inv_march per level down to 3  ->  k_rowfinal (level-1 row filter + levels 2 and 1 of the synthesis + finish)
+// An unsplit cohort runs the wide levels' k_hist and k_rowfilter on a helper stream beside the coarse levels' launches.
+// Planes the fused kernels do not take (widths that are no multiple of 4 / 8, float32, other FFT plans) fall back piece
+// by piece: k_inv_march<fused final> + k_rowfilter for level 1, one k_fwd_march / k_inv_march per level.
 // A wavelet other than db3 (dsx_set_wavelet) swaps k_fwd_gen / k_inv_gen (dsx_wavelet.h) in for the marching kernels.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -22,6 +27,7 @@
 #include "dsx_pyramid.h"
 #include "dsx_wavelet.h"
 #include "dsx_plan.h"
+#include "dsx_chain.h"
 #include "dsx_io.h"
 #include "dsx_streaks.h"
 #include "dsx_zenc_kernels.h"
@@ -43,31 +49,10 @@ struct ProfRec {
 
 }  // namespace
 
-// Launch-geometry switches of a context, read from the environment ONCE PER CONTEXT by dsx_init (INTEGRATION.md
-// section 6).  None of them may change a result: tools/fuzz_parity.py draws them per case (a fresh context each) and
-// tests/test_gpu_fuzz.py holds 30 such cases to the parity statement; out-of-range values are clamped here.
-struct DsxTuning {
-  int row_wpb = 0;            // DSX_ROW_WPB: waves per k_rowfilter block (0 = chosen per transform length)
-  int march_waves = 256 * 16; // DSX_MARCH_WAVES: waves a march launch aims at
-  bool no_quant = false;      // DSX_NO_QUANT: segment counts without the launch-quantisation score
-  int seg_min_rows = 4;       // DSX_SEG_MIN_ROWS: least rows per march segment of the plain level kernels
-  bool no_fuse = false;       // DSX_NO_FUSE: one forward launch per level (aa_1 materialised)
-  bool no_fuse_inv = false;   // DSX_NO_FUSE_INV: one inverse launch per level
-  bool no_pair = false;       // DSX_NO_PAIR: 8-byte pixel / result accesses in the final kernels
-  int hist_rows = 0;          // DSX_HIST_ROWS: rows per k_hist block (0 = chosen per cohort size)
-  int fwd_wpb = 8, inv_wpb = 8;  // DSX_FWD_WPB / DSX_INV_WPB: waves per block of the fused march kernels (4 or 8)
-  bool no_row_multi = false;  // DSX_NO_ROW_MULTI: one row-filter launch per coarse level
-  int row_multi_alone = 48;   // DSX_ROW_MULTI_ALONE: largest unsplit cohort that takes the merged coarse row filter
-  int helper = -1;            // DSX_HELPER: -1 = helper stream for unsplit cohorts only, 0 / 1 = never / always
-  bool no_pipeline = false;   // DSX_NO_PIPELINE: join the sub-cohort streams at every call
-#ifdef DSX_DIAG
-  int skip_hist = 0, skip_row = 0, skip_from = 1000;  // timing-only: WRONG results (DSX_SKIP_HIST / _ROW / _COARSE)
-#endif
-};
-
 struct dsx_ctx {
   int device = 0;
   DsxTuning tune;
+  int cus = 256;  // compute units of the device (march_segments' launch-quantisation score); 256 when it does not say
   hipStream_t stream_ = nullptr;  // the context ("compute") stream; entry points reach it through use_main()
   std::string err;
   bool planned = false;
@@ -130,8 +115,6 @@ struct dsx_ctx {
   unsigned* d_sticky = nullptr;
   // dsx_set_stack_mode: the planes of a call share ONE Otsu threshold per level (the reference's 3-D input mode)
   bool stack_mode = false;
-  bool no_fuse_rf = false;  // DSX_NO_FUSE_RF=1: k_rowfilter + k_inv_march instead of k_rowfinal (same bits)
-  bool fuse_rf_wide = false;  // DSX_FUSE_RF_WIDE=1: k_rowfinal for 2000- / 1800-wide planes too (slower there; rowfinal_plan)
   // DSX_ABLATE environment variable (timing-only switches that return WRONG pixels): read only by a library built
   // with -DDSX_DIAG (tools/build_variant.sh); the product build has no such switch
   int ablate = 0;
@@ -219,42 +202,6 @@ struct CohortView {
 
 namespace {
 
-// the tuning of the context whose launch chain this thread is enqueueing (set by run_cohort_split / the stand-alone
-// entry points; the launch helpers below have no context argument)
-thread_local const DsxTuning* t_tune = nullptr;
-const DsxTuning& tune() {
-  static const DsxTuning defaults;
-  return t_tune ? *t_tune : defaults;
-}
-
-int env_int(const char* name, int fallback) {
-  const char* v = getenv(name);
-  return (v && *v) ? atoi(v) : fallback;
-}
-
-void read_tuning(DsxTuning& t) {
-  t.row_wpb = env_int("DSX_ROW_WPB", 0);
-  if (t.row_wpb != 0) t.row_wpb = std::max(4, std::min(t.row_wpb, (int)dsx::kRowMaxWaves));
-  t.march_waves = std::max(64, env_int("DSX_MARCH_WAVES", 256 * 16));
-  t.no_quant = env_int("DSX_NO_QUANT", 0) != 0;
-  t.seg_min_rows = std::max(2, env_int("DSX_SEG_MIN_ROWS", 4));
-  t.no_fuse = env_int("DSX_NO_FUSE", 0) != 0;
-  t.no_fuse_inv = env_int("DSX_NO_FUSE_INV", 0) != 0;
-  t.no_pair = env_int("DSX_NO_PAIR", 0) != 0;
-  t.hist_rows = std::max(0, env_int("DSX_HIST_ROWS", 0));
-  t.fwd_wpb = env_int("DSX_FWD_WPB", 8) == 4 ? 4 : 8;
-  t.inv_wpb = env_int("DSX_INV_WPB", 8) == 4 ? 4 : 8;
-  t.no_row_multi = env_int("DSX_NO_ROW_MULTI", 0) != 0;
-  t.row_multi_alone = std::max(0, env_int("DSX_ROW_MULTI_ALONE", 48));
-  t.helper = getenv("DSX_HELPER") ? (env_int("DSX_HELPER", 0) != 0 ? 1 : 0) : -1;
-  t.no_pipeline = env_int("DSX_NO_PIPELINE", 0) != 0;
-#ifdef DSX_DIAG
-  t.skip_hist = env_int("DSX_SKIP_HIST", 0);
-  t.skip_row = env_int("DSX_SKIP_ROW", 0);
-  t.skip_from = env_int("DSX_SKIP_COARSE", 1000);
-#endif
-}
-
 int fail(dsx_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
   else g_init_error = msg;  // context-free calls (dsx_io_*): dsx_last_error(NULL) reports it
@@ -321,139 +268,67 @@ struct LaunchScope {
   }
 };
 
-// Waves (row pairs) per block: they share one twiddle table in LDS; pick the count that puts the
-// most waves on a CU (160 KiB LDS, at most 16 waves at 4 waves per SIMD).
-int rowfilter_waves_per_block(int M) {
-  int best_w = 4, best_total = 0;
-  for (int w = 4; w <= dsx::kRowMaxWaves; ++w) {
-    const size_t bytes = (size_t)M * (w + 1) * sizeof(float2);
-    const int blocks = (int)std::min<size_t>(160 * 1024 / bytes, 8);
-    const int total = std::min(blocks * w, 16);
-    if (total > best_total) { best_total = total; best_w = w; }
-  }
-  return best_w;
+// Raises a kernel's dynamic LDS limit, once per device (one flag array per kernel: a template over its address).
+template <auto KERN>
+hipError_t raise_lds_limit(size_t bytes = dsx::kLdsLimit) {
+  static bool done[64] = {};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (done[dev & 63]) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) done[dev & 63] = true;
+  return e;
 }
 
 template <int CPL, int GF = -1, int NT = -1, int HALO = -1, int PLAN = 0>
-hipError_t launch_rowfilter(const dsx::RowArgs& a_in, int npairs, int nb, hipStream_t s) {
-  static bool attr_set[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!attr_set[dev & 63]) {
-    hipError_t e = hipFuncSetAttribute((const void*)dsx::k_rowfilter<CPL, GF, NT, HALO, PLAN>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set[dev & 63] = true;
-  }
-  int force_wpb = tune().row_wpb;
-  if (force_wpb && (size_t)a_in.M * (force_wpb + 1) * sizeof(float2) > 160 * 1024) force_wpb = 0;  // would not fit the LDS
-  // M >= 1024 (level 2 of the hot shapes, 77 KB per 8-wave block): 4-wave blocks of 43 KB.  Alone the kernel does not
-  // care; beside the 74 KB blocks of k_rowfinal and the small coarse-level blocks three of them still find room on a CU
-  // where two of the big ones do not (+0.6 % 4-stream, +1.3 % single-stream, gpurun_out/wpb_sweep.txt)
-  const int wpb = force_wpb ? force_wpb : ((CPL > 18 || a_in.M >= 1024) ? 4 : rowfilter_waves_per_block(a_in.M));
-  const size_t smem = (size_t)a_in.M * (wpb + 1) * sizeof(float2);
-  const dsx::RowArgs& a = a_in;
-  const dim3 grid((npairs + wpb - 1) / wpb, nb);
-  hipLaunchKernelGGL((dsx::k_rowfilter<CPL, GF, NT, HALO, PLAN>), grid, dim3(64 * wpb), smem, s, a);
+hipError_t launch_rowfilter(const DsxTuning& t, const dsx::RowArgs& a, int npairs, int nb, hipStream_t s) {
+  if (hipError_t e = raise_lds_limit<dsx::k_rowfilter<CPL, GF, NT, HALO, PLAN>>()) return e;
+  const dsx::RowLaunch g = dsx::rowfilter_launch(t, CPL, a.M, npairs);
+  hipLaunchKernelGGL((dsx::k_rowfilter<CPL, GF, NT, HALO, PLAN>), dim3(g.grid_x, nb), dim3(64 * g.wpb), g.lds, s, a);
   return hipGetLastError();
 }
 
 // rows longer than one wave holds: one 512-lane block per row pair, the row buffer is the block's LDS
 hipError_t launch_rowfilter_wide(const dsx::RowArgs& a, int npairs, int nb, hipStream_t s) {
-  static bool attr_set[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!attr_set[dev & 63]) {
-    hipError_t e = hipFuncSetAttribute((const void*)dsx::k_rowfilter_wide, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(dsx::kWideMaxLen * sizeof(float2)));
-    if (e != hipSuccess) return e;
-    attr_set[dev & 63] = true;
-  }
+  if (hipError_t e = raise_lds_limit<dsx::k_rowfilter_wide>(dsx::kWideMaxLen * sizeof(float2))) return e;
   if (a.M > dsx::kWideMaxLen || a.w >= 65536) return hipErrorInvalidValue;  // (the plan refuses these lengths)
   hipLaunchKernelGGL(dsx::k_rowfilter_wide, dim3(npairs, nb), dim3(dsx::kWideThreads), (size_t)a.M * sizeof(float2), s, a);
   return hipGetLastError();
 }
 
-hipError_t dispatch_rowfilter(const dsx::RowArgs& a, int npairs, int nb, hipStream_t s) {
-  const int cpl = (a.M + 63) / 64;
-  if (cpl > 36) return launch_rowfilter_wide(a, npairs, nb, s);
-  // slot structure of the row (full 256-value groups, 64-value tail slots) and pass list: the wide levels of
-  // 2048-, 2000- and 1800-wide planes have instantiations with all of it as compile-time constants
-  const int gf = a.w >> 8, nt = (a.w - (gf << 8) + 63) >> 6;
-  auto plan_is = [&](int m, int r0, int r1, int r2) {
-    return a.M == m && a.npass == 3 && a.radix[0] == r0 && a.radix[1] == r1 && a.radix[2] == r2;
-  };
-  if (cpl <= 2) return launch_rowfilter<2>(a, npairs, nb, s);
-  if (cpl <= 4) return launch_rowfilter<4>(a, npairs, nb, s);
-  if (cpl <= 6) return launch_rowfilter<6>(a, npairs, nb, s);
-  if (cpl <= 10) return launch_rowfilter<10>(a, npairs, nb, s);
-  if (cpl <= 18) {
-    if (gf == 4 && nt == 1 && a.K == 0) {
-      if (plan_is(1026, 19, 9, 6))
-        return launch_rowfilter<18, 4, 1, 0, 1>(a, npairs, nb, s);
-      return launch_rowfilter<18, 4, 1, 0>(a, npairs, nb, s);
-    }
-    if (gf == 2 && nt == 1 && a.K > 0) {
-      if (plan_is(1071, 17, 9, 7))
-        return launch_rowfilter<18, 2, 1, 1, 2>(a, npairs, nb, s);
-      return launch_rowfilter<18, 2, 1, 1>(a, npairs, nb, s);
-    }
-    if (gf == 1 && nt == 4 && a.K > 0) {
-      if (plan_is(1024, 16, 8, 8)) return launch_rowfilter<18, 1, 4, 1, 5>(a, npairs, nb, s);
-      if (plan_is(960, 15, 8, 8)) return launch_rowfilter<18, 1, 4, 1, 6>(a, npairs, nb, s);
-    }
-    return launch_rowfilter<18>(a, npairs, nb, s);
+// the k_rowfilter instantiation of a row's class (dsx::classify_row)
+hipError_t dispatch_rowfilter(const DsxTuning& t, const dsx::RowArgs& a, int npairs, int nb, hipStream_t s) {
+  const dsx::RowClass c = dsx::classify_row(a.M, a.w, a.K, a.npass, a.radix);
+  if (c.wide) return launch_rowfilter_wide(a, npairs, nb, s);
+  switch (c.cpl) {
+    case 2: return launch_rowfilter<2>(t, a, npairs, nb, s);
+    case 4: return launch_rowfilter<4>(t, a, npairs, nb, s);
+    case 6: return launch_rowfilter<6>(t, a, npairs, nb, s);
+    case 10: return launch_rowfilter<10>(t, a, npairs, nb, s);
+    case 18:
+      if (c.plan == 1) return launch_rowfilter<18, 4, 1, 0, 1>(t, a, npairs, nb, s);
+      if (c.gf == 4) return launch_rowfilter<18, 4, 1, 0>(t, a, npairs, nb, s);
+      if (c.plan == 2) return launch_rowfilter<18, 2, 1, 1, 2>(t, a, npairs, nb, s);
+      if (c.gf == 2) return launch_rowfilter<18, 2, 1, 1>(t, a, npairs, nb, s);
+      if (c.plan == 5) return launch_rowfilter<18, 1, 4, 1, 5>(t, a, npairs, nb, s);
+      if (c.plan == 6) return launch_rowfilter<18, 1, 4, 1, 6>(t, a, npairs, nb, s);
+      return launch_rowfilter<18>(t, a, npairs, nb, s);
+    default:
+      if (c.plan == 3) return launch_rowfilter<36, 3, 4, 1, 3>(t, a, npairs, nb, s);
+      if (c.plan == 4) return launch_rowfilter<36, 3, 3, 1, 4>(t, a, npairs, nb, s);
+      return launch_rowfilter<36>(t, a, npairs, nb, s);
   }
-  if (a.K > 0 && gf == 3) {
-    if (nt == 4 && plan_is(2048, 16, 16, 8)) return launch_rowfilter<36, 3, 4, 1, 3>(a, npairs, nb, s);
-    if (nt == 3 && plan_is(1815, 15, 11, 11)) return launch_rowfilter<36, 3, 3, 1, 4>(a, npairs, nb, s);
-  }
-  return launch_rowfilter<36>(a, npairs, nb, s);
-}
-
-// Level-1 row filter + final synthesis in one kernel (k_rowfinal): Delta_1 stays in LDS.  Shapes that take it: see the
-// kernel's header.  DSX_NO_FUSE_RF=1 (read by dsx_init) keeps the two kernels: A/B runs and the bit-identity test.
-// Returns the StaticFft plan id of the instantiation (1, 3, 4) or 0.
-int rowfinal_plan(const dsx::Plan& p, const dsx::LevelPlan& lp, int in_dtype, int out_dtype, bool pair_io, bool wide) {
-  if (!pair_io || in_dtype != DSX_U16 || out_dtype != DSX_U16) return 0;
-  if ((lp.w & 1) != 0 || (p.Wout + dsx::kMarchCols - 1) / dsx::kMarchCols > dsx::kRfWaves) return 0;
-  const int gf = lp.w >> 8, nt = (lp.w - (gf << 8) + 63) >> 6;
-  auto plan_is = [&](int m, int r0, int r1, int r2) {
-    return lp.M == m && lp.npass == 3 && lp.radix[0] == r0 && lp.radix[1] == r1 && lp.radix[2] == r2;
-  };
-  // wide (DSX_FUSE_RF_WIDE=1, read by dsx_init; OFF by default): the embedded plans of 2000- and 1800-wide planes.  Their
-  // FFT buffers are 16 KB per wave: one 8-wave block per CU, the two phases of a block cannot hide behind another
-  // block's, and the fused kernel LOSES 10-12 % against k_rowfilter + k_inv_march there (1600 x 2000: 53.8 k against
-  // 59.8 k planes/s, 1800^2: 54.8 k against 62.8 k; profiles/r3_fused_rowfinal_ab.txt).  Bit-identical all the same
-  // (tests/test_gpu_parity.py::test_fused_rowfinal_is_bit_identical_to_the_unfused_chain runs them with the switch on).
-  if (gf == 4 && nt == 1 && lp.K == 0 && plan_is(1026, 19, 9, 6)) return 1;
-  if (wide && lp.K > 0 && gf == 3 && nt == 4 && plan_is(2048, 16, 16, 8)) return 3;
-  if (wide && lp.K > 0 && gf == 3 && nt == 3 && plan_is(1815, 15, 11, 11)) return 4;
-  return 0;
 }
 
 template <int CPL, int GF, int NT, int HALO, int PLAN>
 hipError_t launch_rowfinal_t(const dsx::RowFinalArgs& a, int nb, hipStream_t s) {
-  static bool attr_set[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  auto kern = dsx::k_rowfinal<CPL, GF, NT, HALO, PLAN>;
-  if (!attr_set[dev & 63]) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set[dev & 63] = true;
-  }
-  const size_t smem = (size_t)a.r.M * (dsx::kRfWaves + 1) * sizeof(float2);
-  const int np = (a.f.hout + 1) / 2;
-  int nblk = (np + dsx::kRfRows - 1) / dsx::kRfRows;
-#if DSX_RF_XCD
-  nblk = (nblk + 7) / 8 * 8;  // the kernel deals runs of consecutive blocks to the 8 compute dies
-#endif
-  const dim3 grid(nblk, nb);
-  hipLaunchKernelGGL(kern, grid, dim3(64 * dsx::kRfWaves), smem, s, a);
+  if (hipError_t e = raise_lds_limit<dsx::k_rowfinal<CPL, GF, NT, HALO, PLAN>>()) return e;
+  const dsx::RowLaunch g = dsx::rowfinal_launch(a.r.M, a.f.hout, DSX_RF_XCD != 0);
+  hipLaunchKernelGGL((dsx::k_rowfinal<CPL, GF, NT, HALO, PLAN>), dim3(g.grid_x, nb), dim3(64 * g.wpb), g.lds, s, a);
   return hipGetLastError();
 }
 
+// plan: dsx::rowfinal_plan of the part (the plan id the classifier gives level 1)
 hipError_t launch_rowfinal(int plan, const dsx::RowFinalArgs& a, int nb, hipStream_t s) {
   if (plan == 1) return launch_rowfinal_t<18, 4, 1, 0, 1>(a, nb, s);
   if (plan == 3) return launch_rowfinal_t<36, 3, 4, 1, 3>(a, nb, s);
@@ -463,266 +338,192 @@ hipError_t launch_rowfinal(int plan, const dsx::RowFinalArgs& a, int nb, hipStre
 
 // Levels whose row filters all fit the CPL = 6 class, in ONE launch (k_rowfilter_multi).
 hipError_t launch_rowfilter_multi(const dsx::RowMultiArgs& a_in, const int* npairs, int nb, hipStream_t s) {
-  static bool attr_set[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!attr_set[dev & 63]) {
-    hipError_t e = hipFuncSetAttribute((const void*)dsx::k_rowfilter_multi<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set[dev & 63] = true;
-  }
-  const int wpb = dsx::kRowMaxWaves;
+  if (hipError_t e = raise_lds_limit<dsx::k_rowfilter_multi<6>>()) return e;
   dsx::RowMultiArgs a = a_in;
-  int blocks = 0, max_m = 1;
-  for (int i = 0; i < a.nlev; ++i) {
-    blocks += (npairs[i] + wpb - 1) / wpb;
-    a.blk_end[i] = blocks;
-    max_m = std::max(max_m, a.lv[i].M);
-  }
-  const size_t smem = (size_t)max_m * (wpb + 1) * sizeof(float2);
-  hipLaunchKernelGGL(dsx::k_rowfilter_multi<6>, dim3(blocks, nb), dim3(64 * wpb), smem, s, a);
+  int M[dsx::kRowMultiMax];
+  for (int i = 0; i < a.nlev; ++i) M[i] = a.lv[i].M;
+  const dsx::RowLaunch g = dsx::row_multi_launch(a.nlev, npairs, M, a.blk_end);
+  hipLaunchKernelGGL(dsx::k_rowfilter_multi<6>, dim3(g.grid_x, nb), dim3(64 * g.wpb), g.lds, s, a);
   return hipGetLastError();
 }
 
-// Row segmentation of the marching kernels: enough waves to fill the chip for small cohorts,
-// one segment per strip for large ones (each extra segment re-reads a 4-row halo).
-// wpb > 0 (the fused level-1 kernels, wpb waves per block, 16 waves per CU): the segment count is also chosen against
-// the QUANTISATION of the launch -- blocks run in rounds of (CUs x 16 / wpb); 576 equal blocks on 512 slots take two
-// rounds, 512 take one.  Among the counts around the target the one with the smallest rounds x (rows per segment +
-// halo_rows) wins (halo_rows: the rows a segment recomputes, in the units of `rows`).
-void march_segments(int nb, int nstrips, int rows, int* nseg, int* rows_per_seg, int wpb = 0, int halo_rows = 0,
-                    bool coarse = false) {
-  const int target_waves = tune().march_waves;
-  const bool no_quant = tune().no_quant;
-  int want = (target_waves + nb * nstrips - 1) / (nb * nstrips);
-  // Rows per segment, at least: 24 until late in round 3.  The coarse levels (260 rows and fewer) then ran as a few
-  // hundred waves marching 24+ rows each -- launches that are short on parallelism, not on work: levels 3 ... 8 hold 6 % of
-  // the coefficients and cost 19 % of the run (timing-only DSX_SKIP_COARSE, profiles/r3_coarse_levels.txt).  4 rows per
-  // segment (2 more of halo) gives them 3-6 x the waves and a march a sixth as long: +0.8 % on the whole run.  Only the
-  // plain level kernels take it (coarse = true); the fused level-1 + 2 kernels keep 24: at the cohort sizes that matter
-  // their segment count is set by the wave target, not by this floor.  (The first attempt gave them 4 rows too and failed
-  // the GPU suite -- through last segments of one or two level-2 rows, the bug fwd_march_body's i_first now fixes.)
-  const int seg_min_coarse = tune().seg_min_rows;
-  const int seg_min_rows = coarse ? seg_min_coarse : 24;
-  const int max_seg = std::max(1, rows / seg_min_rows);
-  want = std::max(1, std::min(want, max_seg));
-  if (wpb > 0 && !no_quant) {
-    static int cus = 0;
-    if (cus == 0) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-      if (cus <= 0) cus = 256;
-    }
-    const long long slots = (long long)cus * (16 / wpb);
-    double best = 1e300;
-    int best_n = want;
-    for (int n = std::max(1, want / 2); n <= std::min(max_seg, 2 * want + 1); ++n) {
-      const int rps = (rows + n - 1) / n;
-      const int ns = (rows + rps - 1) / rps;
-      const long long blocks = (long long)nb * ((nstrips * ns + wpb - 1) / wpb);
-      const long long rounds = (blocks + slots - 1) / slots;
-      // a launch that leaves most of the chip empty is no bargain either: count at least half a round
-      const double fill = std::max(0.5, (double)blocks / (double)slots);
-      const double cost = std::max((double)rounds, fill) * (double)(rps + halo_rows);
-      if (cost < best * 0.999) { best = cost; best_n = n; }
-    }
-    want = best_n;
-  }
-  int rps = (rows + want - 1) / want;
-  rps = std::max(1, std::min(rps, 4096));  // uint32 partial sums of k_fwd1_march
-  *rows_per_seg = rps;
-  *nseg = (rows + rps - 1) / rps;
+// One cohort part on its way through the chain: what the stages of run_cohort share.
+struct Chain {
+  dsx_ctx* ctx;
+  const CohortView& v;
+  dsx::ChainShape sh;
+  const void* d_in;
+  int in_dtype, nb;
+  void* d_out;
+  int out_dtype;
+};
+
+// DSX_SKIP_HIST / DSX_SKIP_ROW: bit masks of level indices whose histogram / row-filter launch is left out, and
+// DSX_SKIP_COARSE=k: no launch for levels with index >= k (what the chain would gain if those kernels were free).
+// The results are WRONG: the switches only exist in a -DDSX_DIAG build.
+struct Skips {
+  int hist, row, from;
+};
+Skips skips(const DsxTuning& t) {
+#ifdef DSX_DIAG
+  return {t.skip_hist, t.skip_row, t.skip_from};
+#else
+  (void)t;
+  return {0, 0, 1000};
+#endif
 }
 
-// One cohort of nb planes through the whole chain (asynchronous).
-int run_cohort(dsx_ctx* ctx, const CohortView& v, const void* d_in, int in_dtype, int nb, void* d_out,
-               int out_dtype, int32_t* d_cfg_used) {
-  const dsx::Plan& p = ctx->plan;
-  hipStream_t s = v.stream;
-  const int L = p.L;
-  const int Lc = L > 0 ? L : 1;
-  t_tune = &ctx->tune;  // the launch helpers of this thread follow this context's switches
-  {
-    // stats: 32 B per plane; minmax: 8 Lc B per plane (parts start at even planes -> 16-byte aligned
-    // except for odd Lc * po, handled by rounding the count up inside the part's own slice);
-    // hist: 1 KiB per plane and level
-    const int n0 = (int)(sizeof(dsx::PlaneStats) * nb / 16);
-    const int n2 = (int)(sizeof(unsigned) * 256 * Lc * (size_t)nb / 16);
-    const size_t mm_bytes = sizeof(unsigned) * 2 * Lc * (size_t)nb;
-    if ((mm_bytes % 16) == 0 && (((uintptr_t)v.minmax) % 16) == 0) {
-      const int n1 = (int)(mm_bytes / 16);
-      const int total = n0 + n1 + n2;
-      hipLaunchKernelGGL(dsx::k_zero3, dim3(std::min((total + 255) / 256, 1024)), dim3(256), 0, s, (uint4*)v.stats, n0,
-                         (uint4*)v.minmax, n1, (uint4*)v.hist, n2);
-      DSX_HIP(hipGetLastError());
-    } else {
-      DSX_HIP(hipMemsetAsync(v.stats, 0, sizeof(dsx::PlaneStats) * nb, s));
-      DSX_HIP(hipMemsetAsync(v.minmax, 0, mm_bytes, s));
-      DSX_HIP(hipMemsetAsync(v.hist, 0, sizeof(unsigned) * 256 * Lc * nb, s));
-    }
-  }
+// The IN_KIND instantiation of a level kernel: 0 / 1 = the level reads (or finishes) uint16 / float32 pixels, 2 = it
+// reads and writes the workspace only.  (The instantiations are named in the order 2, 0, 1 at every call: the order the
+// compiler emits them in, which the device-code comparison of profiles/chain_stages_device_code.txt holds still.)
+template <typename K>
+K pixel_kernel(int in_dtype, K k_u16, K k_f32) {
+  return in_dtype == DSX_U16 ? k_u16 : k_f32;
+}
+template <typename K>
+K level_kernel(bool pixels, int in_dtype, K k_ws, K k_u16, K k_f32) {
+  return pixels ? pixel_kernel(in_dtype, k_u16, k_f32) : k_ws;
+}
 
-  // ---- forward transform ------------------------------------------------------------------
-  // levels 1 + 2 in one kernel when the plane allows it (aa_1 never leaves the chip)
-  const bool no_fuse = ctx->tune.no_fuse;
-  // any wavelet but db3: tap-count-generic level kernels, one launch per level, nothing fused
-  const bool generic = ctx->wl_len > 0 && L > 0;
-  const bool fuse12 = !generic && !no_fuse && L >= 2 && (p.W % 4) == 0 && (p.lv[0].ldin % 4) == 0 && p.lv[0].h >= 16 &&
-                      p.lv[0].w >= 16;
-  const bool no_fuse_inv = ctx->tune.no_fuse_inv;
-  const bool fuse21 = fuse12 && !no_fuse_inv;
-  // uint16 planes whose rows and bases allow 16-byte pixel / result accesses by lane pairs (inv_march_body<.., PAIR>)
-  const bool no_pair = ctx->tune.no_pair;
-  const bool pair_io = !no_pair && in_dtype == DSX_U16 && (p.W % 8) == 0 && (p.H % 2) == 0 && p.Wout == p.W &&
-                       (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0 && ((size_t)p.H * p.W * 2) % 16 == 0;
-  // level-1 row filter inside the final kernel (k_rowfinal): not for the staged debug runs, which read Delta_1 back
-  const int rf_plan = (fuse21 && !ctx->no_fuse_rf && ctx->stop_after == 0) ? rowfinal_plan(p, p.lv[0], in_dtype, out_dtype, pair_io, ctx->fuse_rf_wide) : 0;
-  const bool fuse_rf = rf_plan != 0;
-  // The wide levels (1, 2) hold 94 % of the coefficients; the coarse levels are chains of small launches that
-  // leave most of the chip idle.  With the fused forward kernel the wide levels' data is complete early, so
-  // their histograms (and, below, their row filters) run on the part's helper stream BESIDE the coarse
-  // levels' launches instead of after them.
-  const bool split = v.helper != nullptr && fuse12 && L >= 3;
-  // DSX_SKIP_HIST / DSX_SKIP_ROW: bit masks of level indices whose histogram / row-filter launch is left out, and
-  // DSX_SKIP_COARSE=k: no launch for levels with index >= k (what the chain would gain if those kernels were free).
-  // The results are WRONG: the switches only exist in a -DDSX_DIAG build.
-#ifdef DSX_DIAG
-  const int skip_hist = ctx->tune.skip_hist, skip_row = ctx->tune.skip_row, skip_from = ctx->tune.skip_from;
-#else
-  constexpr int skip_hist = 0, skip_row = 0, skip_from = 1000;
-#endif
-  // histograms of levels [l0, l1) in ONE launch (k_hist finds its level from the block index)
-  auto hist_levels = [&](int l0, int l1, hipStream_t hs) -> int {
-    if (ctx->st_march) return DSX_OK;  // no mask: thr / cfg come from k_st_chainfill
-    dsx::HistArgs a;
-    memset(&a, 0, sizeof(a));
-    a.ws = v.ws;
-    a.ws_plane_stride = p.plane_floats;
-    a.minmax = v.minmax;
-    a.hist = v.hist;
-    a.L = L;
-    a.shared = ctx->stack_mode ? 1 : 0;
-    int blocks = 0;
-    for (int l = l0; l < l1 && l < skip_from; ++l) {
-      if ((skip_hist >> l) & 1) continue;
-      const dsx::LevelPlan& lp = p.lv[l];
-      const int i = a.nlev++;
-      a.lvl[i] = l;
-      a.da_off[i] = lp.da_off;
-      a.h[i] = lp.h; a.w[i] = lp.w; a.ld[i] = lp.ld;
-      // rows per block: each block zeroes and folds 32 KB of counters, so big cohorts take tall blocks (128 rows: + 1-2 %
-      // in the 4-stream run against 32), small ones keep enough blocks to spread over the chip (~512 per launch)
-      const int hist_rows = ctx->tune.hist_rows;
-      const int auto_rows = std::max(32, std::min(128, (int)((long long)lp.h * nb / 512)));
-      // k_hist counts in 16-bit per-lane counters shared by the waves of a block: a lane sees 4 values per 16-byte load
-      // and (w >> 8) + 1 loads per row at most, and in the worst case they all fall into ONE bin (bin 0 of a plane with
-      // one outlier) -- the rows of a block are capped so that even then no counter carries into its neighbour
-      // (w = 18 432, the widest level k_rowfilter_wide admits: 227 rows)
-      const int rows_cap = std::min(256, 65535 / (4 * (lp.w >> 8) + 4));
-      a.rows_per_block[i] = std::max(1, std::min(hist_rows > 0 ? hist_rows : auto_rows, rows_cap));
-      blocks += (lp.h + a.rows_per_block[i] - 1) / a.rows_per_block[i];
-      a.blk_end[i] = blocks;
-    }
-    if (a.nlev == 0) return DSX_OK;
-    LaunchScope ls(ctx, KC_HIST);
-    hipLaunchKernelGGL(dsx::k_hist, dim3(blocks, nb), dim3(64 * dsx::kHistWaves), 0, hs, a);
+// ---- stage 0: zero the control block --------------------------------------------------------------------------------
+int stage_zero(const Chain& c) {
+  dsx_ctx* ctx = c.ctx;
+  const CohortView& v = c.v;
+  const int nb = c.nb, Lc = std::max(1, ctx->plan.L);
+  static_assert(sizeof(dsx::PlaneStats) == dsx::kPlaneStatsBytes, "dsx_chain.h counts the control block in these");
+  const dsx::ZeroLaunch z = dsx::zero_launch(nb, Lc, (size_t)(uintptr_t)v.minmax);
+  if (z.grid_x > 0) {
+    hipLaunchKernelGGL(dsx::k_zero3, dim3(z.grid_x), dim3(256), 0, v.stream, (uint4*)v.stats, z.n0, (uint4*)v.minmax, z.n1,
+                       (uint4*)v.hist, z.n2);
     DSX_HIP(hipGetLastError());
-    return DSX_OK;
-  };
-  for (int l = 0; l < L; ++l) {
-    if (fuse12 && l == 1) continue;
-    if (l >= skip_from) continue;
+  } else {
+    DSX_HIP(hipMemsetAsync(v.stats, 0, sizeof(dsx::PlaneStats) * nb, v.stream));
+    DSX_HIP(hipMemsetAsync(v.minmax, 0, sizeof(unsigned) * 2 * Lc * (size_t)nb, v.stream));
+    DSX_HIP(hipMemsetAsync(v.hist, 0, sizeof(unsigned) * 256 * Lc * nb, v.stream));
+  }
+  return DSX_OK;
+}
+
+// histograms of levels [l0, l1) in ONE launch (k_hist finds its level from the block index)
+int hist_levels(const Chain& c, int l0, int l1, hipStream_t hs) {
+  dsx_ctx* ctx = c.ctx;
+  const dsx::Plan& p = ctx->plan;
+  const Skips sk = skips(ctx->tune);
+  if (!c.sh.thresholds) return DSX_OK;
+  dsx::HistArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ws = c.v.ws;
+  a.ws_plane_stride = p.plane_floats;
+  a.minmax = c.v.minmax;
+  a.hist = c.v.hist;
+  a.L = p.L;
+  a.shared = ctx->stack_mode ? 1 : 0;
+  int blocks = 0;
+  for (int l = l0; l < l1 && l < sk.from; ++l) {
+    if ((sk.hist >> l) & 1) continue;
     const dsx::LevelPlan& lp = p.lv[l];
-    if (generic) {
+    const int i = a.nlev++;
+    a.lvl[i] = l;
+    a.da_off[i] = lp.da_off;
+    a.h[i] = lp.h; a.w[i] = lp.w; a.ld[i] = lp.ld;
+    a.rows_per_block[i] = dsx::hist_rows_per_block(ctx->tune, lp.h, lp.w, c.nb);
+    blocks += (lp.h + a.rows_per_block[i] - 1) / a.rows_per_block[i];
+    a.blk_end[i] = blocks;
+  }
+  if (a.nlev == 0) return DSX_OK;
+  LaunchScope ls(ctx, KC_HIST);
+  hipLaunchKernelGGL(dsx::k_hist, dim3(blocks, c.nb), dim3(64 * dsx::kHistWaves), 0, hs, a);
+  DSX_HIP(hipGetLastError());
+  return DSX_OK;
+}
+
+// the fields Fwd1Args and GenFwdArgs share: analysis level l (index) of the part
+template <typename A>
+void fill_fwd(A& a, const Chain& c, int l) {
+  const dsx_ctx* ctx = c.ctx;
+  const dsx::Plan& p = ctx->plan;
+  const dsx::LevelPlan& lp = p.lv[l];
+  memset(&a, 0, sizeof(a));
+  a.in = c.d_in;
+  a.in_plane_stride = (long long)p.H * p.W;
+  a.ws = c.v.ws;
+  a.ws_plane_stride = p.plane_floats;
+  a.in_off = (l > 0) ? p.lv[l - 1].aa_off : 0;
+  a.H = lp.hin; a.W = lp.win; a.ldin = lp.ldin;
+  a.aa_off = lp.aa_off; a.da_off = lp.da_off;
+  a.h = lp.h; a.w = lp.w; a.ld = lp.ld; a.lda = lp.lda;
+  a.minmax = c.v.minmax;
+  a.lvl = l; a.L = p.L;
+  a.stats = c.v.stats;
+  a.fg_cutoff = ctx->fg_cutoff;
+  a.shared = ctx->stack_mode ? 1 : 0;
+}
+
+// ---- stage 1: forward transform --------------------------------------------------------------------------------------
+// db3: k_fwd_march per level, levels 1 + 2 in ONE launch when the plane allows it (fuse12); any other wavelet: k_fwd_gen
+// per level.  split: once levels 1 and 2 are complete their histograms start on the helper stream (ev[0] -> ev[1]).
+int stage_forward(const Chain& c) {
+  dsx_ctx* ctx = c.ctx;
+  const dsx::Plan& p = ctx->plan;
+  const CohortView& v = c.v;
+  const dsx::ChainShape& sh = c.sh;
+  hipStream_t s = v.stream;
+  const int nb = c.nb;
+  for (int l = 0; l < p.L; ++l) {
+    if (sh.fuse12 && l == 1) continue;
+    if (l >= skips(ctx->tune).from) continue;
+    const dsx::LevelPlan& lp = p.lv[l];
+    LaunchScope ls(ctx, l == 0 ? KC_FWD1 : KC_FWD);
+    if (sh.generic) {
       dsx::GenFwdArgs g;
-      memset(&g, 0, sizeof(g));
-      g.in = d_in;
-      g.in_plane_stride = (long long)p.H * p.W;
-      g.ws = v.ws;
-      g.ws_plane_stride = p.plane_floats;
-      g.in_off = (l > 0) ? p.lv[l - 1].aa_off : 0;
-      g.H = lp.hin; g.W = lp.win; g.ldin = lp.ldin;
-      g.aa_off = lp.aa_off; g.da_off = lp.da_off;
-      g.h = lp.h; g.w = lp.w; g.ld = lp.ld; g.lda = lp.lda;
-      g.minmax = v.minmax;
-      g.lvl = l; g.L = L;
-      g.stats = v.stats;
-      g.fg_cutoff = ctx->fg_cutoff;
+      fill_fwd(g, c, l);
       g.F = ctx->wl_len;
-      g.shared = ctx->stack_mode ? 1 : 0;
       memcpy(g.lo, ctx->wl[0], sizeof(float) * ctx->wl_len);
       memcpy(g.hi, ctx->wl[1], sizeof(float) * ctx->wl_len);
       const dim3 gg((lp.w + dsx::kGenTW - 1) / dsx::kGenTW, (lp.h + dsx::kGenTH - 1) / dsx::kGenTH, nb);
-      const size_t smem = dsx::gen_fwd_lds_bytes(g.F);
-      LaunchScope ls(ctx, l == 0 ? KC_FWD1 : KC_FWD);
-      if (l > 0) hipLaunchKernelGGL(dsx::k_fwd_gen<2>, gg, dim3(256), smem, s, g);
-      else if (in_dtype == DSX_U16) hipLaunchKernelGGL(dsx::k_fwd_gen<0>, gg, dim3(256), smem, s, g);
-      else hipLaunchKernelGGL(dsx::k_fwd_gen<1>, gg, dim3(256), smem, s, g);
+      auto kern = level_kernel(l == 0, c.in_dtype, dsx::k_fwd_gen<2>, dsx::k_fwd_gen<0>, dsx::k_fwd_gen<1>);
+      hipLaunchKernelGGL(kern, gg, dim3(256), dsx::gen_fwd_lds_bytes(g.F), s, g);
       DSX_HIP(hipGetLastError());
       continue;
     }
     dsx::Fwd1Args f;
-    memset(&f, 0, sizeof(f));
-    f.in = d_in;
-    f.in_plane_stride = (long long)p.H * p.W;
-    f.ws = v.ws;
-    f.ws_plane_stride = p.plane_floats;
-    f.in_off = (l > 0) ? p.lv[l - 1].aa_off : 0;
-    f.H = lp.hin; f.W = lp.win; f.ldin = lp.ldin;
-    f.aa_off = lp.aa_off; f.da_off = lp.da_off;
-    f.h = lp.h; f.w = lp.w; f.ld = lp.ld; f.lda = lp.lda;
-    f.minmax = v.minmax;
-    f.lvl = l; f.L = L;
-    f.stats = v.stats;
-    f.fg_cutoff = ctx->fg_cutoff;
+    fill_fwd(f, c, l);
     f.ablate = ctx->ablate;
-    f.shared = ctx->stack_mode ? 1 : 0;
     f.fg_cutoff_u16 = (unsigned)std::min(65536.0, std::max(0.0, ceil((double)ctx->fg_cutoff)));
-    f.nstrips = (lp.w + dsx::kMarchOut - 1) / dsx::kMarchOut;
-    march_segments(nb, f.nstrips, lp.h, &f.nseg, &f.rows_per_seg, 0, 0, /*coarse=*/l >= 2);
-    if (fuse12 && l == 0) {
+    const bool fused = sh.fuse12 && l == 0;
+    if (fused) {
       const dsx::LevelPlan& l2 = p.lv[1];
       f.aa2_off = l2.aa_off; f.da2_off = l2.da_off;
       f.h2 = l2.h; f.w2 = l2.w; f.ld2 = l2.ld; f.lda2 = l2.lda;
-      f.nstrips = (l2.w + dsx::kFuseOut - 1) / dsx::kFuseOut;
-      // (a cohort split over the streams shares the chip with the other parts' kernels: rounds mean nothing there --
-      //  measured 65.6 k with against 66.2 k planes/s without; alone: forward kernel 1.39 -> 1.14 ms per 256 planes)
-      march_segments(nb, f.nstrips, l2.h, &f.nseg, &f.rows_per_seg, v.alone ? 8 : 0, 2);
     }
-    dim3 grid((f.nstrips * f.nseg + 3) / 4, nb);
-    LaunchScope ls(ctx, l == 0 ? KC_FWD1 : KC_FWD);
-    // 8 waves per block for the fused kernels: a block covers 8 consecutive strips of one row segment (4 KB of
-    // contiguous pixels per row at 2048 columns), and at most 8 march waves sit on a CU next to the other
-    // streams' row-filter blocks: +4 % in the 4-stream run (DSX_FWD_WPB / DSX_INV_WPB = 4 restores 4)
-    const int fwd_wpb = ctx->tune.fwd_wpb;
-    if (fuse12 && l == 0 && fwd_wpb == 8) {
-      const dim3 g8((f.nstrips * f.nseg + 7) / 8, nb);
-      if (in_dtype == DSX_U16) hipLaunchKernelGGL((dsx::k_fwd_march<0, true, 8>), g8, dim3(512), 0, s, f);
-      else hipLaunchKernelGGL((dsx::k_fwd_march<1, true, 8>), g8, dim3(512), 0, s, f);
-    } else if (fuse12 && l == 0) {
-      if (in_dtype == DSX_U16) hipLaunchKernelGGL((dsx::k_fwd_march<0, true>), grid, dim3(256), 0, s, f);
-      else hipLaunchKernelGGL((dsx::k_fwd_march<1, true>), grid, dim3(256), 0, s, f);
-    } else if (l > 0) {
-      hipLaunchKernelGGL(dsx::k_fwd_march<2>, grid, dim3(256), 0, s, f);
-    } else if (in_dtype == DSX_U16) {
-      hipLaunchKernelGGL(dsx::k_fwd_march<0>, grid, dim3(256), 0, s, f);
-    } else {
-      hipLaunchKernelGGL(dsx::k_fwd_march<1>, grid, dim3(256), 0, s, f);
-    }
+    const dsx::MarchLaunch m = dsx::fwd_launch(p, sh, ctx->tune, ctx->cus, nb, v.alone, l);
+    f.nstrips = m.nstrips; f.nseg = m.nseg; f.rows_per_seg = m.rows_per_seg;
+    auto kern = (fused && m.wpb == 8) ? pixel_kernel(c.in_dtype, dsx::k_fwd_march<0, true, 8>, dsx::k_fwd_march<1, true, 8>)
+                : fused ? pixel_kernel(c.in_dtype, dsx::k_fwd_march<0, true>, dsx::k_fwd_march<1, true>)
+                : level_kernel(l == 0, c.in_dtype, dsx::k_fwd_march<2>, dsx::k_fwd_march<0>, dsx::k_fwd_march<1>);
+    hipLaunchKernelGGL(kern, dim3(m.grid_x, nb), dim3(64 * m.wpb), 0, s, f);
     DSX_HIP(hipGetLastError());
-    if (split && l == 0) {  // levels 1 and 2 are complete: their histograms start now, on the helper stream
+    if (sh.split && l == 0) {  // levels 1 and 2 are complete: their histograms start now, on the helper stream
       DSX_HIP(hipEventRecord(v.ev[0], s));
       DSX_HIP(hipStreamWaitEvent(v.helper, v.ev[0], 0));
-      if (int rc = hist_levels(0, 2, v.helper)) return rc;
+      if (int rc = hist_levels(c, 0, 2, v.helper)) return rc;
       DSX_HIP(hipEventRecord(v.ev[1], v.helper));
     }
   }
+  return DSX_OK;
+}
 
-  // ---- thresholds -----------------------------------------------------------------------------
-  if (int rc = hist_levels(split ? 2 : 0, L, s)) return rc;
-  if (split) DSX_HIP(hipStreamWaitEvent(s, v.ev[1], 0));  // histograms of levels 1, 2 (helper stream)
-  if (L > 0 && !ctx->st_march) {
+// ---- stage 2: thresholds ---------------------------------------------------------------------------------------------
+// the histograms that did not go to the helper stream, k_otsu (config decision, threshold per level) and the cfg_used copy
+int stage_thresholds(const Chain& c, int32_t* d_cfg_used) {
+  dsx_ctx* ctx = c.ctx;
+  const dsx::Plan& p = ctx->plan;
+  const CohortView& v = c.v;
+  hipStream_t s = v.stream;
+  const int L = p.L;
+  if (int rc = hist_levels(c, c.sh.split ? 2 : 0, L, s)) return rc;
+  if (c.sh.split) DSX_HIP(hipStreamWaitEvent(s, v.ev[1], 0));  // histograms of levels 1, 2 (helper stream)
+  if (L > 0 && c.sh.thresholds) {
     dsx::OtsuArgs a;
     a.stats = v.stats;
     a.npix = (double)p.H * (double)p.W;
@@ -739,216 +540,238 @@ int run_cohort(dsx_ctx* ctx, const CohortView& v, const void* d_in, int in_dtype
     a.sticky = ctx->d_sticky;
     a.shared = ctx->stack_mode ? 1 : 0;
     LaunchScope ls(ctx, KC_OTSU);
-    hipLaunchKernelGGL(dsx::k_otsu, dim3(L, nb), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(dsx::k_otsu, dim3(L, c.nb), dim3(64), 0, s, a);
     DSX_HIP(hipGetLastError());
     if (d_cfg_used)
-      DSX_HIP(hipMemcpyAsync(d_cfg_used, v.cfg, sizeof(int32_t) * nb, hipMemcpyDeviceToDevice, s));
+      DSX_HIP(hipMemcpyAsync(d_cfg_used, v.cfg, sizeof(int32_t) * c.nb, hipMemcpyDeviceToDevice, s));
   } else if (d_cfg_used) {
-    DSX_HIP(hipMemsetAsync(d_cfg_used, 0, sizeof(int32_t) * nb, s));
+    DSX_HIP(hipMemsetAsync(d_cfg_used, 0, sizeof(int32_t) * c.nb, s));
   }
-  if (ctx->stop_after == 1) return DSX_OK;
+  return DSX_OK;
+}
 
-  // ---- row filter -----------------------------------------------------------------------------
-  // split: levels 1, 2 on the helper stream (1.5 ms of the 5.3 ms chain per 256 planes), the coarse levels'
-  // row filters AND the coarse inverse levels on the part's own stream beside them; joined before the final kernel
-  const bool split_inv = split && fuse21;  // the fused final kernel consumes Delta_1, Delta_2 and c_2 only
-  if (split_inv) {
+dsx::RowArgs row_args(const Chain& c, int l) {
+  const dsx_ctx* ctx = c.ctx;
+  const dsx::Plan& p = ctx->plan;
+  const dsx::LevelPlan& lp = p.lv[l];
+  dsx::RowArgs a;
+  memset(&a, 0, sizeof(a));
+  a.ws = c.v.ws;
+  a.ws_plane_stride = p.plane_floats;
+  a.da_off = lp.da_off;
+  a.h = lp.h; a.w = lp.w; a.ld = lp.ld;
+  a.thr = c.v.thr;
+  a.cfg = c.v.cfg;
+  a.lvl = l; a.L = p.L;
+  a.lvl_active[0] = p.cfg_levels[0];
+  a.lvl_active[1] = p.cfg_levels[1];
+  a.M = lp.M; a.K = lp.K;
+  a.npass = lp.npass;
+  for (int i = 0; i < lp.npass; ++i) a.radix[i] = lp.radix[i];
+  a.tw = (const float2*)(ctx->d_consts + lp.tw_off);
+  a.g[0] = (const float2*)(ctx->d_consts + lp.g_off[0]);
+  a.g[1] = (const float2*)(ctx->d_consts + lp.g_off[1]);
+  a.kcut[0] = lp.kcut[0];
+  a.kcut[1] = lp.kcut[1];
+  a.inv_M = 1.0f / (float)lp.M;
+  a.ablate = ctx->ablate;
+  return a;
+}
+
+// ---- stage 3: row filters --------------------------------------------------------------------------------------------
+// split_inv: levels 1, 2 on the helper stream behind ev[2] ("thresholds are known"), ev[3] marks their end; the coarse
+// levels on the part's own stream, in one merged launch where dsx::row_multi_takes says so.  With k_rowfinal level 1 is
+// not launched here: *row1 carries its arguments to the final kernel.
+int stage_rowfilters(const Chain& c, dsx::RowArgs* row1) {
+  dsx_ctx* ctx = c.ctx;
+  const dsx::Plan& p = ctx->plan;
+  const CohortView& v = c.v;
+  hipStream_t s = v.stream;
+  const Skips sk = skips(ctx->tune);
+  if (c.sh.split_inv) {
     DSX_HIP(hipEventRecord(v.ev[2], s));                  // thresholds are known
     DSX_HIP(hipStreamWaitEvent(v.helper, v.ev[2], 0));
   }
-  dsx::RowArgs row1;  // level 1, for k_rowfinal
-  memset(&row1, 0, sizeof(row1));
-  // coarse levels (M <= 384) that run on the part's own stream: one launch for all of them (DSX_NO_ROW_MULTI=1: one each)
-  const bool no_multi = ctx->tune.no_row_multi;
+  memset(row1, 0, sizeof(*row1));
   dsx::RowMultiArgs multi;
   memset(&multi, 0, sizeof(multi));
   int multi_pairs[dsx::kRowMultiMax] = {};
-  for (int l = 0; l < L && l < skip_from; ++l) {
-    hipStream_t rs = (split_inv && l < 2) ? v.helper : s;
-    if ((skip_row >> l) & 1) continue;
-    const dsx::LevelPlan& lp = p.lv[l];
-    dsx::RowArgs a;
-    memset(&a, 0, sizeof(a));
-    a.ws = v.ws;
-    a.ws_plane_stride = p.plane_floats;
-    a.da_off = lp.da_off;
-    a.h = lp.h; a.w = lp.w; a.ld = lp.ld;
-    a.thr = v.thr;
-    a.cfg = v.cfg;
-    a.lvl = l; a.L = L;
-    a.lvl_active[0] = p.cfg_levels[0];
-    a.lvl_active[1] = p.cfg_levels[1];
-    a.M = lp.M; a.K = lp.K;
-    a.npass = lp.npass;
-    for (int i = 0; i < lp.npass; ++i) a.radix[i] = lp.radix[i];
-    a.tw = (const float2*)(ctx->d_consts + lp.tw_off);
-    a.g[0] = (const float2*)(ctx->d_consts + lp.g_off[0]);
-    a.g[1] = (const float2*)(ctx->d_consts + lp.g_off[1]);
-    a.kcut[0] = lp.kcut[0];
-    a.kcut[1] = lp.kcut[1];
-    a.inv_M = 1.0f / (float)lp.M;
-    a.ablate = ctx->ablate;
-    if (fuse_rf && l == 0) {
-      row1 = a;
+  for (int l = 0; l < p.L && l < sk.from; ++l) {
+    hipStream_t rs = (c.sh.split_inv && l < 2) ? v.helper : s;
+    if ((sk.row >> l) & 1) continue;
+    const dsx::RowArgs a = row_args(c, l);
+    if (c.sh.rf_plan != 0 && l == 0) {
+      *row1 = a;
       continue;
     }
-    const int npairs = (lp.h + 1) / 2;
-    // (only for cohorts split over the streams, where the launch gaps of six small kernels cost more than the
-    //  specialised CPL = 2 / 4 instantiations save: +2.4 % there, -5 % for a cohort that runs alone -- its coarse chain
-    //  is the critical path beside the level-2 row filter on the helper stream; profiles/r3_merged_small_launches_ab.txt)
-    // ... and small cohorts that run alone are launch-bound again: one plane 418 -> 358 us per call, 32 planes + 7 %,
-    // 64 planes even, 128 planes - 2.7 % (profiles/r3_merged_small_launches_ab.txt); DSX_ROW_MULTI_ALONE = the limit
-    const int multi_alone = ctx->tune.row_multi_alone;
-    if (!no_multi && (!v.alone || nb <= multi_alone) && rs == s && a.M <= 6 * 64 && multi.nlev < dsx::kRowMultiMax) {
+    const int npairs = (a.h + 1) / 2;
+    if (dsx::row_multi_takes(c.sh, rs == s, a.M, multi.nlev)) {
       multi_pairs[multi.nlev] = npairs;
       multi.lv[multi.nlev++] = a;
       continue;
     }
     LaunchScope ls(ctx, KC_ROW);
-    DSX_HIP(dispatch_rowfilter(a, npairs, nb, rs));
+    DSX_HIP(dispatch_rowfilter(ctx->tune, a, npairs, c.nb, rs));
   }
   if (multi.nlev == 1) {
     LaunchScope ls(ctx, KC_ROW);
-    DSX_HIP(dispatch_rowfilter(multi.lv[0], multi_pairs[0], nb, s));
+    DSX_HIP(dispatch_rowfilter(ctx->tune, multi.lv[0], multi_pairs[0], c.nb, s));
   } else if (multi.nlev > 1) {
     LaunchScope ls(ctx, KC_ROW);
-    DSX_HIP(launch_rowfilter_multi(multi, multi_pairs, nb, s));
+    DSX_HIP(launch_rowfilter_multi(multi, multi_pairs, c.nb, s));
   }
-  if (split_inv) DSX_HIP(hipEventRecord(v.ev[3], v.helper));
-  if (ctx->stop_after == 2) return DSX_OK;
+  if (c.sh.split_inv) DSX_HIP(hipEventRecord(v.ev[3], v.helper));
+  return DSX_OK;
+}
 
-  // ---- inverse transform of the Delta pyramid + finish ---------------------------------------
-  // level-2 synthesis inside the final kernel when the plane allows it (c_1 never leaves the chip): fuse21
+// the fields FinalArgs and GenInvArgs share: synthesis level l (index; -1: a plan without levels) of the part, the last
+// one (l <= 0) writes the result
+template <typename A>
+void fill_inv(A& a, const Chain& c, int l) {
+  const dsx_ctx* ctx = c.ctx;
+  const dsx::Plan& p = ctx->plan;
+  memset(&a, 0, sizeof(a));
+  a.ws = c.v.ws;
+  a.ws_plane_stride = p.plane_floats;
+  if (l >= 0) {
+    const dsx::LevelPlan& lp = p.lv[l];
+    a.c_off = lp.aa_off;
+    a.d_off = lp.da_off;
+    a.hc = lp.h; a.wc = lp.w; a.ldc = lp.lda; a.ldd = lp.ld;
+    a.has_c = (l < p.L - 1) ? 1 : 0;
+    a.has_pyr = 1;
+  }
+  if (l > 0) {
+    const dsx::LevelPlan& lo = p.lv[l - 1];
+    a.out_off = lo.aa_off;
+    a.hout = lo.h; a.wout = lo.w; a.ldout = lo.lda;
+  } else {
+    a.img = c.d_in;
+    a.img_plane_stride = (long long)p.H * p.W;
+    a.H = p.H; a.W = p.W;
+    a.out = c.d_out;
+    a.out_plane_stride = (long long)p.Hout * p.Wout;
+    a.hout = p.Hout; a.wout = p.Wout;
+    a.out_dtype = (c.out_dtype == DSX_U16) ? 0 : 1;
+    a.flat = ctx->d_flat;
+    a.dark = ctx->d_dark;
+    a.dark_ld = ctx->dark_w;
+  }
+}
+
+// ---- stage 4: inverse transform of the Delta pyramid + finish ----------------------------------------------------------
+// coarsest level first; level-2 synthesis inside the final kernel when the plane allows it (fuse21), the level-1 row filter
+// too where k_rowfinal takes the shape (row1 from stage_rowfilters).  split_inv: the final kernel waits for ev[3].
+int stage_inverse(const Chain& c, const dsx::RowArgs& row1) {
+  dsx_ctx* ctx = c.ctx;
+  const dsx::Plan& p = ctx->plan;
+  const CohortView& v = c.v;
+  const dsx::ChainShape& sh = c.sh;
+  hipStream_t s = v.stream;
+  const int L = p.L, nb = c.nb;
   for (int l = L - 1; l >= (L > 0 ? 0 : -1); --l) {
-    if (fuse21 && l == 1) continue;
-    if (l >= skip_from) continue;
-    if (generic) {
+    if (sh.fuse21 && l == 1) continue;
+    if (l >= skips(ctx->tune).from) continue;
+    const bool last = (l <= 0);
+    LaunchScope ls(ctx, last ? KC_FINAL : KC_INV);
+    if (sh.generic) {
       dsx::GenInvArgs g;
-      memset(&g, 0, sizeof(g));
-      const dsx::LevelPlan& lp = p.lv[l];
-      g.ws = v.ws;
-      g.ws_plane_stride = p.plane_floats;
-      g.c_off = lp.aa_off; g.d_off = lp.da_off;
-      g.hc = lp.h; g.wc = lp.w; g.ldc = lp.lda; g.ldd = lp.ld;
-      g.has_c = (l < L - 1) ? 1 : 0;
-      g.has_pyr = 1;
+      fill_inv(g, c, l);
       g.F = ctx->wl_len;
       memcpy(g.lo, ctx->wl[2], sizeof(float) * ctx->wl_len);
       memcpy(g.hi, ctx->wl[3], sizeof(float) * ctx->wl_len);
-      const bool last_g = (l == 0);
-      if (!last_g) {
-        const dsx::LevelPlan& lo = p.lv[l - 1];
-        g.out_off = lo.aa_off;
-        g.hout = lo.h; g.wout = lo.w; g.ldout = lo.lda;
-      } else {
-        g.img = d_in;
-        g.img_plane_stride = (long long)p.H * p.W;
-        g.H = p.H; g.W = p.W;
-        g.out = d_out;
-        g.out_plane_stride = (long long)p.Hout * p.Wout;
-        g.hout = p.Hout; g.wout = p.Wout;
-        g.out_dtype = (out_dtype == DSX_U16) ? 0 : 1;
-        g.flat = ctx->d_flat;
-        g.dark = ctx->d_dark;
-        g.dark_ld = ctx->dark_w;
-      }
       const dim3 gg((g.wout + dsx::kGenOW - 1) / dsx::kGenOW, (g.hout + dsx::kGenOH - 1) / dsx::kGenOH, nb);
-      const size_t smem = dsx::gen_inv_lds_bytes(g.F);
-      LaunchScope ls(ctx, last_g ? KC_FINAL : KC_INV);
-      if (!last_g) hipLaunchKernelGGL(dsx::k_inv_gen<2>, gg, dim3(256), smem, s, g);
-      else if (in_dtype == DSX_U16) hipLaunchKernelGGL(dsx::k_inv_gen<0>, gg, dim3(256), smem, s, g);
-      else hipLaunchKernelGGL(dsx::k_inv_gen<1>, gg, dim3(256), smem, s, g);
+      auto kern = level_kernel(last, c.in_dtype, dsx::k_inv_gen<2>, dsx::k_inv_gen<0>, dsx::k_inv_gen<1>);
+      hipLaunchKernelGGL(kern, gg, dim3(256), dsx::gen_inv_lds_bytes(g.F), s, g);
       DSX_HIP(hipGetLastError());
       continue;
     }
     dsx::FinalArgs f;
-    memset(&f, 0, sizeof(f));
-    f.ws = v.ws;
-    f.ws_plane_stride = p.plane_floats;
-    if (l >= 0) {
-      const dsx::LevelPlan& lp = p.lv[l];
-      f.c_off = lp.aa_off;
-      f.d_off = lp.da_off;
-      f.hc = lp.h; f.wc = lp.w; f.ldc = lp.lda; f.ldd = lp.ld;
-      f.has_c = (l < L - 1) ? 1 : 0;
-      f.has_pyr = 1;
-    }
-    const bool last = (l <= 0);
-    if (!last) {
-      const dsx::LevelPlan& lo = p.lv[l - 1];
-      f.ws_out = v.ws;
-      f.out_off = lo.aa_off;
-      f.hout = lo.h; f.wout = lo.w; f.ldout = lo.lda;
-    } else {
-      f.img = d_in;
-      f.img_plane_stride = (long long)p.H * p.W;
-      f.H = p.H; f.W = p.W;
-      f.out = d_out;
-      f.out_plane_stride = (long long)p.Hout * p.Wout;
-      f.hout = p.Hout; f.wout = p.Wout;
-      f.out_dtype = (out_dtype == DSX_U16) ? 0 : 1;
-      f.flat = ctx->d_flat;
-      f.dark = ctx->d_dark;
-      f.dark_ld = ctx->dark_w;
-    }
+    fill_inv(f, c, l);
+    if (!last) f.ws_out = v.ws;
     f.ablate = ctx->ablate;
-    f.nstrips = (f.wout + dsx::kMarchCols - 1) / dsx::kMarchCols;
-    march_segments(nb, f.nstrips, (f.hout + 1) / 2, &f.nseg, &f.rows_per_seg, 0, 0, /*coarse=*/l >= 2);
-    const bool fused = fuse21 && last;
-    if (last && split_inv) DSX_HIP(hipStreamWaitEvent(s, v.ev[3], 0));  // Delta_1, Delta_2 (helper stream)
+    const dsx::MarchLaunch m = dsx::inv_launch(sh, ctx->tune, ctx->cus, nb, l, f.hout, f.wout);
+    f.nstrips = m.nstrips; f.nseg = m.nseg; f.rows_per_seg = m.rows_per_seg;
+    const bool fused = sh.fuse21 && last;
+    if (last && sh.split_inv) DSX_HIP(hipStreamWaitEvent(s, v.ev[3], 0));  // Delta_1, Delta_2 (helper stream)
     if (fused) {
       const dsx::LevelPlan& l2 = p.lv[1];
       f.c2_off = l2.aa_off; f.d2_off = l2.da_off;
       f.hc2 = l2.h; f.wc2 = l2.w; f.ldc2 = l2.lda; f.ldd2 = l2.ld;
       f.has_c2 = (L > 2) ? 1 : 0;
       f.has_c = 1;
-      f.pair_io = pair_io ? 1 : 0;
-      if (f.rows_per_seg & 1) {  // segments start at even level-1 rows
-        f.rows_per_seg += 1;
-        f.nseg = ((f.hout + 1) / 2 + f.rows_per_seg - 1) / f.rows_per_seg;
-      }
+      f.pair_io = sh.pair_io ? 1 : 0;
     }
-    dim3 grid((f.nstrips * f.nseg + 3) / 4, nb);
-    LaunchScope ls(ctx, last ? KC_FINAL : KC_INV);
-    const int inv_wpb = ctx->tune.inv_wpb;
-    if (fused && fuse_rf) {
+    if (fused && sh.rf_plan != 0) {
       dsx::RowFinalArgs rf;
       rf.r = row1;
       rf.f = f;
-      DSX_HIP(launch_rowfinal(rf_plan, rf, nb, s));
-    } else if (fused && inv_wpb == 8) {
-      const dim3 g8((f.nstrips * f.nseg + 7) / 8, nb);
-      if (in_dtype == DSX_U16) hipLaunchKernelGGL((dsx::k_inv_march<0, true, 8>), g8, dim3(512), 0, s, f);
-      else hipLaunchKernelGGL((dsx::k_inv_march<1, true, 8>), g8, dim3(512), 0, s, f);
-    } else if (fused) {
-      if (in_dtype == DSX_U16) hipLaunchKernelGGL((dsx::k_inv_march<0, true>), grid, dim3(256), 0, s, f);
-      else hipLaunchKernelGGL((dsx::k_inv_march<1, true>), grid, dim3(256), 0, s, f);
-    } else if (!last) {
-      hipLaunchKernelGGL(dsx::k_inv_march<2>, grid, dim3(256), 0, s, f);
-    } else if (in_dtype == DSX_U16) {
-      hipLaunchKernelGGL(dsx::k_inv_march<0>, grid, dim3(256), 0, s, f);
-    } else {
-      hipLaunchKernelGGL(dsx::k_inv_march<1>, grid, dim3(256), 0, s, f);
+      DSX_HIP(launch_rowfinal(sh.rf_plan, rf, nb, s));
+      continue;
     }
+    auto kern = (fused && m.wpb == 8) ? pixel_kernel(c.in_dtype, dsx::k_inv_march<0, true, 8>, dsx::k_inv_march<1, true, 8>)
+                : fused ? pixel_kernel(c.in_dtype, dsx::k_inv_march<0, true>, dsx::k_inv_march<1, true>)
+                : level_kernel(last, c.in_dtype, dsx::k_inv_march<2>, dsx::k_inv_march<0>, dsx::k_inv_march<1>);
+    hipLaunchKernelGGL(kern, dim3(m.grid_x, nb), dim3(64 * m.wpb), 0, s, f);
     DSX_HIP(hipGetLastError());
   }
   return DSX_OK;
 }
 
+// One cohort part of nb planes through the whole chain (asynchronous): the shape of the chain (dsx_chain.h: what is
+// fused, what runs beside what), then its stages in launch order.  The helper-stream events of a split part: ev[0] /
+// ev[1] around the wide levels' histograms (stage_forward -> stage_thresholds), ev[2] / ev[3] around their row filters
+// (stage_rowfilters -> the final kernel of stage_inverse).
+int run_cohort(dsx_ctx* ctx, const CohortView& v, const void* d_in, int in_dtype, int nb, void* d_out,
+               int out_dtype, int32_t* d_cfg_used) {
+  dsx::ChainCall call;
+  call.in_u16 = in_dtype == DSX_U16;
+  call.out_u16 = out_dtype == DSX_U16;
+  call.nb = nb;
+  call.aligned16 = (((uintptr_t)d_in | (uintptr_t)d_out) & 15) == 0;
+  call.bank = ctx->wl_len > 0;
+  call.stop_after = ctx->stop_after;
+  call.st_march = ctx->st_march;
+  call.has_helper = v.helper != nullptr;
+  call.alone = v.alone;
+  const Chain c = {ctx, v, dsx::chain_shape(ctx->plan, ctx->tune, call), d_in, in_dtype, nb, d_out, out_dtype};
+  if (int rc = stage_zero(c)) return rc;
+  if (int rc = stage_forward(c)) return rc;
+  if (int rc = stage_thresholds(c, d_cfg_used)) return rc;
+  if (ctx->stop_after == 1) return DSX_OK;
+  dsx::RowArgs row1;  // level 1, for k_rowfinal
+  if (int rc = stage_rowfilters(c, &row1)) return rc;
+  if (ctx->stop_after == 2) return DSX_OK;
+  return stage_inverse(c, row1);
+}
+
 size_t elem_size(int dtype) { return dtype == DSX_U16 ? 2 : 4; }
 
-// helper: 1 = this part may use its helper stream (run_cohort).  Measured at 2048^2: a cohort that runs as ONE
-// part gains 6 % (52.5 k against 49.5 k planes/s), a cohort split over 4 streams LOSES 2-8 % (the other parts
-// already fill the chip, the extra streams only add contention), so only unsplit cohorts use it; DSX_HELPER=0 / 1
-// forces it off / on.
-CohortView make_view(dsx_ctx* ctx, int po, hipStream_t stream, int part = 0, bool helper = false) {
+// pointer, count and element-type check of the run entry points
+int check_run_args(dsx_ctx* ctx, const void* in, const void* out, int n, int in_dtype, int out_dtype) {
+  if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, DSX_EINVAL, "bad plane pointers / count");
+  if ((in_dtype != DSX_U16 && in_dtype != DSX_F32) || (out_dtype != DSX_U16 && out_dtype != DSX_F32))
+    return fail(ctx, DSX_EINVAL, "unknown element type");
+  return DSX_OK;
+}
+
+// a staging buffer of dsx_run_host: at least `need` bytes
+int grow_stage(dsx_ctx* ctx, void** buf, size_t* have, size_t need) {
+  if (*have >= need) return DSX_OK;
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr; *have = 0;
+  DSX_HIP(hipMalloc(buf, need));
+  *have = need;
+  return DSX_OK;
+}
+
+// alone: the cohort runs as this ONE part (which may then use its helper stream: dsx::part_uses_helper)
+CohortView make_view(dsx_ctx* ctx, int po, hipStream_t stream, int part = 0, bool alone = false) {
   const int Lc = ctx->plan.L > 0 ? ctx->plan.L : 1;
   CohortView v;
   v.stream = stream;
-  const int force_helper = ctx->tune.helper;
-  const bool use = force_helper >= 0 ? force_helper != 0 : helper;
-  v.helper = (!use || ctx->profiling || ctx->stop_after != 0) ? nullptr : ctx->helper[part];
-  v.alone = helper;
+  v.helper = dsx::part_uses_helper(ctx->tune, alone, ctx->profiling || ctx->stop_after != 0) ? ctx->helper[part] : nullptr;
+  v.alone = alone;
   v.ev = ctx->ev_h[part];
   v.ws = ctx->d_ws + (size_t)po * ctx->plan.plane_floats;
   v.stats = ctx->d_stats + po;
@@ -959,6 +782,61 @@ CohortView make_view(dsx_ctx* ctx, int po, hipStream_t stream, int part = 0, boo
   v.cfg = ctx->d_cfg + po;
   v.means = ctx->d_means + 2 * (size_t)po;
   return v;
+}
+
+// An unsplit cohort through the graph cache (DSX_GRAPH=1, see dsx_ctx::GraphEntry): replay of a call seen before (same
+// buffers, count and types under the current plan); first sight eager, second sight capture; a runtime that cannot
+// capture falls back to eager launches for good.
+int run_cohort_graphed(dsx_ctx* ctx, const CohortView& view, hipStream_t main, const void* d_in, int in_dtype, int nb,
+                       void* d_out, int out_dtype, int32_t* d_cfg_used) {
+  dsx_ctx::GraphEntry* hit = nullptr;
+  for (auto& g : ctx->graphs)
+    if (g.in == d_in && g.out == d_out && g.cfg == (const void*)d_cfg_used && g.n == nb && g.in_dtype == in_dtype &&
+        g.out_dtype == out_dtype) { hit = &g; break; }
+  if (!hit) {
+    if ((int)ctx->graphs.size() >= dsx_ctx::kGraphSlots) {  // evict the least recently used tuple
+      size_t lru = 0;
+      for (size_t i = 1; i < ctx->graphs.size(); ++i)
+        if (ctx->graphs[i].last_use < ctx->graphs[lru].last_use) lru = i;
+      if (ctx->graphs[lru].exec) (void)hipGraphExecDestroy(ctx->graphs[lru].exec);
+      ctx->graphs.erase(ctx->graphs.begin() + (long)lru);
+    }
+    ctx->graphs.push_back({d_in, d_out, (const void*)d_cfg_used, nb, in_dtype, out_dtype, 0, nullptr, 0});
+    hit = &ctx->graphs.back();
+  }
+  hit->last_use = ++ctx->graph_clock;
+  if (hit->exec) {
+    ++ctx->graph_launches;
+    DSX_HIP(hipGraphLaunch(hit->exec, main));
+    return DSX_OK;
+  }
+  if (hit->seen++ == 0)  // first sight: eager (one-off calls never pay for a capture; function attributes get set)
+    return run_cohort(ctx, view, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
+  // second sight: capture the chain (the helper stream joins the capture through its fork event and is joined
+  // back before the final kernel), instantiate, launch
+  if (hipStreamBeginCapture(main, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->graph_mode = 0;
+    return run_cohort(ctx, view, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
+  }
+  const int rc = run_cohort(ctx, view, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
+  hipGraph_t graph = nullptr;
+  const hipError_t ce = hipStreamEndCapture(main, &graph);
+  hipGraphExec_t exec = nullptr;
+  if (rc == DSX_OK && ce == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+    (void)hipGraphDestroy(graph);
+    hit->exec = exec;
+    ++ctx->graph_captures;
+    ++ctx->graph_launches;
+    DSX_HIP(hipGraphLaunch(exec, main));
+    return DSX_OK;
+  }
+  // capture is not usable here: nothing has run yet -- fall back to eager launches for good
+  (void)hipGetLastError();
+  if (graph) (void)hipGraphDestroy(graph);
+  ctx->graph_mode = 0;
+  if (rc != DSX_OK) return rc;
+  return run_cohort(ctx, view, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
 }
 
 // One cohort (<= max_batch planes), split into parts on the context's streams.
@@ -972,63 +850,13 @@ CohortView make_view(dsx_ctx* ctx, int po, hipStream_t stream, int part = 0, boo
 // draining the chip at every call boundary.  Anything else joins first, then forks again.
 int run_cohort_split(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d_out, int out_dtype,
                      int32_t* d_cfg_used, size_t in_plane, size_t out_plane) {
-  int parts = ctx->n_streams;
-  if (ctx->profiling || ctx->stop_after != 0 || ctx->stack_mode) parts = 1;  // stack mode: one control block, one chain
-  while (parts > 1 && nb / parts < 16) --parts;  // keep every part big enough to fill the chip
+  const int parts = dsx::cohort_parts(ctx->n_streams, nb, ctx->profiling || ctx->stop_after != 0 || ctx->stack_mode);
   if (parts <= 1) {
     hipStream_t main = use_main(ctx);  // joins whatever split cohort is still running
     const CohortView view = make_view(ctx, 0, main, 0, true);
     if (ctx->graph_mode == 0 || ctx->profiling || ctx->stop_after != 0 || ctx->ablate != 0)
       return run_cohort(ctx, view, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
-    // ---- graph replay of a call seen before (same buffers, count and types under the current plan) ----
-    dsx_ctx::GraphEntry* hit = nullptr;
-    for (auto& g : ctx->graphs)
-      if (g.in == d_in && g.out == d_out && g.cfg == (const void*)d_cfg_used && g.n == nb && g.in_dtype == in_dtype &&
-          g.out_dtype == out_dtype) { hit = &g; break; }
-    if (!hit) {
-      if ((int)ctx->graphs.size() >= dsx_ctx::kGraphSlots) {  // evict the least recently used tuple
-        size_t lru = 0;
-        for (size_t i = 1; i < ctx->graphs.size(); ++i)
-          if (ctx->graphs[i].last_use < ctx->graphs[lru].last_use) lru = i;
-        if (ctx->graphs[lru].exec) (void)hipGraphExecDestroy(ctx->graphs[lru].exec);
-        ctx->graphs.erase(ctx->graphs.begin() + (long)lru);
-      }
-      ctx->graphs.push_back({d_in, d_out, (const void*)d_cfg_used, nb, in_dtype, out_dtype, 0, nullptr, 0});
-      hit = &ctx->graphs.back();
-    }
-    hit->last_use = ++ctx->graph_clock;
-    if (hit->exec) {
-      ++ctx->graph_launches;
-      DSX_HIP(hipGraphLaunch(hit->exec, main));
-      return DSX_OK;
-    }
-    if (hit->seen++ == 0)  // first sight: eager (one-off calls never pay for a capture; function attributes get set)
-      return run_cohort(ctx, view, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
-    // second sight: capture the chain (the helper stream joins the capture through its fork event and is joined
-    // back before the final kernel), instantiate, launch
-    if (hipStreamBeginCapture(main, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-      (void)hipGetLastError();
-      ctx->graph_mode = 0;
-      return run_cohort(ctx, view, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
-    }
-    const int rc = run_cohort(ctx, view, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
-    hipGraph_t graph = nullptr;
-    const hipError_t ce = hipStreamEndCapture(main, &graph);
-    hipGraphExec_t exec = nullptr;
-    if (rc == DSX_OK && ce == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-      (void)hipGraphDestroy(graph);
-      hit->exec = exec;
-      ++ctx->graph_captures;
-      ++ctx->graph_launches;
-      DSX_HIP(hipGraphLaunch(exec, main));
-      return DSX_OK;
-    }
-    // capture is not usable here: nothing has run yet -- fall back to eager launches for good
-    (void)hipGetLastError();
-    if (graph) (void)hipGraphDestroy(graph);
-    ctx->graph_mode = 0;
-    if (rc != DSX_OK) return rc;
-    return run_cohort(ctx, view, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
+    return run_cohort_graphed(ctx, view, main, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
   }
   const bool no_pipe = ctx->tune.no_pipeline;
   auto& ls = ctx->last_split;
@@ -1261,27 +1089,15 @@ int streaks_cohort(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d
 
 // dsx_run_host (host = true: staged through the context's device buffers) / dsx_run_device of a streaks plan
 int streaks_run(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, int out_dtype, bool host) {
-  if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, DSX_EINVAL, "bad plane pointers / count");
-  if ((in_dtype != DSX_U16 && in_dtype != DSX_F32) || (out_dtype != DSX_U16 && out_dtype != DSX_F32))
-    return fail(ctx, DSX_EINVAL, "unknown element type");
+  if (int rc = check_run_args(ctx, in, out, n, in_dtype, out_dtype)) return rc;
   DSX_HIP(hipSetDevice(ctx->device));
   const dsx::st::StreaksPlan& p = ctx->sp;
   const size_t in_plane = (size_t)p.H * p.W * elem_size(in_dtype);
   const size_t out_plane = (size_t)p.H * p.W * elem_size(out_dtype);
   const int B = p.B;
   if (host) {
-    if (ctx->stage_in_bytes < in_plane * B) {
-      if (ctx->d_stage_in) (void)hipFree(ctx->d_stage_in);
-      ctx->d_stage_in = nullptr; ctx->stage_in_bytes = 0;
-      DSX_HIP(hipMalloc(&ctx->d_stage_in, in_plane * B));
-      ctx->stage_in_bytes = in_plane * B;
-    }
-    if (ctx->stage_out_bytes < out_plane * B) {
-      if (ctx->d_stage_out) (void)hipFree(ctx->d_stage_out);
-      ctx->d_stage_out = nullptr; ctx->stage_out_bytes = 0;
-      DSX_HIP(hipMalloc(&ctx->d_stage_out, out_plane * B));
-      ctx->stage_out_bytes = out_plane * B;
-    }
+    if (int rc = grow_stage(ctx, &ctx->d_stage_in, &ctx->stage_in_bytes, in_plane * B)) return rc;
+    if (int rc = grow_stage(ctx, &ctx->d_stage_out, &ctx->stage_out_bytes, out_plane * B)) return rc;
   }
   if (host) {  // a value error of an earlier asynchronous call is reported now, not wiped by this call's check
     DSX_HIP(hipStreamSynchronize(use_main(ctx)));
@@ -1333,13 +1149,13 @@ int dsx_init(int device, dsx_ctx** out_ctx) {
   if (e != hipSuccess) { g_init_error = std::string("hipSetDevice: ") + hipGetErrorString(e); return DSX_EHIP; }
   dsx_ctx* c = new dsx_ctx();
   c->device = device;
-  read_tuning(c->tune);
+  dsx::read_tuning(c->tune);
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) c->cus = cus;
 #ifdef DSX_DIAG
   if (const char* ab = getenv("DSX_ABLATE")) c->ablate = atoi(ab);
 #endif
   if (const char* gm = getenv("DSX_GRAPH")) c->graph_mode = atoi(gm) != 0 ? 1 : 0;
-  if (const char* nf = getenv("DSX_NO_FUSE_RF")) c->no_fuse_rf = atoi(nf) != 0;
-  if (const char* fw = getenv("DSX_FUSE_RF_WIDE")) c->fuse_rf_wide = atoi(fw) != 0;
   if (const char* ns = getenv("DSX_STREAMS")) c->n_streams = std::max(1, std::min(atoi(ns), (int)dsx_ctx::kMaxStreams));
   // DSX_PRIO=p0,p1,...: stream priority per sub-cohort stream (experiment hook; default: all equal)
   int prio[dsx_ctx::kMaxStreams] = {};
@@ -1383,7 +1199,6 @@ int dsx_init(int device, dsx_ctx** out_ctx) {
 
 void dsx_destroy(dsx_ctx* ctx) {
   if (!ctx) return;
-  if (t_tune == &ctx->tune) t_tune = nullptr;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(use_main(ctx));
   (void)dsx_comm_destroy(ctx);
@@ -1462,7 +1277,7 @@ int plan_chain(dsx_ctx* ctx, int height, int width, int max_batch, bool bank, do
     const void* fns[6] = {(const void*)dsx::k_fwd_gen<0>, (const void*)dsx::k_fwd_gen<1>, (const void*)dsx::k_fwd_gen<2>,
                           (const void*)dsx::k_inv_gen<0>, (const void*)dsx::k_inv_gen<1>, (const void*)dsx::k_inv_gen<2>};
     for (const void* fn : fns)
-      DSX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      DSX_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dsx::kLdsLimit));
   }
   const std::string perr = dsx::build_plan(height, width, ctx->cfg, ctx->plan, bank ? ctx->wl_bank_len : dsx::kFilterLen);
   if (!perr.empty()) {
@@ -1593,9 +1408,7 @@ int dsx_run_device(dsx_ctx* ctx, const void* d_in, int in_dtype, int n, void* d_
   if (!ctx) return DSX_EINVAL;
   if (ctx->streaks) return streaks_run(ctx, d_in, in_dtype, n, d_out, out_dtype, false);
   if (!ctx->planned) return fail(ctx, DSX_ENOPLAN, "dsx_plan has not been called");
-  if (n < 0 || (n > 0 && (!d_in || !d_out))) return fail(ctx, DSX_EINVAL, "bad plane pointers / count");
-  if ((in_dtype != DSX_U16 && in_dtype != DSX_F32) || (out_dtype != DSX_U16 && out_dtype != DSX_F32))
-    return fail(ctx, DSX_EINVAL, "unknown element type");
+  if (int rc = check_run_args(ctx, d_in, d_out, n, in_dtype, out_dtype)) return rc;
   DSX_HIP(hipSetDevice(ctx->device));
   if (ctx->stack_mode && n > ctx->max_batch)
     return fail(ctx, DSX_ELIMIT, "stack mode: all planes of the stack must fit one cohort (plan with max_batch >= n)");
@@ -1625,9 +1438,7 @@ int dsx_run_host(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, i
   if (!ctx) return DSX_EINVAL;
   if (ctx->streaks) return streaks_run(ctx, in, in_dtype, n, out, out_dtype, true);
   if (!ctx->planned) return fail(ctx, DSX_ENOPLAN, "dsx_plan has not been called");
-  if (n < 0 || (n > 0 && (!in || !out))) return fail(ctx, DSX_EINVAL, "bad plane pointers / count");
-  if ((in_dtype != DSX_U16 && in_dtype != DSX_F32) || (out_dtype != DSX_U16 && out_dtype != DSX_F32))
-    return fail(ctx, DSX_EINVAL, "unknown element type");
+  if (int rc = check_run_args(ctx, in, out, n, in_dtype, out_dtype)) return rc;
   DSX_HIP(hipSetDevice(ctx->device));
   const dsx::Plan& p = ctx->plan;
   const size_t in_plane = (size_t)p.H * p.W * elem_size(in_dtype);
@@ -1636,18 +1447,8 @@ int dsx_run_host(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, i
   if (ctx->stack_mode && n > B)
     return fail(ctx, DSX_ELIMIT, "stack mode: all planes of the stack must fit one cohort (plan with max_batch >= n)");
   const size_t need_in = in_plane * B, need_out = out_plane * B + sizeof(int32_t) * B;
-  if (ctx->stage_in_bytes < need_in) {
-    if (ctx->d_stage_in) (void)hipFree(ctx->d_stage_in);
-    ctx->d_stage_in = nullptr; ctx->stage_in_bytes = 0;
-    DSX_HIP(hipMalloc(&ctx->d_stage_in, need_in));
-    ctx->stage_in_bytes = need_in;
-  }
-  if (ctx->stage_out_bytes < need_out) {
-    if (ctx->d_stage_out) (void)hipFree(ctx->d_stage_out);
-    ctx->d_stage_out = nullptr; ctx->stage_out_bytes = 0;
-    DSX_HIP(hipMalloc(&ctx->d_stage_out, need_out));
-    ctx->stage_out_bytes = need_out;
-  }
+  if (int rc = grow_stage(ctx, &ctx->d_stage_in, &ctx->stage_in_bytes, need_in)) return rc;
+  if (int rc = grow_stage(ctx, &ctx->d_stage_out, &ctx->stage_out_bytes, need_out)) return rc;
   int32_t* d_cfg = (int32_t*)((char*)ctx->d_stage_out + out_plane * B);
   // A value error of an EARLIER asynchronous dsx_run_device call on this context that nobody has synchronised with yet
   // is reported now (this call synchronises) instead of being wiped by this call's own bookkeeping below.

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dsx_chain.h"  // launch-geometry constants (kMarchCols, kRowMaxWaves, kRfWaves, ...)
 #include "dsx_fft_core.h"
 
 // ---- build-time switches (defaults = the product; tools/build_variant.sh builds A/B variants with -D...) ----------
@@ -302,9 +303,6 @@ struct Fwd1Args {
   int shared;
 };
 
-constexpr int kMarchCols = 256;                 // input columns per wave
-constexpr int kMarchOut = (kMarchCols - 4) / 2;  // 126 coefficient columns per wave
-constexpr int kFuseOut = (kMarchOut - 4) / 2;    // 61 level-2 columns per wave of the fused kernel
 constexpr int kRingRows = 8;                     // aa_1 rows a wave keeps in LDS (6 are needed)
 constexpr int kRingPitch = 128;                  // floats per ring row (126 columns + margin positions)
 constexpr int kX2Pitch = 136;                    // (lo, hi) pairs of the level-2 row exchange (reads run to 2*63+5)
@@ -1089,8 +1087,6 @@ struct HistBins {
 // values of a thread, far below 65536).  10 vector + 2 LDS instructions per value; no data-dependent branch.
 constexpr int kHistLoads = 8;  // 16-byte loads in flight per lane
 
-constexpr int kHistWaves = 8;  // waves per block: they share one 32 KB counter array (LDS is what the 4-stream mix runs short of)
-
 __global__ __launch_bounds__(64 * kHistWaves) void k_hist(HistArgs args) {
   __shared__ __attribute__((aligned(16))) unsigned s_cnt[256 * 32];
   __shared__ float s_edge[264];
@@ -1633,7 +1629,6 @@ template <int CPL>
 constexpr int row_waves_per_simd() {
   return CPL <= 18 ? 4 : 1;
 }
-constexpr int kRowMaxWaves = 8;  // waves (row pairs) per block; they share one twiddle table
 
 // One wave per pair of rows.  CPL = complex values per lane = ceil(M / 64).
 // GF_ / NT_ >= 0: the slot structure of the row (full groups, tail slots) is a compile-time constant
@@ -2016,7 +2011,6 @@ __global__ __launch_bounds__(64 * kRowMaxWaves, row_waves_per_simd<CPL>()) void 
 // The row filters of SEVERAL coarse levels in one launch (round 3): levels 3 ... 8 of a 2048^2 plane are six launches of
 // a few hundred to a few thousand row pairs, each behind a launch gap; their rows all fit the CPL = 6 class (M <= 384),
 // so one grid carries them all and every block picks the RowArgs of its level from the block index.
-constexpr int kRowMultiMax = 8;
 struct RowMultiArgs {
   int nlev;
   int blk_end[kRowMultiMax];  // cumulative block counts
@@ -2043,9 +2037,6 @@ __global__ __launch_bounds__(64 * kRowMaxWaves, row_waves_per_simd<CPL>()) void 
 // order-preserving integer keys (both rows in lockstep, one block-wide count per step): simple and bounded; these
 // shapes are rare (no SmartSPIM camera is that wide) and the kernel is written for the reference's "any width"
 // (filtering.py:206), not for speed.  Same arithmetic as rf_pair_body everywhere else.
-constexpr int kWideThreads = 512;
-constexpr int kWideCpl = 36;                              // complex values per lane
-constexpr int kWideMaxLen = kWideThreads * kWideCpl;      // 18 432: transform lengths the kernel takes
 
 __device__ __forceinline__ unsigned wide_block_sum(unsigned v, unsigned* s_red, int& turn) {
   v = __reduce_add_sync(~0ull, v);
@@ -2813,8 +2804,6 @@ __global__ __launch_bounds__(64 * WPB, (FUSE && IN_KIND == 0) ? DSX_INV_MINW : 1
 // 2048 (2000-wide: the production tile) and 902 in 1815 (1800-wide) -- one block of 8 waves per CU for those two,
 // against ONE block of 4 waves for their k_rowfilter.  Everything else takes k_rowfilter + k_inv_march.
 // ================================================================================================
-constexpr int kRfWaves = 8;
-constexpr int kRfRows = 2 * kRfWaves - 2;  // coefficient rows p per block
 
 struct RowFinalArgs {
   RowArgs r;

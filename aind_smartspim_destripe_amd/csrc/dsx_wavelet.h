@@ -24,8 +24,6 @@
 namespace dsx {
 
 constexpr int kMaxTaps = 104;  // coif17 has 102
-constexpr int kGenTH = 16, kGenTW = 32;    // coefficients per block of k_fwd_gen
-constexpr int kGenOH = 32, kGenOW = 64;    // results per block of k_inv_gen
 
 struct GenFwdArgs {
   const void* in;  // IN_KIND 0 / 1: pixels [B][H][W]
@@ -45,12 +43,7 @@ struct GenFwdArgs {
   float lo[kMaxTaps], hi[kMaxTaps];  // dec_lo, dec_hi
 };
 
-// LDS floats of k_fwd_gen for F taps
-inline __host__ __device__ int gen_fwd_cols(int F) { return 2 * kGenTW + F - 2 + 1; }  // + 1: odd pitch
-inline __host__ __device__ int gen_fwd_rows(int F) { return 2 * kGenTH + F - 2; }
-inline size_t gen_fwd_lds_bytes(int F) {
-  return sizeof(float) * (size_t)(gen_fwd_rows(F) + 2 * kGenTH) * gen_fwd_cols(F);
-}
+// (LDS geometry of k_fwd_gen: gen_fwd_cols / gen_fwd_rows / gen_fwd_lds_bytes, dsx_chain.h)
 
 template <int IN_KIND>
 __global__ __launch_bounds__(256) void k_fwd_gen(GenFwdArgs a) {
@@ -173,11 +166,7 @@ struct GenInvArgs {
   float lo[kMaxTaps], hi[kMaxTaps];  // rec_lo, rec_hi
 };
 
-inline __host__ __device__ int gen_inv_krows(int F) { return kGenOH / 2 + F / 2 - 1; }
-inline __host__ __device__ int gen_inv_kcols(int F) { return kGenOW / 2 + F / 2 - 1; }
-inline size_t gen_inv_lds_bytes(int F) {
-  return sizeof(float) * 2 * (size_t)gen_inv_krows(F) * (gen_inv_kcols(F) + 1 + kGenOW + 1);
-}
+// (LDS geometry of k_inv_gen: gen_inv_krows / gen_inv_kcols / gen_inv_lds_bytes, dsx_chain.h)
 
 // MODE 0 / 1: last level with uint16 / float32 pixels; MODE 2: pyramid level (writes c_{l-1} into the workspace)
 template <int MODE>
