@@ -57,6 +57,13 @@
 #ifndef DSX_FWD_MINW
 #define DSX_FWD_MINW 4  // waves per SIMD the fused uint16 forward kernel is compiled for (register cap 128)
 #endif
+#ifndef DSX_RF_STEADY
+// k_rowfinal, synthesis phase: 1 = the row loop is straight-line with respect to vector memory (no load or store under a
+// condition, the level-2 step at a fixed place, exits between row pairs only), so that the compiler counts its waits and
+// the pixel rows it prefetches stay in flight; 0 = the loop of three predicated steps, which drained the memory queue in
+// every step (rowfinal_synth, DESIGN.md section 4.5, profiles/march_waits_before.txt)
+#define DSX_RF_STEADY 1
+#endif
 
 
 // Timing-only switches (DSX_ABLATE bits: kernels skip a phase or a store path and return WRONG pixels) exist in
@@ -100,6 +107,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t dsx_rsrc(const void* p) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, -1, 0x00020000);
 }
 constexpr int kBufNT = 2;  // aux bits of a streaming (non-temporal) buffer access on gfx94x / gfx950
+// The same over [p, p + bytes): a load at or past `bytes` returns zeros and a store there is dropped by the address unit, so
+// a wave can issue a memory instruction unconditionally and discard it per lane through the offset it passes.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t dsx_rsrc_bounded(const void* p, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, (int)bytes, 0x00020000);
+}
+// lane offset of a discarded access: past every bounded descriptor (dsx_rsrc_bounded is given at most this many bytes),
+// and far enough below 2^32 that adding a row offset to it cannot wrap back into range
+constexpr unsigned kBufDiscard = 0x80000000u;
 
 // Packed multiply-add with a FIXED evaluation order.  (a * b + c * d + e * f written with operators leaves
 // the choice of which product is rounded first to the compiler, and two inlined copies of one expression --
@@ -2817,7 +2832,11 @@ struct RowFinalPre {
 
 };
 
-template <bool SHADE, bool PREFETCH_ONLY = false>
+// STEADY_: the row loop without a memory instruction under a condition (DSX_RF_STEADY; see the loop).  Not with shading
+// and not for the wide plans: the dark / flat values of a step, or what the wide plans' first phase keeps per lane,
+// leave the six unrolled steps no room under the register count the kernel has without them (with shading it spilled,
+// 192 bytes per lane; the wide plans went from 125 / 148 to 165 registers).
+template <bool SHADE, bool STEADY_, bool PREFETCH_ONLY = false>
 __device__ __forceinline__ void rowfinal_synth(const FinalArgs& a, const float2* smem, int M, int lane, int strip, int plane,
                                                int p_begin, int p_end, int row0, RowFinalPre& pre) {
   constexpr float RL0[6] = DSX_REC_LO;
@@ -2825,6 +2844,7 @@ __device__ __forceinline__ void rowfinal_synth(const FinalArgs& a, const float2*
   constexpr float KS = 1.44269504088896340736f;  // the result feeds exp2(): the axis-0 taps of level 1 carry log2(e)
   constexpr float RL[6] = {RL0[0] * KS, RL0[1] * KS, RL0[2] * KS, RL0[3] * KS, RL0[4] * KS, RL0[5] * KS};
   constexpr float RH[6] = {RH0[0] * KS, RH0[1] * KS, RH0[2] * KS, RH0[3] * KS, RH0[4] * KS, RH0[5] * KS};
+  constexpr bool STEADY = STEADY_ && !SHADE;
   const int x0 = kMarchCols * strip + 4 * lane;
   const int xl = min(x0, a.W - 4);  // lanes right of the plane: clamped (valid) addresses, results never stored
   const int ql = xl >> 1;           // first Delta_1 / c_1 column of the lane
@@ -2832,9 +2852,16 @@ __device__ __forceinline__ void rowfinal_synth(const FinalArgs& a, const float2*
   const int oddm = odd_lane_mask(lane);
   const int xb = min(kMarchCols * strip + 8 * (lane >> 1), a.W - 8);  // first column of the lane pair (clamped)
   const __amdgpu_buffer_rsrc_t rs_img = dsx_rsrc((const char*)a.img + plane * a.img_plane_stride * 2);
-  const __amdgpu_buffer_rsrc_t rs_out = dsx_rsrc((const char*)a.out + plane * a.out_plane_stride * 2);
+  // STEADY: the result plane and not a byte more: stores are issued by every lane in every step, and the lanes and rows that
+  // have nothing to write pass kBufDiscard as their offset (see step)
+  const long long out_bytes = (long long)a.hout * a.wout * 2;
+  const __amdgpu_buffer_rsrc_t rs_out =
+      STEADY ? dsx_rsrc_bounded((const char*)a.out + plane * a.out_plane_stride * 2, (unsigned)min(out_bytes, (long long)kBufDiscard))
+             : dsx_rsrc((const char*)a.out + plane * a.out_plane_stride * 2);
   const unsigned vo_pair0 = (unsigned)xb * 2u, vo_pair = vo_pair0 + (odd_lane ? (unsigned)a.W * 2u : 0u);
   const unsigned vo_pair_out = (unsigned)xb * 2u + (odd_lane ? (unsigned)a.wout * 2u : 0u);
+  const unsigned vo_store = x0 < a.wout ? vo_pair_out : kBufDiscard;  // lanes right of the result write nothing
+  const int store_rows = a.hout - (odd_lane ? 1 : 0);                 // the lane writes row 2 p + (lane & 1) if 2 p < store_rows
   const int xs = min(x0, max(a.wout - 4, 0));
   const __amdgpu_buffer_rsrc_t rs_dark = dsx_rsrc(SHADE ? a.dark : a.ws), rs_flat = dsx_rsrc(SHADE ? a.flat : a.ws);
   const unsigned vo_shade = (unsigned)xs * 4u;
@@ -2845,13 +2872,16 @@ __device__ __forceinline__ void rowfinal_synth(const FinalArgs& a, const float2*
   const int Q = ql >> 1;
   const float* c2base = a.ws + plane * a.ws_plane_stride + a.c2_off;
   const float* d2base = a.ws + plane * a.ws_plane_stride + a.d2_off;
-  const __amdgpu_buffer_rsrc_t rs_c2 = dsx_rsrc(c2base), rs_d2 = dsx_rsrc(d2base);
+  // STEADY: has_c2 decided once, outside the loop and without a second copy of it: a chain that has no c_2 reads it
+  // through a descriptor of zero bytes, and every such load returns the zeros that the predicated load leaves in place
+  const __amdgpu_buffer_rsrc_t rs_c2 = STEADY ? dsx_rsrc_bounded(c2base, a.has_c2 ? kBufDiscard : 0u) : dsx_rsrc(c2base);
+  const __amdgpu_buffer_rsrc_t rs_d2 = dsx_rsrc(d2base);
   const unsigned vo_2 = (unsigned)Q * 4u;
   auto l2_load = [&](int P2) {
     FinalRawC r;
     r.c01 = r.c23 = make_float2(0.f, 0.f);
     const int pr = min(P2, a.hc2 - 1);  // rows past the end only feed c_1 rows that are never used
-    if (a.has_c2) {
+    if (STEADY || a.has_c2) {
       const dsx_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(rs_c2, vo_2, (unsigned)(pr * a.ldc2) * 4u, 0);
       r.c01 = make_float2(__uint_as_float(u.x), __uint_as_float(u.y));
       r.c23 = make_float2(__uint_as_float(u.z), __uint_as_float(u.w));
@@ -2861,8 +2891,11 @@ __device__ __forceinline__ void rowfinal_synth(const FinalArgs& a, const float2*
     r.d23 = make_float2(__uint_as_float(u.z), __uint_as_float(u.w));
     return r;
   };
+  // STEADY: the loop prefetches three steps ahead without asking whether those steps exist: past the block's last row
+  // pair it loads that pair again (a row this wave has just read) and not the next block's rows
+  const int gy_last = STEADY ? min(2 * p_end - 2, a.H - 1) : a.H - 1;
   auto issue_i = [&](int gy) {  // 16 bytes of pixel row gy + (lane & 1), one load per row pair
-    const int ge = min(gy, a.H - 1);                          // wave-uniform
+    const int ge = min(gy, gy_last);                          // wave-uniform
     const unsigned vo = (ge + 1 < a.H) ? vo_pair : vo_pair0;  // the odd lane's row exists (scalar condition)
     const dsx_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(rs_img, vo, (unsigned)(ge * a.W) * 2u, kBufNT);
     return make_uint4(u.x, u.y, u.z, u.w);
@@ -2899,12 +2932,23 @@ __device__ __forceinline__ void rowfinal_synth(const FinalArgs& a, const float2*
     ++next_P;
     c1_ready += 2;
   };
-  // row-synthesised c_1 row p (rows are asked for in increasing order, each once)
-  auto c1_row = [&](int p, dsx_f2 (&out)[2]) {
-    if (c1_ready <= p) l2_step();  // wave-uniform
-    const dsx_f2 lo = (p & 1) ? c1o[0] : c1e[0], hi = (p & 1) ? c1o[1] : c1e[1];
+  // row-synthesised c_1 row p (rows are asked for in increasing order, each once).  par: the parity of p where the caller
+  // knows it (p_begin is even, so it is the parity of the step) -- the level-2 step then sits in the even rows, at a fixed
+  // place of the code, and its loads are under no condition; -1: decided at run time
+  auto c1_row = [&](auto par, int p, dsx_f2 (&out)[2]) {
+    constexpr int PAR = decltype(par)::value;
+    if constexpr (PAR < 0) {
+      if (c1_ready <= p) l2_step();  // wave-uniform
+    } else if constexpr (PAR == 0) {
+      l2_step();
+    }
+    const bool odd = PAR < 0 ? (p & 1) != 0 : PAR != 0;
+    const dsx_f2 lo = odd ? c1o[0] : c1e[0], hi = odd ? c1o[1] : c1e[1];
     final_xsynth(make_float2(lo.x, lo.y), make_float2(hi.x, hi.y), out);
   };
+  using RowEven = std::integral_constant<int, STEADY ? 0 : -1>;
+  using RowOdd = std::integral_constant<int, STEADY ? 1 : -1>;
+  using AtRunTime = std::integral_constant<int, -1>;
   // row-synthesised Delta_1 row r out of the block's FFT buffers (planar rows, see rf_pair_body<.., TO_LDS>)
   auto d1_row = [&](int r, dsx_f2 (&out)[2]) {
     const int rr = r - row0;  // 0 .. 2 kRfWaves - 1 (wave-uniform)
@@ -2915,19 +2959,20 @@ __device__ __forceinline__ void rowfinal_synth(const FinalArgs& a, const float2*
 
   dsx_f2 A[3][2], D[3][2];  // windows: rows p, p + 1, p + 2
   uint4 ni[3] = {pre.ni[0], pre.ni[1], issue_i(2 * (p_begin + 2))};
-  c1_row(p_begin, A[0]);
+  c1_row(RowEven(), p_begin, A[0]);
   d1_row(p_begin, D[0]);
-  c1_row(p_begin + 1, A[1]);
+  c1_row(RowOdd(), p_begin + 1, A[1]);
   d1_row(p_begin + 1, D[1]);
 
-  auto px_row = [&](int gy, uint2 u, const dsx_f2 (&c0p)[2], unsigned (&pk)[2]) {
+  // vec: shade_vec as a constant (0 / 1) where the loop is compiled for one answer, AtRunTime where it asks in every row
+  auto px_row = [&](auto vec, int gy, uint2 u, const dsx_f2 (&c0p)[2], unsigned (&pk)[2]) {
     const float c0[4] = {c0p[0].x, c0p[0].y, c0p[1].x, c0p[1].y};
     const float px[4] = {(float)(u.x & 0xFFFFu), (float)(u.x >> 16), (float)(u.y & 0xFFFFu), (float)(u.y >> 16)};
     float r[4];
     if (SHADE) {
       float dk[4], fl[4];
       const int gys = min(gy, a.hout - 1);
-      if (shade_vec) {
+      if (decltype(vec)::value < 0 ? shade_vec : decltype(vec)::value != 0) {
         const dsx_u32x4 d4 = __builtin_amdgcn_raw_buffer_load_b128(rs_dark, vo_shade, (unsigned)(gys * a.dark_ld) * 4u, 0);
         const dsx_u32x4 f4 = __builtin_amdgcn_raw_buffer_load_b128(rs_flat, vo_shade, (unsigned)(gys * a.wout) * 4u, 0);
         dk[0] = __uint_as_float(d4.x); dk[1] = __uint_as_float(d4.y); dk[2] = __uint_as_float(d4.z); dk[3] = __uint_as_float(d4.w);
@@ -2957,9 +3002,9 @@ __device__ __forceinline__ void rowfinal_synth(const FinalArgs& a, const float2*
     pk[1] = pack_u16_sat(r[2], r[3]);
   };
   // one coefficient row p -> result rows 2p, 2p + 1; (A0, A1, A2) = window rows p, p + 1, p + 2
-  auto step = [&](int p, const uint4& ri, dsx_f2 (&A0)[2], dsx_f2 (&A1)[2], dsx_f2 (&A2w)[2], dsx_f2 (&D0)[2],
-                  dsx_f2 (&D1)[2], dsx_f2 (&D2w)[2]) {
-    c1_row(p + 2, A2w);
+  auto step = [&](auto par, auto vec, int p, const uint4& ri, dsx_f2 (&A0)[2], dsx_f2 (&A1)[2], dsx_f2 (&A2w)[2],
+                  dsx_f2 (&D0)[2], dsx_f2 (&D1)[2], dsx_f2 (&D2w)[2]) {
+    c1_row(par, p + 2, A2w);
     d1_row(p + 2, D2w);
     dsx_f2 even[2], odd[2];
 #pragma unroll
@@ -2974,26 +3019,80 @@ __device__ __forceinline__ void rowfinal_synth(const FinalArgs& a, const float2*
     const uint2 r0 = make_uint2(bit_select(oddm, gx, ri.x), bit_select(oddm, gyv, ri.y));  // row 2p, own 4 columns
     const uint2 r1 = make_uint2(bit_select(oddm, ri.z, gx), bit_select(oddm, ri.w, gyv));  // row 2p + 1
     unsigned pe[2], po[2];
-    px_row(2 * p, r0, even, pe);
-    px_row(2 * p + 1, r1, odd, po);
+    px_row(vec, 2 * p, r0, even, pe);
+    px_row(vec, 2 * p + 1, r1, odd, po);
     const unsigned tx = swap_adjacent(bit_select(oddm, pe[0], po[0])), ty = swap_adjacent(bit_select(oddm, pe[1], po[1]));
     dsx_u32x4 o4;
     o4.x = bit_select(oddm, tx, pe[0]);
     o4.y = bit_select(oddm, ty, pe[1]);
     o4.z = bit_select(oddm, po[0], tx);
     o4.w = bit_select(oddm, po[1], ty);
-    const int gyl = 2 * p + (odd_lane ? 1 : 0);
-    if (gyl < a.hout && x0 < a.wout)
-      __builtin_amdgcn_raw_buffer_store_b128(o4, rs_out, vo_pair_out, (unsigned)(2 * p * a.wout) * 2u, kBufNT);
+    if constexpr (decltype(par)::value >= 0) {
+      // every lane stores in every step; a row past the result (the second step of a last, odd pair included) and a lane
+      // right of it go to kBufDiscard, which rs_out drops
+      const unsigned vo = 2 * p < store_rows ? vo_store : kBufDiscard;
+      __builtin_amdgcn_raw_buffer_store_b128(o4, rs_out, vo, (unsigned)(2 * p * a.wout) * 2u, kBufNT);
+      // The store reads its 16 bytes of data over several cycles, and in straight-line code the next instruction is the
+      // prefetch's address select, for which the register allocator takes the first data register: 28 x 2048 planes came
+      // out with that address in 192 pixels of result rows 4, 5, 12 and 13.  The compiler pads a 16-byte store only when its
+      // row offset is an immediate (the documented case); with the offset in a scalar register it pads nothing, so the wait
+      // states stand here, fenced so that nothing is scheduled between the store and them (the documented 2, and one).
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_nop 2");
+      __builtin_amdgcn_sched_barrier(0);
+    } else {
+      const int gyl = 2 * p + (odd_lane ? 1 : 0);
+      if (gyl < a.hout && x0 < a.wout)
+        __builtin_amdgcn_raw_buffer_store_b128(o4, rs_out, vo_pair_out, (unsigned)(2 * p * a.wout) * 2u, kBufNT);
+    }
   };
-  for (int p = p_begin; p < p_end; p += 3) {
-    const bool more = p + 3 < p_end;  // wave-uniform
-    step(p, ni[0], A[0], A[1], A[2], D[0], D[1], D[2]);
-    if (more) ni[0] = issue_i(2 * (p + 3));
-    if (p + 1 < p_end) step(p + 1, ni[1], A[1], A[2], A[0], D[1], D[2], D[0]);
-    if (more) ni[1] = issue_i(2 * (p + 4));
-    if (p + 2 < p_end) step(p + 2, ni[2], A[2], A[0], A[1], D[2], D[0], D[1]);
-    if (more) ni[2] = issue_i(2 * (p + 5));
+  // STEADY.  Six steps per trip: the windows and the pixel rows rotate with period three and the level-2 step comes every
+  // second row, so after six steps every value is back in the register it started in and nothing is decided at run time
+  // inside the body.  Steps come in pairs (one level-2 row each); the loop is left between pairs only, and a pair whose second
+  // row does not exist computes it from clamped rows and stores nowhere.  The body has no join: the exits branch out of
+  // it and nothing branches around a memory instruction, so the compiler knows how many operations are younger than the
+  // one it waits for.  A wave issues 2 level-2 loads at the head of an even step and, at the end of every step, the
+  // result store and the pixel-row load for the step three ahead.  The waits that follow from it
+  // (profiles/march_waits_after.txt):
+  //   level-2 row, loaded one pair before the even step that consumes it: the 2 stores and 2 pixel loads of that pair are
+  //     younger than its Delta_2 half, the c_2 half is one older -- vmcnt(5) / vmcnt(4); where the scheduler issues the
+  //     next level-2 loads (or the pixel load) first, the same wait reads vmcnt(7) / vmcnt(6).  The even step's own pixel
+  //     row is older than both: no wait of its own.
+  //   odd step, its pixel row: [store, pixel load] of the step after it and [2 level-2 loads, store, pixel load] of the
+  //     even step that follows are younger -- vmcnt(6).
+  //   first wait of a trip: reached from the prologue as well, which has issued fewer operations behind the same loads;
+  //     the compiler takes the smaller count of the two ways in -- vmcnt(3).
+  // Never vmcnt(0): three pixel rows, one level-2 row and the stores stay in flight across every wait.
+  if constexpr (STEADY) {
+    const std::integral_constant<int, 1> vec;  // no shading here: px_row asks nothing
+    for (int p = p_begin;; p += 6) {
+      step(RowEven(), vec, p, ni[0], A[0], A[1], A[2], D[0], D[1], D[2]);
+      ni[0] = issue_i(2 * (p + 3));
+      step(RowOdd(), vec, p + 1, ni[1], A[1], A[2], A[0], D[1], D[2], D[0]);
+      ni[1] = issue_i(2 * (p + 4));
+      if (p + 2 >= p_end) break;
+      step(RowEven(), vec, p + 2, ni[2], A[2], A[0], A[1], D[2], D[0], D[1]);
+      ni[2] = issue_i(2 * (p + 5));
+      step(RowOdd(), vec, p + 3, ni[0], A[0], A[1], A[2], D[0], D[1], D[2]);
+      ni[0] = issue_i(2 * (p + 6));
+      if (p + 4 >= p_end) break;
+      step(RowEven(), vec, p + 4, ni[1], A[1], A[2], A[0], D[1], D[2], D[0]);
+      ni[1] = issue_i(2 * (p + 7));
+      step(RowOdd(), vec, p + 5, ni[2], A[2], A[0], A[1], D[2], D[0], D[1]);
+      ni[2] = issue_i(2 * (p + 8));
+      if (p + 6 >= p_end) break;
+    }
+  } else {
+    const AtRunTime rt;
+    for (int p = p_begin; p < p_end; p += 3) {
+      const bool more = p + 3 < p_end;  // wave-uniform
+      step(rt, rt, p, ni[0], A[0], A[1], A[2], D[0], D[1], D[2]);
+      if (more) ni[0] = issue_i(2 * (p + 3));
+      if (p + 1 < p_end) step(rt, rt, p + 1, ni[1], A[1], A[2], A[0], D[1], D[2], D[0]);
+      if (more) ni[1] = issue_i(2 * (p + 4));
+      if (p + 2 < p_end) step(rt, rt, p + 2, ni[2], A[2], A[0], A[1], D[2], D[0], D[1]);
+      if (more) ni[2] = issue_i(2 * (p + 5));
+    }
   }
 }
 
@@ -3023,11 +3122,12 @@ __global__ __launch_bounds__(64 * kRfWaves, CPL <= 18 ? 4 : 2) void k_rowfinal(R
   RowFinalPre pre;
   asm volatile("" ::: "memory");  // keep the prefetch loads (and their registers) out of the row-filter phase
   __builtin_amdgcn_sched_barrier(0);
-  if (synth) rowfinal_synth<false, true>(a.f, dsx_smem, M, lane, wave, plane, p_begin, p_end, 2 * pair0, pre);
+  constexpr bool STEADY = DSX_RF_STEADY != 0 && CPL <= 18;  // the 2048-wide plan: see rowfinal_synth
+  if (synth) rowfinal_synth<false, STEADY, true>(a.f, dsx_smem, M, lane, wave, plane, p_begin, p_end, 2 * pair0, pre);
   __syncthreads();  // all 2 kRfWaves Delta_1 rows of the block are in LDS
   if (!synth) return;
-  if (a.f.flat != nullptr) rowfinal_synth<true>(a.f, dsx_smem, M, lane, wave, plane, p_begin, p_end, 2 * pair0, pre);
-  else rowfinal_synth<false>(a.f, dsx_smem, M, lane, wave, plane, p_begin, p_end, 2 * pair0, pre);
+  if (a.f.flat != nullptr) rowfinal_synth<true, STEADY>(a.f, dsx_smem, M, lane, wave, plane, p_begin, p_end, 2 * pair0, pre);
+  else rowfinal_synth<false, STEADY>(a.f, dsx_smem, M, lane, wave, plane, p_begin, p_end, 2 * pair0, pre);
 }
 
 }  // namespace dsx
