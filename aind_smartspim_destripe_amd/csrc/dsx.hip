@@ -25,6 +25,7 @@
 #include "dsx_kernels.h"
 #include "dsx_retile.h"
 #include "dsx_pyramid.h"
+#include "dsx_volhist.h"
 #include "dsx_wavelet.h"
 #include "dsx_plan.h"
 #include "dsx_chain.h"
@@ -113,6 +114,8 @@ struct dsx_ctx {
   uint8_t* zdec_scratch = nullptr;
   size_t zdec_bytes = 0;
   unsigned* d_sticky = nullptr;
+  // dsx_volhist_*: 65 536 uint64 bins, allocated by the first dsx_volhist_reset; no plan call touches it
+  unsigned long long* volhist = nullptr;
   // dsx_set_stack_mode: the planes of a call share ONE Otsu threshold per level (the reference's 3-D input mode)
   bool stack_mode = false;
   // DSX_ABLATE environment variable (timing-only switches that return WRONG pixels): read only by a library built
@@ -1223,6 +1226,7 @@ void dsx_destroy(dsx_ctx* ctx) {
   if (ctx->zenc_sizes) (void)hipFree(ctx->zenc_sizes);
   if (ctx->zenc_lits) (void)hipFree(ctx->zenc_lits);
   if (ctx->zdec_scratch) (void)hipFree(ctx->zdec_scratch);
+  if (ctx->volhist) (void)hipFree(ctx->volhist);
   if (ctx->ev_xs) (void)hipEventDestroy(ctx->ev_xs);
   for (int i = 0; i < dsx_ctx::kEventSlots; ++i)
     if (ctx->ev_slot[i]) (void)hipEventDestroy(ctx->ev_slot[i]);
@@ -1689,6 +1693,57 @@ int dsx_downsample2_u16(dsx_ctx* ctx, const void* d_src, void* d_dst, int Z, int
   if (vec) hipLaunchKernelGGL(dsx::k_downsample2<true>, grid, dim3(256), 0, use_main(ctx), a);
   else hipLaunchKernelGGL(dsx::k_downsample2<false>, grid, dim3(256), 0, use_main(ctx), a);
   DSX_HIP(hipGetLastError());
+  return DSX_OK;
+}
+
+/* ---- histogram of the written volume (dsx_volhist.h): the display window of zarr_destriper.py:722-726 ------------ */
+int dsx_volhist_reset(dsx_ctx* ctx) {
+  if (!ctx) return DSX_EINVAL;
+  DSX_HIP(hipSetDevice(ctx->device));
+  if (!ctx->volhist && hipMalloc((void**)&ctx->volhist, (size_t)dsx::vh::kVhBins * 8) != hipSuccess) {
+    ctx->volhist = nullptr;
+    return fail(ctx, DSX_ENOMEM, "volhist: no device memory for the histogram");
+  }
+  DSX_HIP(hipMemsetAsync(ctx->volhist, 0, (size_t)dsx::vh::kVhBins * 8, use_main(ctx)));
+  return DSX_OK;
+}
+
+int dsx_volhist_add_device(dsx_ctx* ctx, const void* d_vox, size_t n) {
+  namespace vh = dsx::vh;
+  if (!ctx) return DSX_EINVAL;
+  if (n == 0) return DSX_OK;
+  if (!d_vox) return fail(ctx, DSX_EINVAL, "volhist: the voxel pointer is NULL");
+  if ((uintptr_t)d_vox & 1) return fail(ctx, DSX_EINVAL, "volhist: uint16 voxels must be 2-byte aligned");
+  if (!ctx->volhist) return fail(ctx, DSX_EINVAL, "volhist: dsx_volhist_reset has not been called");
+  if (n >= ((size_t)1 << 32)) return fail(ctx, DSX_ELIMIT, "volhist: 2^32 voxels or more in one call");
+  const size_t head = vh::head_voxels(d_vox, n);
+  const size_t n_vec = (n - head) / 8, tail = n - head - n_vec * 8;
+  const size_t per_block = (size_t)vh::kVhThreads * vh::kVhUnroll;
+  const size_t want = std::max<size_t>(1, (n_vec + per_block - 1) / per_block);
+  const unsigned grid = (unsigned)std::min<size_t>(want, (size_t)2 * ctx->cus);
+  DSX_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(vh::k_volhist_u16, dim3(grid), dim3(vh::kVhThreads), 0, use_main(ctx), (const uint16_t*)d_vox, head,
+                     n_vec, tail, ctx->volhist);
+  DSX_HIP(hipGetLastError());
+  return DSX_OK;
+}
+
+int dsx_volhist_get(dsx_ctx* ctx, uint64_t* hist) {
+  if (!ctx) return DSX_EINVAL;
+  if (!hist) return fail(ctx, DSX_EINVAL, "volhist: the result pointer is NULL");
+  if (!ctx->volhist) return fail(ctx, DSX_EINVAL, "volhist: dsx_volhist_reset has not been called");
+  DSX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = use_main(ctx);
+  DSX_HIP(hipMemcpyAsync(hist, ctx->volhist, (size_t)dsx::vh::kVhBins * 8, hipMemcpyDeviceToHost, s));
+  DSX_HIP(hipStreamSynchronize(s));
+  return DSX_OK;
+}
+
+int dsx_volhist_ref(const void* vox, size_t n, uint64_t* hist) {
+  if (n == 0) return DSX_OK;
+  if (!vox || !hist) return fail(nullptr, DSX_EINVAL, "volhist: NULL pointer");
+  if ((uintptr_t)vox & 1) return fail(nullptr, DSX_EINVAL, "volhist: uint16 voxels must be 2-byte aligned");
+  dsx::vh::volhist_host((const uint16_t*)vox, n, hist);
   return DSX_OK;
 }
 

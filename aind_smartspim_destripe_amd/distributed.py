@@ -267,6 +267,24 @@ class RankGroup:
             return obj
         return json.loads(self.rdzv.get(key).decode())
 
+    def sum_counts(self, counts):
+        """Element-wise sum of every rank's ``int64`` array (a voxel histogram: 65 536 bins) on every rank, through the
+        rendezvous directory whatever the transport, as :meth:`broadcast_json` travels: once per tile and 512 KiB, where
+        the device all-reduce takes 64 doubles a call.  Integer sums: exact.  One rank, or an inactive group, returns the
+        input."""
+        mine = np.ascontiguousarray(counts, dtype=np.int64)
+        if not self.active:
+            return mine
+        self._seq += 1
+        self.rdzv.put("sc.{}.{}".format(self._seq, self.rank), mine.tobytes())
+        total = np.zeros_like(mine)
+        for r in range(self.world):
+            row = np.frombuffer(self.rdzv.get("sc.{}.{}".format(self._seq, r)), dtype=np.int64)
+            if row.size != mine.size:
+                raise ValueError("sum_counts: rank {} sent {} counts, this rank {}".format(r, row.size, mine.size))
+            total += row.reshape(mine.shape)
+        return total
+
     def broadcast_array(self, array, dtype, shape, root=0):
         """A NumPy array held by ``root`` (``array`` is ignored elsewhere) -> a host copy on every rank.
 

@@ -33,6 +33,7 @@ TASK_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<u4"), ("dst
                        ("chunk", "<u4")])  # fmt: skip
 
 COMM_ID_BYTES = 128
+VOLHIST_BINS = 65536  # one bin per uint16 value (dsx_volhist_*)
 _ERRORS = {-1: "DSX_EINVAL", -2: "DSX_ENOPLAN", -3: "DSX_EHIP", -4: "DSX_ENOMEM", -5: "DSX_ELIMIT",
            -6: "DSX_ECOMM", -7: "DSX_EIO", -8: "DSX_EVALUE"}  # fmt: skip
 
@@ -55,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "dsx_io_read_zlib_chunks", "dsx_io_write_chunks_blosc_lz4", "dsx_blosc_encode_lz4",
     "dsx_pyramid_work_bytes", "dsx_pyramid_block_u16", "dsx_pyramid_block_ref",
     "dsx_pyramid_bricks_u16", "dsx_pyramid_bricks_ref",
+    "dsx_volhist_reset", "dsx_volhist_add_device", "dsx_volhist_get", "dsx_volhist_ref",
 ]  # fmt: skip
 
 
@@ -223,6 +225,10 @@ def load_library(path=None):
     lib.dsx_pyramid_bricks_u16.argtypes = [vp, vp] + [i32] * 7 + [ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp), vp,
                                                                   ctypes.c_size_t]  # fmt: skip
     lib.dsx_pyramid_bricks_ref.argtypes = [vp] + [i32] * 7 + [ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp)]
+    lib.dsx_volhist_reset.argtypes = [vp]
+    lib.dsx_volhist_add_device.argtypes = [vp, vp, ctypes.c_size_t]
+    lib.dsx_volhist_get.argtypes = [vp, vp]
+    lib.dsx_volhist_ref.argtypes = [vp, ctypes.c_size_t, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("dsx_destroy", "dsx_last_error"):
@@ -723,6 +729,25 @@ class DestripeEngine:
             raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
         self._check(rc)
 
+    # -- histogram of the written volume (display window of the OME-NGFF metadata) ---------------
+    def volhist_reset(self):
+        """Zero the engine's 65 536-bin voxel histogram (``dsx_volhist_reset``; allocated on first use)."""
+        self._check(self._lib.dsx_volhist_reset(self._ctx))
+
+    def volhist_add(self, d_buf_or_ptr, n):
+        """Count ``n`` contiguous uint16 voxels at a :class:`DeviceBuffer` or a device address into the histogram
+        (``dsx_volhist_add_device``; ``zarr_destriper.py:722-726``).  Asynchronous on the engine stream."""
+        ptr = getattr(d_buf_or_ptr, "ptr", d_buf_or_ptr)
+        nbytes = getattr(d_buf_or_ptr, "nbytes", None)
+        assert nbytes is None or 2 * int(n) <= nbytes, "volhist_add: more voxels than the buffer holds"
+        self._check(self._lib.dsx_volhist_add_device(self._ctx, ctypes.c_void_p(ptr), int(n)))
+
+    def volhist_get(self):
+        """The counts so far as ``np.int64[65536]`` (``dsx_volhist_get``; waits for the engine stream)."""
+        out = np.zeros(VOLHIST_BINS, np.uint64)
+        self._check(self._lib.dsx_volhist_get(self._ctx, out.ctypes.data_as(ctypes.c_void_p)))
+        return out.astype(np.int64)
+
     def foreground_background(self, image, cutoff, want_mask=True):
         """``(fore_mean, back_mean, mask uint8)`` of a host image (uint16 / float32, any shape)."""
         a = np.ascontiguousarray(image)
@@ -837,6 +862,23 @@ def pyramid_work_bytes(zyx, n_levels):
     if lib.dsx_pyramid_work_bytes(*map(int, zyx), int(n_levels), ctypes.byref(n)) != 0:
         raise ValueError("pyramid_work_bytes: bad geometry {} / {} levels".format(tuple(zyx), n_levels))
     return int(n.value)
+
+
+def volhist_ref(array, hist=None):
+    """Host build of the voxel histogram (``dsx_volhist_ref``): the counts of a uint16 ``array`` of any shape as
+    ``np.int64[65536]``; with ``hist`` (an ``np.int64[65536]`` of an earlier call) the counts are added to it."""
+    lib = load_library()
+    a = np.ascontiguousarray(array)
+    if a.dtype != np.uint16:
+        raise ValueError("the voxel histogram takes uint16, got {}".format(a.dtype))
+    if hist is None:
+        hist = np.zeros(VOLHIST_BINS, np.int64)
+    elif hist.dtype != np.int64 or hist.shape != (VOLHIST_BINS,) or not hist.flags["C_CONTIGUOUS"]:
+        raise ValueError("hist must be a C-contiguous int64 array of {} bins".format(VOLHIST_BINS))
+    rc = lib.dsx_volhist_ref(a.ctypes.data_as(ctypes.c_void_p), a.size, hist.ctypes.data_as(ctypes.c_void_p))
+    if rc != 0:
+        raise ValueError((lib.dsx_last_error(None) or b"volhist_ref failed").decode())
+    return hist
 
 
 def pyramid_block_ref(planes, chunks, z0s=None, bricks=None, rows=None):

@@ -153,7 +153,8 @@ def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_leve
     """Level loop of ``compute_multiscale`` (``zarr_destriper.py:746-782``) over Zarr-v2 directory stores
     (``zarr_destriper.compute_multiscale`` is the entry point with the reference's signature and calls this):
     writes ``<group_path>/<i>`` for ``i = 1 .. n_levels - 1`` (uint16, ``"/"`` separator), every level from the
-    previous one.  OME-NGFF metadata (``:728-742``) is out of scope.  Returns the written arrays' shapes.
+    previous one.  The OME-NGFF metadata (``:728-742``) is written by the caller
+    (``zarr_destriper.compute_multiscale(ome_metadata=True)``), not here.  Returns the written arrays' shapes.
 
     The volume is streamed in z-slabs (a 34 GB channel does not fit one allocation, nor host RAM twice):
     a slab of ``2 * output z-chunk`` source planes is read, reduced by one ``dsx_downsample2_u16`` launch

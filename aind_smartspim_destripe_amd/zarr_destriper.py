@@ -22,7 +22,9 @@ Row f1 of SURVEY section 8: when the store holds uint16 bricks, :func:`destripe_
 decompressed chunks as they lie in the store and re-tiles them into planes (and the filtered planes back
 into bricks) on the device (``dsx_bricks_to_planes_u16`` / ``dsx_planes_to_bricks_u16``), so the host only
 (de)compresses -- no NumPy gather / scatter of 128 x 128 tiles.  The multiscale pyramid is in ``pyramid.py``.
-Out of scope here: OME-NGFF metadata, the psutil profiler.
+The OME-NGFF metadata of the group (``:410-674``) is written on request (``ome_metadata=True``), with the display window
+the reference hard-codes or the percentiles of an exact device histogram of the written voxels.
+Out of scope here: the psutil profiler.
 """
 
 import itertools
@@ -244,6 +246,7 @@ def execute_worker(
         filtered = filtered[:, : data.shape[1], : data.shape[2]]
     block = pad_array_n_d(filtered[tuple(unpadded_local_slice[-3:])], dim=len(output_destriped_zarr.shape))
     output_destriped_zarr[tuple(output_slices)] = block
+    return block  # (the reference returns nothing; the chunk map counts what was assigned: ``histogram``)
 
 
 def iter_blocks(zyx_shape, prediction_chunksize, z_range=None):
@@ -381,6 +384,7 @@ class _DeviceBlocks:
         self.pyr_schedule, self.pyr_cur, self.pyr_flushes = {}, [0] * len(self.pyr_levels), [[] for _ in range(self.N_BUF)]
         self.io_threads = int(io_threads)
         self.timing = _new_timing()
+        self.histogram = False  # destripe_zarr_store(histogram=...): count every block's filtered planes (volhist_add)
 
     def close(self):
         for b in (self.pyr_bufs + self.d_bricks_in + self.d_bricks_out + [self.d_planes, self.d_out] + self.h_in + self.h_out
@@ -494,6 +498,8 @@ class _DeviceBlocks:
                 eng.copy_d2h_async(self.status[k][:nt], self.d_status[k], C)
         eng.bricks_to_planes(self.d_bricks_in[k], self.d_planes, (Z, H, W), self.ci, zoff)
         eng.run_device(self.d_planes, np.uint16, Z, self.d_out, np.uint16, None)
+        if self.histogram:                # the block's real planes, where every later stage reads them
+            eng.volhist_add(self.d_out, Z * H * W)
 
     def _submit_out(self, z0, z1, k):
         """Compute(b) from planes_to_bricks on, and download(b): once pinned output buffer k has been written out."""
@@ -776,6 +782,7 @@ def destripe_zarr_store(
     pyramid_group=None,
     n_levels=1,
     streaks=None,
+    histogram=None,
 ):
     """Chunk map of ``destripe_zarr`` (``zarr_destriper.py:909-1211``) over a Zarr-v2 directory store -- the engine-level
     form (explicit configs and ``shadow_correction``); :func:`destripe_zarr` is the entry point with the reference's
@@ -849,10 +856,21 @@ def destripe_zarr_store(
     ``no_cells_config`` may be ``None`` then; the dual-band filter has no dark / flat step, so a ``shadow_correction``
     raises ``ValueError`` before anything is created.  ``LAST_RUN["filter"]`` is ``"stripes"`` or ``"streaks"``,
     ``LAST_RUN["streaks_route"]`` the route taken (``None`` for the stripe filter).
+
+    ``histogram``: a zeroed ``np.int64[65536]``; this rank's share of the level-0 voxels it writes is added to it, one
+    count per value -- what the display window of the OME-NGFF metadata is taken from
+    (:func:`display_window_from_histogram`; ``zarr_destriper.py:722-726``).  On the device path the filtered planes of
+    every block are counted where they lie, right behind the filter (``dsx_volhist_add_device``, one more read of them);
+    the host path counts what it assigns.  ``LAST_RUN["histogram_voxels"]`` is the number added (``None`` without the
+    option).  Anything but a C-contiguous ``int64`` array of 65 536 bins raises ``ValueError`` before anything is created.
     """
     from . import pyramid
 
     logger = logger or logging.getLogger("dsx.zarr")
+    if histogram is not None and not (isinstance(histogram, np.ndarray) and histogram.dtype == np.int64
+                                      and histogram.shape == (engine_mod.VOLHIST_BINS,)
+                                      and histogram.flags["C_CONTIGUOUS"] and histogram.flags["WRITEABLE"]):  # fmt: skip
+        raise ValueError("histogram must be a writeable C-contiguous int64 array of {} bins".format(engine_mod.VOLHIST_BINS))
     if streaks is not None:
         streaks = fl.streaks_options(streaks)
         if shadow_correction is not None:
@@ -930,6 +948,7 @@ def destripe_zarr_store(
         pyramid.fused_check_blocks(levels, block_z)
     LAST_RUN.update(device_codec=device_codec, device_codec_mode=codec_mode, device_decode=bool(device_decode),
                     device_decode_mode=decode_mode, decode_routes=None, fused_pyramid=bool(levels), pyramid_levels=[lv.level for lv in levels])  # fmt: skip
+    LAST_RUN["histogram_voxels"] = None if histogram is None else 0
     if can and device_retile is not False:
         if streaks is not None:
             eng = fl._streaks_engine(zyx[1:], *streaks["sigma"], streaks["level"], streaks["wavelet"], streaks["crossover"],
@@ -940,11 +959,18 @@ def destripe_zarr_store(
                                 max_batch=min(block_z, 64), device=dev)  # fmt: skip
         blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, "runs" if codec_mode == "runs" else device_codec,
                                 device_decode, (levels, pyr_arrays) if levels else None)  # fmt: skip
+        blocks.histogram = histogram is not None
+        if histogram is not None:
+            eng.volhist_reset()
         try:
             n_planes = blocks.run_range(z0, z1)
         finally:
             LAST_RUN["decode_routes"] = dict(blocks.timing["decode_routes"])
         eng.sync()
+        if histogram is not None:
+            counts = eng.volhist_get()
+            histogram += counts
+            LAST_RUN["histogram_voxels"] = int(counts.sum())
         dt = time.perf_counter() - t0
         logger.info("rank %d: %d planes z[%d:%d) in %.2f s (device re-tiling%s, overlapped; read %.2f s, write %.2f s)",
                     rank, n_planes, z0, z1, dt, (", device codec" + (" ({})".format(codec_mode) if codec_mode in ("runs", "lz4") else "") if device_codec else "")
@@ -956,8 +982,12 @@ def destripe_zarr_store(
         lead = (0,) * (len(src.shape) - 3)
         block = src[lead + sc]
         data = block[np.newaxis].astype(np.float32) if block.dtype != np.uint16 else block[np.newaxis]
-        execute_worker(data, sc, internal, cells_config, no_cells_config, (0, 0, 0), dst, shadow_correction,
-                       name, logger, device=dev, streaks=streaks)  # fmt: skip
+        written = execute_worker(data, sc, internal, cells_config, no_cells_config, (0, 0, 0), dst, shadow_correction,
+                                 name, logger, device=dev, streaks=streaks)  # fmt: skip
+        if histogram is not None:
+            counts = np.bincount(written.ravel(), minlength=engine_mod.VOLHIST_BINS)
+            histogram += counts
+            LAST_RUN["histogram_voxels"] += int(counts.sum())
         n_planes += block.shape[0]
     dt = time.perf_counter() - t0
     logger.info("rank %d: %d planes z[%d:%d) in %.2f s", rank, n_planes, z0, z1, dt)
@@ -1041,6 +1071,262 @@ def compute_pyramid(data, n_lvls, scale_axis, chunks="auto", device=0, engine=No
     return pyramid.compute_pyramid(data, n_lvls, scale_axis, chunks=chunks, device=device, engine=engine)
 
 
+# ---------------------------------------------------------------------------------------------
+# OME-NGFF metadata of the group (reference ``zarr_destriper.py:410-674``) and its display window
+# ---------------------------------------------------------------------------------------------
+REFERENCE_DISPLAY_WINDOW = (0.0, 350.0)  # what the reference writes for every SmartSPIM channel (``:722-726``)
+REFERENCE_CHANNEL_COLOR = 0x690AFE  # (``:737``)
+
+
+def _get_axes_5d(time_unit="millisecond", space_unit="micrometer"):
+    """The five OME-NGFF axes t, c, z, y, x (reference ``zarr_destriper.py:507-528``): the channel axis has no unit."""
+    axes = [{"name": "t", "type": "time", "unit": str(time_unit)}, {"name": "c", "type": "channel"}]
+    axes += [{"name": name, "type": "space", "unit": str(space_unit)} for name in "zyx"]
+    return axes
+
+
+def _compute_scales(scale_num_levels, scale_factor, pixelsizes, chunks, data_shape, translation=None):
+    """Per-level coordinate transformations and chunk options (reference ``zarr_destriper.py:410-504``).
+
+    Level 0 has the voxel size ``pixelsizes`` (z, y, x) behind two unit axes; every further level multiplies the spatial
+    scales by ``scale_factor`` and divides the spatial shape by it, rounding up; the chunk option of a level is
+    ``chunks`` clamped to the level's spatial shape, ``(1, 1)`` in front.  ``translation`` (five numbers) is appended to
+    every level's list.  Returns ``(transforms, chunk options)``, one entry per level (at least one)."""
+    transforms, chunk_sizes = [], []
+    scale = [float(p) if isinstance(p, (int, np.integer)) else p for p in tuple(pixelsizes)[:3]]
+    shape = [int(n) for n in tuple(data_shape)[2:5]]
+    for level in range(max(1, int(scale_num_levels))):
+        if level:
+            scale = [s * f for s, f in zip(scale, scale_factor)]
+            shape = [int(np.ceil(n / f)) for n, f in zip(shape, scale_factor)]
+        entry = [{"type": "scale", "scale": [1.0, 1.0] + list(scale)}]
+        if translation is not None:
+            entry.append({"type": "translation", "translation": translation})
+        transforms.append(entry)
+        chunk_sizes.append({"chunks": (1, 1) + tuple(min(n, int(c)) for n, c in zip(shape, tuple(chunks)[2:5]))})
+    return transforms, chunk_sizes
+
+
+def _build_ome(data_shape, image_name, channel_names=None, channel_colors=None, channel_minmax=None,
+               channel_startend=None):  # fmt: skip
+    """The ``omero`` block of the group attributes (reference ``zarr_destriper.py:531-597``): one channel entry per
+    element of axis 1 of ``data_shape`` (t, c, z, y, x) -- label, colour as six hex digits, the value range ``min`` /
+    ``max`` and the display window ``start`` / ``end`` as floats -- and the middle plane as the default z.  Defaults:
+    names ``Channel:<image_name>:<i>``, colours ``i``, range ``(0.0, 1.0)``, window = range."""
+    n_channels = int(data_shape[1])
+    if channel_names is None:
+        channel_names = ["Channel:{}:{}".format(image_name, i) for i in range(n_channels)]
+    if channel_colors is None:
+        channel_colors = list(range(n_channels))
+    if channel_minmax is None:
+        channel_minmax = [(0.0, 1.0)] * n_channels
+    if channel_startend is None:
+        channel_startend = channel_minmax
+    channels = []
+    for i in range(n_channels):
+        lo, hi = channel_minmax[i]
+        start, end = channel_startend[i]
+        channels.append({
+            "active": True,
+            "coefficient": 1,
+            "color": "{:06x}".format(channel_colors[i]),
+            "family": "linear",
+            "inverted": False,
+            "label": channel_names[i],
+            "window": {"end": float(end), "max": float(hi), "min": float(lo), "start": float(start)},
+        })  # fmt: skip
+    return {
+        "id": 1,
+        "name": image_name,
+        "version": "0.4",
+        "channels": channels,
+        "rdefs": {"defaultT": 0, "defaultZ": int(data_shape[2]) // 2, "model": "color"},
+    }
+
+
+def _validate_coordinate_transformations(ndim, n_levels, transforms):
+    """What ``ome_zarr.format.FormatV04.validate_coordinate_transformations`` checks (the reference calls it at
+    ``zarr_destriper.py:664-666``), as ``ValueError``: one list per level, each with exactly one ``scale`` of ``ndim``
+    numbers in first place and at most one ``translation`` of ``ndim`` numbers after it."""
+    if len(transforms) != n_levels:
+        raise ValueError("coordinate transformations: {} lists for {} levels".format(len(transforms), n_levels))
+    for level, entry in enumerate(transforms):
+        if not isinstance(entry, (list, tuple)):
+            raise ValueError("coordinate transformations of level {}: not a list".format(level))
+        types = [t.get("type") if isinstance(t, dict) else None for t in entry]
+        if types.count("scale") != 1 or types[0] != "scale":
+            raise ValueError("coordinate transformations of level {}: exactly one scale, in first place, not {}"
+                             .format(level, types))  # fmt: skip
+        if types[1:] not in ([], ["translation"]):
+            raise ValueError("coordinate transformations of level {}: only one translation may follow the scale, not {}"
+                             .format(level, types[1:]))  # fmt: skip
+        for t in entry:
+            values = t.get(t["type"])
+            if not isinstance(values, (list, tuple)) or len(values) != ndim:
+                raise ValueError("coordinate transformations of level {}: {} needs {} numbers, got {!r}"
+                                 .format(level, t["type"], ndim, values))  # fmt: skip
+            if not all(isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) for v in values):
+                raise ValueError("coordinate transformations of level {}: {} holds a non-number: {!r}"
+                                 .format(level, t["type"], values))  # fmt: skip
+
+
+def _write_json_atomic(path, obj):
+    """``obj`` as JSON under ``path``, through a temporary file and a rename (as ``MiniZarrArray.create`` writes
+    ``.zarray``): a reader sees the file whole or not at all."""
+    tmp = "{}.tmp.{}".format(path, os.getpid())
+    with open(tmp, "w") as f:
+        json.dump(obj, f, indent=4)
+    os.replace(tmp, path)
+
+
+def _plain_json(obj):
+    """NumPy scalars / arrays / tuples -> what ``json`` writes."""
+    if isinstance(obj, dict):
+        return {str(k): _plain_json(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return [_plain_json(v) for v in obj]
+    if isinstance(obj, np.ndarray):
+        return _plain_json(obj.tolist())
+    if isinstance(obj, np.generic):
+        return obj.item()
+    return obj
+
+
+def write_ome_ngff_metadata(group, arr, image_name, n_lvls, scale_factors, voxel_size, channel_names=None,
+                            channel_colors=None, channel_minmax=None, channel_startend=None, metadata=None):  # fmt: skip
+    """The OME-NGFF 0.4 metadata of a multiscale group (reference ``zarr_destriper.py:600-674``).
+
+    ``group``: the group folder (a path, or anything with ``.path``); ``arr``: level 0 -- anything with ``.shape``
+    (t, c, z, y, x) and ``.chunks`` or ``.chunksize`` (a :class:`MiniZarrArray`).  Written into the folder, each file
+    through a temporary file and a rename:
+
+    * ``.zgroup``: ``{"zarr_format": 2}``;
+    * ``.zattrs``: ``"omero"`` = :func:`_build_ome`; ``"multiscales"`` = one entry ``{"version": "0.4", "name": "/",
+      "axes": the five axes, "datasets": [{"path": "<i>", "coordinateTransformations": [scale (, translation)]}, ...],
+      **metadata}`` for the levels ``0 .. n_lvls - 1`` (:func:`_compute_scales` from ``voxel_size`` = z, y, x and
+      ``scale_factors``).  Keys of an existing ``.zattrs`` other than these two are kept.
+
+    ``"name": "/"`` is what ome-zarr-py's ``write_multiscales_metadata`` is understood to put for a root group
+    (``group.name``); no interpreter this was written with has ome-zarr installed, so this one value is NOT verified
+    against the library.  The checks of its ``validate_coordinate_transformations`` are restated and raise
+    ``ValueError`` before anything is written."""
+    group_path = str(getattr(group, "path", group))
+    shape = tuple(int(n) for n in arr.shape)
+    if len(shape) != 5:
+        raise ValueError("write_ome_ngff_metadata: level 0 must be 5-D (t, c, z, y, x), not {}".format(shape))
+    chunks = getattr(arr, "chunks", None)
+    if chunks is None:
+        chunks = arr.chunksize
+    n_lvls = int(n_lvls)
+    ome = _build_ome(shape, image_name, channel_names=channel_names, channel_colors=channel_colors,
+                     channel_minmax=channel_minmax, channel_startend=channel_startend)  # fmt: skip
+    transforms, _ = _compute_scales(n_lvls, scale_factors, voxel_size, tuple(chunks), shape, None)
+    _validate_coordinate_transformations(len(shape), n_lvls, transforms)
+    datasets = [{"path": str(i), "coordinateTransformations": t} for i, t in enumerate(transforms)]
+    multiscale = {"version": "0.4", "name": "/", "axes": _get_axes_5d(), "datasets": datasets}
+    multiscale.update(metadata or {})
+    attrs_path = os.path.join(group_path, ".zattrs")
+    attrs = read_json_as_dict(attrs_path)
+    attrs["omero"] = ome
+    attrs["multiscales"] = [multiscale]
+    attrs = _plain_json(attrs)
+    json.dumps(attrs)  # (anything json cannot write fails here, before a file exists)
+    os.makedirs(group_path, exist_ok=True)
+    _write_json_atomic(os.path.join(group_path, ".zgroup"), {"zarr_format": 2})
+    _write_json_atomic(attrs_path, attrs)
+
+
+def display_window_from_histogram(hist, percentiles=(0.1, 95.0)):
+    """Display window ``(start, end)`` of a volume from its exact histogram ``hist`` (one count per integer value): the
+    ``da.percentile(image_data, (0.1, 95))`` the reference names as the ideal and does not compute
+    (``zarr_destriper.py:722-726``).
+
+    For each ``q`` of ``percentiles`` the data value ``np.percentile(volume, q, method="lower")`` returns: the element
+    of the sorted volume at index ``floor((N - 1) * (q / 100.0))`` (NumPy's own float64 arithmetic), i.e. the smallest
+    ``v`` with ``cumsum(hist)[v]`` above that index.  Floats; ``end = max(end, start + 1.0)``, so a constant volume
+    still gives a window a viewer can use.  An all-zero histogram raises ``ValueError``."""
+    h = np.asarray(hist)
+    if h.ndim != 1 or h.size == 0 or not np.issubdtype(h.dtype, np.integer):
+        raise ValueError("display_window_from_histogram: hist is a 1-D array of integer counts")
+    if (h < 0).any():
+        raise ValueError("display_window_from_histogram: negative counts")
+    qs = tuple(percentiles)
+    if len(qs) != 2 or not all(0.0 <= float(q) <= 100.0 for q in qs):
+        raise ValueError("display_window_from_histogram: percentiles are two numbers in [0, 100], not {!r}".format(percentiles))
+    cum = np.cumsum(h.astype(np.int64))
+    total = int(cum[-1])
+    if total == 0:
+        raise ValueError("display_window_from_histogram: the histogram is empty")
+    values = []
+    for q in qs:
+        index = int(np.floor((total - 1) * (np.float64(q) / 100.0)))
+        values.append(float(np.searchsorted(cum, index, side="right")))
+    start, end = values
+    return start, max(end, start + 1.0)
+
+
+def _resolve_display_window(display_window, histogram):
+    """The ``(start, end)`` pair a ``display_window`` option selects (:func:`compute_multiscale`); ``ValueError`` for
+    anything it does not take."""
+    if display_window is None:
+        return REFERENCE_DISPLAY_WINDOW
+    if isinstance(display_window, str):
+        if display_window != "percentile":
+            raise ValueError("display_window is None, a (start, end) pair or \"percentile\", not {!r}".format(display_window))
+        if histogram is None:
+            raise ValueError("display_window=\"percentile\" needs the histogram of the volume")
+        return display_window_from_histogram(histogram)
+    try:
+        start, end = display_window
+        if isinstance(start, (str, bool)) or isinstance(end, (str, bool)):
+            raise TypeError
+        pair = (float(start), float(end))
+    except (TypeError, ValueError):
+        raise ValueError("display_window is None, a (start, end) pair or \"percentile\", not {!r}"
+                         .format(display_window)) from None  # fmt: skip
+    if not all(np.isfinite(pair)):
+        raise ValueError("display_window: the pair must be finite, not {!r}".format(display_window))
+    return pair
+
+
+def _check_ome_options(ome_metadata, display_window, histogram, voxel_size, image_name):
+    """The option rules of :func:`compute_multiscale` (``ValueError`` before anything is written); returns the window
+    to write, or ``None`` with the metadata off."""
+    if not ome_metadata:
+        if display_window is not None or histogram is not None:
+            raise ValueError("display_window / histogram need ome_metadata=True")
+        return None
+    try:
+        sizes = [float(v) for v in voxel_size]
+    except (TypeError, ValueError):
+        raise ValueError("ome_metadata: voxel_size is three positive numbers (z, y, x), not {!r}".format(voxel_size)) from None
+    if len(sizes) != 3 or not all(np.isfinite(v) and v > 0 for v in sizes):
+        raise ValueError("ome_metadata: voxel_size is three positive numbers (z, y, x), not {!r}".format(voxel_size))
+    if not isinstance(image_name, str):
+        raise ValueError("ome_metadata: image_name is a string, not {!r}".format(image_name))
+    return _resolve_display_window(display_window, histogram)
+
+
+def _write_group_metadata(group_path, level0, image_name, n_levels, scale_factor, voxel_size, window):
+    """``write_ome_ngff_metadata`` with the reference's values (``zarr_destriper.py:713-741``) and the window."""
+    arr = level0 if hasattr(level0, "shape") else MiniZarrArray.open(str(level0))
+    n_channels = int(arr.shape[1]) if len(arr.shape) == 5 else 1
+    info = np.iinfo(np.uint16)
+    write_ome_ngff_metadata(
+        group=group_path,
+        arr=arr,
+        image_name=image_name,
+        n_lvls=n_levels,
+        scale_factors=scale_factor,
+        voxel_size=voxel_size,
+        channel_names=[image_name],
+        channel_colors=[REFERENCE_CHANNEL_COLOR],
+        channel_minmax=[(int(info.min), int(info.max))] * n_channels,
+        channel_startend=[tuple(window)] * n_channels,
+        metadata=None,
+    )
+
+
 def compute_multiscale(
     output_zarr,
     zarr_group,
@@ -1059,14 +1345,26 @@ def compute_multiscale(
     device_codec=False,
     device_decode=False,
     io_threads=None,
+    ome_metadata=False,
+    display_window=None,
+    histogram=None,
 ):
     """``compute_multiscale`` of the reference (``zarr_destriper.py:677-794``) with its signature.
 
     ``output_zarr``: level 0 (a :class:`MiniZarrArray` or its path); ``zarr_group``: the group folder the levels
     ``1 .. n_levels - 1`` are written into (a path, or anything with ``.path``).  ``n_workers`` /
-    ``threads_per_worker`` sized the reference's dask ``LocalCluster`` (``:689-697``) and ``voxel_size`` /
-    ``image_name`` feed its OME-NGFF metadata (``:728-742``): accepted, not used -- one HIP kernel per level replaces the
-    cluster, the metadata is out of scope.  Returns the shapes of the written levels.
+    ``threads_per_worker`` sized the reference's dask ``LocalCluster`` (``:689-697``): accepted, not used -- one HIP
+    kernel per level replaces the cluster.  ``voxel_size`` (z, y, x) / ``image_name`` feed the OME-NGFF metadata
+    (``:728-742``), which is written with ``ome_metadata=True`` only.  Returns the shapes of the written levels.
+
+    ``ome_metadata=True``: once the levels are written, ``.zgroup`` and ``.zattrs`` of the group
+    (:func:`write_ome_ngff_metadata`) with the reference's values (``:713-741``): channel name ``image_name``, colour
+    ``690afe``, range ``(0, 65535)``.  ``display_window`` is the channel's ``start`` / ``end``: ``None`` = the
+    reference's ``(0.0, 350.0)``, a pair of numbers = that pair, ``"percentile"`` = the 0.1 % / 95 % points of
+    ``histogram`` (``np.int64[65536]`` counts of level 0, :func:`display_window_from_histogram`; this call does not
+    compute one itself).  ``voxel_size`` must then be three positive numbers and ``image_name`` a string;
+    ``display_window`` / ``histogram`` without ``ome_metadata``, ``"percentile"`` without ``histogram`` and any other
+    value raise ``ValueError`` before anything is written.  Off by default: no file is added to the group.
 
     ``pipelined=True``: the same stores from one software-pipelined pass over level 0 -- level 0 is read by ``io_threads``
     native threads into pinned staging, every level comes from the block where it lies in chunk order
@@ -1077,13 +1375,19 @@ def compute_multiscale(
     """
     from . import pyramid
 
-    del n_workers, voxel_size, image_name, threads_per_worker
+    del n_workers, threads_per_worker
+    window = _check_ome_options(ome_metadata, display_window, histogram, voxel_size, image_name)
     level0 = getattr(output_zarr, "path", output_zarr)
     group_path = getattr(zarr_group, "path", zarr_group)
-    return pyramid.write_pyramid_levels(str(level0), str(group_path), scale_factor=tuple(scale_factor), n_levels=n_levels,
-                                        chunks=chunks, compressor=compressor, device=device, slab_planes=slab_planes,
-                                        pipelined=pipelined, device_codec=device_codec, device_decode=device_decode,
-                                        io_threads=io_threads)  # fmt: skip
+    if window is not None and len(MiniZarrArray.open(str(level0)).shape) != 5:
+        raise ValueError("ome_metadata: level 0 must be 5-D (t, c, z, y, x)")
+    shapes = pyramid.write_pyramid_levels(str(level0), str(group_path), scale_factor=tuple(scale_factor), n_levels=n_levels,
+                                          chunks=chunks, compressor=compressor, device=device, slab_planes=slab_planes,
+                                          pipelined=pipelined, device_codec=device_codec, device_decode=device_decode,
+                                          io_threads=io_threads)  # fmt: skip
+    if window is not None:
+        _write_group_metadata(str(group_path), str(level0), image_name, n_levels, scale_factor, voxel_size, window)
+    return shapes
 
 
 def destripe_zarr(
@@ -1117,6 +1421,8 @@ def destripe_zarr(
     fused_pyramid=False,
     pipelined_pyramid=False,
     streaks=None,
+    ome_metadata=False,
+    display_window=None,
 ):
     """``destripe_zarr`` of the reference (``zarr_destriper.py:909-1211``) with its 14 parameters, on the GPU chunk map.
 
@@ -1134,8 +1440,8 @@ def destripe_zarr(
       normalised microscope flats + tile config); no derivatives folder and no flat = no shading correction.
     * ``n_workers``: ``ValueError`` when above the CPU limit, like ``:977-978``; otherwise unused -- so are
       ``target_size_mb``, ``batch_size``, ``super_chunksize`` (sizing of the reference's data loader, ``:1041-1057``),
-      ``results_folder`` (log file and resource plots, ``:980, 1202-1211``) and ``xyz_resolution`` (OME-NGFF voxel size,
-      ``:1181-1185``): loader, logging and metadata are out of scope.
+      ``results_folder`` (log file and resource plots, ``:980, 1202-1211``): loader and logging are out of scope (SURVEY
+      section 2.1).  ``xyz_resolution`` (OME-NGFF voxel size, ``:1181-1185``) is used with ``ome_metadata=True``.
     * ``lazy_callback_fn``: applied by the reference's loader to the lazy array (``:1052``); ``None`` in production
       (``:1266``).  Anything else raises ``NotImplementedError`` -- silently skipping a transform would change the data.
 
@@ -1150,13 +1456,31 @@ def destripe_zarr(
     run's own output; same stores; ``ValueError`` together with ``fused_pyramid``), ``streaks`` (the dict of
     :func:`destripe_zarr_store`: the dual-band filter instead of the stripe filter; ``parameters`` need no configs then,
     and a derivatives folder that exists or a ``flatfield`` raises ``ValueError`` before anything is created -- that
-    filter has no dark / flat step).
+    filter has no dark / flat step), ``ome_metadata`` / ``display_window`` (rank 0 writes the group's ``.zgroup`` and
+    OME-NGFF ``.zattrs`` once the levels are written -- inside :func:`compute_multiscale`, or itself on the
+    ``fused_pyramid`` route; the same file on every route.  ``xyz_resolution`` is the voxel size, handed on as
+    ``[z, y, x]``; ``display_window`` as in :func:`compute_multiscale`, except that ``"percentile"`` needs nothing from
+    the caller: every rank counts the voxels it writes (``destripe_zarr_store(histogram=...)``), ``group.sum_counts``
+    adds the ranks' counts after the barrier, and rank 0 raises ``RuntimeError`` unless they add up to the voxels of
+    level 0.  ``"percentile"`` with ``world_size > 1`` and a group without ``sum_counts`` raises ``ValueError`` before
+    anything is created.  ``LAST_RUN["display_window"]`` is the pair written, or ``None``).
     Returns ``(planes processed by this rank, seconds)``.
     """
     output_codec_mode(device_codec, compressor)  # (a wrong string or mode fails before anything is written)
     device_decode_mode(device_decode)
     if fused_pyramid and pipelined_pyramid:
         raise ValueError("fused_pyramid and pipelined_pyramid are two routes to the same pyramid: choose one")
+    percentile = isinstance(display_window, str) and display_window == "percentile"
+    try:  # (x, y, z) -> the [z, y, x] the metadata wants; anything else is left for the check below to refuse
+        voxel_size = [xyz_resolution[-1], xyz_resolution[-2], xyz_resolution[-3]]
+    except (TypeError, IndexError, KeyError):
+        voxel_size = None
+    fixed_window = _check_ome_options(ome_metadata, None if percentile and ome_metadata else display_window, None,
+                                      voxel_size, Path(output_destriped_zarr).name)  # fmt: skip
+    if percentile and world_size > 1 and not hasattr(group, "sum_counts"):
+        raise ValueError("display_window=\"percentile\" with world_size > 1 needs a group with sum_counts "
+                         "(distributed.RankGroup): the ranks' voxel counts must be added")  # fmt: skip
+    histogram = np.zeros(engine_mod.VOLHIST_BINS, np.int64) if percentile else None
     if streaks is not None:
         streaks = fl.streaks_options(streaks)
         if flatfield is not None or os.path.exists(Path(derivatives_path)):
@@ -1243,9 +1567,25 @@ def destripe_zarr(
         pyramid_group=str(output_destriped_zarr) if fused_pyramid else None,
         n_levels=n_levels if fused_pyramid else 1,
         streaks=streaks,
+        histogram=histogram,
     )
     if group is not None and world_size > 1:
         group.barrier()  # level 0 of this tile is complete on every rank: the pyramid may read it
+    window, ome_kw = fixed_window, {}
+    if percentile:
+        total = group.sum_counts(histogram) if world_size > 1 else histogram
+        voxels = int(np.prod(MiniZarrArray.open(str(level0)).shape[-3:]))
+        if rank == 0 and int(total.sum()) != voxels:  # padded, skipped or twice-counted voxels would move the percentiles
+            raise RuntimeError("display_window=\"percentile\": the ranks counted {} voxels, level 0 holds {}"
+                               .format(int(total.sum()), voxels))  # fmt: skip
+        window = display_window_from_histogram(total)
+        ome_kw = dict(ome_metadata=True, display_window="percentile", histogram=total)
+    elif ome_metadata:
+        ome_kw = dict(ome_metadata=True, display_window=display_window)
+    LAST_RUN["display_window"] = window
+    if rank == 0 and ome_metadata and (fused_pyramid or n_levels <= 1):  # compute_multiscale is not called: the same file
+        _write_group_metadata(str(output_destriped_zarr), str(level0), dataset_name, n_levels, scale_factor, voxel_size,
+                              window)  # fmt: skip
     if rank == 0 and n_levels > 1 and not fused_pyramid:
         dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device
         pipelined_kw = {}
@@ -1267,6 +1607,7 @@ def destripe_zarr(
             compressor=compressor,
             device=dev,
             **pipelined_kw,
+            **ome_kw,
         )
         logger.info(f"Processing multiscale time: {time.perf_counter() - t0} seconds")
     logger.info(f"Processing destripe flatfield time: {seconds} seconds")
@@ -1299,6 +1640,8 @@ def destripe_channel(
     device_decode=False,
     fused_pyramid=False,
     pipelined_pyramid=False,
+    ome_metadata=False,
+    display_window=None,
 ):
     """``destripe_channel`` of the reference (``zarr_destriper.py:1214-1267``), same eight parameters (the reference's
     caller passes them by keyword, ``run_capsule.py:394-403``), wired to the GPU chunk map.
@@ -1307,7 +1650,9 @@ def destripe_channel(
     (``laser_tiles`` = ``{side: [tile stems]}``, ``ValueError`` for a tile in neither, ``:1239-1247``), read it
     (``:1249``) and call :func:`destripe_zarr` with the reference's arguments (``:1252-1267``):
     ``<results>/destriped_data/<channel>/<tile>.zarr/0`` plus pyramid levels ``1 .. n_levels - 1``.
-    ``xyz_resolution`` only feeds OME-NGFF metadata in the reference (out of scope): accepted, handed on.
+    ``xyz_resolution`` is the voxel size of the OME-NGFF metadata: handed on, and written with ``ome_metadata=True``
+    (``ome_metadata`` / ``display_window`` go to every tile's :func:`destripe_zarr`; with ``"percentile"`` each tile
+    gets the window of its own voxels).
     Returns ``{tile name: planes processed by this rank}``.
 
     Keyword-only extras: ``rank`` / ``world_size`` / ``group`` / ``device`` (one process per GPU), output codec and
@@ -1322,6 +1667,12 @@ def destripe_channel(
     device_decode_mode(device_decode)
     if fused_pyramid and pipelined_pyramid:
         raise ValueError("fused_pyramid and pipelined_pyramid are two routes to the same pyramid: choose one")
+    if not ome_metadata and display_window is not None:
+        raise ValueError("display_window needs ome_metadata=True")
+    if (isinstance(display_window, str) and display_window == "percentile" and world_size > 1
+            and not hasattr(group, "sum_counts")):  # fmt: skip
+        raise ValueError("display_window=\"percentile\" with world_size > 1 needs a group with sum_counts "
+                         "(distributed.RankGroup): the ranks' voxel counts must be added")  # fmt: skip
     logger = logger or logging.getLogger("dsx.zarr")
     zarr_dataset_path, results_folder = Path(zarr_dataset_path), Path(results_folder)
     channel_dataset = zarr_dataset_path.joinpath(channel_name)
@@ -1369,6 +1720,8 @@ def destripe_channel(
             device_decode=device_decode,
             fused_pyramid=fused_pyramid,
             pipelined_pyramid=pipelined_pyramid,
+            ome_metadata=ome_metadata,
+            display_window=display_window,
         )
         done[tile_path.name] = n
     return done

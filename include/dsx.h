@@ -213,6 +213,22 @@ int dsx_pyramid_bricks_u16(dsx_ctx* ctx, const void* d_src_bricks, int Z, int H,
 int dsx_pyramid_bricks_ref(const void* src_bricks, int Z, int H, int W, int src_cz, int src_cy, int src_cx,
                            int n_levels, const dsx_pyramid_level* levels, void* const* bricks);
 
+/* Exact histogram of the uint16 voxels a pass writes, for the display window of the OME-NGFF metadata: the reference
+ * says the window should be da.percentile(image_data, (0.1, 95)) and hard-codes (0.0, 350.0) because of the cost
+ * (zarr_destriper.py:722-726); a histogram taken while the filtered planes lie in device memory makes it exact for one
+ * more read of them (csrc/dsx_volhist.h).  The context owns 65 536 uint64 bins that accumulate over calls.  n == 0 is a
+ * no-op; a NULL (or odd) pointer with n > 0, and add / get before the first reset, are DSX_EINVAL; n >= 2^32 in one call
+ * is DSX_ELIMIT (the block-local counters are 32 bits wide).  dsx_destroy frees the bins; no plan call touches them. */
+/* zarr_destriper.py:722-726: allocate the bins on first use and zero them (asynchronous on the context stream). */
+int dsx_volhist_reset(dsx_ctx* ctx);
+/* zarr_destriper.py:722-726: count n contiguous uint16 voxels in device memory (2-byte aligned; asynchronous on the
+ * context's current stream). */
+int dsx_volhist_add_device(dsx_ctx* ctx, const void* d_vox, size_t n);
+/* zarr_destriper.py:722-726: the 65 536 counts to the host; synchronises that stream. */
+int dsx_volhist_get(dsx_ctx* ctx, uint64_t* hist);
+/* zarr_destriper.py:722-726: the host build -- adds the counts of n host voxels into hist (65 536 bins). */
+int dsx_volhist_ref(const void* vox, size_t n, uint64_t* hist);
+
 /* Host side of the chunk map: n Zarr chunk files <-> memory (normally the pinned staging buffers) on
  * `threads` native threads -- what zarr / numcodecs do under the reference's worker processes
  * (zarr_destriper.py:336, 1042-1074).  codec: raw chunks, zlib streams, or Blosc frames -- the production

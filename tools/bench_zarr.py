@@ -6,7 +6,7 @@ download) into another store.  Prints one JSON line; the roofline of this path i
 
     bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode|device-decode-any|device-decode-all]
                   [lz4|blosc-zlib|blosc-blosclz|plain-zlib] [pyramid|fused-pyramid|pipelined-pyramid] [lz4-out] [read-back]
-                  [streaks|streaks-generic|streaks-march]
+                  [streaks|streaks-generic|streaks-march] [ome-percentile]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
 line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
@@ -31,6 +31,10 @@ comparison are then LZ4 frames too.
 filter ("auto" is the generic route until the march route's rate is on record, engine.AUTO_ROUTE); `streaks-generic` /
 `streaks-march` name the route.  The picked planes are then held to destripe_streaks_planes of
 the same route, bit for bit (no CPU oracle pass).
+`ome-percentile`: both metadata options on -- every timed pass counts its filtered voxels on the device
+(destripe_zarr_store(histogram=...)), takes the display window from the counts (display_window_from_histogram) and, with
+a pyramid word (the output is then a group), writes .zgroup / .zattrs (write_ome_ngff_metadata), all inside the timed
+seconds; the line reports the window and the voxels counted under "ome", and a count other than N * 2048 * 2048 fails the run.
 `pyramid`: after the timed level-0 pass, compute_multiscale(n_levels=3) on the store is timed too (the two-pass route);
 `fused-pyramid`: level 0 and levels 1-2 in one destripe_zarr_store call (pyramid_group / n_levels);
 `pipelined-pyramid`: level 0 is timed as without a pyramid word, then compute_multiscale(pipelined=True, n_levels=3) with the
@@ -57,6 +61,7 @@ two_pass, fused, pipelined = ("pyramid" in sys.argv[3:], "fused-pyramid" in sys.
 lz4_out, read_back = "lz4-out" in sys.argv[3:], "read-back" in sys.argv[3:]
 streaks = ([{"sigma": (64.0, 128.0), "route": r} for w, r in (("streaks", "auto"), ("streaks-generic", "generic"),
                                                                ("streaks-march", "march")) if w in sys.argv[3:]] + [None])[0]
+ome = "ome-percentile" in sys.argv[3:]
 if (lz4_out or read_back) and codec != "blosc":
     sys.exit("lz4-out / read-back: a Blosc store")
 out_codec = {"id": "blosc", "cname": "lz4", "clevel": 5, "shuffle": 1, "blocksize": 0} if lz4_out else codec
@@ -108,10 +113,18 @@ try:
     for name, kw in (("overlapped", {"pyramid_group": group, "n_levels": 3} if fused else {}),):
         for rep in range(2):  # second pass: plan + pinned buffers exist, page cache warm
             t0 = time.perf_counter()
+            hist = np.zeros(65536, np.int64) if ome else None
             planes, dt = zd.destripe_zarr_store(os.path.join(root, "in.zarr"), level0, synth.CELLS_CONFIG,
                                           synth.NO_CELLS_CONFIG, None, prediction_chunksize=(64, H, W),
                                           output_chunks=(1, 1, 64, 128, 128), device=0, device_retile=True, io_threads=16, compressor=out_codec,
-                                          device_codec=device_codec, device_decode=device_decode, streaks=streaks, **kw)
+                                          device_codec=device_codec, device_decode=device_decode, streaks=streaks,
+                                          **({"histogram": hist} if ome else {}), **kw)
+            if ome:
+                window = zd.display_window_from_histogram(hist)
+                if level0 != group:
+                    zd.write_ome_ngff_metadata(group, MiniZarrArray.open(level0), "bench", 3, [2, 2, 2], [2.0, 1.8, 1.8],
+                                               channel_names=["bench"], channel_colors=[zd.REFERENCE_CHANNEL_COLOR],
+                                               channel_minmax=[(0, 65535)], channel_startend=[window])
             res[name] = {"planes": planes, "seconds": round(time.perf_counter() - t0, 3)}
     timing = dict(zd._BLOCKS["blocks"][1].timing)  # the timed (second) pass
     decode = {"decode_routes": zd.LAST_RUN.get("decode_routes")}
@@ -120,6 +133,10 @@ try:
                                           for f in fs if not f.startswith("."))
         decode["input_ratio_to_raw"] = round(decode["input_store_bytes"] / (n * H * W * 2), 4)
     secs = res["overlapped"]["seconds"]
+    ome_info = {}
+    if ome:
+        ome_info = {"ome": {"display_window": list(window), "histogram_voxels": int(hist.sum()),
+                            "metadata_written": os.path.exists(os.path.join(group, ".zattrs"))}}
     pyr = {}
     if two_pass or fused or pipelined:
         pyramid_s = 0.0
@@ -191,6 +208,9 @@ try:
     nblk = (n + 63) // 64
     blocks = sorted({0, nblk // 2, nblk - 1})
     verified, checked, oracle_checked = True, [], []
+    if ome and int(hist.sum()) != n * H * W:
+        verified = False
+        print("histogram counted", int(hist.sum()), "voxels of", n * H * W, file=sys.stderr)
     for b in blocks:
         z0, z1 = 64 * b, min(64 * b + 64, n)
         for z in stream_part_picks(64, z0, z1):
@@ -220,7 +240,7 @@ try:
                       "roofline": {"bound": "host link", "peak_planes_per_s": 3750, "frac": round(v / 3750.0, 3)},
                       "read_s": round(timing["read_s"], 3), "write_s": round(timing["write_s"], 3), "host_link": link,
                       "plane0_checksum": chk, "verified": verified,
-                      "filter": zd.LAST_RUN.get("filter"), "streaks_route": zd.LAST_RUN.get("streaks_route"), **decode, **sizes, **({"pyramid": pyr} if pyr else {}),
+                      "filter": zd.LAST_RUN.get("filter"), "streaks_route": zd.LAST_RUN.get("streaks_route"), **decode, **sizes, **ome_info, **({"pyramid": pyr} if pyr else {}),
                       "verification": {"planes_bit_identical_to_single_plane_runs": checked,
                                        "planes_against_the_cpu_oracle": oracle_checked, "blocks": blocks}}))
     if not verified or not pyr.get("verified", True):
