@@ -104,12 +104,12 @@ struct dsx_ctx {
   // the call; the next synchronising entry point (dsx_sync, dsx_event_sync, dsx_stream_sync, dsx_get_stats) reports
   // DSX_EVALUE instead and clears the word.
   unsigned* h_sticky = nullptr;
-  // dsx_blosc_encode_device: encoded zstd blocks (slots) and their sizes, grown on demand
+  // dsx_blosc_encode_device: encoded zstd blocks (slots) and their sizes, grown on demand (grow_device; *_bytes held)
   uint8_t* zenc_slots = nullptr;
   uint32_t* zenc_sizes = nullptr;
-  size_t zenc_blocks = 0;
+  size_t zenc_slot_bytes = 0, zenc_size_bytes = 0;
   uint8_t* zenc_lits = nullptr;  // runs mode: the literals the runs leave, per zstd block
-  size_t zenc_lit_blocks = 0;
+  size_t zenc_lit_bytes = 0;
   // dsx_blosc_decode_device: shuffled blocks are decoded here before the un-shuffle, grown on demand
   uint8_t* zdec_scratch = nullptr;
   size_t zdec_bytes = 0;
@@ -766,6 +766,28 @@ int grow_stage(dsx_ctx* ctx, void** buf, size_t* have, size_t need) {
   DSX_HIP(hipMalloc(buf, need));
   *have = need;
   return DSX_OK;
+}
+
+// a work buffer of the codec entry points on the device: at least `need` bytes.  The stream may still use the buffer
+// it replaces, so it is drained first.
+template <class T>
+int grow_device(dsx_ctx* ctx, hipStream_t s, T** buf, size_t* have, size_t need, const char* message) {
+  if (need <= *have) return DSX_OK;
+  DSX_HIP(hipStreamSynchronize(s));
+  if (*buf) DSX_HIP(hipFree(*buf));
+  *buf = nullptr;
+  *have = 0;
+  if (hipMalloc(buf, need) != hipSuccess) return fail(ctx, DSX_ENOMEM, message);
+  *have = need;
+  return DSX_OK;
+}
+
+// the pack stage of dsx_blosc_encode_device_ex for the container C: sizes -> offsets, slots (or the source) -> frames
+template <class C>
+void launch_pack(hipStream_t s, const dsx::zenc::PackArgs& pa) {
+  hipLaunchKernelGGL(dsx::zenc::k_pack_scan<C>, dim3(1), dim3(256), 0, s, pa);
+  if (pa.n_chunks > 0)
+    hipLaunchKernelGGL(dsx::zenc::k_pack_copy<C>, dim3((unsigned)(pa.n_chunks * pa.nblocks)), dim3(256), 0, s, pa);
 }
 
 // alone: the cohort runs as this ONE part (which may then use its helper stream: dsx::part_uses_helper)
@@ -2126,13 +2148,11 @@ int dsx_blosc_encode_ref_ex(const void* src, int n_chunks, size_t chunk_bytes, i
                             int64_t* offsets, int mode) {
   if ((!src && n_chunks > 0 && chunk_bytes) || !frames || !offsets) return DSX_EINVAL;
   if (const char* e = zenc_params(n_chunks, chunk_bytes, typesize, clevel, mode)) return fail(nullptr, DSX_EINVAL, e);
-  if (mode == DSX_ZENC_LZ4) {
-    dsx::lz4enc::blosc_encode_host((const uint16_t*)src, (uint64_t)n_chunks, chunk_bytes, clevel, (uint8_t*)frames,
-                                   offsets);
-    return DSX_OK;
-  }
-  dsx::zenc::blosc_encode_host((const uint16_t*)src, (uint64_t)n_chunks, chunk_bytes, clevel, (uint8_t*)frames, offsets,
-                               mode);
+  const uint16_t* e = (const uint16_t*)src;
+  if (mode == DSX_ZENC_LZ4)  // (either is blosc::assemble_chunks_host over the mode's block encoder)
+    dsx::lz4enc::blosc_encode_host(e, (uint64_t)n_chunks, chunk_bytes, clevel, (uint8_t*)frames, offsets);
+  else
+    dsx::zenc::blosc_encode_host(e, (uint64_t)n_chunks, chunk_bytes, clevel, (uint8_t*)frames, offsets, mode);
   return DSX_OK;
 }
 int dsx_blosc_encode_ref(const void* src, int n_chunks, size_t chunk_bytes, int typesize, int clevel, void* frames,
@@ -2157,51 +2177,25 @@ int dsx_blosc_encode_device_ex(dsx_ctx* ctx, const void* d_src, int n_chunks, si
   const size_t nblocks = store ? 0 : (size_t)n_chunks * g.nblocks * z::kZPerBlosc;
   if ((size_t)n_chunks * g.nblocks > 0x7FFFFFFFu / z::kZPerBlosc)
     return fail(ctx, DSX_ELIMIT, "blosc_encode: too many blocks per call");
-  if (nblocks > ctx->zenc_blocks) {
-    DSX_HIP(hipStreamSynchronize(s));
-    if (ctx->zenc_slots) DSX_HIP(hipFree(ctx->zenc_slots));
-    if (ctx->zenc_sizes) DSX_HIP(hipFree(ctx->zenc_sizes));
-    ctx->zenc_slots = nullptr;
-    ctx->zenc_sizes = nullptr;
-    ctx->zenc_blocks = 0;
-    if (hipMalloc(&ctx->zenc_slots, nblocks * (size_t)z::kSlotStride) != hipSuccess ||
-        hipMalloc(&ctx->zenc_sizes, nblocks * sizeof(uint32_t)) != hipSuccess)
-      return fail(ctx, DSX_ENOMEM, "blosc_encode: cannot allocate the work buffer");
-    ctx->zenc_blocks = nblocks;
-  }
-  if (mode == DSX_ZENC_RUNS && nblocks > ctx->zenc_lit_blocks) {
-    DSX_HIP(hipStreamSynchronize(s));
-    if (ctx->zenc_lits) DSX_HIP(hipFree(ctx->zenc_lits));
-    ctx->zenc_lits = nullptr;
-    ctx->zenc_lit_blocks = 0;
-    if (hipMalloc(&ctx->zenc_lits, nblocks * (size_t)z::kSlotStride) != hipSuccess)
-      return fail(ctx, DSX_ENOMEM, "blosc_encode: cannot allocate the work buffer");
-    ctx->zenc_lit_blocks = nblocks;
-  }
+  const char* nomem = "blosc_encode: cannot allocate the work buffer";
+  const size_t slot_bytes = nblocks * (size_t)z::kSlotStride, lit_bytes = mode == DSX_ZENC_RUNS ? slot_bytes : 0;
+  if (int rc = grow_device(ctx, s, &ctx->zenc_slots, &ctx->zenc_slot_bytes, slot_bytes, nomem)) return rc;
+  if (int rc = grow_device(ctx, s, &ctx->zenc_sizes, &ctx->zenc_size_bytes, nblocks * sizeof(uint32_t), nomem)) return rc;
+  if (int rc = grow_device(ctx, s, &ctx->zenc_lits, &ctx->zenc_lit_bytes, lit_bytes, nomem)) return rc;
   const z::EncArgs ea{(const uint16_t*)d_src, ctx->zenc_slots, ctx->zenc_sizes, (uint64_t)chunk_bytes, g.nblocks};
-  if (mode == DSX_ZENC_LZ4) {  // one wave per stream; the streams use the slots and sizes of the zstd blocks
-    namespace l = dsx::lz4enc;
-    if (!store && nblocks) hipLaunchKernelGGL(l::k_lz4_stream, dim3((unsigned)nblocks), dim3(64), 0, s, ea);
-    z::PackArgs pa{(const uint16_t*)d_src, ctx->zenc_slots, ctx->zenc_sizes, (uint8_t*)d_frames, d_offsets,
-                   (uint64_t)chunk_bytes, n_chunks, store ? 1 : g.nblocks, store};
-    hipLaunchKernelGGL(l::k_lz4_scan, dim3(1), dim3(256), 0, s, pa);
-    if (n_chunks > 0)
-      hipLaunchKernelGGL(l::k_lz4_copy, dim3((unsigned)(n_chunks * pa.nblocks)), dim3(256), 0, s, pa);
-    DSX_HIP(hipGetLastError());
-    return DSX_OK;
-  }
-  if (!store && nblocks) {
-    if (mode == DSX_ZENC_RUNS)
+  if (nblocks) {  // one workgroup per slot: a zstd block, or (one wave) an LZ4 stream
+    if (mode == DSX_ZENC_LZ4)
+      hipLaunchKernelGGL(dsx::lz4enc::k_lz4_stream, dim3((unsigned)nblocks), dim3(64), 0, s, ea);
+    else if (mode == DSX_ZENC_RUNS)
       hipLaunchKernelGGL(z::k_zenc_block_runs, dim3((unsigned)nblocks), dim3(z::kEncThreads), 0, s,
                          z::RunArgs{ea, ctx->zenc_lits});
     else
       hipLaunchKernelGGL(z::k_zenc_block, dim3((unsigned)nblocks), dim3(z::kEncThreads), 0, s, ea);
   }
-  z::PackArgs pa{(const uint16_t*)d_src, ctx->zenc_slots, ctx->zenc_sizes, (uint8_t*)d_frames, d_offsets,
-                 (uint64_t)chunk_bytes, n_chunks, store ? 1 : g.nblocks, store};
-  hipLaunchKernelGGL(z::k_zenc_scan, dim3(1), dim3(256), 0, s, pa);
-  if (n_chunks > 0)
-    hipLaunchKernelGGL(z::k_zenc_copy, dim3((unsigned)(n_chunks * pa.nblocks)), dim3(256), 0, s, pa);
+  const z::PackArgs pa{(const uint16_t*)d_src, ctx->zenc_slots, ctx->zenc_sizes, (uint8_t*)d_frames, d_offsets,
+                       (uint64_t)chunk_bytes, n_chunks, store ? 1 : g.nblocks, store};
+  if (mode == DSX_ZENC_LZ4) launch_pack<dsx::lz4enc::Lz4Streams>(s, pa);
+  else launch_pack<z::ZstdFrames>(s, pa);
   DSX_HIP(hipGetLastError());
   return DSX_OK;
 }
@@ -2266,15 +2260,9 @@ int dsx_blosc_decode_device(dsx_ctx* ctx, const void* d_packed, size_t packed_by
   namespace z = dsx::zdec;
   DSX_HIP(hipSetDevice(ctx->device));
   hipStream_t s = use_main(ctx);
-  if (out_bytes > ctx->zdec_bytes) {
-    DSX_HIP(hipStreamSynchronize(s));
-    if (ctx->zdec_scratch) DSX_HIP(hipFree(ctx->zdec_scratch));
-    ctx->zdec_scratch = nullptr;
-    ctx->zdec_bytes = 0;
-    if (hipMalloc(&ctx->zdec_scratch, out_bytes) != hipSuccess)
-      return fail(ctx, DSX_ENOMEM, "blosc_decode: cannot allocate the work buffer");
-    ctx->zdec_bytes = out_bytes;
-  }
+  if (int rc = grow_device(ctx, s, &ctx->zdec_scratch, &ctx->zdec_bytes, out_bytes,
+                           "blosc_decode: cannot allocate the work buffer"))
+    return rc;
   if (n_tasks > 0) {
     const z::DecArgs da{(const uint8_t*)d_packed, (const z::DecTask*)d_tasks, (uint8_t*)d_out,
                         ctx->zdec_scratch, d_status, (uint64_t)packed_bytes, (uint64_t)out_bytes};

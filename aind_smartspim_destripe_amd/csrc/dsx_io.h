@@ -111,9 +111,7 @@ inline std::string io_parallel(int n, int threads, F&& one) {
 
 // ---- Blosc 1 container ---------------------------------------------------------------------------------------
 constexpr int kCodecRaw = 0, kCodecZlib = 1, kCodecBlosc = 2;  // DSX_CODEC_* of include/dsx.h
-constexpr int kBloscHeader = 16, kBloscMinBuffer = 128, kBloscMaxSplits = 16;
-constexpr unsigned kBloscShuffle = 0x1, kBloscMemcpyed = 0x2, kBloscBitshuffle = 0x4, kBloscDontSplit = 0x10;
-enum BloscInner { kInnerBlosclz = 0, kInnerLz4 = 1, kInnerSnappy = 2, kInnerZlib = 3, kInnerZstd = 4 };
+using namespace blosc;  // dsx_blosc_frame.h: kBloscHeader, kBloscMinBuffer, the flag bits, BloscInner, blosc_header
 
 struct InnerCodecs {
   // libzstd.so.1
@@ -195,7 +193,6 @@ inline bool zstd_available() {
 }
 
 inline uint32_t le32(const unsigned char* p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
-inline void put_le32(unsigned char* p, uint32_t v) { p[0] = v & 255; p[1] = (v >> 8) & 255; p[2] = (v >> 16) & 255; p[3] = v >> 24; }
 
 // byte shuffle of one block: element i, byte j -> position j * nelem + i; the (blocksize % typesize) tail is copied
 inline void blosc_shuffle(size_t typesize, size_t blocksize, const unsigned char* src, unsigned char* dst) {
@@ -373,21 +370,17 @@ inline std::string blosc_encode(const void* src_, size_t n, int typesize, int cl
   if (n > 0x7FFFFFEFu) return "blosc: buffer larger than a frame can hold";
   if (typesize < 1 || typesize > 255) return "blosc: bad type size";
   const unsigned char* src = (const unsigned char*)src_;
+  const unsigned flags = (shuffle && typesize > 1 ? kBloscShuffle : 0u) | kBloscDontSplit | (kInnerZstd << 5);
   auto stored = [&]() {
     out.resize(kBloscHeader + n);
     memcpy(out.data() + kBloscHeader, src, n);
-    out[0] = 2; out[1] = 1; out[2] = (unsigned char)(kBloscMemcpyed | (shuffle && typesize > 1 ? kBloscShuffle : 0) |
-                                                     kBloscDontSplit | (kInnerZstd << 5));
-    out[3] = (unsigned char)typesize;
-    put_le32(out.data() + 4, (uint32_t)n);
-    put_le32(out.data() + 8, (uint32_t)n);
-    put_le32(out.data() + 12, (uint32_t)(kBloscHeader + n));
+    blosc_header(out.data(), flags, typesize, n, n, kBloscHeader + n, true);
     return std::string();
   };
   if (n < (size_t)kBloscMinBuffer || clevel <= 0) return stored();
   if (!zstd_available()) return "blosc: libzstd.so.1 is not available";
   const InnerCodecs& lib = inner_codecs();
-  size_t blocksize = std::min<size_t>(n, 256 * 1024);
+  size_t blocksize = std::min<size_t>(n, kBloscBlock);
   if (blocksize > (size_t)typesize) blocksize -= blocksize % typesize;
   const size_t nblocks = (n + blocksize - 1) / blocksize;
   const bool do_shuffle = shuffle && typesize > 1;
@@ -405,17 +398,12 @@ inline std::string blosc_encode(const void* src_, size_t n, int typesize, int cl
     if (raw) cs = bsize;
     const size_t at = out.size();
     if (at + 4 + cs >= kBloscHeader + n) return stored();  // not smaller than the data: store the whole buffer
-    put_le32(out.data() + kBloscHeader + 4 * b, (uint32_t)at);
+    put_le(out.data() + kBloscHeader + 4 * b, at, 4);
     out.resize(at + 4 + cs);
-    put_le32(out.data() + at, (uint32_t)cs);
+    put_le(out.data() + at, cs, 4);
     memcpy(out.data() + at + 4, raw ? blk : comp.data(), cs);
   }
-  out[0] = 2; out[1] = 1;
-  out[2] = (unsigned char)((do_shuffle ? kBloscShuffle : 0) | kBloscDontSplit | (kInnerZstd << 5));
-  out[3] = (unsigned char)typesize;
-  put_le32(out.data() + 4, (uint32_t)n);
-  put_le32(out.data() + 8, (uint32_t)blocksize);
-  put_le32(out.data() + 12, (uint32_t)out.size());
+  blosc_header(out.data(), flags, typesize, n, blocksize, out.size(), false);
   return "";
 }
 

@@ -32,16 +32,12 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "dsx_zstd_enc.h"  // DSX_ZHD, Geometry, put_le, shuffled_byte, kBloscHeader, kBloscMinBuffer, kSlotStride
+#include "dsx_blosc_frame.h"  // the container: Geometry, shuffled_byte, put_le, the slots, assemble_chunk_host
 
 namespace dsx {
 namespace lz4enc {
 
-using zenc::Geometry;
-using zenc::kBloscHeader;
-using zenc::kBloscMinBuffer;
-using zenc::put_le;
-using zenc::shuffled_byte;
+using namespace blosc;
 
 constexpr int kGroup = 64;                 // positions per step (one wave)
 constexpr int kHashLog = 12;
@@ -51,8 +47,7 @@ constexpr uint32_t kMinMatch = 4;
 constexpr uint32_t kLastLiterals = 5;      // the last bytes of a block are literals
 constexpr uint32_t kMatchFreeTail = 12;    // no match starts within the last bytes
 constexpr uint32_t kMinSplitPlane = 128;   // c-blosc splits a block when blocksize / typesize >= 128
-constexpr int kStreamsPerBlock = 2;        // planes of a split block (= the slots a Blosc block owns)
-static_assert(kStreamsPerBlock == zenc::kZPerBlosc, "the LZ4 streams use the slot layout of the zstd blocks");
+constexpr int kStreamsPerBlock = kSlotsPerBlock;  // planes of a split block: one slot each
 
 DSX_ZHD inline uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - kHashLog); }
 
@@ -79,25 +74,17 @@ DSX_ZHD inline uint8_t token(uint32_t lit, uint32_t ml4) {
 DSX_ZHD inline bool block_splits(const Geometry& g, uint64_t n, int b) {
   return g.bsize(n, b) == g.blocksize && g.blocksize / 2 >= kMinSplitPlane;
 }
-// Frame bytes of one chunk from the stream lengths ss[nblocks][kStreamsPerBlock] (a stored stream has its own length;
-// the second entry of an unsplit block is not read); store = the chunk is stored as a whole.
-DSX_ZHD inline uint64_t chunk_frame_bytes(const uint32_t* ss, uint64_t n, bool store) {
-  if (store) return kBloscHeader + n;
-  const Geometry g(n);
-  uint64_t f = kBloscHeader + 4ull * g.nblocks;
-  for (int b = 0; b < g.nblocks; ++b)
-    f += block_splits(g, n, b) ? 8ull + ss[2 * b] + ss[2 * b + 1] : 4ull + ss[2 * b];
-  return f < kBloscHeader + n ? f : kBloscHeader + n;  // not smaller than the data: memcpyed frame
-}
-DSX_ZHD inline void blosc_header(uint8_t* out, uint64_t n, uint32_t blocksize, uint64_t cbytes, bool memcpyed) {
-  out[0] = 2;
-  out[1] = 1;
-  out[2] = (uint8_t)((memcpyed ? 0x2 : 0) | 0x1 | (1 << 5));  // [memcpyed] | shuffle | lz4; split streams
-  out[3] = 2;
-  put_le(out + 4, n, 4);
-  put_le(out + 8, memcpyed ? (uint32_t)n : blocksize, 4);
-  put_le(out + 12, cbytes, 4);
-}
+// The container of the LZ4 mode (dsx_blosc_frame.h): split streams.  Stream j is slot j as it is, sizes[j] bytes (a
+// stored stream has its own length; the second entry of an unsplit block is not read); the one stream of an unsplit
+// block runs on from slot 0 into slot 1.
+struct Lz4Streams {
+  static constexpr unsigned kFlags = kBloscShuffle | (kInnerLz4 << 5);
+  static constexpr int kParts = 1;
+  DSX_ZHD static int streams(const Geometry& g, uint64_t n, int b) { return block_splits(g, n, b) ? kStreamsPerBlock : 1; }
+  DSX_ZHD static uint32_t stream_bytes(const uint32_t* ss, uint32_t, int j) { return ss[j]; }
+  DSX_ZHD static int prefix(uint32_t, uint8_t*) { return 0; }
+  DSX_ZHD static int prefix_bytes(uint32_t) { return 0; }
+};
 
 // ---- host build ---------------------------------------------------------------------------------------------------
 // One stream s[0 .. n) -> out (n bytes of room); returns the bytes of the LZ4 block, 0 when the stream is stored.
@@ -158,54 +145,34 @@ inline uint32_t encode_stream_host(const Src& s, uint32_t n, uint8_t* out, uint3
 // Work space of the host build
 struct HostWork {
   uint32_t table[kTable];
-  uint8_t lit[zenc::kBloscBlock];    // the shuffled block
-  uint8_t slot[zenc::kBloscBlock];   // one encoded stream
+  uint8_t lit[kBloscBlock];                      // the shuffled block
+  uint8_t slots[kSlotsPerBlock * kSlotStride];   // its encoded streams
+};
+
+// The ns streams of the shuffled block lit[0 .. bsize) -> its slots and sizes (the encode_block of assemble_chunk_host)
+struct BlockEncoderHost {
+  uint32_t* table;
+  void operator()(const uint8_t* lit, uint32_t bsize, int ns, uint8_t* slots, uint32_t* ss) const {
+    const uint32_t sn = bsize / (uint32_t)ns;
+    for (int j = 0; j < ns; ++j) {
+      const uint32_t coded = encode_stream_host(lit + (size_t)j * sn, sn, slots + (size_t)j * kSlotStride, table);
+      ss[j] = coded ? coded : sn;
+    }
+  }
 };
 
 // One chunk of n bytes (uint16, n even) -> out (n + 16 bytes of room); returns the frame's bytes.
 inline uint64_t encode_chunk_host(HostWork& w, const uint16_t* e, uint64_t n, int clevel, uint8_t* out) {
-  const bool store = n < (uint64_t)kBloscMinBuffer || clevel <= 0;
-  const Geometry g(n ? n : 1);
-  uint64_t pos = kBloscHeader + 4ull * g.nblocks;
-  bool memcpyed = store;
-  for (int b = 0; b < g.nblocks && !memcpyed; ++b) {
-    const uint32_t bsize = g.bsize(n, b);
-    for (uint32_t p = 0; p < bsize; ++p) w.lit[p] = shuffled_byte(e + (uint64_t)b * (g.blocksize / 2), bsize / 2, p);
-    const int ns = block_splits(g, n, b) ? kStreamsPerBlock : 1;
-    const uint32_t sn = bsize / (uint32_t)ns;
-    put_le(out + kBloscHeader + 4 * b, pos, 4);
-    for (int j = 0; j < ns; ++j) {
-      const uint8_t* s = w.lit + (size_t)j * sn;
-      const uint32_t coded = encode_stream_host(s, sn, w.slot, w.table);
-      const uint32_t sb = coded ? coded : sn;
-      if (pos + 4 + sb >= kBloscHeader + n) { memcpyed = true; break; }
-      put_le(out + pos, sb, 4);
-      const uint8_t* from = coded ? w.slot : s;
-      for (uint32_t i = 0; i < sb; ++i) out[pos + 4 + i] = from[i];
-      pos += 4 + sb;
-    }
-  }
-  if (memcpyed) {
-    const uint8_t* raw = (const uint8_t*)e;
-    for (uint64_t i = 0; i < n; ++i) out[kBloscHeader + i] = raw[i];
-    pos = kBloscHeader + n;
-  }
-  blosc_header(out, n, g.blocksize, pos, memcpyed);
-  return pos;
+  return assemble_chunk_host<Lz4Streams>(e, n, clevel, w.lit, w.slots, out, BlockEncoderHost{w.table});
 }
 
 // n_chunks chunks of chunk_bytes (uint16) -> packed frames + offsets[n_chunks + 1] (the device encoder's output).
 // frames: n_chunks * (chunk_bytes + 16) bytes at most.
 inline void blosc_encode_host(const uint16_t* src, uint64_t n_chunks, uint64_t chunk_bytes, int clevel, uint8_t* frames,
                               int64_t* offsets) {
-  HostWork* w = new HostWork;
-  uint64_t at = 0;
-  offsets[0] = 0;
-  for (uint64_t c = 0; c < n_chunks; ++c) {
-    at += encode_chunk_host(*w, src + c * (chunk_bytes / 2), chunk_bytes, clevel, frames + at);
-    offsets[c + 1] = (int64_t)at;
-  }
-  delete w;
+  uint32_t* table = new uint32_t[kTable];
+  assemble_chunks_host<Lz4Streams>(src, n_chunks, chunk_bytes, clevel, frames, offsets, BlockEncoderHost{table});
+  delete[] table;
 }
 
 }  // namespace lz4enc

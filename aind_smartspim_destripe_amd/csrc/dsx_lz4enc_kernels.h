@@ -1,5 +1,6 @@
 // dsx_lz4enc_kernels.h -- Blosc-LZ4 frames on the device (dsx_blosc_encode_device_ex, DSX_ZENC_LZ4): the finder of
-// dsx_lz4_enc.h run by one wave per stream, then a size scan and a copy into one packed buffer.
+// dsx_lz4_enc.h run by one wave per stream; the pack stage of dsx_zenc_kernels.h (k_pack_scan / k_pack_copy over
+// Lz4Streams) then makes the frames.
 //
 //   k_lz4_stream   grid = chunks x Blosc blocks x 2, one wave each: stream j of the block (plane j of a split block;
 //                  the whole shuffled block for j = 0 of an unsplit one, whose j = 1 leaves at once).  Serial over the
@@ -12,17 +13,13 @@
 //                  position are wave-uniform.  The stream lands in its slot (kSlotStride bytes; an unsplit block of up
 //                  to 256 KiB - 2 bytes runs on into the slot of its idle j = 1), its length in sizes[] (the stream's
 //                  own length = stored: nothing in the slot is read then).
-//   k_lz4_scan     one workgroup: frame bytes per chunk (chunk_frame_bytes) and their exclusive scan -> offsets: the
-//                  scan of k_zenc_scan (zenc::scan_frame_bytes) over this container's frame bytes.
-//   k_lz4_copy     grid = chunks x Blosc blocks: block table entry, then per stream its length and the slot's bytes
-//                  (or the stored plane), or the chunk's bytes of a memcpyed frame.
 #ifndef DSX_LZ4ENC_KERNELS_H
 #define DSX_LZ4ENC_KERNELS_H
 
 #include <hip/hip_runtime.h>
 
 #include "dsx_lz4_enc.h"
-#include "dsx_zenc_kernels.h"  // EncArgs, PackArgs, shuffled_word, scan_frame_bytes
+#include "dsx_zenc_kernels.h"  // EncArgs, shuffled_word
 
 namespace dsx {
 namespace lz4enc {
@@ -46,7 +43,7 @@ __global__ void __launch_bounds__(64) k_lz4_stream(zenc::EncArgs a) {
   const uint32_t ne = bsize / 2;
   const uint32_t n = split ? ne : bsize;   // bytes of the stream
   const uint32_t s0 = (uint32_t)j * ne;    // its first byte in the shuffled block; it ends at s0 + n
-  uint8_t* out = a.slots + (uint64_t)blockIdx.x * zenc::kSlotStride;
+  uint8_t* out = a.slots + (uint64_t)blockIdx.x * kSlotStride;
   auto rd4 = [&](uint32_t p) {
     return (uint32_t)shuffled_byte(e, ne, s0 + p) | ((uint32_t)shuffled_byte(e, ne, s0 + p + 1) << 8) |
            ((uint32_t)shuffled_byte(e, ne, s0 + p + 2) << 16) | ((uint32_t)shuffled_byte(e, ne, s0 + p + 3) << 24);
@@ -130,56 +127,6 @@ __global__ void __launch_bounds__(64) k_lz4_stream(zenc::EncArgs a) {
   for (uint32_t i = lane; i < kl; i += 64) d[1 + i] = chain_byte(lit, i);
   d += 1 + kl;
   for (uint32_t i = lane; i < lit; i += 64) d[i] = shuffled_byte(e, ne, s0 + anchor + i);
-}
-
-__global__ void __launch_bounds__(256) k_lz4_scan(zenc::PackArgs a) {
-  zenc::scan_frame_bytes(a, [](const uint32_t* ss, uint64_t n, bool store) { return chunk_frame_bytes(ss, n, store); });
-}
-
-__global__ void __launch_bounds__(256) k_lz4_copy(zenc::PackArgs a) {
-  const int tid = threadIdx.x;
-  const uint64_t chunk = blockIdx.x / (uint32_t)a.nblocks;
-  const int b = (int)(blockIdx.x % (uint32_t)a.nblocks);
-  const uint64_t n = a.chunk_bytes;
-  const Geometry g(n ? n : 1);
-  uint8_t* out = a.frames + a.offsets[chunk];
-  const uint64_t fbytes = (uint64_t)(a.offsets[chunk + 1] - a.offsets[chunk]);
-  const bool memcpyed = fbytes >= kBloscHeader + n;
-  if (b == 0 && tid == 0) blosc_header(out, n, g.blocksize, fbytes, memcpyed);
-  const uint8_t* raw = (const uint8_t*)(a.src + chunk * (n / 2));
-  if (memcpyed) {
-    const uint32_t bsize = a.store ? (uint32_t)n : g.bsize(n, b);
-    const uint64_t o = (uint64_t)b * g.blocksize;
-    if (a.store && b > 0) return;
-    for (uint32_t i = tid; i < bsize; i += 256) out[kBloscHeader + o + i] = raw[o + i];
-    return;
-  }
-  const uint32_t* ss = a.sizes + chunk * (uint64_t)(a.nblocks * kStreamsPerBlock);
-  uint64_t pos = kBloscHeader + 4ull * g.nblocks;
-  for (int k = 0; k < b; ++k) pos += block_splits(g, n, k) ? 8ull + ss[2 * k] + ss[2 * k + 1] : 4ull + ss[2 * k];
-  if (tid == 0) put_le(out + kBloscHeader + 4 * b, pos, 4);
-  const uint32_t bsize = g.bsize(n, b), ne = bsize / 2;
-  const int ns = block_splits(g, n, b) ? kStreamsPerBlock : 1;
-  const uint32_t sn = bsize / (uint32_t)ns;
-  const uint16_t* e = a.src + chunk * (n / 2) + (uint64_t)b * (g.blocksize / 2);
-  for (int j = 0; j < ns; ++j) {
-    const uint32_t m = ss[2 * b + j];
-    if (tid == 0) put_le(out + pos, m, 4);
-    uint8_t* d = out + pos + 4;
-    if (m == sn) {  // stored stream: the shuffled bytes
-      for (uint32_t p = tid; p < sn; p += 256) d[p] = shuffled_byte(e, ne, (uint32_t)j * sn + p);
-    } else {
-      const uint32_t* sl = (const uint32_t*)(a.slots + ((uint64_t)blockIdx.x * kStreamsPerBlock + j) * zenc::kSlotStride);
-      for (uint32_t q = tid; 4 * q < m; q += 256) {
-        const uint32_t v = sl[q];
-        const uint32_t i = 4 * q;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-          if (i + t < m) d[i + t] = (uint8_t)(v >> (8 * t));
-      }
-    }
-    pos += 4 + m;
-  }
 }
 
 }  // namespace lz4enc

@@ -15,12 +15,15 @@
 //                  remain, a scan gives every piece its literal index, a third walk compacts the literals into the
 //                  block's work buffer, counts them per literal stream and writes the sequence list.  Then three
 //                  threads work side by side: the entropy-only plan, the plan of the literals section, the sequences
-//                  bit stream (behind the compacted literals); the smaller block is written, its streams packed as
-//                  in k_zenc_block, from the source or from the compacted literals.  A block without a run of
-//                  kMinRun bytes, or of one value, leaves after pass 1 and is encoded as k_zenc_block does.
-//   k_zenc_scan    one workgroup: frame bytes per chunk (chunk_frame_bytes) and their exclusive scan -> offsets.
-//   k_zenc_copy    grid = chunks x Blosc blocks: block table entry, stream length and stream (zstd frame header + the
-//                  slots, or the stored shuffled block), or the chunk's bytes of a memcpyed frame.
+//                  bit stream (behind the compacted literals); the smaller block is written, its streams packed by
+//                  the same pack_streams, from the source or from the compacted literals.  A block without a run of
+//                  kMinRun bytes, or of one value, leaves after pass 1 and is written as k_zenc_block writes it
+//                  (write_entropy_block).
+// The pack stage is the same for every encoder that fills slots and sizes (k_lz4_stream of dsx_lz4enc_kernels.h too),
+// templated on the container C of dsx_blosc_frame.h (ZstdFrames here, lz4enc::Lz4Streams):
+//   k_pack_scan<C> one workgroup: frame bytes per chunk (chunk_frame_bytes<C>) and their exclusive scan -> offsets.
+//   k_pack_copy<C> grid = chunks x Blosc blocks: block table entry, then per stream its length and its bytes (C's prefix
+//                  + the slots, or the stored shuffled bytes), or the chunk's bytes of a memcpyed frame.
 #ifndef DSX_ZENC_KERNELS_H
 #define DSX_ZENC_KERNELS_H
 
@@ -44,64 +47,61 @@ struct EncArgs {
   int nblocks;
 };
 
-__global__ void __launch_bounds__(kEncThreads) k_zenc_block(EncArgs a) {
-  __shared__ HufWork h;
-  __shared__ uint32_t win[4][kWinWords];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const uint32_t zb = blockIdx.x % (uint32_t)(a.nblocks * kZPerBlosc);
-  const uint64_t chunk = blockIdx.x / (uint32_t)(a.nblocks * kZPerBlosc);
-  const int b = (int)(zb / kZPerBlosc), j = (int)(zb % kZPerBlosc);
-  const Geometry g(a.chunk_bytes);
-  const uint32_t bsize = g.bsize(a.chunk_bytes, b);
-  const uint32_t z0 = (uint32_t)j * kZBlock;
-  if (z0 >= bsize) {
-    if (tid == 0) a.sizes[blockIdx.x] = 0;
-    return;
-  }
-  const int n = (int)((bsize - z0) < (uint32_t)kZBlock ? bsize - z0 : (uint32_t)kZBlock);
-  const bool last = z0 + (uint32_t)n == bsize;
-  const uint16_t* e = a.src + chunk * (a.chunk_bytes / 2) + (uint64_t)b * (g.blocksize / 2);
-  const uint32_t ne = bsize / 2;
-  uint8_t* slot = a.slots + (uint64_t)blockIdx.x * kSlotStride;
-
-  for (int i = tid; i < 4 * 256; i += kEncThreads) (&h.scount[0][0])[i] = 0;
-  __syncthreads();
-  const int s0 = stream_begin(n, wave), s1 = stream_begin(n, wave + 1);
-  for (int i = s0 + lane; i < s1; i += 64) atomicAdd(&h.scount[wave][shuffled_byte(e, ne, z0 + i)], 1u);
-  __syncthreads();
-  {
-    const int s = tid;
-    h.count[s] = h.scount[0][s] + h.scount[1][s] + h.scount[2][s] + h.scount[3][s];
-  }
-  __syncthreads();
-  {
-    const int s = tid;
-    if (h.count[s]) h.sorted[sort_rank(h, s)] = sort_key(h, s);
-    const int present = __syncthreads_count(h.count[s] != 0);
-    if (tid == 0) {
-      h.nsym = present;
-      plan_block(h, n);
-      write_block_frame(h, n, last, slot);
-      a.sizes[blockIdx.x] = (uint32_t)h.block_bytes;
+// The zstd block of workgroup blockIdx.x: block j of Blosc block b of a chunk
+struct ZBlock {
+  uint64_t chunk;
+  int b, j;
+  uint32_t bsize, z0;  // bytes of the Blosc block; first byte of the zstd block in it
+  int n;               // bytes of the zstd block
+  bool last;           // the last zstd block of its frame
+  const uint16_t* e;   // elements of the Blosc block
+  uint32_t ne;
+  uint8_t* slot;
+  // false: the slot lies beyond the Blosc block -- its size is written as 0 and the workgroup leaves
+  __device__ __forceinline__ bool locate(const EncArgs& a) {
+    const uint32_t zb = blockIdx.x % (uint32_t)(a.nblocks * kZPerBlosc);
+    chunk = blockIdx.x / (uint32_t)(a.nblocks * kZPerBlosc);
+    b = (int)(zb / kZPerBlosc);
+    j = (int)(zb % kZPerBlosc);
+    const Geometry g(a.chunk_bytes);
+    bsize = g.bsize(a.chunk_bytes, b);
+    z0 = (uint32_t)j * kZBlock;
+    if (z0 >= bsize) {
+      if (threadIdx.x == 0) a.sizes[blockIdx.x] = 0;
+      return false;
     }
+    n = (int)((bsize - z0) < (uint32_t)kZBlock ? bsize - z0 : (uint32_t)kZBlock);
+    last = z0 + (uint32_t)n == bsize;
+    e = a.src + chunk * (a.chunk_bytes / 2) + (uint64_t)b * (g.blocksize / 2);
+    ne = bsize / 2;
+    slot = a.slots + (uint64_t)blockIdx.x * kSlotStride;
+    return true;
   }
-  __syncthreads();
-  if (h.type == kRaw) {
-    for (int i = tid; i < n; i += kEncThreads) slot[3 + i] = shuffled_byte(e, ne, z0 + i);
-    return;
-  }
-  if (h.type != kCompressed) return;
+};
 
-  // ---- stream `wave`: literals s1 - 1 down to s0, rounds of 64 x 8 (equal round count in every wave: __syncthreads)
-  uint8_t* dst = slot + h.prefix_bytes;
+// count[] and sorted[] of h from its stream histograms; returns the symbols present (every thread)
+__device__ inline int finish_counts(HufWork& h) {
+  const int s = threadIdx.x;
+  h.count[s] = h.scount[0][s] + h.scount[1][s] + h.scount[2][s] + h.scount[3][s];
+  __syncthreads();
+  if (h.count[s]) h.sorted[sort_rank(h, s)] = sort_key(h, s);
+  return __syncthreads_count(h.count[s] != 0);
+}
+
+// The four Huffman streams of nlit literals lit(i) -> dst, wave k packs stream k: literals s1 - 1 down to s0 in rounds
+// of 64 x 8 (an equal round count in every wave: __syncthreads)
+template <class Lit>
+__device__ inline void pack_streams(const HufWork& h, uint32_t (*win)[kWinWords], int nlit, uint8_t* dst, Lit&& lit) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int s0 = stream_begin(nlit, wave), s1 = stream_begin(nlit, wave + 1);
   for (int k = 0; k < wave; ++k) dst += h.stream_bytes[k];
-  const int rounds = (stream_begin(n, 1) + kRound - 1) / kRound;
+  const int rounds = (stream_begin(nlit, 1) + kRound - 1) / kRound;
   uint32_t* w = win[wave];
   for (int q = lane; q < kWinWords; q += 64) w[q] = 0;
-  uint32_t bitpos = 0;  // bits of this stream written so far (uniform in the wave)
+  uint32_t bitpos = 0;
   __syncthreads();
   for (int r = 0; r < rounds; ++r) {
-    const int rev0 = r * kRound + lane * kLitPerLane;  // reversed index of this lane's first literal
+    const int rev0 = r * kRound + lane * kLitPerLane;
     uint32_t codes[kLitPerLane];
     int lens[kLitPerLane];
     int mine = 0;
@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(kEncThreads) k_zenc_block(EncArgs a) {
     for (int t = 0; t < kLitPerLane; ++t) {
       const int i = s1 - 1 - (rev0 + t);
       if (i >= s0) {
-        const uint8_t v = shuffled_byte(e, ne, z0 + i);
+        const uint8_t v = lit(i);
         codes[t] = h.code[v];
         lens[t] = h.len[v];
       } else {
@@ -149,12 +149,48 @@ __global__ void __launch_bounds__(kEncThreads) k_zenc_block(EncArgs a) {
     bitpos += (uint32_t)total;
     __syncthreads();
   }
-  if (lane == 0) {  // end mark, then the bytes of the partial word
+  if (lane == 0) {
     const uint32_t v = w[0] | (1u << (bitpos & 31u));
     const int rest = (int)h.stream_bytes[wave] - 4 * (int)(bitpos >> 5);
     uint8_t* wd = dst + 4 * (bitpos >> 5);
     for (int i = 0; i < rest; ++i) wd[i] = (uint8_t)(v >> (8 * i));
   }
+}
+
+// The entropy-only block planned in h (plan_block) -> the slot: block frame and size by thread 0, then the raw bytes
+// or the four streams, read from the source
+__device__ __forceinline__ void write_entropy_block(const HufWork& h, uint32_t (*win)[kWinWords], const EncArgs& a,
+                                                    const ZBlock& k) {
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    write_block_frame(h, k.n, k.last, k.slot);
+    a.sizes[blockIdx.x] = (uint32_t)h.block_bytes;
+  }
+  if (h.type == kRaw) {
+    for (int i = tid; i < k.n; i += kEncThreads) k.slot[3 + i] = shuffled_byte(k.e, k.ne, k.z0 + i);
+  } else if (h.type == kCompressed) {
+    pack_streams(h, win, k.n, k.slot + h.prefix_bytes, [&](int i) { return shuffled_byte(k.e, k.ne, k.z0 + i); });
+  }
+}
+
+__global__ void __launch_bounds__(kEncThreads) k_zenc_block(EncArgs a) {
+  __shared__ HufWork h;
+  __shared__ uint32_t win[4][kWinWords];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  ZBlock k;
+  if (!k.locate(a)) return;
+  for (int i = tid; i < 4 * 256; i += kEncThreads) (&h.scount[0][0])[i] = 0;
+  __syncthreads();
+  const int s0 = stream_begin(k.n, wave), s1 = stream_begin(k.n, wave + 1);
+  for (int i = s0 + lane; i < s1; i += 64) atomicAdd(&h.scount[wave][shuffled_byte(k.e, k.ne, k.z0 + i)], 1u);
+  __syncthreads();
+  const int nsym = finish_counts(h);
+  if (tid == 0) {
+    h.nsym = nsym;
+    plan_block(h, k.n);
+  }
+  __syncthreads();
+  write_entropy_block(h, win, a, k);
 }
 
 // ---- runs mode ---------------------------------------------------------------------------------------------------
@@ -239,83 +275,6 @@ __device__ inline uint32_t block_scan(uint32_t v, uint32_t* ws, uint32_t* total)
   return base + incl - v;
 }
 
-// count[] and sorted[] of h from its stream histograms; returns the symbols present (every thread)
-__device__ inline int finish_counts(HufWork& h) {
-  const int s = threadIdx.x;
-  h.count[s] = h.scount[0][s] + h.scount[1][s] + h.scount[2][s] + h.scount[3][s];
-  __syncthreads();
-  if (h.count[s]) h.sorted[sort_rank(h, s)] = sort_key(h, s);
-  return __syncthreads_count(h.count[s] != 0);
-}
-
-// The four Huffman streams of nlit literals lit(i) -> dst, wave k packs stream k (the loop of k_zenc_block)
-template <class Lit>
-__device__ inline void pack_streams(const HufWork& h, uint32_t (*win)[kWinWords], int nlit, uint8_t* dst, Lit&& lit) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int s0 = stream_begin(nlit, wave), s1 = stream_begin(nlit, wave + 1);
-  for (int k = 0; k < wave; ++k) dst += h.stream_bytes[k];
-  const int rounds = (stream_begin(nlit, 1) + kRound - 1) / kRound;
-  uint32_t* w = win[wave];
-  for (int q = lane; q < kWinWords; q += 64) w[q] = 0;
-  uint32_t bitpos = 0;
-  __syncthreads();
-  for (int r = 0; r < rounds; ++r) {
-    const int rev0 = r * kRound + lane * kLitPerLane;
-    uint32_t codes[kLitPerLane];
-    int lens[kLitPerLane];
-    int mine = 0;
-#pragma unroll
-    for (int t = 0; t < kLitPerLane; ++t) {
-      const int i = s1 - 1 - (rev0 + t);
-      if (i >= s0) {
-        const uint8_t v = lit(i);
-        codes[t] = h.code[v];
-        lens[t] = h.len[v];
-      } else {
-        codes[t] = 0;
-        lens[t] = 0;
-      }
-      mine += lens[t];
-    }
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += o;
-    }
-    const int total = __shfl(incl, 63, 64);
-    int off = (int)(bitpos & 31u) + incl - mine;
-#pragma unroll
-    for (int t = 0; t < kLitPerLane; ++t) {
-      if (lens[t]) {
-        const int q = off >> 5, sh = off & 31;
-        atomicOr(&w[q], codes[t] << sh);
-        if (sh + lens[t] > 32) atomicOr(&w[q + 1], codes[t] >> (32 - sh));
-        off += lens[t];
-      }
-    }
-    __syncthreads();
-    const int nfull = ((int)(bitpos & 31u) + total) >> 5;
-    uint8_t* wd = dst + 4 * (bitpos >> 5);
-    for (int q = lane; q < nfull; q += 64) {
-      const uint32_t v = w[q];
-      wd[4 * q] = (uint8_t)v; wd[4 * q + 1] = (uint8_t)(v >> 8); wd[4 * q + 2] = (uint8_t)(v >> 16);
-      wd[4 * q + 3] = (uint8_t)(v >> 24);
-    }
-    const uint32_t carry = w[nfull];
-    __syncthreads();
-    for (int q = lane; q <= nfull; q += 64) w[q] = (q == 0) ? carry : 0u;
-    bitpos += (uint32_t)total;
-    __syncthreads();
-  }
-  if (lane == 0) {
-    const uint32_t v = w[0] | (1u << (bitpos & 31u));
-    const int rest = (int)h.stream_bytes[wave] - 4 * (int)(bitpos >> 5);
-    uint8_t* wd = dst + 4 * (bitpos >> 5);
-    for (int i = 0; i < rest; ++i) wd[i] = (uint8_t)(v >> (8 * i));
-  }
-}
-
 __global__ void __launch_bounds__(kEncThreads) k_zenc_block_runs(RunArgs ra) {
   __shared__ HufWork h, h2;
   __shared__ SeqWork sw;
@@ -323,21 +282,12 @@ __global__ void __launch_bounds__(kEncThreads) k_zenc_block_runs(RunArgs ra) {
   __shared__ uint32_t run_first[kEncThreads], run_last[kEncThreads], ws[4];
   const EncArgs& a = ra.e;
   const int tid = threadIdx.x;
-  const uint32_t zb = blockIdx.x % (uint32_t)(a.nblocks * kZPerBlosc);
-  const uint64_t chunk = blockIdx.x / (uint32_t)(a.nblocks * kZPerBlosc);
-  const int b = (int)(zb / kZPerBlosc), j = (int)(zb % kZPerBlosc);
-  const Geometry g(a.chunk_bytes);
-  const uint32_t bsize = g.bsize(a.chunk_bytes, b);
-  const uint32_t z0 = (uint32_t)j * kZBlock;
-  if (z0 >= bsize) {
-    if (tid == 0) a.sizes[blockIdx.x] = 0;
-    return;
-  }
-  const int n = (int)((bsize - z0) < (uint32_t)kZBlock ? bsize - z0 : (uint32_t)kZBlock);
-  const bool last = z0 + (uint32_t)n == bsize;
-  const uint16_t* e = a.src + chunk * (a.chunk_bytes / 2) + (uint64_t)b * (g.blocksize / 2);
-  const uint32_t ne = bsize / 2;
-  uint8_t* slot = a.slots + (uint64_t)blockIdx.x * kSlotStride;
+  ZBlock k;
+  if (!k.locate(a)) return;
+  const int n = k.n;
+  const uint32_t z0 = k.z0, ne = k.ne;
+  const uint16_t* e = k.e;
+  uint8_t* slot = k.slot;
   uint8_t* lits = ra.lits + (uint64_t)blockIdx.x * kSlotStride;
 
   for (int i = tid; i < 4 * 256; i += kEncThreads) {
@@ -423,19 +373,11 @@ __global__ void __launch_bounds__(kEncThreads) k_zenc_block_runs(RunArgs ra) {
   __syncthreads();
   const int bytes1 = nq_all ? runs_block_bytes(h2, sw.seq_bytes) : 0;
   if (!nq_all || sw.seq_bytes < 0 || bytes1 >= h.block_bytes) {  // the entropy-only block is not larger: it stays
-    if (tid == 0) {
-      write_block_frame(h, n, last, slot);
-      a.sizes[blockIdx.x] = (uint32_t)h.block_bytes;
-    }
-    if (h.type == kRaw) {
-      for (int i = tid; i < n; i += kEncThreads) slot[3 + i] = shuffled_byte(e, ne, z0 + i);
-    } else if (h.type == kCompressed) {
-      pack_streams(h, win, n, slot + h.prefix_bytes, [&](int i) { return shuffled_byte(e, ne, z0 + i); });
-    }
+    write_entropy_block(h, win, a, k);
     return;
   }
   if (tid == 0) {
-    write_runs_block_header(bytes1, last, slot);
+    write_runs_block_header(bytes1, k.last, slot);
     write_literals_head(h2, nl, slot + 3);
     a.sizes[blockIdx.x] = (uint32_t)bytes1;
   }
@@ -448,6 +390,7 @@ __global__ void __launch_bounds__(kEncThreads) k_zenc_block_runs(RunArgs ra) {
   }
 }
 
+// ---- pack: the frames of a call from its slots, for a container C of dsx_blosc_frame.h -------------------------------
 struct PackArgs {
   const uint16_t* src;
   const uint8_t* slots;
@@ -459,8 +402,8 @@ struct PackArgs {
   bool store;        // every chunk is a memcpyed frame (short chunks, clevel <= 0)
 };
 
-// The scan of k_zenc_scan and of its LZ4 sibling (dsx_lz4enc_kernels.h), one workgroup of 256: frame_bytes(sizes of
-// the chunk's slots, chunk bytes, store) per chunk and the exclusive scan of these -> offsets.
+// One workgroup of 256: frame_bytes(sizes of the chunk's slots, chunk bytes, store) per chunk and the exclusive scan
+// of these -> offsets.
 template <class FrameBytes>
 __device__ __forceinline__ void scan_frame_bytes(const PackArgs& a, FrameBytes frame_bytes) {
   __shared__ int64_t part[256];
@@ -468,7 +411,7 @@ __device__ __forceinline__ void scan_frame_bytes(const PackArgs& a, FrameBytes f
   const int tid = threadIdx.x;
   if (tid == 0) { carry = 0; a.offsets[0] = 0; }
   __syncthreads();
-  const int per = a.nblocks * kZPerBlosc;
+  const int per = a.nblocks * kSlotsPerBlock;
   for (int c0 = 0; c0 < a.n_chunks; c0 += 256) {
     const int c = c0 + tid;
     int64_t v = c < a.n_chunks ? (int64_t)frame_bytes(a.sizes + (uint64_t)c * per, a.chunk_bytes, a.store) : 0;
@@ -487,11 +430,16 @@ __device__ __forceinline__ void scan_frame_bytes(const PackArgs& a, FrameBytes f
   }
 }
 
-__global__ void __launch_bounds__(256) k_zenc_scan(PackArgs a) {
-  scan_frame_bytes(a, [](const uint32_t* ss, uint64_t n, bool store) { return chunk_frame_bytes(ss, n, store); });
+template <class C>
+__global__ void __launch_bounds__(256) k_pack_scan(PackArgs a) {
+  scan_frame_bytes(a, [](const uint32_t* ss, uint64_t n, bool store) { return chunk_frame_bytes<C>(ss, n, store); });
 }
 
-__global__ void __launch_bounds__(256) k_zenc_copy(PackArgs a) {
+// grid = chunks x Blosc blocks: the header (block 0), then the block's share of a memcpyed frame, or its block table
+// entry and per stream the length and the bytes -- the shuffled source for a stored stream, else C's prefix and the
+// stream's slots, word-wise.
+template <class C>
+__global__ void __launch_bounds__(256) k_pack_copy(PackArgs a) {
   const int tid = threadIdx.x;
   const uint64_t chunk = blockIdx.x / (uint32_t)a.nblocks;
   const int b = (int)(blockIdx.x % (uint32_t)a.nblocks);
@@ -500,44 +448,52 @@ __global__ void __launch_bounds__(256) k_zenc_copy(PackArgs a) {
   uint8_t* out = a.frames + a.offsets[chunk];
   const uint64_t fbytes = (uint64_t)(a.offsets[chunk + 1] - a.offsets[chunk]);
   const bool memcpyed = fbytes >= kBloscHeader + n;
-  if (b == 0 && tid == 0) blosc_header(out, n, g.blocksize, fbytes, memcpyed);
-  const uint8_t* raw = (const uint8_t*)(a.src + chunk * (n / 2));
+  if (b == 0 && tid == 0) blosc_header(out, C::kFlags, 2, n, g.blocksize, fbytes, memcpyed);
   const uint32_t bsize = a.store ? (uint32_t)n : g.bsize(n, b);
   if (memcpyed) {
+    const uint8_t* raw = (const uint8_t*)(a.src + chunk * (n / 2));
     const uint64_t o = (uint64_t)b * g.blocksize;
     if (a.store && b > 0) return;
     for (uint32_t i = tid; i < bsize; i += 256) out[kBloscHeader + o + i] = raw[o + i];
     return;
   }
-  const uint32_t* zs_chunk = a.sizes + chunk * (uint64_t)(a.nblocks * kZPerBlosc);
+  const uint32_t* ss_chunk = a.sizes + chunk * (uint64_t)(a.nblocks * kSlotsPerBlock);
   uint64_t pos = kBloscHeader + 4ull * g.nblocks;
-  for (int k = 0; k < b; ++k) pos += 4 + blosc_stream_bytes(zs_chunk + k * kZPerBlosc, g.bsize(n, k));
-  const uint32_t* zs = zs_chunk + b * kZPerBlosc;
-  const uint32_t sb = blosc_stream_bytes(zs, bsize);
-  uint8_t* d = out + pos + 4;
-  if (tid == 0) {
-    put_le(out + kBloscHeader + 4 * b, pos, 4);
-    put_le(out + pos, sb, 4);
-  }
-  if (sb == bsize) {  // stored stream: the shuffled block
-    const uint16_t* e = a.src + chunk * (n / 2) + (uint64_t)b * (g.blocksize / 2);
-    for (uint32_t p = tid; p < bsize; p += 256) d[p] = shuffled_byte(e, bsize / 2, p);
-    return;
-  }
-  const int fh = frame_header_bytes(bsize);
-  if (tid == 0) frame_header(bsize, d);
-  d += fh;
-  for (int j = 0; j < kZPerBlosc; ++j) {
-    const uint32_t* sl = (const uint32_t*)(a.slots + ((uint64_t)blockIdx.x * kZPerBlosc + j) * kSlotStride);
-    const uint32_t m = zs[j];
-    for (uint32_t q = tid; 4 * q < m; q += 256) {
-      const uint32_t v = sl[q];
-      const uint32_t i = 4 * q;
+  for (int k = 0; k < b; ++k) pos += block_bytes<C>(g, n, k, ss_chunk + k * kSlotsPerBlock);
+  if (tid == 0) put_le(out + kBloscHeader + 4 * b, pos, 4);
+  const uint32_t* ss = ss_chunk + b * kSlotsPerBlock;
+  const uint16_t* e = a.src + chunk * (n / 2) + (uint64_t)b * (g.blocksize / 2);
+  const int ns = C::streams(g, n, b);
+  const uint32_t sn = bsize / (uint32_t)ns;
+  for (int j = 0; j < ns; ++j) {
+    uint32_t len[C::kParts];  // (read before the stores below: behind a byte store the sizes would be loaded again)
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (i + t < m) d[i + t] = (uint8_t)(v >> (8 * t));
+    for (int k = 0; k < C::kParts; ++k) len[k] = ss[j + k];
+    const uint32_t m = C::stream_bytes(ss, sn, j);
+    if (tid == 0) put_le(out + pos, m, 4);
+    uint8_t* d = out + pos + 4;
+    pos += 4 + m;
+    if (m == sn) {  // stored stream: shuffled_byte at s0 ... s0 + sn -- low bytes up to ne, high bytes from there on
+      const uint32_t s0 = (uint32_t)j * sn, ne = bsize / 2;
+      const uint32_t nlow = s0 >= ne ? 0u : (ne - s0 < sn ? ne - s0 : sn);
+      for (uint32_t p = tid; p < nlow; p += 256) d[p] = (uint8_t)(e[s0 + p] & 255u);
+      for (uint32_t p = nlow + tid; p < sn; p += 256) d[p] = (uint8_t)(e[s0 + p - ne] >> 8);
+      continue;
     }
-    d += m;
+    if (tid == 0) C::prefix(sn, d);
+    d += C::prefix_bytes(sn);
+#pragma unroll
+    for (int k = 0; k < C::kParts; ++k) {
+      const uint32_t* sl = (const uint32_t*)(a.slots + ((uint64_t)blockIdx.x * kSlotsPerBlock + j + k) * kSlotStride);
+      for (uint32_t q = tid; 4 * q < len[k]; q += 256) {
+        const uint32_t v = sl[q];
+        const uint32_t i = 4 * q;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          if (i + t < len[k]) d[i + t] = (uint8_t)(v >> (8 * t));
+      }
+      d += len[k];
+    }
   }
 }
 

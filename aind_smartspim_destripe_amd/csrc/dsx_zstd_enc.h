@@ -27,8 +27,9 @@
 //   stay literals.
 // No general matches, no offsets other than 1, no fitted FSE tables.
 //
-// Blosc container: what dsx_io.h blosc_encode writes -- version 2, 256 KiB blocks, byte shuffle, "don't split", a
-// stream as long as its block = stored; a frame not smaller than its data becomes a memcpyed frame.  Typesize 2 only.
+// Blosc container (dsx_blosc_frame.h, ZstdFrames below): what dsx_io.h blosc_encode writes -- version 2, 256 KiB
+// blocks, byte shuffle, "don't split", a stream as long as its block = stored; a frame not smaller than its data
+// becomes a memcpyed frame.  Typesize 2 only.
 //
 // Determinism: every choice below (the histogram, the sort key, the code lengths, the weight normalisation) is a
 // function of the block's bytes, so the device kernels write exactly the bytes of the host build.
@@ -38,7 +39,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "dsx_zstd_dec.h"  // DSX_ZHD; the predefined distributions and the length-code baselines of the sequences
+#include "dsx_blosc_frame.h"  // the container: Geometry, shuffled_byte, put_le, the slots, assemble_chunks_host
+#include "dsx_zstd_dec.h"     // the predefined distributions and the length-code baselines of the sequences
 
 // The single-thread planners below are used by two kernels; left to the inliner they become calls (k_zenc_block then
 // takes 88 VGPRs instead of 50).
@@ -47,13 +49,11 @@
 namespace dsx {
 namespace zenc {
 
+using namespace blosc;
+
 constexpr int kZBlock = 128 * 1024;             // zstd Block_Maximum_Size
-constexpr int kBloscBlock = 256 * 1024;         // Blosc block of the host writer
-constexpr int kBloscHeader = 16;
-constexpr int kBloscMinBuffer = 128;            // shorter buffers are stored (c-blosc MIN_BUFFERSIZE)
 constexpr int kMaxBits = 11;                    // Huffman code length limit
 constexpr int kMinHuf = 64;                     // shorter blocks: raw or RLE (4 streams need a few literals each)
-constexpr int kSlotStride = kZBlock + 16;       // one encoded zstd block: 3-byte header + <= 128 KiB
 constexpr int kTreeCap = 160;                   // Huffman tree description: 1 + <= 128 bytes (+ slack for FSE)
 constexpr int kFseLog = 6;                      // table log of the weight FSE
 enum BlockType { kRaw = 0, kRle = 1, kCompressed = 2 };  // also the literals section types of the runs mode
@@ -116,10 +116,6 @@ struct BitW {
     return flush();
   }
 };
-
-DSX_ZHD inline void put_le(uint8_t* p, uint64_t v, int n) {
-  for (int i = 0; i < n; ++i) p[i] = (uint8_t)(v >> (8 * i));
-}
 
 // literal stream k of a block of n literals covers [stream_begin(k), stream_begin(k + 1))
 DSX_ZHD inline int stream_begin(int n, int k) {
@@ -540,52 +536,23 @@ DSX_ZHD inline int frame_header(uint32_t size, uint8_t* out) {
 }
 DSX_ZHD inline int frame_header_bytes(uint32_t size) { return size < 256 ? 6 : (size < 65536 + 256 ? 7 : 9); }
 
-// Blosc geometry of one chunk of n bytes (n even, >= kBloscMinBuffer)
-struct Geometry {
-  uint32_t blocksize;  // 256 KiB or the whole chunk
-  int nblocks;         // Blosc blocks
-  DSX_ZHD Geometry(uint64_t n) {
-    blocksize = (uint32_t)(n < (uint64_t)kBloscBlock ? n : (uint64_t)kBloscBlock);
-    nblocks = blocksize ? (int)((n + blocksize - 1) / blocksize) : 0;
+constexpr int kZPerBlosc = kSlotsPerBlock;  // zstd blocks per Blosc block (at most): one slot each
+static_assert(kZPerBlosc * kZBlock == kBloscBlock && kSlotStride >= 3 + kZBlock, "a zstd block fits its slot");
+
+// The container of the zstd modes (dsx_blosc_frame.h): "don't split", so a Blosc block is one stream -- a zstd frame
+// header and the zstd blocks of its slots, stored when that is not below the block.
+struct ZstdFrames {
+  static constexpr unsigned kFlags = kBloscShuffle | kBloscDontSplit | (kInnerZstd << 5);
+  static constexpr int kParts = kZPerBlosc;
+  DSX_ZHD static int streams(const Geometry&, uint64_t, int) { return 1; }
+  DSX_ZHD static uint32_t stream_bytes(const uint32_t* zs, uint32_t bsize, int) {
+    uint32_t f = (uint32_t)frame_header_bytes(bsize);
+    for (int j = 0; j < kZPerBlosc; ++j) f += zs[j];
+    return f < bsize ? f : bsize;
   }
-  DSX_ZHD uint32_t bsize(uint64_t n, int b) const {
-    const uint64_t left = n - (uint64_t)b * blocksize;
-    return (uint32_t)(left < blocksize ? left : blocksize);
-  }
+  DSX_ZHD static int prefix(uint32_t bsize, uint8_t* out) { return frame_header(bsize, out); }
+  DSX_ZHD static int prefix_bytes(uint32_t bsize) { return frame_header_bytes(bsize); }
 };
-constexpr int kZPerBlosc = kBloscBlock / kZBlock;  // zstd blocks per Blosc block (at most)
-
-// byte p of a byte-shuffled typesize-2 Blosc block of `ne` elements starting at `e`
-DSX_ZHD inline uint8_t shuffled_byte(const uint16_t* e, uint32_t ne, uint32_t p) {
-  return p < ne ? (uint8_t)(e[p] & 255u) : (uint8_t)(e[p - ne] >> 8);
-}
-
-// Stream length of Blosc block b (zstd frame, or bsize = stored) from the encoded zstd block sizes zs[kZPerBlosc]
-DSX_ZHD inline uint32_t blosc_stream_bytes(const uint32_t* zs, uint32_t bsize) {
-  uint32_t f = (uint32_t)frame_header_bytes(bsize);
-  for (int j = 0; j < kZPerBlosc; ++j) f += zs[j];
-  return f < bsize ? f : bsize;
-}
-
-// Frame bytes of one chunk (n bytes) from the zstd block sizes of its Blosc blocks zs[nblocks][kZPerBlosc];
-// store = the chunk is stored as a whole (short chunk or clevel <= 0).
-DSX_ZHD inline uint64_t chunk_frame_bytes(const uint32_t* zs, uint64_t n, bool store) {
-  if (store) return kBloscHeader + n;
-  const Geometry g(n);
-  uint64_t f = kBloscHeader + 4ull * g.nblocks;
-  for (int b = 0; b < g.nblocks; ++b) f += 4 + blosc_stream_bytes(zs + b * kZPerBlosc, g.bsize(n, b));
-  return f < kBloscHeader + n ? f : kBloscHeader + n;  // not smaller than the data: memcpyed frame
-}
-
-DSX_ZHD inline void blosc_header(uint8_t* out, uint64_t n, uint32_t blocksize, uint64_t cbytes, bool memcpyed) {
-  out[0] = 2;
-  out[1] = 1;
-  out[2] = (uint8_t)((memcpyed ? 0x2 : 0) | 0x1 | 0x10 | (4 << 5));  // [memcpyed] | shuffle | don't split | zstd
-  out[3] = 2;
-  put_le(out + 4, n, 4);
-  put_le(out + 8, memcpyed ? (uint32_t)n : blocksize, 4);
-  put_le(out + 12, cbytes, 4);
-}
 
 // ---- host build: one zstd block, and whole chunks ------------------------------------------------------------
 // histograms, symbol count and sort of lit[0 .. n) -> h
@@ -674,52 +641,15 @@ inline void blosc_encode_host(const uint16_t* src, uint64_t n_chunks, uint64_t c
                               uint8_t* frames, int64_t* offsets, int mode = kModeLiterals) {
   HufWork* h = new HufWork;
   RunsHost* runs = mode == kModeRuns ? new RunsHost : nullptr;
-  uint8_t* slot = new uint8_t[(size_t)kSlotStride * kZPerBlosc];
-  uint8_t* lit = new uint8_t[kBloscBlock];
-  const bool store = chunk_bytes < (uint64_t)kBloscMinBuffer || clevel <= 0;
-  const Geometry g(chunk_bytes ? chunk_bytes : 1);
-  uint64_t at = 0;
-  offsets[0] = 0;
-  for (uint64_t c = 0; c < n_chunks; ++c) {
-    const uint16_t* e = src + c * (chunk_bytes / 2);
-    uint8_t* out = frames + at;
-    uint64_t pos = kBloscHeader + 4ull * g.nblocks;
-    bool memcpyed = store;
-    for (int b = 0; b < g.nblocks && !memcpyed; ++b) {
-      const uint32_t bsize = g.bsize(chunk_bytes, b);
-      for (uint32_t p = 0; p < bsize; ++p) lit[p] = shuffled_byte(e + (uint64_t)b * (g.blocksize / 2), bsize / 2, p);
-      uint32_t zs[kZPerBlosc] = {};
-      for (int j = 0; j < kZPerBlosc && (uint32_t)j * kZBlock < bsize; ++j) {
-        const uint32_t z0 = (uint32_t)j * kZBlock, z1 = bsize - z0 < (uint32_t)kZBlock ? bsize : z0 + kZBlock;
-        uint8_t* sl = slot + (size_t)j * kSlotStride;
-        zs[j] = (uint32_t)(runs ? encode_block_runs_host(*h, *runs, lit + z0, (int)(z1 - z0), z1 == bsize, sl)
-                                : encode_block_host(*h, lit + z0, (int)(z1 - z0), z1 == bsize, sl));
-      }
-      const uint32_t sb = blosc_stream_bytes(zs, bsize);
-      if (pos + 4 + sb >= kBloscHeader + chunk_bytes) { memcpyed = true; break; }
-      put_le(out + kBloscHeader + 4 * b, pos, 4);
-      put_le(out + pos, sb, 4);
-      uint8_t* d = out + pos + 4;
-      if (sb == bsize) {
-        for (uint32_t p = 0; p < bsize; ++p) d[p] = lit[p];
-      } else {
-        d += frame_header(bsize, d);
-        for (int j = 0; j < kZPerBlosc; ++j)
-          for (uint32_t i = 0; i < zs[j]; ++i) *d++ = slot[(size_t)j * kSlotStride + i];
-      }
-      pos += 4 + sb;
+  assemble_chunks_host<ZstdFrames>(src, n_chunks, chunk_bytes, clevel, frames, offsets,
+                                   [&](const uint8_t* lit, uint32_t bsize, int, uint8_t* slots, uint32_t* zs) {
+    for (int j = 0; j < kZPerBlosc && (uint32_t)j * kZBlock < bsize; ++j) {
+      const uint32_t z0 = (uint32_t)j * kZBlock, z1 = bsize - z0 < (uint32_t)kZBlock ? bsize : z0 + kZBlock;
+      uint8_t* sl = slots + (size_t)j * kSlotStride;
+      zs[j] = (uint32_t)(runs ? encode_block_runs_host(*h, *runs, lit + z0, (int)(z1 - z0), z1 == bsize, sl)
+                              : encode_block_host(*h, lit + z0, (int)(z1 - z0), z1 == bsize, sl));
     }
-    if (memcpyed) {
-      const uint8_t* raw = (const uint8_t*)e;
-      for (uint64_t i = 0; i < chunk_bytes; ++i) out[kBloscHeader + i] = raw[i];
-      pos = kBloscHeader + chunk_bytes;
-    }
-    blosc_header(out, chunk_bytes, g.blocksize, pos, memcpyed);
-    at += pos;
-    offsets[c + 1] = (int64_t)at;
-  }
-  delete[] lit;
-  delete[] slot;
+  });
   delete runs;
   delete h;
 }

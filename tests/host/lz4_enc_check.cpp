@@ -1,6 +1,7 @@
 // Host build of the Blosc-LZ4 encoder (csrc/dsx_lz4_enc.h), for tests/test_lz4_encoder_host.py:
-//   lz4_enc_check <chunks.raw> <chunk_bytes> <clevel> <frames.out> <offsets.out>
-// encodes the uint16 chunks of <chunks.raw> (back to back) and writes the packed frames and the n + 1 int64 offsets.
+//   lz4_enc_check <chunks.raw> <chunk_bytes> <clevel> <frames.out> <offsets.out> [<chunks>]
+// encodes the uint16 chunks of <chunks.raw> (back to back) and writes the packed frames and the n + 1 int64 offsets;
+// <chunks>: how many chunks of 0 bytes there are (a file does not say).
 // The frame buffer is exactly n * (chunk_bytes + 16) bytes, so a sanitizer build sees a frame that outgrows its bound.
 //   lz4_enc_check --stream <bytes.in> <block.out>
 // encodes the bytes of <bytes.in> as one stream (encode_stream_host, into a buffer of the stream's own length) and
@@ -36,7 +37,7 @@ static int one_stream(const char* in, const char* out) {
 
 int main(int argc, char** argv) {
   if (argc == 4 && !strcmp(argv[1], "--stream")) return one_stream(argv[2], argv[3]);
-  if (argc != 6) {
+  if (argc != 6 && argc != 7) {
     fprintf(stderr, "usage: %s chunks.raw chunk_bytes clevel frames.out offsets.out | --stream bytes.in block.out\n", argv[0]);
     return 2;
   }
@@ -45,7 +46,7 @@ int main(int argc, char** argv) {
   const uint64_t chunk = strtoull(argv[2], nullptr, 10);
   const int clevel = atoi(argv[3]);
   if (chunk % 2 || (chunk && raw.size() % chunk)) { fprintf(stderr, "bad chunk size\n"); return 2; }
-  const uint64_t n = chunk ? raw.size() / chunk : 0;
+  const uint64_t n = chunk ? raw.size() / chunk : (argc == 7 ? strtoull(argv[6], nullptr, 10) : 0);
   std::vector<uint8_t> frames(n * (chunk + 16));
   std::vector<int64_t> offsets(n + 1);
   std::vector<uint16_t> src(raw.size() / 2);

@@ -1,6 +1,7 @@
 // Host build of the device Blosc-zstd encoder (csrc/dsx_zstd_enc.h), for tests/test_zstd_encoder_host.py:
-//   zstd_enc_check <chunks.raw> <chunk_bytes> <clevel> <frames.out> <offsets.out>
+//   zstd_enc_check <chunks.raw> <chunk_bytes> <clevel> <frames.out> <offsets.out> [<chunks>]
 // encodes the uint16 chunks of <chunks.raw> (back to back) and writes the packed frames and the n + 1 int64 offsets.
+// <chunks>: how many chunks of 0 bytes there are (a file does not say).
 #include "../../aind_smartspim_destripe_amd/csrc/dsx_zstd_enc.h"
 
 #include <cstdio>
@@ -8,7 +9,10 @@
 #include <vector>
 
 int main(int argc, char** argv) {
-  if (argc != 6) { fprintf(stderr, "usage: %s chunks.raw chunk_bytes clevel frames.out offsets.out\n", argv[0]); return 2; }
+  if (argc != 6 && argc != 7) {
+    fprintf(stderr, "usage: %s chunks.raw chunk_bytes clevel frames.out offsets.out [chunks]\n", argv[0]);
+    return 2;
+  }
   FILE* f = fopen(argv[1], "rb");
   if (!f) return 2;
   std::vector<uint8_t> raw;
@@ -19,7 +23,7 @@ int main(int argc, char** argv) {
   const uint64_t chunk = strtoull(argv[2], nullptr, 10);
   const int clevel = atoi(argv[3]);
   if (chunk % 2 || (chunk && raw.size() % chunk)) { fprintf(stderr, "bad chunk size\n"); return 2; }
-  const uint64_t n = chunk ? raw.size() / chunk : 0;
+  const uint64_t n = chunk ? raw.size() / chunk : (argc == 7 ? strtoull(argv[6], nullptr, 10) : 0);
   std::vector<uint8_t> frames(n * (chunk + 16) + 1);
   std::vector<int64_t> offsets(n + 1);
   std::vector<uint16_t> src(raw.size() / 2 + 1);

@@ -1,7 +1,8 @@
 // Host build of the device Blosc-zstd encoder with its mode (csrc/dsx_zstd_enc.h), for
 // tests/test_zstd_encoder_runs_host.py:
-//   zstd_enc_runs_check <chunks.raw> <chunk_bytes> <clevel> <mode> <frames.out> <offsets.out>
+//   zstd_enc_runs_check <chunks.raw> <chunk_bytes> <clevel> <mode> <frames.out> <offsets.out> [<chunks>]
 // encodes the uint16 chunks of <chunks.raw> (back to back) and writes the packed frames and the n + 1 int64 offsets.
+// <chunks>: how many chunks of 0 bytes there are (a file does not say).
 //   zstd_enc_runs_check --codes
 // checks the length-code formulas of the encoder against the baselines of the decoder, for every length of a block.
 #include "../../aind_smartspim_destripe_amd/csrc/dsx_zstd_enc.h"
@@ -33,7 +34,7 @@ static int check_codes() {
 
 int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "--codes")) return check_codes();
-  if (argc != 7) {
+  if (argc != 7 && argc != 8) {
     fprintf(stderr, "usage: %s chunks.raw chunk_bytes clevel mode frames.out offsets.out | --codes\n", argv[0]);
     return 2;
   }
@@ -47,7 +48,7 @@ int main(int argc, char** argv) {
   const uint64_t chunk = strtoull(argv[2], nullptr, 10);
   const int clevel = atoi(argv[3]), mode = atoi(argv[4]);
   if (chunk % 2 || (chunk && raw.size() % chunk)) { fprintf(stderr, "bad chunk size\n"); return 2; }
-  const uint64_t n = chunk ? raw.size() / chunk : 0;
+  const uint64_t n = chunk ? raw.size() / chunk : (argc == 8 ? strtoull(argv[7], nullptr, 10) : 0);
   std::vector<uint8_t> frames(n * (chunk + 16) + 1);
   std::vector<int64_t> offsets(n + 1);
   std::vector<uint16_t> src(raw.size() / 2 + 1);
