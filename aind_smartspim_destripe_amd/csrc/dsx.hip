@@ -299,7 +299,15 @@ hipError_t launch_rowfilter_wide(const dsx::RowArgs& a, int npairs, int nb, hipS
   return hipGetLastError();
 }
 
+// the instantiation of a compile-time plan: its template arguments are its row of dsx::kRowPlans
+template <int ID>
+hipError_t launch_rowfilter_plan(const DsxTuning& t, const dsx::RowArgs& a, int npairs, int nb, hipStream_t s) {
+  constexpr dsx::RowPlan p = dsx::row_plan(ID);
+  return launch_rowfilter<p.cpl, p.gf, p.nt, p.halo, ID>(t, a, npairs, nb, s);
+}
+
 // the k_rowfilter instantiation of a row's class (dsx::classify_row)
+// (the compiler emits the kernels in the order in which they are named here: keep it when a plan is added)
 hipError_t dispatch_rowfilter(const DsxTuning& t, const dsx::RowArgs& a, int npairs, int nb, hipStream_t s) {
   const dsx::RowClass c = dsx::classify_row(a.M, a.w, a.K, a.npass, a.radix);
   if (c.wide) return launch_rowfilter_wide(a, npairs, nb, s);
@@ -309,33 +317,35 @@ hipError_t dispatch_rowfilter(const DsxTuning& t, const dsx::RowArgs& a, int npa
     case 6: return launch_rowfilter<6>(t, a, npairs, nb, s);
     case 10: return launch_rowfilter<10>(t, a, npairs, nb, s);
     case 18:
-      if (c.plan == 1) return launch_rowfilter<18, 4, 1, 0, 1>(t, a, npairs, nb, s);
+      if (c.plan == 1) return launch_rowfilter_plan<1>(t, a, npairs, nb, s);
       if (c.gf == 4) return launch_rowfilter<18, 4, 1, 0>(t, a, npairs, nb, s);
-      if (c.plan == 2) return launch_rowfilter<18, 2, 1, 1, 2>(t, a, npairs, nb, s);
+      if (c.plan == 2) return launch_rowfilter_plan<2>(t, a, npairs, nb, s);
       if (c.gf == 2) return launch_rowfilter<18, 2, 1, 1>(t, a, npairs, nb, s);
-      if (c.plan == 5) return launch_rowfilter<18, 1, 4, 1, 5>(t, a, npairs, nb, s);
-      if (c.plan == 6) return launch_rowfilter<18, 1, 4, 1, 6>(t, a, npairs, nb, s);
+      if (c.plan == 5) return launch_rowfilter_plan<5>(t, a, npairs, nb, s);
+      if (c.plan == 6) return launch_rowfilter_plan<6>(t, a, npairs, nb, s);
       return launch_rowfilter<18>(t, a, npairs, nb, s);
     default:
-      if (c.plan == 3) return launch_rowfilter<36, 3, 4, 1, 3>(t, a, npairs, nb, s);
-      if (c.plan == 4) return launch_rowfilter<36, 3, 3, 1, 4>(t, a, npairs, nb, s);
+      if (c.plan == 3) return launch_rowfilter_plan<3>(t, a, npairs, nb, s);
+      if (c.plan == 4) return launch_rowfilter_plan<4>(t, a, npairs, nb, s);
       return launch_rowfilter<36>(t, a, npairs, nb, s);
   }
 }
 
-template <int CPL, int GF, int NT, int HALO, int PLAN>
-hipError_t launch_rowfinal_t(const dsx::RowFinalArgs& a, int nb, hipStream_t s) {
-  if (hipError_t e = raise_lds_limit<dsx::k_rowfinal<CPL, GF, NT, HALO, PLAN>>()) return e;
-  const dsx::RowLaunch g = dsx::rowfinal_launch(a.r.M, a.f.hout, DSX_RF_XCD != 0);
-  hipLaunchKernelGGL((dsx::k_rowfinal<CPL, GF, NT, HALO, PLAN>), dim3(g.grid_x, nb), dim3(64 * g.wpb), g.lds, s, a);
+template <int ID>
+hipError_t launch_rowfinal_plan(const dsx::RowFinalArgs& a, int nb, hipStream_t s) {
+  constexpr dsx::RowPlan p = dsx::row_plan(ID);
+  constexpr auto kernel = dsx::k_rowfinal<p.cpl, p.gf, p.nt, p.halo, ID>;
+  if (hipError_t e = raise_lds_limit<kernel>()) return e;
+  const dsx::RowLaunch g = dsx::rowfinal_launch(a.r.M, a.f.hout);
+  hipLaunchKernelGGL(kernel, dim3(g.grid_x, nb), dim3(64 * g.wpb), g.lds, s, a);
   return hipGetLastError();
 }
 
 // plan: dsx::rowfinal_plan of the part (the plan id the classifier gives level 1)
 hipError_t launch_rowfinal(int plan, const dsx::RowFinalArgs& a, int nb, hipStream_t s) {
-  if (plan == 1) return launch_rowfinal_t<18, 4, 1, 0, 1>(a, nb, s);
-  if (plan == 3) return launch_rowfinal_t<36, 3, 4, 1, 3>(a, nb, s);
-  if (plan == 4) return launch_rowfinal_t<36, 3, 3, 1, 4>(a, nb, s);
+  if (plan == 1) return launch_rowfinal_plan<1>(a, nb, s);
+  if (plan == 3) return launch_rowfinal_plan<3>(a, nb, s);
+  if (plan == 4) return launch_rowfinal_plan<4>(a, nb, s);
   return hipErrorInvalidValue;
 }
 

@@ -110,36 +110,51 @@ inline void read_tuning(DsxTuning& t) {
 // ---- one row-kernel classifier ---------------------------------------------------------------------------------------
 // What a row of a level runs: k_rowfilter_wide, or the k_rowfilter<CPL, GF, NT, HALO, PLAN> instantiation.  gf / nt are
 // the slot structure of the row (full 256-value groups, 64-value tail slots), halo says whether the plan embeds the row
-// (K > 0), plan the compile-time pass list (StaticFft id): the wide levels of 2048-, 2000- and 1800-wide planes have
+// (K > 0), plan the compile-time pass list (a row of kRowPlans): the wide levels of 2048-, 2000- and 1800-wide planes have
 // instantiations with all of it as compile-time constants.  gf = nt = halo = -1, plan = 0: the generic body of the class.
 struct RowClass {
   bool wide;  // k_rowfilter_wide: rows longer than one wave holds
   int cpl;    // 2, 4, 6, 10, 18, 36
   int gf, nt, halo;
-  int plan;   // 1: 1026 = 19.9.6   2: 1071 = 17.9.7   3: 2048 = 16.16.8   4: 1815 = 15.11.11   5: 1024 = 16.8.8   6: 960 = 15.8.8
+  int plan;   // id of a kRowPlans row, or 0
 };
+
+// The compile-time plans, each stated once: the classifier matches a row against them, StaticFft<id> (dsx_kernels.h) runs
+// the passes, and the launches of dsx.hip take the template arguments of k_rowfilter / k_rowfinal from here.
+struct RowPlan {
+  int M, radix[3];    // transform length = radix[0] * radix[1] * radix[2], passes in this order
+  int cpl;            // cpl_class(M)
+  int gf, nt, halo;   // the row it takes: full 256-value groups, 64-value tail slots, embedded (K > 0) or direct
+  bool swz;           // power-of-two passes scatter at power-of-two strides: bank-swizzled addressing (dsx_fft_core.h: dsx_idx_swz)
+};
+constexpr int kRowPlanCount = 6;
+constexpr RowPlan kRowPlans[kRowPlanCount] = {
+    {1026, {19, 9, 6}, 18, 4, 1, 0, false},    // 1: level 1 of a 2048-wide plane, direct
+    {1071, {17, 9, 7}, 18, 2, 1, 1, false},    // 2: level 2 of a 2048-wide plane: 515 values embedded in 1071
+    {2048, {16, 16, 8}, 36, 3, 4, 1, true},    // 3: level 1 of a 2000-wide plane (the production tile): 1002 in 2048
+    {1815, {15, 11, 11}, 36, 3, 3, 1, false},  // 4: level 1 of an 1800-wide plane: 902 in 1815
+    {1024, {16, 8, 8}, 18, 1, 4, 1, true},     // 5: level 2 of a 2000-wide plane: 503 in 1024
+    {960, {15, 8, 8}, 18, 1, 4, 1, false},     // 6: level 2 of an 1800-wide plane: 453 in 960
+};
+constexpr const RowPlan& row_plan(int id) { return kRowPlans[id - 1]; }
 
 inline RowClass classify_row(int M, int w, int K, int npass, const int* radix) {
   RowClass c = {false, 0, -1, -1, -1, 0};
   const int cpl = (M + 63) / 64;
   if (cpl > 36) { c.wide = true; return c; }
   c.cpl = cpl_class(M);
-  const int gf = w >> 8, nt = (w - (gf << 8) + 63) >> 6;
-  auto plan_is = [&](int m, int r0, int r1, int r2) {
-    return M == m && npass == 3 && radix[0] == r0 && radix[1] == r1 && radix[2] == r2;
-  };
-  auto set = [&](int halo, int plan) { c.gf = gf; c.nt = nt; c.halo = halo; c.plan = plan; };
-  if (c.cpl == 18) {
-    if (gf == 4 && nt == 1 && K == 0) set(0, plan_is(1026, 19, 9, 6) ? 1 : 0);
-    else if (gf == 2 && nt == 1 && K > 0) set(1, plan_is(1071, 17, 9, 7) ? 2 : 0);
-    else if (gf == 1 && nt == 4 && K > 0) {
-      if (plan_is(1024, 16, 8, 8)) set(1, 5);
-      else if (plan_is(960, 15, 8, 8)) set(1, 6);
+  const int gf = w >> 8, nt = (w - (gf << 8) + 63) >> 6, halo = K > 0 ? 1 : 0;
+  auto set = [&](int plan) { c.gf = gf; c.nt = nt; c.halo = halo; c.plan = plan; };
+  for (int id = 1; id <= kRowPlanCount; ++id) {
+    const RowPlan& p = row_plan(id);
+    if (M == p.M && npass == 3 && radix[0] == p.radix[0] && radix[1] == p.radix[1] && radix[2] == p.radix[2] &&
+        c.cpl == p.cpl && gf == p.gf && nt == p.nt && halo == p.halo) {
+      set(id);
+      return c;
     }
-  } else if (c.cpl == 36 && K > 0 && gf == 3) {
-    if (nt == 4 && plan_is(2048, 16, 16, 8)) set(1, 3);
-    else if (nt == 3 && plan_is(1815, 15, 11, 11)) set(1, 4);
   }
+  // two row shapes of the 18-value class have an instantiation with any pass list (plan 0)
+  if (c.cpl == 18 && ((gf == 4 && nt == 1 && halo == 0) || (gf == 2 && nt == 1 && halo == 1))) set(0);
   return c;
 }
 inline RowClass classify_row(const LevelPlan& lp) { return classify_row(lp.M, lp.w, lp.K, lp.npass, lp.radix); }
@@ -387,11 +402,9 @@ inline RowLaunch rowfilter_launch(const DsxTuning& t, int cpl, int M, int npairs
 }
 
 // k_rowfinal: kRfWaves row pairs per block, of which the last is the first of the next block
-inline RowLaunch rowfinal_launch(int M, int hout, bool xcd_runs = false) {
+inline RowLaunch rowfinal_launch(int M, int hout) {
   const int np = (hout + 1) / 2;
-  int nblk = (np + kRfRows - 1) / kRfRows;
-  if (xcd_runs) nblk = (nblk + 7) / 8 * 8;  // the kernel deals runs of consecutive blocks to the 8 compute dies
-  return {kRfWaves, (size_t)M * (kRfWaves + 1) * kC32Bytes, nblk};
+  return {kRfWaves, (size_t)M * (kRfWaves + 1) * kC32Bytes, (np + kRfRows - 1) / kRfRows};
 }
 
 // Levels whose row filters all fit the CPL = 6 class, in ONE launch (k_rowfilter_multi): blk_end[i] = blocks of levels

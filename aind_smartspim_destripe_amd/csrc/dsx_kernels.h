@@ -21,51 +21,6 @@
 #include "dsx_chain.h"  // launch-geometry constants (kMarchCols, kRowMaxWaves, kRfWaves, ...)
 #include "dsx_fft_core.h"
 
-// ---- build-time switches (defaults = the product; tools/build_variant.sh builds A/B variants with -D...) ----------
-// Streaming (non-temporal) accesses for intermediates that the next kernel reads only after hundreds of MB of
-// other traffic (da_1 out of the forward kernel, cH into the histogram, Delta out of the row filter).
-// (Not for the Delta_1 loads of the final kernel: +2 % there.)
-#ifndef DSX_NT
-#define DSX_NT 1
-#endif
-#ifndef DSX_MEDIAN_BALLOT
-#define DSX_MEDIAN_BALLOT 1
-#endif
-#ifndef DSX_FWD_STEADY
-#define DSX_FWD_STEADY 1  // bit 0: steady-state row loop in interior strips, bit 1: in edge strips too (spills)
-#endif
-#ifndef DSX_RF_XCD
-// k_rowfinal: blocks that share rows on the same compute die.  Measured and left OFF: 1.6 MB per plane less HBM traffic
-// (25.0 -> 23.4), but 4 % SLOWER (61.9 k against 64.5 k planes/s, profiles/r3_fused_rowfinal_ab.txt): with runs of blocks
-// per die the eight dies stream eight distant regions of a plane instead of one front.
-#define DSX_RF_XCD 0
-#endif
-#ifndef DSX_INV_MINW
-#define DSX_INV_MINW 1  // waves per SIMD the fused uint16 final kernel is compiled for
-#endif
-#ifndef DSX_FWD_PRUNE
-// level-1 row filter of 2048-wide planes: forward passes in the order 6, 9, 19 with the last (radix-19) pass pruned to the
-// output pairs inside the low-pass band (StaticFft<1>::run_forward); 0 = the order 19, 9, 6, every bin computed
-#define DSX_FWD_PRUNE 1
-#endif
-#ifndef DSX_SWZ
-// bank-swizzled LDS addressing (dsx_fft_core.h: dsx_idx_swz) for the power-of-two row-filter plans 2 048 = 16 * 16 * 8 and
-// 1 024 = 16 * 8 * 8 (levels 1 and 2 of 2000-wide planes); 0 = plain addressing, 2 = the swizzle through the generic index
-// policy instead of the written-out addressing (A/B builds)
-#define DSX_SWZ 1
-#endif
-#ifndef DSX_FWD_MINW
-#define DSX_FWD_MINW 4  // waves per SIMD the fused uint16 forward kernel is compiled for (register cap 128)
-#endif
-#ifndef DSX_RF_STEADY
-// k_rowfinal, synthesis phase: 1 = the row loop is straight-line with respect to vector memory (no load or store under a
-// condition, the level-2 step at a fixed place, exits between row pairs only), so that the compiler counts its waits and
-// the pixel rows it prefetches stay in flight; 0 = the loop of three predicated steps, which drained the memory queue in
-// every step (rowfinal_synth, DESIGN.md section 4.5, profiles/march_waits_before.txt)
-#define DSX_RF_STEADY 1
-#endif
-
-
 // Timing-only switches (DSX_ABLATE bits: kernels skip a phase or a store path and return WRONG pixels) exist in
 // -DDSX_DIAG builds only (tools/build_variant.sh); in the product build the tests fold to `false`.
 #ifdef DSX_DIAG
@@ -106,7 +61,10 @@ typedef unsigned dsx_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t dsx_rsrc(const void* p) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, -1, 0x00020000);
 }
-constexpr int kBufNT = 2;  // aux bits of a streaming (non-temporal) buffer access on gfx94x / gfx950
+// aux bits of a streaming (non-temporal) buffer access on gfx94x / gfx950.  Streaming accesses are for intermediates that
+// the next kernel reads only after hundreds of MB of other traffic (da_1 out of the forward kernel, cH into the
+// histogram, Delta out of the row filter).  (Not for the Delta_1 loads of the final kernel: +2 % there.)
+constexpr int kBufNT = 2;
 // The same over [p, p + bytes): a load at or past `bytes` returns zeros and a store there is dropped by the address unit, so
 // a wave can issue a memory instruction unconditionally and discard it per lane through the offset it passes.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t dsx_rsrc_bounded(const void* p, unsigned bytes) {
@@ -119,22 +77,11 @@ constexpr unsigned kBufDiscard = 0x80000000u;
 // Packed multiply-add with a FIXED evaluation order.  (a * b + c * d + e * f written with operators leaves
 // the choice of which product is rounded first to the compiler, and two inlined copies of one expression --
 // a segment's prologue and its steady-state loop -- did pick differently: results then depended on where
-// the row segments of a launch start, i.e. on the batch size.)
-#if DSX_SCALAR_FMA
+// the row segments of a launch start, i.e. on the batch size.)  Each half is a scalar v_fma_f32: a v_pk_fma_f32 with three
+// register operands costs more of a SIMD than the two of them (__graft_entry__.build).
 __device__ __forceinline__ dsx_f2 pk_fma(dsx_f2 a, dsx_f2 b, dsx_f2 c) { return dsx_f2{fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y)}; }
 __device__ __forceinline__ dsx_f2 pk_fma(dsx_f2 a, float b, dsx_f2 c) { return dsx_f2{fmaf(a.x, b, c.x), fmaf(a.y, b, c.y)}; }
 __device__ __forceinline__ dsx_f2 pk_fma(float a, dsx_f2 b, dsx_f2 c) { return dsx_f2{fmaf(a, b.x, c.x), fmaf(a, b.y, c.y)}; }
-#else
-__device__ __forceinline__ dsx_f2 pk_fma(dsx_f2 a, dsx_f2 b, dsx_f2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ dsx_f2 pk_fma(dsx_f2 a, float b, dsx_f2 c) {
-  const dsx_f2 bb = {b, b};
-  return __builtin_elementwise_fma(a, bb, c);
-}
-__device__ __forceinline__ dsx_f2 pk_fma(float a, dsx_f2 b, dsx_f2 c) {
-  const dsx_f2 aa = {a, a};
-  return __builtin_elementwise_fma(aa, b, c);
-}
-#endif
 
 struct PlaneStats {
   double sum_fg;               // sum of pixels in the foreground class (>= cut-off)
@@ -256,18 +203,6 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-#ifndef DSX_SCALAR_FMA
-#define DSX_SCALAR_FMA 1  // the multiply-adds of pk_fma / the complex helpers as scalar v_fma_f32 (see __graft_entry__.build)
-#endif
-#ifndef DSX_FWD_PAIR
-#define DSX_FWD_PAIR 1  // interior strips of the fused uint16 forward kernel load pixel rows by lane pairs (16 bytes per lane)
-#endif
-#ifndef DSX_FWD_SPLIT
-#define DSX_FWD_SPLIT 1
-#endif
-#ifndef DSX_DPP_X
-#define DSX_DPP_X 1
-#endif
 // Value of the same register in lane + 1 (DPP wave_shl:1); lane 63 reads 0.  All 64 lanes must be active.
 __device__ __forceinline__ float lane_above(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, true));
@@ -289,8 +224,8 @@ __global__ __launch_bounds__(256) void k_zero3(uint4* p0, int n0, uint4* p1, int
 //
 // One WAVE owns a strip of 256 input columns (4 per lane, one 8/16-byte load per lane and row) and
 // streams down the rows with a 6-row sliding window in registers, so the column (axis-0) filter
-// never touches LDS; only the freshly filtered row pair (a0, d0) goes through a 2 KiB per-wave LDS
-// row to be low-passed along the row (axis 1).  No block barriers, no input halo re-reads along y.
+// never touches LDS, and the freshly filtered row pair (a0, d0) is low-passed along the row (axis 1)
+// with the neighbouring lane's columns over the DPP crossbar.  No block barriers, no input halo re-reads along y.
 // Strips advance by 252 input columns = 126 coefficient columns.
 // ================================================================================================
 struct Fwd1Args {
@@ -320,7 +255,6 @@ struct Fwd1Args {
 
 constexpr int kRingRows = 8;                     // aa_1 rows a wave keeps in LDS (6 are needed)
 constexpr int kRingPitch = 128;                  // floats per ring row (126 columns + margin positions)
-constexpr int kX2Pitch = 136;                    // (lo, hi) pairs of the level-2 row exchange (reads run to 2*63+5)
 
 template <int IN_KIND>
 struct MarchStats {
@@ -554,10 +488,8 @@ __device__ __forceinline__ FuseGeom fuse_geom(const Fwd1Args& a, int strip) {
 // mirrored column groups, no margin columns to write, every level-1 / level-2 column of the wave exists, and the
 // ownership ranges start and end on even columns.  The row loop of such a strip has no per-lane branches left.
 template <int IN_KIND, bool FAST, bool FUSE, bool EDGE = true>
-__device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)[2][2][kMarchCols / 2],
-                                               float (*s_ring)[kRingRows][kRingPitch], float2 (*s_x2)[kX2Pitch],
-                                               int lane, int wave, int strip, int seg, int plane,
-                                               const MarchCol& col, bool any_rev_in) {
+__device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_ring)[kRingRows][kRingPitch], int lane, int wave,
+                                               int strip, int seg, int plane, const MarchCol& col, bool any_rev_in) {
   const bool any_rev = EDGE && any_rev_in;
   constexpr float LO[6] = DSX_DEC_LO;
   constexpr float HI[6] = DSX_DEC_HI;
@@ -595,7 +527,7 @@ __device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)
   // (the pair's 8 columns) of raw row g, the odd lane those of row g + 1, and the halves are exchanged over the DPP
   // crossbar when the group is consumed: half as many load instructions, and 16-byte accesses (8-byte ones top out at
   // 3.9 TB/s on this chip, which is where this kernel ran alone; tools/bw_access_width.py, inv_march_body<.., PAIR>)
-  constexpr bool PAIRLD = DSX_FWD_PAIR && FUSE && FAST && !EDGE && IN_KIND == 0;
+  constexpr bool PAIRLD = FUSE && FAST && !EDGE && IN_KIND == 0;
   const bool odd_lane = (lane & 1) != 0;
   const int oddm = odd_lane_mask(lane);
   const unsigned pitch_b = (unsigned)a.ldin * 2u;
@@ -622,8 +554,6 @@ __device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)
   float* da = a.ws + plane * a.ws_plane_stride + a.da_off;
   // fused kernel: coefficient rows are stored through buffer descriptors (row offset in an SGPR)
   const __amdgpu_buffer_rsrc_t rs_da = dsx_rsrc(da), rs_aa2 = dsx_rsrc(aa2), rs_da2 = dsx_rsrc(da2);
-  float2* sE[2] = {(float2*)s_row[wave][0][0], (float2*)s_row[wave][1][0]};
-  float2* sO[2] = {(float2*)s_row[wave][0][1], (float2*)s_row[wave][1][1]};
 
   MarchStats<IN_KIND> st;
   float win[6][4];  // sliding window: rows 2i-4 .. 2i+1 of this lane's 4 columns
@@ -662,9 +592,7 @@ __device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)
   auto l2_step = [&](auto steady_c, int i2) {
     constexpr bool STEADY = decltype(steady_c)::value;
     dsx_f2 c[6];
-#if DSX_DPP_X
     if (EDGE) wave_sync();  // edge strips: the ring's mirrored columns were written by other lanes
-#endif
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       int r = 2 * i2 - 4 + k;
@@ -680,26 +608,15 @@ __device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)
     }
     dsx_f4 pk = {lo2.x, hi2.x, lo2.y, hi2.y};  // (lo, hi) per column: the row pass filters both at once
     // axis 1, low-pass only: out[o2 + t] = sum_k LO[k] x[2 t + 5 - k] (local columns), t = lane
-#if DSX_DPP_X
     const dsx_f4 p0 = pk;  // columns 2t, 2t+1 are the lane's own; 2t+2.. come from lanes t+1, t+2 (DPP)
     const dsx_f4 p1 = {lane_above(p0.x), lane_above(p0.y), lane_above(p0.z), lane_above(p0.w)};
     const dsx_f4 p2 = {lane_above(p1.x), lane_above(p1.y), lane_above(p1.z), lane_above(p1.w)};
-#else
-    *(dsx_f4*)&s_x2[wave][jj0] = pk;
-    wave_sync();
-    const dsx_f4 p0 = *(const dsx_f4*)&s_x2[wave][2 * lane];
-    const dsx_f4 p1 = *(const dsx_f4*)&s_x2[wave][2 * lane + 2];
-    const dsx_f4 p2 = *(const dsx_f4*)&s_x2[wave][2 * lane + 4];
-#endif
     dsx_f2 v = LO[5] * p0.xy;
     v = pk_fma(LO[4], p0.zw, v);
     v = pk_fma(LO[3], p1.xy, v);
     v = pk_fma(LO[2], p1.zw, v);
     v = pk_fma(LO[1], p2.xy, v);
     v = pk_fma(LO[0], p2.zw, v);
-#if !DSX_DPP_X
-    wave_sync();
-#endif
     const float q = v.y * v.y;
     // (running extrema as bare v_min / v_max: fminf / fmaxf quiet a possible signalling NaN of every operand first, one
     //  more 5-cycle instruction each -- a NaN coefficient means a flagged plane, PlaneStats::flags)
@@ -737,7 +654,6 @@ __device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)
       lo[e] = fmaf(LOV[4], r1[e], lo[e]); hi[e] = fmaf(HIV[4], r1[e], hi[e]);
       lo[e] = fmaf(LOV[5], r0[e], lo[e]); hi[e] = fmaf(HIV[5], r0[e], hi[e]);
     }
-#if DSX_DPP_X
     // axis 1, low-pass only.  A lane's two outputs need its own four columns and the first four of the lane
     // above: those come over the DPP crossbar (wave_shl:1, lane L reads lane L + 1) -- no LDS round trip.
     // out[jj] = LO0 x[2jj+5] + LO1 x[2jj+4] + ... + LO5 x[2jj], x = (lo[0..3], next lane's lo[0..3])
@@ -771,31 +687,6 @@ __device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)
       v1h = fmaf(LO[4], hi[3], v1h); v1h = fmaf(LO[5], hi[2], v1h);
       res[0][0] = v0l; res[0][1] = v1l; res[1][0] = v0h; res[1][1] = v1h;
     }
-#else
-    sE[0][lane] = make_float2(lo[0], lo[2]);
-    sO[0][lane] = make_float2(lo[1], lo[3]);
-    sE[1][lane] = make_float2(hi[0], hi[2]);
-    sO[1][lane] = make_float2(hi[1], hi[3]);
-    wave_sync();
-    // axis 1, low-pass only: out[jj] = LO0 O[jj+2] + LO1 E[jj+2] + LO2 O[jj+1] + LO3 E[jj+1] + LO4 O[jj] + LO5 E[jj]
-    float res[2][2];
-    if (out_lane) {
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const float2 e01 = sE[b][lane], e23 = sE[b][lane + 1];
-        const float2 o01 = sO[b][lane], o23 = sO[b][lane + 1];
-        float v0 = LO[0] * o23.x;
-        v0 = fmaf(LO[1], e23.x, v0); v0 = fmaf(LO[2], o01.y, v0); v0 = fmaf(LO[3], e01.y, v0);
-        v0 = fmaf(LO[4], o01.x, v0); v0 = fmaf(LO[5], e01.x, v0);
-        float v1 = LO[0] * o23.y;
-        v1 = fmaf(LO[1], e23.y, v1); v1 = fmaf(LO[2], o23.x, v1); v1 = fmaf(LO[3], e23.x, v1);
-        v1 = fmaf(LO[4], o01.y, v1); v1 = fmaf(LO[5], e01.y, v1);
-        res[b][0] = v0;
-        res[b][1] = v1;
-      }
-    }
-    wave_sync();
-#endif
     if (FUSE) {
       if (out_lane) {
         const int j = jl;
@@ -803,13 +694,12 @@ __device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)
         if (own_row && !DSX_ABL(a, 16 | 256)) {  // (256: diagnosis, only the da_1 stores are left out)  da_1: owned rows and columns only (overlap rows / columns belong to a neighbour)
           // (64: diagnosis, with the 512-byte strip pieces above: a row pitch of 33 cache lines -- no partial line at all)
           const unsigned soff = DSX_ABL(a, 64) ? (unsigned)i * 4224u : (unsigned)(i * a.ld) * 4u;
-          constexpr int aux = DSX_NT ? kBufNT : 0;
           if (c_s0 && c_s1) {
             const dsx_u32x2 dv = {__float_as_uint(res[1][0]), __float_as_uint(res[1][1])};
-            __builtin_amdgcn_raw_buffer_store_b64(dv, rs_da, off_da, soff, aux);
+            __builtin_amdgcn_raw_buffer_store_b64(dv, rs_da, off_da, soff, kBufNT);
           } else {
-            if (c_s0) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(res[1][0]), rs_da, off_da, soff, aux);
-            if (c_s1) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(res[1][1]), rs_da, off_da + 4u, soff, aux);
+            if (c_s0) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(res[1][0]), rs_da, off_da, soff, kBufNT);
+            if (c_s1) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(res[1][1]), rs_da, off_da + 4u, soff, kBufNT);
           }
         }
         qmin = min_no_nan(qmin, min_no_nan(c_v0 ? q0 : __builtin_huge_valf(), c_v1 ? q1 : __builtin_huge_valf()));
@@ -898,7 +788,7 @@ __device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)
         nxt[d][r] = march_issue<IN_KIND, FAST>(ms, a.ldin, a.H, 2 * (i_begin + 3 * d) + r, col);
     }
   }
-  // One group of three output rows.  The steady groups run in a loop of their own (DSX_FWD_SPLIT): with both kinds of
+  // One group of three output rows.  The steady groups run in a loop of their own: with both kinds of
   // group in one loop body the two paths merge every iteration, and the compiler reconciles their register assignments
   // with ~70 copies per group (the window, the prefetched rows, the level-2 state) -- a sixth of the loop's vector work.
   auto group = [&](auto steady_c, int i) {
@@ -945,8 +835,7 @@ __device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)
       if (i + 2 < i_end) step(std::false_type(), i + 2, cur[4], cur[5], win[4], win[5], win[0], win[1], win[2], win[3]);
     }
   };
-  const bool steady_on = FUSE && DSX_FWD_STEADY && (EDGE ? (DSX_FWD_STEADY & 2) != 0 : true);
-#if DSX_FWD_SPLIT
+  const bool steady_on = FUSE && !EDGE;  // interior strips only: in edge strips the steady row loop spills
   {
     // groups start at i_begin + 3 g; the steady ones are those with steady_lo <= i and i + 3 <= steady_hi: a run
     int i = i_begin;
@@ -964,12 +853,6 @@ __device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)
         for (; i < run_hi; i += 3) group(std::true_type(), i);
     }
   }
-#else
-  for (int i = i_begin; i < i_end; i += 3) {
-    if (steady_on && i >= steady_lo && i + 3 <= steady_hi) group(std::true_type(), i);  // wave-uniform
-    else group(std::false_type(), i);
-  }
-#endif
 
   qmin = wave_min_f32(qmin);
   qmax = wave_max_f32(qmax);
@@ -1012,13 +895,12 @@ __device__ __forceinline__ void fwd_march_body(const Fwd1Args& a, float (*s_row)
   }
 }
 
+constexpr int kFwdMinWaves = 4;  // waves per SIMD the fused uint16 forward kernel is compiled for (register cap 128)
 // IN_KIND: 0 = uint16 pixels (log + statistic fused), 1 = float32 pixels (same), 2 = float32 aa_{l-1}
 // WPB: waves per block (consecutive strips of one row segment: a block reads WPB x 512 contiguous bytes per row)
 template <int IN_KIND, bool FUSE = false, int WPB = 4>
-__global__ __launch_bounds__(64 * WPB, (FUSE && IN_KIND == 0) ? DSX_FWD_MINW : 1) void k_fwd_march(Fwd1Args a) {
-  __shared__ __attribute__((aligned(16))) float s_row[WPB][2][2][kMarchCols / 2];  // [wave][lo|hi][parity][col/2]
+__global__ __launch_bounds__(64 * WPB, (FUSE && IN_KIND == 0) ? kFwdMinWaves : 1) void k_fwd_march(Fwd1Args a) {
   __shared__ __attribute__((aligned(16))) float s_ring[FUSE ? WPB : 1][kRingRows][FUSE ? kRingPitch : 4];
-  __shared__ __attribute__((aligned(16))) float2 s_x2[FUSE ? WPB : 1][FUSE ? kX2Pitch : 2];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: keeps row math on the SALU
   const int item = blockIdx.x * WPB + wave;
@@ -1038,20 +920,17 @@ __global__ __launch_bounds__(64 * WPB, (FUSE && IN_KIND == 0) ? DSX_FWD_MINW : 1
     // interior strip (wave-uniform): see fwd_march_body, EDGE = false
     const bool interior = strip > 0 && strip < a.nstrips - 1 && fg.j0 > 0 && fg.j0 + kMarchOut + 2 < a.w - 8 &&
                           fg.o2 + kFuseOut < a.w2 - 8 && __all(col.vec && !col.rev && !col.dead) != 0;
-    if (interior)
-      fwd_march_body<IN_KIND, true, true, false>(a, s_row, (float (*)[kRingRows][kRingPitch])s_ring,
-                                                 (float2 (*)[kX2Pitch])s_x2, lane, wave, strip, seg, plane, col, false);
-    else
-      fwd_march_body<IN_KIND, true, true, true>(a, s_row, (float (*)[kRingRows][kRingPitch])s_ring,
-                                                (float2 (*)[kX2Pitch])s_x2, lane, wave, strip, seg, plane, col, any_rev);
+    float (*ring)[kRingRows][kRingPitch] = (float (*)[kRingRows][kRingPitch])s_ring;
+    if (interior) fwd_march_body<IN_KIND, true, true, false>(a, ring, lane, wave, strip, seg, plane, col, false);
+    else fwd_march_body<IN_KIND, true, true, true>(a, ring, lane, wave, strip, seg, plane, col, any_rev);
     return;
   }
   // lane 0 re-reads the last 4 columns of the previous strip and does not account them
   const MarchCol col = march_col(2 * kMarchOut * strip - 4 + 4 * lane, a.W, a.ldin, a.w, lane >= 1, IN_KIND == 2);
   const bool all_vec = __all(col.vec || (col.dead && a.W >= 4 && (a.ldin & 3) == 0)) != 0;
   const bool any_rev = __any(col.rev) != 0;
-  if (all_vec) fwd_march_body<IN_KIND, true, false>(a, s_row, nullptr, nullptr, lane, wave, strip, seg, plane, col, any_rev);
-  else fwd_march_body<IN_KIND, false, false>(a, s_row, nullptr, nullptr, lane, wave, strip, seg, plane, col, any_rev);
+  if (all_vec) fwd_march_body<IN_KIND, true, false>(a, nullptr, lane, wave, strip, seg, plane, col, any_rev);
+  else fwd_march_body<IN_KIND, false, false>(a, nullptr, lane, wave, strip, seg, plane, col, any_rev);
 }
 
 // ================================================================================================
@@ -1153,11 +1032,7 @@ __global__ __launch_bounds__(64 * kHistWaves) void k_hist(HistArgs args) {
       const int it = min(it0 + kHistWaves * k, nitems - 1);  // clamped: what a clamped load returns is not counted
       const int row = it / gf, g = it - row * gf;   // wave-uniform (scalar unit)
       const float* p = da + (long long)(r0 + row) * a.ld + 256 * g + 4 * lane;
-#if DSX_NT
       v[k] = __builtin_nontemporal_load((const dsx_f4*)p);
-#else
-      v[k] = *(const dsx_f4*)p;
-#endif
     }
 #pragma unroll
     for (int k = 0; k < kHistLoads; ++k) {
@@ -1340,7 +1215,19 @@ __device__ __forceinline__ float key_f32(unsigned k) {
   return as_f32((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-template <int R, int CPL, int JK = (R - 1) / 2, int KO = (R - 1) / 2, class IX = dsx_idx_plain>
+// The lanes that share one row buffer: how far apart the butterflies of a lane lie, and the barrier between the reads
+// of a pass and its writes.
+struct WaveGroup {  // one wave per row pair (k_rowfilter, k_rowfinal)
+  static constexpr int kLanes = kWave;
+  // LDS operations of one wave execute in program order: every read before it precedes the writes after it
+  static __device__ __forceinline__ void sync() { wave_sync(); }
+};
+struct BlockGroup {  // one block per row pair (k_rowfilter_wide)
+  static constexpr int kLanes = kWideThreads;
+  static __device__ __forceinline__ void sync() { __syncthreads(); }
+};
+
+template <int R, int CPL, class G = WaveGroup, int JK = (R - 1) / 2, int KO = (R - 1) / 2>
 __device__ __forceinline__ void fft_pass(float2* buf, const float2* tw, int M, int s, float inv_s,
                                          int lane) {
   constexpr int MAXB = (CPL + R - 1) / R;
@@ -1349,45 +1236,45 @@ __device__ __forceinline__ void fft_pass(float2* buf, const float2* tw, int M, i
   dsx_c32 v[MAXB][R];
 #pragma unroll
   for (int i = 0; i < MAXB; ++i) {
-    const int b = lane + kWave * i;
-    if (b < nb) dsx_bfly_load<R, JK, IX>((const dsx_c32*)buf, b, nb, v[i]);
+    const int b = lane + G::kLanes * i;
+    if (b < nb) dsx_bfly_load<R, JK>((const dsx_c32*)buf, b, nb, v[i]);
   }
-  // LDS operations of one wave execute in program order: every read above precedes the writes below
-  wave_sync();
+  G::sync();
 #pragma unroll
   for (int i = 0; i < MAXB; ++i) {
-    const int b = lane + kWave * i;
-    if (b < nb) dsx_bfly_store<R, JK, KO, IX>((dsx_c32*)buf, (const dsx_c32*)tw, b, s, inv_s, v[i], unit_tw);
+    const int b = lane + G::kLanes * i;
+    if (b < nb) dsx_bfly_store<R, JK, KO>((dsx_c32*)buf, (const dsx_c32*)tw, b, s, inv_s, v[i], unit_tw);
     // keep the unrolled butterflies from being interleaved: their temporaries would all be live
     // at once (215+ VGPRs at 18 values per lane) for no gain -- other waves hide the latency
     __builtin_amdgcn_sched_barrier(0);
   }
-  wave_sync();
+  G::sync();
 }
 
-template <int CPL>
+template <int CPL, class G>
 __device__ __forceinline__ void fft_pass_generic(float2* buf, const float2* tw, int M, int s,
                                                  float inv_s, int R, int lane) {
   float2 acc[CPL];
 #pragma unroll
   for (int i = 0; i < CPL; ++i) {
-    const int o = lane + kWave * i;
+    const int o = lane + G::kLanes * i;
     acc[i] = make_float2(0.f, 0.f);
     if (o < M) {
       const dsx_c32 r = dsx_generic_output((const dsx_c32*)buf, (const dsx_c32*)tw, o, M, s, inv_s, R);
       acc[i] = make_float2(r.x, r.y);
     }
   }
-  wave_sync();
+  G::sync();
 #pragma unroll
   for (int i = 0; i < CPL; ++i) {
-    const int o = lane + kWave * i;
+    const int o = lane + G::kLanes * i;
     if (o < M) buf[o] = acc[i];
   }
-  wave_sync();
+  G::sync();
 }
 
-template <int CPL>
+// the passes of RowArgs; lane_in: the lane's index in its group
+template <int CPL, class G = WaveGroup>
 __device__ __forceinline__ void fft_run(float2* buf, const float2* tw, const RowArgs& a, int lane_in) {
   int s = 1;
   for (int pi = 0; pi < a.npass; ++pi) {
@@ -1398,25 +1285,25 @@ __device__ __forceinline__ void fft_run(float2* buf, const float2* tw, const Row
     int lane = lane_in, M = a.M;
     asm volatile("" : "+v"(lane), "+s"(M));
     switch (R) {
-      case 2: fft_pass<2, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 3: fft_pass<3, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 4: fft_pass<4, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 5: fft_pass<5, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 6: fft_pass<6, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 8: fft_pass<8, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 9: fft_pass<9, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 10: fft_pass<10, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 12: fft_pass<12, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 15: fft_pass<15, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 16: fft_pass<16, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 20: fft_pass<20, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 25: fft_pass<25, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 7: fft_pass<7, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 11: fft_pass<11, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 13: fft_pass<13, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 17: fft_pass<17, CPL>(buf, tw, M, s, inv_s, lane); break;
-      case 19: fft_pass<19, CPL>(buf, tw, M, s, inv_s, lane); break;
-      default: fft_pass_generic<CPL>(buf, tw, M, s, inv_s, R, lane); break;
+      case 2: fft_pass<2, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 3: fft_pass<3, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 4: fft_pass<4, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 5: fft_pass<5, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 6: fft_pass<6, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 8: fft_pass<8, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 9: fft_pass<9, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 10: fft_pass<10, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 12: fft_pass<12, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 15: fft_pass<15, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 16: fft_pass<16, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 20: fft_pass<20, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 25: fft_pass<25, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 7: fft_pass<7, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 11: fft_pass<11, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 13: fft_pass<13, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 17: fft_pass<17, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      case 19: fft_pass<19, CPL, G>(buf, tw, M, s, inv_s, lane); break;
+      default: fft_pass_generic<CPL, G>(buf, tw, M, s, inv_s, R, lane); break;
     }
     s *= R;
   }
@@ -1456,29 +1343,23 @@ template <int CPL, int M_, int S_, int R, int... REST>
 __device__ __forceinline__ void fft_static_passes_swz(float2* buf, const float2* tw, int lane_in) {
   int lane = lane_in;
   asm volatile("" : "+v"(lane));
-#if DSX_SWZ == 2
-  fft_pass<R, CPL, (R - 1) / 2, (R - 1) / 2, dsx_idx_swz>(buf, tw, M_, S_, 1.0f / (float)S_, lane);  // the generic policy (A/B)
-#else
   fft_pass_swz<R, CPL, M_, S_>(buf, tw, lane);
-#endif
   if constexpr (sizeof...(REST) > 0) fft_static_passes_swz<CPL, M_, S_ * R, REST...>(buf, tw, lane_in);
 }
-// PLAN_ ids of k_rowfilter: 0 = passes from RowArgs; the others must match dsx.hip's dispatch.
+// PLAN_ ids of k_rowfilter: 0 = passes from RowArgs; the others are the rows of kRowPlans (dsx_chain.h).
 template <int PLAN_>
 struct StaticFft {
-  static constexpr int M = 0;
-  static constexpr bool kSwz = false;  // dsx_idx_swz addressing of the row buffer and the twiddle table (rf_pair_body)
-};
-template <>
-struct StaticFft<1> {  // level 1 of a 2048-wide plane
-  static constexpr int M = 1026;
-  static constexpr bool kSwz = false;
-  static constexpr int kRadix[3] = {19, 9, 6};
+  static constexpr RowPlan kPlan = PLAN_ > 0 ? row_plan(PLAN_) : RowPlan{};
+  static constexpr int M = kPlan.M;
+  static constexpr bool kSwz = kPlan.swz;  // dsx_idx_swz addressing of the row buffer and the twiddle table (rf_pair_body)
+  static constexpr bool kPruned = PLAN_ == 1;  // level 1 of a 2048-wide plane: band-limited, the radix-19 pass is pruned
+  static_assert(!kPruned || (M == 1026 && kPlan.radix[0] == 19 && kPlan.radix[1] == 9 && kPlan.radix[2] == 6),
+                "the pruned passes below are written for 1026 = 19 * 9 * 6");
   template <int CPL>
   static __device__ __forceinline__ void run(float2* buf, const float2* tw, int lane) {
-    fft_static_passes<CPL, 1026, 1, 19, 9, 6>(buf, tw, lane);
+    if constexpr (kSwz) fft_static_passes_swz<CPL, M, 1, kPlan.radix[0], kPlan.radix[1], kPlan.radix[2]>(buf, tw, lane);
+    else fft_static_passes<CPL, M, 1, kPlan.radix[0], kPlan.radix[1], kPlan.radix[2]>(buf, tw, lane);
   }
-#if DSX_FWD_PRUNE
   // Forward transform whose consumer (the spectral step) only reads the bins k <= kcut and k >= M - kcut (the low-pass
   // is an exact zero beyond, dsx_plan.h: kcut = 103 / 206 of 513 for the production configs): the passes run in the
   // order 6, 9, 19, so that the LAST pass is the expensive radix-19 one -- outputs q + 54 k, q < 54 -- and only its
@@ -1489,79 +1370,40 @@ struct StaticFft<1> {  // level 1 of a 2048-wide plane
     fft_static_passes<CPL, 1026, 1, 6, 9>(buf, tw, lane_in);
     int lane = lane_in;
     asm volatile("" : "+v"(lane));
-    fft_pass<19, CPL, 9, KO>(buf, tw, 1026, 54, 1.0f / 54.0f, lane);
+    fft_pass<19, CPL, WaveGroup, 9, KO>(buf, tw, 1026, 54, 1.0f / 54.0f, lane);
   }
   template <int CPL>
   static __device__ __forceinline__ void run_forward(float2* buf, const float2* tw, int lane, int kcut) {
-    const int ko = (kcut + 53) / 54;
-    if (ko <= 2) run_last_pruned<CPL, 2>(buf, tw, lane);
-    else if (ko <= 4) run_last_pruned<CPL, 4>(buf, tw, lane);
-    else run<CPL>(buf, tw, lane);
+    if constexpr (kPruned) {
+      const int ko = (kcut + 53) / 54;
+      if (ko <= 2) run_last_pruned<CPL, 2>(buf, tw, lane);
+      else if (ko <= 4) run_last_pruned<CPL, 4>(buf, tw, lane);
+      else run<CPL>(buf, tw, lane);
+    } else {
+      run<CPL>(buf, tw, lane);
+    }
   }
-#else
-  template <int CPL>
-  static __device__ __forceinline__ void run_forward(float2* buf, const float2* tw, int lane, int) { run<CPL>(buf, tw, lane); }
-#endif
   // Inverse transform of a spectrum that vanishes for kcut < k < M - kcut: the first pass (radix 19,
   // sources b + 54 j) only sees non-zero input pairs (j, 19 - j) for j <= (kcut + 53) / 54.
   template <int CPL, int JK>
   static __device__ __forceinline__ void run_first_pruned(float2* buf, const float2* tw, int lane_in) {
     int lane = lane_in;
     asm volatile("" : "+v"(lane));
-    fft_pass<19, CPL, JK>(buf, tw, 1026, 1, 1.0f, lane);
+    fft_pass<19, CPL, WaveGroup, JK>(buf, tw, 1026, 1, 1.0f, lane);
     fft_static_passes<CPL, 1026, 19, 9, 6>(buf, tw, lane_in);
   }
   template <int CPL>
   static __device__ __forceinline__ void run_inverse(float2* buf, const float2* tw, int lane, int kcut) {
-    const int jk = (kcut + 53) / 54;
-    if (jk <= 2) run_first_pruned<CPL, 2>(buf, tw, lane);
-    else if (jk <= 4) run_first_pruned<CPL, 4>(buf, tw, lane);
-    else run<CPL>(buf, tw, lane);
+    if constexpr (kPruned) {
+      const int jk = (kcut + 53) / 54;
+      if (jk <= 2) run_first_pruned<CPL, 2>(buf, tw, lane);
+      else if (jk <= 4) run_first_pruned<CPL, 4>(buf, tw, lane);
+      else run<CPL>(buf, tw, lane);
+    } else {
+      run<CPL>(buf, tw, lane);  // the embedded operators are not band-limited
+    }
   }
 };
-template <>
-struct StaticFft<2> {  // level 2 of a 2048-wide plane: 515 values embedded in 1071
-  static constexpr int M = 1071;
-  static constexpr bool kSwz = false;
-  static constexpr int kRadix[3] = {17, 9, 7};
-  template <int CPL>
-  static __device__ __forceinline__ void run(float2* buf, const float2* tw, int lane) {
-    fft_static_passes<CPL, 1071, 1, 17, 9, 7>(buf, tw, lane);
-  }
-  template <int CPL>
-  static __device__ __forceinline__ void run_forward(float2* buf, const float2* tw, int lane, int) { run<CPL>(buf, tw, lane); }
-  template <int CPL>
-  static __device__ __forceinline__ void run_inverse(float2* buf, const float2* tw, int lane, int) {
-    run<CPL>(buf, tw, lane);  // the embedded operator is not band-limited
-  }
-};
-
-// Further compile-time plans: the wide levels of the production tile (1600 x 2000) and of 1800 x 1800 planes.
-#define DSX_STATIC_FFT(ID, LEN, R0, R1, R2, SWZ)                                                   \
-  template <>                                                                                      \
-  struct StaticFft<ID> {                                                                           \
-    static constexpr int M = LEN;                                                                  \
-    static constexpr bool kSwz = SWZ;                                                              \
-    template <int CPL>                                                                             \
-    static __device__ __forceinline__ void run(float2* buf, const float2* tw, int lane) {          \
-      if constexpr (SWZ) fft_static_passes_swz<CPL, LEN, 1, R0, R1, R2>(buf, tw, lane);            \
-      else fft_static_passes<CPL, LEN, 1, R0, R1, R2>(buf, tw, lane);                              \
-    }                                                                                              \
-    template <int CPL>                                                                             \
-    static __device__ __forceinline__ void run_forward(float2* buf, const float2* tw, int lane, int) { \
-      run<CPL>(buf, tw, lane);                                                                     \
-    }                                                                                              \
-    template <int CPL>                                                                             \
-    static __device__ __forceinline__ void run_inverse(float2* buf, const float2* tw, int lane, int) { \
-      run<CPL>(buf, tw, lane);                                                                     \
-    }                                                                                              \
-  };
-// (power-of-two lengths: their passes scatter at power-of-two strides -- bank-swizzled addressing, dsx_fft_core.h: dsx_idx_swz)
-DSX_STATIC_FFT(3, 2048, 16, 16, 8, DSX_SWZ != 0)  // 1002 values (level 1 of a 2000-wide plane) embedded in 2048
-DSX_STATIC_FFT(4, 1815, 15, 11, 11, false)         // 902 values (level 1 of an 1800-wide plane) embedded in 1815
-DSX_STATIC_FFT(5, 1024, 16, 8, 8, DSX_SWZ != 0)   // 503 values (level 2 of a 2000-wide plane) embedded in 1024
-DSX_STATIC_FFT(6, 960, 15, 8, 8, false)            // 453 values (level 2 of an 1800-wide plane) embedded in 960
-#undef DSX_STATIC_FFT
 
 typedef short dsx_s16x2 __attribute__((ext_vector_type(2)));
 
@@ -1777,7 +1619,6 @@ __device__ __forceinline__ void rf_pair_body(const RowArgs& a, float2* s_tw, flo
     const unsigned k1 = (unsigned)(N - 1) >> 1;
     const bool even = (N & 1) == 0;
     auto count2 = [&](float ta, float tb, bool le) -> unsigned {  // (#a < ta) | (#b < tb) << 16, wave totals
-#if DSX_MEDIAN_BALLOT
       // one vector compare per value; the wave total is a scalar population count of the compare mask
       unsigned ca = 0, cb = 0;
       for_slots<GV>(gf, nt, [&](int e) {
@@ -1785,14 +1626,6 @@ __device__ __forceinline__ void rf_pair_body(const RowArgs& a, float2* s_tw, flo
         cb += (unsigned)__popcll(__ballot(le ? (vb[e] <= tb) : (vb[e] < tb)));
       });
       return ca | (cb << 16);
-#else
-      unsigned ca = 0, cb = 0;
-      for_slots<GV>(gf, nt, [&](int e) {
-        ca += (le ? (va[e] <= ta) : (va[e] < ta)) ? 1u : 0u;
-        cb += (le ? (vb[e] <= tb) : (vb[e] < tb)) ? 1u : 0u;
-      });
-      return (unsigned)__builtin_amdgcn_readfirstlane((int)__reduce_add_sync(~0ull, ca | (cb << 16)));
-#endif
     };
     // bracket state per row r (0 = a, 1 = b), wave-uniform
     float lo[2], hi[2];
@@ -1991,14 +1824,9 @@ __device__ __forceinline__ void rf_pair_body(const RowArgs& a, float2* s_tw, flo
         da_[i] = bit_select(slot_mask(maska, e), 0.f, -y.y * a.inv_M);
         db_[i] = bit_select(slot_mask(maskb, e), 0.f, -y.x * a.inv_M);
       }
-#if DSX_NT
       const dsx_f4 oa = {da_[0], da_[1], da_[2], da_[3]}, ob = {db_[0], db_[1], db_[2], db_[3]};
       __builtin_nontemporal_store(oa, (dsx_f4*)(rowa + nb0));
       if (has_b) __builtin_nontemporal_store(ob, (dsx_f4*)(rowb + nb0));
-#else
-      *(float4*)(rowa + nb0) = make_float4(da_[0], da_[1], da_[2], da_[3]);
-      if (has_b) *(float4*)(rowb + nb0) = make_float4(db_[0], db_[1], db_[2], db_[3]);
-#endif
     }
   }
 #pragma unroll
@@ -2074,80 +1902,6 @@ __device__ __forceinline__ unsigned wide_block_min(unsigned v, unsigned* s_red, 
   for (int w = 0; w < kWideThreads / 64; ++w) t = min(t, slot[w]);
   ++turn;
   return t;
-}
-
-template <int R, int CPL, int JK = (R - 1) / 2>
-__device__ __forceinline__ void fft_pass_block(float2* buf, const float2* tw, int M, int s, float inv_s, int tid) {
-  constexpr int MAXB = (CPL + R - 1) / R;
-  const int nb = M / R;
-  const bool unit_tw = (s * R == M);
-  dsx_c32 v[MAXB][R];
-#pragma unroll
-  for (int i = 0; i < MAXB; ++i) {
-    const int b = tid + kWideThreads * i;
-    if (b < nb) dsx_bfly_load<R, JK>((const dsx_c32*)buf, b, nb, v[i]);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < MAXB; ++i) {
-    const int b = tid + kWideThreads * i;
-    if (b < nb) dsx_bfly_store<R, JK>((dsx_c32*)buf, (const dsx_c32*)tw, b, s, inv_s, v[i], unit_tw);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  __syncthreads();
-}
-template <int CPL>
-__device__ __forceinline__ void fft_pass_generic_block(float2* buf, const float2* tw, int M, int s, float inv_s, int R,
-                                                       int tid) {
-  float2 acc[CPL];
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-    const int o = tid + kWideThreads * i;
-    acc[i] = make_float2(0.f, 0.f);
-    if (o < M) {
-      const dsx_c32 r = dsx_generic_output((const dsx_c32*)buf, (const dsx_c32*)tw, o, M, s, inv_s, R);
-      acc[i] = make_float2(r.x, r.y);
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-    const int o = tid + kWideThreads * i;
-    if (o < M) buf[o] = acc[i];
-  }
-  __syncthreads();
-}
-template <int CPL>
-__device__ __forceinline__ void fft_run_block(float2* buf, const float2* tw, const RowArgs& a, int tid_in) {
-  int s = 1;
-  for (int pi = 0; pi < a.npass; ++pi) {
-    const int R = a.radix[pi];
-    const float inv_s = 1.0f / (float)s;
-    int tid = tid_in, M = a.M;
-    asm volatile("" : "+v"(tid), "+s"(M));  // (see fft_run)
-    switch (R) {
-      case 2: fft_pass_block<2, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 3: fft_pass_block<3, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 4: fft_pass_block<4, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 5: fft_pass_block<5, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 6: fft_pass_block<6, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 8: fft_pass_block<8, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 9: fft_pass_block<9, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 10: fft_pass_block<10, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 12: fft_pass_block<12, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 15: fft_pass_block<15, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 16: fft_pass_block<16, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 20: fft_pass_block<20, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 25: fft_pass_block<25, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 7: fft_pass_block<7, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 11: fft_pass_block<11, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 13: fft_pass_block<13, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 17: fft_pass_block<17, CPL>(buf, tw, M, s, inv_s, tid); break;
-      case 19: fft_pass_block<19, CPL>(buf, tw, M, s, inv_s, tid); break;
-      default: fft_pass_generic_block<CPL>(buf, tw, M, s, inv_s, R, tid); break;
-    }
-    s *= R;
-  }
 }
 
 __global__ __launch_bounds__(kWideThreads) void k_rowfilter_wide(RowArgs a) {
@@ -2242,7 +1996,7 @@ __global__ __launch_bounds__(kWideThreads) void k_rowfilter_wide(RowArgs a) {
     for (int m = N + 2 * K + 1 + tid; m < M; m += kWideThreads) buf[m] = make_float2(0.f, 0.f);
   }
   __syncthreads();
-  fft_run_block<E>(buf, a.tw, a, tid);
+  fft_run<E, BlockGroup>(buf, a.tw, a, tid);
   {  // V[k] = G1[k] U[k] + G2[k] U[M - k], stored re/im-swapped (see rf_pair_body)
     const float2* g1 = a.g[cfg];
     const float2* g2 = g1 + M;
@@ -2260,7 +2014,7 @@ __global__ __launch_bounds__(kWideThreads) void k_rowfilter_wide(RowArgs a) {
     for (int k = kcut + 1 + tid; k < M - kcut; k += kWideThreads) buf[k] = make_float2(0.f, 0.f);
     __syncthreads();
   }
-  fft_run_block<E>(buf, a.tw, a, tid);
+  fft_run<E, BlockGroup>(buf, a.tw, a, tid);
   // ---- Delta = -(1 - mask) LP (filtering.py:215-217): row a <- .y, row b <- .x ----------------------------------------
 #pragma unroll
   for (int e = 0; e < E; ++e) {
@@ -2756,10 +2510,11 @@ __device__ __forceinline__ void inv_march_body(const FinalArgs& a, int lane, int
   }
 }
 
+constexpr int kInvMinWaves = 1;  // waves per SIMD the fused uint16 final kernel is compiled for
 // IN_KIND: 0 = last level, uint16 pixels; 1 = last level, float32 pixels;
 //          2 = pyramid level: writes c_{l-1} (float32, hout x wout, pitch ldout) into the workspace
 template <int IN_KIND, bool FUSE = false, int WPB = 4>
-__global__ __launch_bounds__(64 * WPB, (FUSE && IN_KIND == 0) ? DSX_INV_MINW : 1) void k_inv_march(FinalArgs a) {
+__global__ __launch_bounds__(64 * WPB, (FUSE && IN_KIND == 0) ? kInvMinWaves : 1) void k_inv_march(FinalArgs a) {
   __shared__ __attribute__((aligned(16))) float s_c1[FUSE ? WPB : 1][FUSE ? kRingRows : 1][FUSE ? kC1Pitch : 4];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: keeps row math on the SALU
@@ -2832,7 +2587,10 @@ struct RowFinalPre {
 
 };
 
-// STEADY_: the row loop without a memory instruction under a condition (DSX_RF_STEADY; see the loop).  Not with shading
+// STEADY_: the row loop is straight-line with respect to vector memory (no load or store under a condition, the level-2
+// step at a fixed place, exits between row pairs only; see the loop), so that the compiler counts its waits and the pixel
+// rows it prefetches stay in flight; the loop of three predicated steps drained the memory queue in every step
+// (profiles/march_waits_before.txt).  Not with shading
 // and not for the wide plans: the dark / flat values of a step, or what the wide plans' first phase keeps per lane,
 // leave the six unrolled steps no room under the register count the kernel has without them (with shading it spilled,
 // 192 bytes per lane; the wide plans went from 125 / 148 to 165 registers).
@@ -3104,15 +2862,11 @@ __global__ __launch_bounds__(64 * kRfWaves, CPL <= 18 ? 4 : 2) void k_rowfinal(R
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int M = StaticFft<PLAN_>::M;
   const int plane = blockIdx.y;
-  // DSX_RF_XCD (off, see the switch): workgroup i of a launch runs on compute die i mod 8 (each die has its own L2).
-  // Neighbouring blocks of a plane share rows -- the row pair both filter, 2 of the 10 level-2 rows -- so the blocks
-  // of one die are made neighbours: die d takes the d-th run of gridDim.x / 8 consecutive blocks.
-#if DSX_RF_XCD
-  const int per_die = gridDim.x >> 3;  // the host launches a multiple of 8 blocks per plane
-  const int bx = (blockIdx.x & 7) * per_die + (blockIdx.x >> 3);
-#else
+  // Blocks take their rows in launch order: workgroup i runs on compute die i mod 8 (each die has its own L2), so the
+  // eight dies stream one front of a plane.  Dealing each die a run of consecutive blocks instead (neighbours share the row
+  // pair both filter and 2 of the 10 level-2 rows) saved 1.6 MB of HBM traffic per plane (25.0 -> 23.4) and was 4 % SLOWER
+  // (61.9 k against 64.5 k planes/s, profiles/r3_fused_rowfinal_ab.txt): the dies then stream eight distant regions.
   const int bx = blockIdx.x;
-#endif
   const int pair0 = (kRfWaves - 1) * bx;  // first row pair of the block; its coefficient rows start at 2 pair0
   rf_pair_body<CPL, GF_, NT_, HALO_, PLAN_, true>(a.r, dsx_smem, dsx_smem + (long long)M * (1 + wave), tid, 64 * kRfWaves, lane,
                                                   pair0 + wave, plane);
@@ -3122,7 +2876,7 @@ __global__ __launch_bounds__(64 * kRfWaves, CPL <= 18 ? 4 : 2) void k_rowfinal(R
   RowFinalPre pre;
   asm volatile("" ::: "memory");  // keep the prefetch loads (and their registers) out of the row-filter phase
   __builtin_amdgcn_sched_barrier(0);
-  constexpr bool STEADY = DSX_RF_STEADY != 0 && CPL <= 18;  // the 2048-wide plan: see rowfinal_synth
+  constexpr bool STEADY = CPL <= 18;  // the 2048-wide plan: see rowfinal_synth
   if (synth) rowfinal_synth<false, STEADY, true>(a.f, dsx_smem, M, lane, wave, plane, p_begin, p_end, 2 * pair0, pre);
   __syncthreads();  // all 2 kRfWaves Delta_1 rows of the block are in LDS
   if (!synth) return;

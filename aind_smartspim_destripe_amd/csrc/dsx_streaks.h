@@ -51,13 +51,7 @@ struct Taps {
   float lo[kMaxTaps], hi[kMaxTaps];  // kMaxTaps: dsx_wavelet.h, the bound dsx_set_wavelet enforces
 };
 
-__device__ __forceinline__ unsigned f32_key(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_f32(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+// (order-preserving integer keys of floats: dsx::f32_key / dsx::key_f32, dsx_kernels.h)
 
 template <typename T>
 __device__ __forceinline__ float pix(const T* p, size_t i) { return (float)p[i]; }

@@ -529,6 +529,19 @@ static int cmd_chain_rules() {
     RULE(g.lds <= dsx::kLdsLimit, "W %d: merged launch lds %zu", W, g.lds);
     ++checked;
   }
+  // the table of compile-time plans agrees with itself: the radices make M, cpl is M's class, and the classifier gives
+  // a row of exactly these numbers the row's id (every width of the slot structure gf / nt)
+  for (int id = 1; id <= dsx::kRowPlanCount; ++id) {
+    const dsx::RowPlan& rp = dsx::row_plan(id);
+    RULE(rp.radix[0] * rp.radix[1] * rp.radix[2] == rp.M, "plan %d: radices of M %d", id, rp.M);
+    RULE(dsx::cpl_class(rp.M) == rp.cpl, "plan %d: cpl %d", id, rp.cpl);
+    for (int w = 256 * rp.gf + 64 * (rp.nt - 1) + 1; w <= 256 * rp.gf + 64 * rp.nt && w < 256 * (rp.gf + 1) && w <= rp.M; ++w) {
+      const dsx::RowClass c = dsx::classify_row(rp.M, w, /*K=*/rp.halo, 3, rp.radix);
+      RULE(!c.wide && c.plan == id && c.cpl == rp.cpl && c.gf == rp.gf && c.nt == rp.nt && c.halo == rp.halo,
+           "plan %d w %d: classified as <%d, %d, %d, %d, %d>", id, w, c.cpl, c.gf, c.nt, c.halo, c.plan);
+      ++checked;
+    }
+  }
   printf("{\"ok\": true, \"checked\": %lld}\n", checked);
   return 0;
 }

@@ -1,7 +1,7 @@
 """The march kernels' steady loops issue loads and stores that they do not use: rows past the end of a block or a plane are
 loaded from clamped addresses, and the result store of k_rowfinal is issued by every lane in every step and DISCARDED
 through its buffer descriptor where a lane or a row has nothing to write (csrc/dsx_kernels.h: rowfinal_synth,
-DSX_RF_STEADY).  What must hold whatever the loops issue:
+STEADY).  What must hold whatever the loops issue:
 
 * a plane of a batch comes out bit for bit as the same plane run alone;
 * every plane passes the parity statement of tests/parity_util.py against the oracle;
