@@ -183,6 +183,14 @@ struct dsx_ctx {
   int st_vdtype = DSX_U16;        // element type of the virtual planes of uint16 input (float32 input: float32)
   void* st_vin = nullptr;         // [bands * B][H][W] virtual input planes
   float* st_vout = nullptr;       // [bands * B][H][W] what the chain writes: band + 2
+  // options of the blend (dsx_plan_streaks_opts); st_opts false: k_st_final / k_st_blend, as dsx_plan_streaks_ex
+  bool st_opts = false;
+  int st_mode = dsx::st::kStBoth; // kStBoth / kStFg / kStBg / kStSingle
+  int st_R = 0;                   // radius of the weight smoothing, 0: none
+  float st_taps[dsx::st::kStMaxR + 1] = {};
+  float* st_flat = nullptr;       // [H][W], or nullptr: no dark / flat step
+  float* st_dark = nullptr;       // [>= H][st_dark_w]
+  int st_dark_w = 0;
 };
 
 namespace {
@@ -944,6 +952,11 @@ void free_streaks(dsx_ctx* c) {
   fr(c->st_info); c->st_info = nullptr;
   fr(c->st_vin); c->st_vin = nullptr;
   fr(c->st_vout); c->st_vout = nullptr;
+  fr(c->st_flat); c->st_flat = nullptr;
+  fr(c->st_dark); c->st_dark = nullptr;
+  c->st_opts = false;
+  c->st_mode = dsx::st::kStBoth;
+  c->st_R = 0;
   c->st_march = false;
   c->streaks = false;
 }
@@ -990,11 +1003,43 @@ int streaks_threshold(dsx_ctx* ctx, hipStream_t s, const void* d_in, bool u16, i
 }
 
 template <typename TI, typename TV>
-void st_bands(hipStream_t s, dim3 g, bool vec, const void* in, size_t px, int bands, const float* t, void* v,
+void st_bands(hipStream_t s, dim3 g, bool vec, const void* in, size_t px, int bands, int clip, const float* t, void* v,
               unsigned* sticky) {
   using namespace dsx::st;
-  if (vec) k_st_bands<TI, TV, 4><<<g, 256, 0, s>>>((const TI*)in, px, bands, t, (TV*)v, sticky);
-  else k_st_bands<TI, TV, 1><<<g, 256, 0, s>>>((const TI*)in, px, bands, t, (TV*)v, sticky);
+  if (vec) k_st_bands<TI, TV, 4><<<g, 256, 0, s>>>((const TI*)in, px, bands, clip, t, (TV*)v, sticky);
+  else k_st_bands<TI, TV, 1><<<g, 256, 0, s>>>((const TI*)in, px, bands, clip, t, (TV*)v, sticky);
+}
+
+// The blend of a plan with options (dsx_plan_streaks_opts) for one cohort, on either route: ld says where the bands
+// are, band_pitch is their row pitch
+template <typename L>
+void st_blendx(dsx_ctx* ctx, hipStream_t s, const L& ld, int band_pitch, const void* d_in, int in_dtype, const float* r,
+               int nb, void* d_out, int out_dtype) {
+  using namespace dsx::st;
+  const StreaksPlan& p = ctx->sp;
+  BlendArgs a;
+  a.in = d_in; a.r = r; a.out = d_out; a.t = ctx->st_t;
+  a.flat = ctx->st_flat; a.dark = ctx->st_dark; a.dark_w = ctx->st_dark_w;
+  a.H = p.H; a.W = p.W; a.mode = ctx->st_mode;
+  a.R = ctx->st_mode == kStSingle ? 0 : ctx->st_R;
+  a.inv_crossover = 1.0f / p.crossover;
+  memcpy(a.taps, ctx->st_taps, sizeof(a.taps));
+  auto aligned = [](const void* q, size_t n) { return ((uintptr_t)q % n) == 0; };
+  a.vec = (p.W % 4) == 0 && (band_pitch % 4) == 0 && aligned(d_in, 4 * elem_size(in_dtype)) &&
+          aligned(d_out, 4 * elem_size(out_dtype)) && aligned(r, 16) &&
+          (a.flat == nullptr || ((a.dark_w % 4) == 0 && aligned(a.flat, 16) && aligned(a.dark, 16)));
+  const dim3 g((unsigned)((p.W + kBtW - 1) / kBtW), (unsigned)((p.H + kBtH - 1) / kBtH), (unsigned)nb);
+  const bool smooth = a.R > 0, u16 = in_dtype == DSX_U16;
+#define DSX_ST_BX(TI, TO)                                                     \
+  do {                                                                        \
+    if (smooth) k_st_blendx<L, TI, TO, true><<<g, 256, 0, s>>>(a, ld);        \
+    else k_st_blendx<L, TI, TO, false><<<g, 256, 0, s>>>(a, ld);              \
+  } while (0)
+  if (u16 && out_dtype == DSX_U16) DSX_ST_BX(uint16_t, uint16_t);
+  else if (u16) DSX_ST_BX(uint16_t, float);
+  else if (out_dtype == DSX_U16) DSX_ST_BX(float, uint16_t);
+  else DSX_ST_BX(float, float);
+#undef DSX_ST_BX
 }
 template <typename TI, typename TO>
 void st_blend(hipStream_t s, dim3 g, bool vec, const void* in, const float* r, size_t px, int bands, const float* t,
@@ -1018,13 +1063,14 @@ int streaks_cohort_march(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, v
   // the context stream, so run_cohort_split forks anew instead of queueing its parts behind their predecessors
   hipStream_t s = use_main(ctx);
   if (int rc = streaks_threshold(ctx, s, d_in, u16, nb)) return rc;
-  k_st_chainfill<<<st_blocks((size_t)std::max(P * Lc, P)), 256, 0, s>>>(ctx->d_thr, P * Lc, ctx->d_cfg, P, p.bands);
+  k_st_chainfill<<<st_blocks((size_t)std::max(P * Lc, P)), 256, 0, s>>>(ctx->d_thr, P * Lc, ctx->d_cfg, P, p.bands,
+                                                                        p.clip == kStBg ? 1 : 0);
   const dim3 g((unsigned)std::max<size_t>(1, std::min<size_t>(1024, px / (256 * 4 * 4))), nb);
   const size_t esz = elem_size(in_dtype);
   const bool vec_in = ((uintptr_t)d_in % (4 * esz)) == 0;
-  if (!u16) st_bands<float, float>(s, g, vec_in, d_in, px, p.bands, ctx->st_t, ctx->st_vin, ctx->d_sticky);
-  else if (vdtype == DSX_U16) st_bands<uint16_t, uint16_t>(s, g, vec_in, d_in, px, p.bands, ctx->st_t, ctx->st_vin, nullptr);
-  else st_bands<uint16_t, float>(s, g, vec_in, d_in, px, p.bands, ctx->st_t, ctx->st_vin, nullptr);
+  if (!u16) st_bands<float, float>(s, g, vec_in, d_in, px, p.bands, p.clip, ctx->st_t, ctx->st_vin, ctx->d_sticky);
+  else if (vdtype == DSX_U16) st_bands<uint16_t, uint16_t>(s, g, vec_in, d_in, px, p.bands, p.clip, ctx->st_t, ctx->st_vin, nullptr);
+  else st_bands<uint16_t, float>(s, g, vec_in, d_in, px, p.bands, p.clip, ctx->st_t, ctx->st_vin, nullptr);
   DSX_HIP(hipGetLastError());
   if (int rc = run_cohort_split(ctx, ctx->st_vin, vdtype, P, ctx->st_vout, DSX_F32, nullptr, px * elem_size(vdtype),
                                 px * sizeof(float)))
@@ -1032,7 +1078,8 @@ int streaks_cohort_march(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, v
   s = use_main(ctx);
   const bool vec = vec_in && ((uintptr_t)d_out % (4 * elem_size(out_dtype))) == 0;
   const float ic = 1.0f / p.crossover;
-  if (u16 && out_dtype == DSX_U16) st_blend<uint16_t, uint16_t>(s, g, vec, d_in, ctx->st_vout, px, p.bands, ctx->st_t, ic, d_out);
+  if (ctx->st_opts) st_blendx(ctx, s, StMarchBands{p.bands, p.W, px}, p.W, d_in, in_dtype, ctx->st_vout, nb, d_out, out_dtype);
+  else if (u16 && out_dtype == DSX_U16) st_blend<uint16_t, uint16_t>(s, g, vec, d_in, ctx->st_vout, px, p.bands, ctx->st_t, ic, d_out);
   else if (u16) st_blend<uint16_t, float>(s, g, vec, d_in, ctx->st_vout, px, p.bands, ctx->st_t, ic, d_out);
   else if (out_dtype == DSX_U16) st_blend<float, uint16_t>(s, g, vec, d_in, ctx->st_vout, px, p.bands, ctx->st_t, ic, d_out);
   else st_blend<float, float>(s, g, vec, d_in, ctx->st_vout, px, p.bands, ctx->st_t, ic, d_out);
@@ -1058,10 +1105,10 @@ int streaks_cohort(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d
     const size_t total = (size_t)p.Hp * p.Wp * nb * p.bands;
     if (u16)
       k_st_prep<uint16_t><<<st_blocks(total), 256, 0, s>>>((const uint16_t*)d_in, nb, nb, p.H, p.W, p.Hp, p.Wp,
-                                                           p.bands, ctx->st_t, ws + p.y, ctx->d_sticky);
+                                                           p.bands, p.clip, ctx->st_t, ws + p.y, ctx->d_sticky);
     else
       k_st_prep<float><<<st_blocks(total), 256, 0, s>>>((const float*)d_in, nb, nb, p.H, p.W, p.Hp, p.Wp, p.bands,
-                                                        ctx->st_t, ws + p.y, ctx->d_sticky);
+                                                        p.clip, ctx->st_t, ws + p.y, ctx->d_sticky);
   }
   // 3. analysis: axis 0 into the temporaries, axis 1 into approx / cV (from lo) and cH / cD (from hi)
   int h = p.Hp, w = p.Wp;
@@ -1113,7 +1160,8 @@ int streaks_cohort(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d
                                                                 p.F, p.rec);
   }
   // 6. exp(r) - 1, blend, crop, store
-  if (u16 && out_dtype == DSX_U16) st_final<uint16_t, uint16_t>(s, p, d_in, ws + p.y, nb, ctx->st_t, d_out);
+  if (ctx->st_opts) st_blendx(ctx, s, StGenericBands{nb, p.Hp, p.Wp}, p.Wp, d_in, in_dtype, ws + p.y, nb, d_out, out_dtype);
+  else if (u16 && out_dtype == DSX_U16) st_final<uint16_t, uint16_t>(s, p, d_in, ws + p.y, nb, ctx->st_t, d_out);
   else if (u16) st_final<uint16_t, float>(s, p, d_in, ws + p.y, nb, ctx->st_t, d_out);
   else if (out_dtype == DSX_U16) st_final<float, uint16_t>(s, p, d_in, ws + p.y, nb, ctx->st_t, d_out);
   else st_final<float, float>(s, p, d_in, ws + p.y, nb, ctx->st_t, d_out);
@@ -2356,7 +2404,34 @@ int dsx_plan_streaks(dsx_ctx* ctx, int height, int width, int max_batch, const d
 }
 
 int dsx_plan_streaks_ex(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_streaks_cfg* cfg, int route) {
+  return dsx_plan_streaks_opts(ctx, height, width, max_batch, cfg, route, nullptr);
+}
+
+int dsx_plan_streaks_opts(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_streaks_cfg* cfg_in, int route,
+                          const dsx_streaks_opts* opts) {
   if (!ctx) return DSX_EINVAL;
+  const bool has_opts = opts && (opts->bands != DSX_STREAKS_BANDS_BOTH || opts->smoothing != 0.f || opts->flat || opts->dark);
+  int clip = 0;
+  dsx_streaks_cfg one_sided;
+  const dsx_streaks_cfg* cfg = cfg_in;
+  if (has_opts) {
+    if (opts->bands != DSX_STREAKS_BANDS_BOTH && opts->bands != DSX_STREAKS_BANDS_FG && opts->bands != DSX_STREAKS_BANDS_BG)
+      return fail(ctx, DSX_EINVAL, "unknown streaks band choice");
+    if (!(opts->smoothing >= 0.f && opts->smoothing <= 2.f))
+      return fail(ctx, DSX_EINVAL, "smoothing must be 0 or a value in (0, 2]");
+    if ((opts->flat == nullptr) != (opts->dark == nullptr))
+      return fail(ctx, DSX_EINVAL, "flatfield and darkfield must be given together");
+    if (opts->flat && (opts->dark_h < height || opts->dark_w < width))
+      return fail(ctx, DSX_EINVAL, "Please, check the shape of the darkfield.");
+    if (max_batch > 65535) return fail(ctx, DSX_EINVAL, "max_batch too large");
+    if (cfg_in && opts->bands != DSX_STREAKS_BANDS_BOTH) {  // the sigma of the band that is not filtered is not read
+      clip = opts->bands == DSX_STREAKS_BANDS_FG ? dsx::st::kStFg : dsx::st::kStBg;
+      one_sided = *cfg_in;
+      if (clip == dsx::st::kStFg) one_sided.sigma_bg = one_sided.sigma_fg;
+      else one_sided.sigma_fg = one_sided.sigma_bg;
+      cfg = &one_sided;
+    }
+  }
   if (route != DSX_STREAKS_GENERIC && route != DSX_STREAKS_MARCH) return fail(ctx, DSX_EINVAL, "unknown streaks route");
   if (!cfg) return fail(ctx, DSX_EINVAL, "config is NULL");
   if (height < 1 || width < 1) return fail(ctx, DSX_EINVAL, "plane must be at least 1 x 1");
@@ -2385,7 +2460,8 @@ int dsx_plan_streaks_ex(dsx_ctx* ctx, int height, int width, int max_batch, cons
   dsx::st::StreaksPlan& p = ctx->sp;
   p = dsx::st::StreaksPlan();
   p.H = height; p.W = width; p.B = max_batch;
-  p.bands = cfg->sigma_fg == cfg->sigma_bg ? 1 : 2;
+  p.bands = cfg->sigma_fg == cfg->sigma_bg ? 1 : 2;  // (a one-sided plan: the two are the filtered band's sigma)
+  p.clip = clip;
   p.sigma[0] = p.bands == 1 ? cfg->sigma_fg : cfg->sigma_bg;
   p.sigma[1] = cfg->sigma_fg;
   p.crossover = cfg->crossover;
@@ -2420,6 +2496,24 @@ int dsx_plan_streaks_ex(dsx_ctx* ctx, int height, int width, int max_batch, cons
     }
     return DSX_OK;
   };
+  // the options of the blend: state of the context, and the shading planes on the device
+  auto apply_opts = [&]() -> int {
+    if (!has_opts) return DSX_OK;
+    ctx->st_mode = clip ? clip : p.bands == 1 ? dsx::st::kStSingle : dsx::st::kStBoth;
+    ctx->st_R = opts->smoothing > 0.f ? dsx::st::st_smooth_radius((double)opts->smoothing) : 0;
+    if (ctx->st_R > 0) dsx::st::st_smooth_taps((double)opts->smoothing, ctx->st_R, ctx->st_taps);
+    if (opts->flat) {
+      const size_t fb = sizeof(float) * (size_t)height * width;
+      const size_t db = sizeof(float) * (size_t)opts->dark_h * opts->dark_w;
+      if (int rc = alloc((void**)&ctx->st_flat, fb)) return rc;
+      if (int rc = alloc((void**)&ctx->st_dark, db)) return rc;
+      DSX_HIP(hipMemcpy(ctx->st_flat, opts->flat, fb, hipMemcpyHostToDevice));
+      DSX_HIP(hipMemcpy(ctx->st_dark, opts->dark, db, hipMemcpyHostToDevice));
+      ctx->st_dark_w = opts->dark_w;
+    }
+    ctx->st_opts = true;
+    return DSX_OK;
+  };
   if (march) {
     // band(z, sigma) = log_space_fft_filtering(z, sigma min(H, W) / H, empty mask) - 2: the two filters differ in the
     // normalisation of s only (h sigma / H against h sigma / min(H, W)); cfg 0 = foreground (or the single) band
@@ -2445,6 +2539,7 @@ int dsx_plan_streaks_ex(dsx_ctx* ctx, int height, int width, int max_batch, cons
     if (int rc = alloc((void**)&ctx->st_t, sizeof(float) * max_batch)) return rc;
     if (int rc = alloc((void**)&ctx->st_info, sizeof(dsx::st::OtsuOut) * max_batch)) return rc;
     ctx->workspace_bytes += 2 * px * P * sizeof(float);
+    if (int rc = apply_opts()) return rc;
     ctx->streaks = true;
     ctx->last_n = 0;
     return DSX_OK;
@@ -2465,6 +2560,7 @@ int dsx_plan_streaks_ex(dsx_ctx* ctx, int height, int width, int max_batch, cons
   if (int rc = alloc((void**)&ctx->st_t, sizeof(float) * max_batch)) return rc;
   if (int rc = alloc((void**)&ctx->st_info, sizeof(dsx::st::OtsuOut) * max_batch)) return rc;
   DSX_HIP(hipMemcpy(ctx->st_mat, mats.data(), sizeof(float) * mats.size(), hipMemcpyHostToDevice));
+  if (int rc = apply_opts()) return rc;
   ctx->streaks = true;
   ctx->last_n = 0;
   return DSX_OK;
@@ -2477,6 +2573,31 @@ int dsx_get_streaks_threshold(dsx_ctx* ctx, int plane, float* threshold) {
   DSX_HIP(hipSetDevice(ctx->device));
   DSX_HIP(hipStreamSynchronize(use_main(ctx)));
   DSX_HIP(hipMemcpy(threshold, ctx->st_t + plane, sizeof(float), hipMemcpyDeviceToHost));
+  return DSX_OK;
+}
+
+int dsx_streaks_blend_ref(const float* x, const float* f, const float* b, int height, int width, float t,
+                          float crossover, const dsx_streaks_opts* opts, void* out, int out_dtype) {
+  using namespace dsx::st;
+  if (!x || !out) return fail(nullptr, DSX_EINVAL, "streaks blend: NULL pointer");
+  if (height < 1 || width < 1) return fail(nullptr, DSX_EINVAL, "plane must be at least 1 x 1");
+  if (!(crossover > 0.f)) return fail(nullptr, DSX_EINVAL, "crossover must be positive");
+  if (out_dtype != DSX_U16 && out_dtype != DSX_F32) return fail(nullptr, DSX_EINVAL, "unknown output type");
+  const int mode = opts ? opts->bands : DSX_STREAKS_BANDS_BOTH;
+  const float smoothing = opts ? opts->smoothing : 0.f;
+  if (mode != kStBoth && mode != kStFg && mode != kStBg) return fail(nullptr, DSX_EINVAL, "unknown streaks band choice");
+  if (!(smoothing >= 0.f && smoothing <= 2.f)) return fail(nullptr, DSX_EINVAL, "smoothing must be 0 or a value in (0, 2]");
+  if ((mode != kStBg && !f) || (mode != kStFg && !b)) return fail(nullptr, DSX_EINVAL, "streaks blend: a band plane is NULL");
+  const float* flat = opts ? opts->flat : nullptr;
+  const float* dark = opts ? opts->dark : nullptr;
+  if ((flat == nullptr) != (dark == nullptr)) return fail(nullptr, DSX_EINVAL, "flatfield and darkfield must be given together");
+  if (flat && (opts->dark_h < height || opts->dark_w < width))
+    return fail(nullptr, DSX_EINVAL, "Please, check the shape of the darkfield.");
+  const int dark_w = flat ? opts->dark_w : 0;
+  if (out_dtype == DSX_U16)
+    st_blend_host<uint16_t>(x, f, b, height, width, t, 1.0f / crossover, mode, (double)smoothing, flat, dark, dark_w, (uint16_t*)out);
+  else
+    st_blend_host<float>(x, f, b, height, width, t, 1.0f / crossover, mode, (double)smoothing, flat, dark, dark_w, (float*)out);
   return DSX_OK;
 }
 

@@ -28,6 +28,15 @@
 //   k_st_chainfill  what the chain's row filters read per virtual plane: mask threshold +inf on every level, cfg = band
 //   k_st_bands      the virtual input planes max(x, t) (2k) and min(x, t) (2k + 1), or x for a single band
 //   k_st_blend      (F - 2) w + (B - 2) (1 - w) of the chain's float32 planes, float32 / uint16 store
+//
+// Options (dsx_plan_streaks_opts: one-sided bands, a smoothed blend weight, dark / flat): k_st_blendx replaces k_st_final
+// and k_st_blend, on either route, when an option is set; with none set those two run as before.
+//   k_st_blendx     one body over a band-loader policy (StGenericBands: expm1 of the band-major [P][Hp][Wp] planes,
+//                   StMarchBands: r - 2 of the virtual planes); a block owns a 64 x 16 output tile, evaluates the
+//                   sigmoid of tile + halo into LDS once, smooths it there in two 1-D passes, blends, applies
+//                   flatfield_correction and stores float32 / uint16
+//   st_blend_host   the same weight, fold, tap, blend and epilogue functions over one plane on the host
+//                   (dsx_streaks_blend_ref)
 #ifndef DSX_STREAKS_H
 #define DSX_STREAKS_H
 
@@ -46,6 +55,9 @@ namespace st {
 constexpr int kStWin = 8192;    // uint16 histogram bins per LDS window (32 KiB)
 constexpr int kStBins = 65536;  // global histogram capacity per plane
 constexpr int kOtsuThreads = 1024;
+// which bands a plan filters (DSX_STREAKS_BANDS_*); kStSingle: equal sigmas, one band of the unclipped plane, no weight
+enum { kStBoth = 0, kStFg = 1, kStBg = 2, kStSingle = 3 };
+#define DSX_ST_HD __host__ __device__ __forceinline__
 
 struct Taps {
   float lo[kMaxTaps], hi[kMaxTaps];  // kMaxTaps: dsx_wavelet.h, the bound dsx_set_wavelet enforces
@@ -242,10 +254,11 @@ __global__ __launch_bounds__(256) void k_st_fill(float* t, int n, float v) {
 }
 
 // y[v][i][j], v = band * B + b: log(1 + min(x, t)) (band 0), log(1 + max(x, t)) (band 1), or log(1 + x) for a
-// single band; x of the plane edge-padded to Hp x Wp (last row / column repeated)
+// single band; x of the plane edge-padded to Hp x Wp (last row / column repeated).  clip (one band only): kStFg the
+// band is max(x, t), kStBg it is min(x, t) -- a one-sided plan writes only the band it filters
 template <typename T>
 __global__ __launch_bounds__(256) void k_st_prep(const T* __restrict__ in, int nb, int B, int H, int W, int Hp, int Wp,
-                                                 int bands, const float* t, float* y, unsigned* sticky) {
+                                                 int bands, int clip, const float* t, float* y, unsigned* sticky) {
   const size_t per = (size_t)Hp * Wp, total = per * nb * bands;
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
@@ -259,10 +272,12 @@ __global__ __launch_bounds__(256) void k_st_prep(const T* __restrict__ in, int n
   if (sizeof(T) == 4 && band == 0 && !(x > -1.0f && x < INFINITY) && sticky != nullptr) *(volatile unsigned*)sticky = 1u;
   float z = x;
   if (bands == 2) z = band == 0 ? fminf(x, t[b]) : fmaxf(x, t[b]);
+  else if (clip == kStFg) z = fmaxf(x, t[b]);
+  else if (clip == kStBg) z = fminf(x, t[b]);
   y[((size_t)band * B + b) * per + (size_t)i * Wp + j] = logf(1.0f + z);
 }
 
-__device__ __forceinline__ int st_refl(int i, int n) {  // half-sample symmetric extension, any distance
+DSX_ST_HD int st_refl(int i, int n) {  // half-sample symmetric extension, any distance
   const int p = 2 * n;
   i %= p;
   if (i < 0) i += p;
@@ -370,7 +385,7 @@ __global__ __launch_bounds__(256) void k_st_rowmat(const float* __restrict__ X, 
 }
 
 // w of the blend: the reference's foreground_fraction(x, t, crossover)
-__device__ __forceinline__ float st_weight(float x, float t, float inv_crossover) {
+DSX_ST_HD float st_weight(float x, float t, float inv_crossover) {
   return 1.0f / (1.0f + expf(-(x - t) * inv_crossover));
 }
 
@@ -411,16 +426,17 @@ struct alignas(sizeof(T) * N) StVec {
   T v[N];
 };
 
-__global__ __launch_bounds__(256) void k_st_chainfill(float* thr, int n_thr, int* cfg, int n_cfg, int bands) {
+// one: the cfg of every plane when there is one band per real plane (1 for a background-only plan, else 0)
+__global__ __launch_bounds__(256) void k_st_chainfill(float* thr, int n_thr, int* cfg, int n_cfg, int bands, int one) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_thr) thr[i] = INFINITY;
-  if (i < n_cfg) cfg[i] = bands == 2 ? (i & 1) : 0;
+  if (i < n_cfg) cfg[i] = bands == 2 ? (i & 1) : one;
 }
 
-// grid (blocks, planes); v: [bands * planes][px]
+// grid (blocks, planes); v: [bands * planes][px].  clip (one band only): kStFg writes max(x, t), kStBg min(x, t)
 template <typename TI, typename TV, int VEC>
-__global__ __launch_bounds__(256) void k_st_bands(const TI* __restrict__ in, size_t px, int bands, const float* t,
-                                                  TV* __restrict__ v, unsigned* sticky) {
+__global__ __launch_bounds__(256) void k_st_bands(const TI* __restrict__ in, size_t px, int bands, int clip,
+                                                  const float* t, TV* __restrict__ v, unsigned* sticky) {
   const int b = blockIdx.y;
   const float tb = t[b];
   const TI* p = in + (size_t)b * px;
@@ -436,7 +452,7 @@ __global__ __launch_bounds__(256) void k_st_bands(const TI* __restrict__ in, siz
       const float xv = (float)x.v[k];
       // as k_st_prep: a float32 pixel without a finite log(1 + x) flags the context's host-mapped word
       if (sizeof(TI) == 4 && !(xv > -1.0f && xv < INFINITY)) bad = true;
-      hi.v[k] = (TV)(bands == 2 ? fmaxf(xv, tb) : xv);
+      hi.v[k] = (TV)(bands == 2 || clip == kStFg ? fmaxf(xv, tb) : clip == kStBg ? fminf(xv, tb) : xv);
       lo.v[k] = (TV)fminf(xv, tb);
     }
     *(StVec<TV, VEC>*)(f + i) = hi;
@@ -480,6 +496,212 @@ __global__ __launch_bounds__(256) void k_st_blend(const TI* __restrict__ in, con
   }
 }
 
+// ---- blend with options ---------------------------------------------------------------------------------------------
+// w0 = st_weight(x) on the unpadded H x W plane; w = w0, or scipy.ndimage.gaussian_filter(w0, s) (separable, radius
+// R = int(4 s + 0.5), taps exp(-k^2 / 2 s^2) normalised to sum 1, indices folded by st_refl); then
+//   both bands f w + b (1 - w), foreground only f w + x (1 - w), background only x w + b (1 - w), single band f,
+// and, with a flat, the reference's flatfield_correction(r, flat, dark).
+constexpr int kStMaxR = 8;                      // s <= 2
+constexpr int kBtW = 64, kBtH = 16;             // output tile of a block: 16 threads of 4 pixels across, 16 rows
+constexpr int kBtPitch0 = kBtW + 2 * kStMaxR;   // row pitch of the sigmoid tile
+// The row pass writes rows of kBtW = 64 floats: a whole bank row, so the four 16-lane groups of the column pass's
+// ds_read_b128 (each 8 lanes of one tile row and 8 of the next, MI355X LDS banking) fall on 64 distinct banks.
+
+inline int st_smooth_radius(double s) { return (int)(4.0 * s + 0.5); }
+
+inline void st_smooth_taps(double s, int R, float* taps) {  // taps[k], k = 0 .. R (the kernel is symmetric)
+  double k[kStMaxR + 1], sum = 0.0;
+  for (int q = 0; q <= R; ++q) {
+    k[q] = exp(-0.5 * (double)q * q / (s * s));
+    sum += q ? 2.0 * k[q] : k[q];
+  }
+  for (int q = 0; q <= kStMaxR; ++q) taps[q] = q <= R ? (float)(k[q] / sum) : 0.f;
+}
+
+// one 1-D pass at N neighbouring centres p[0 .. N): taps[0] p[q] + sum_k taps[k] (p[q - k stride] + p[q + k stride])
+template <int N>
+DSX_ST_HD void st_tap_sum(const float* p, int stride, const float* taps, int R, float* out) {
+  const StVec<float, N> c = *(const StVec<float, N>*)p;
+#pragma unroll
+  for (int q = 0; q < N; ++q) out[q] = taps[0] * c.v[q];
+  for (int k = 1; k <= R; ++k) {
+    const StVec<float, N> lo = *(const StVec<float, N>*)(p - k * stride);
+    const StVec<float, N> hi = *(const StVec<float, N>*)(p + k * stride);
+#pragma unroll
+    for (int q = 0; q < N; ++q) out[q] = fmaf(taps[k], lo.v[q] + hi.v[q], out[q]);
+  }
+}
+
+DSX_ST_HD float st_blend_px(int mode, float f, float b, float x, float w) {
+  if (mode == kStSingle) return f;
+  const float hi = mode == kStBg ? x : f, lo = mode == kStFg ? x : b;
+  return hi * w + lo * (1.0f - w);
+}
+
+// flatfield_correction(r, flat, dark) of the float result, before the store's truncation
+DSX_ST_HD float st_shade_px(float v, float flat, float dark) {
+  v = v > dark ? v - dark : 0.f;
+  v = v / flat;
+  return fminf(fmaxf(v, 0.f), 65535.f);
+}
+
+template <typename TO>
+DSX_ST_HD TO st_store_px(float v) {
+  if (sizeof(TO) == 2) return (TO)(unsigned)fminf(fmaxf(v, 0.0f), 65535.0f);
+  return (TO)v;
+}
+
+// Band loaders: where band `slot` of real plane b keeps pixel (i, j), which slot a band has, and band value from r.
+struct StGenericBands {  // [P][Hp][Wp], band-major: the background (or only) band first, then the foreground
+  int nb, Hp, Wp;
+  DSX_ST_HD size_t at(int slot, int b, int i, int j) const {
+    return ((size_t)slot * nb + b) * ((size_t)Hp * Wp) + (size_t)i * Wp + j;
+  }
+  DSX_ST_HD int fg_slot(int mode) const { return mode == kStBoth ? 1 : 0; }
+  DSX_ST_HD int bg_slot(int) const { return 0; }
+  static DSX_ST_HD float value(float r) { return expm1f(r); }
+};
+struct StMarchBands {  // virtual planes bands * b (foreground or only band) and bands * b + 1 (background), band + 2
+  int bands, W;
+  size_t px;
+  DSX_ST_HD size_t at(int slot, int b, int i, int j) const {
+    return ((size_t)bands * b + slot) * px + (size_t)i * W + j;
+  }
+  DSX_ST_HD int fg_slot(int) const { return 0; }
+  DSX_ST_HD int bg_slot(int mode) const { return mode == kStBoth ? 1 : 0; }
+  static DSX_ST_HD float value(float r) { return r - 2.0f; }
+};
+
+struct BlendArgs {
+  const void* in;     // [nb][H][W]
+  const float* r;     // the band planes, laid out as the loader says
+  void* out;          // [nb][H][W]
+  const float* t;     // [nb]
+  const float* flat;  // [H][W], or nullptr: no dark / flat step
+  const float* dark;  // [>= H][dark_w]
+  int H, W, dark_w, mode, R;
+  int vec;            // W, the band pitch and dark_w are multiples of 4 and every pointer is 16-byte aligned
+  float inv_crossover;
+  float taps[kStMaxR + 1];
+};
+
+// n <= 4 pixels from p into dst (the rest 0); vec: one 16- (float) or 8-byte (uint16) access
+template <typename T>
+__device__ __forceinline__ void st_load4(const T* p, bool vec, int n, float* dst) {
+  if (vec) {
+    const StVec<T, 4> v = *(const StVec<T, 4>*)p;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dst[q] = (float)v.v[q];
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dst[q] = q < n ? (float)p[q] : 0.f;
+  }
+}
+
+// grid (ceil(W / 64), ceil(H / 16), planes); SMOOTH: a.R >= 1 and the weight goes through the two LDS passes
+template <typename L, typename TI, typename TO, bool SMOOTH>
+__global__ __launch_bounds__(256) void k_st_blendx(BlendArgs a, L ld) {
+  constexpr int kRows = kBtH + 2 * kStMaxR;
+  __shared__ float sw[SMOOTH ? kRows * kBtPitch0 : 1];                     // sigmoid of tile + halo
+  __shared__ __attribute__((aligned(16))) float sh[SMOOTH ? kRows * kBtW : 4];  // after the row pass
+  __shared__ __attribute__((aligned(16))) float sx[SMOOTH ? kBtH * kBtW : 4];   // x of the tile
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int b = blockIdx.z, i0 = blockIdx.y * kBtH, j0 = blockIdx.x * kBtW;
+  const int i = i0 + ty, j = j0 + 4 * tx;
+  const float tb = a.t[b];
+  const TI* xin = (const TI*)a.in + (size_t)b * a.H * a.W;
+  const int mode = a.mode;
+  const bool vec = a.vec != 0;
+  float w[4] = {0.f, 0.f, 0.f, 0.f}, x[4] = {0.f, 0.f, 0.f, 0.f};
+  if (SMOOTH) {
+    const int R = a.R, th = kBtH + 2 * R, tw = kBtW + 2 * R;
+    for (int e = tid; e < th * tw; e += 256) {
+      const int rr = e / tw, cc = e - rr * tw;
+      int gi = i0 + rr - R, gj = j0 + cc - R;
+      if ((unsigned)gi >= (unsigned)a.H) gi = st_refl(gi, a.H);
+      if ((unsigned)gj >= (unsigned)a.W) gj = st_refl(gj, a.W);
+      const float xv = pix(xin, (size_t)gi * a.W + gj);
+      sw[rr * kBtPitch0 + cc] = st_weight(xv, tb, a.inv_crossover);
+      if (rr >= R && rr < R + kBtH && cc >= R && cc < R + kBtW) sx[(rr - R) * kBtW + (cc - R)] = xv;
+    }
+    __syncthreads();
+    for (int e = tid; e < th * kBtW; e += 256) {
+      const int rr = e >> 6, cc = e & 63;
+      st_tap_sum<1>(&sw[rr * kBtPitch0 + cc + R], 1, a.taps, R, &sh[rr * kBtW + cc]);
+    }
+    __syncthreads();
+    st_tap_sum<4>(&sh[(ty + R) * kBtW + 4 * tx], kBtW, a.taps, R, w);
+    const StVec<float, 4> xs = *(const StVec<float, 4>*)&sx[ty * kBtW + 4 * tx];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) x[q] = xs.v[q];
+  }
+  if (i >= a.H || j >= a.W) return;
+  const int n = min(4, a.W - j);
+  const size_t o = (size_t)i * a.W + j;
+  if (!SMOOTH && mode != kStSingle) {
+    st_load4(xin + o, vec, n, x);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) w[q] = st_weight(x[q], tb, a.inv_crossover);
+  }
+  float f[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
+  if (mode != kStBg) st_load4(a.r + ld.at(ld.fg_slot(mode), b, i, j), vec, n, f);
+  if (mode == kStBoth || mode == kStBg) st_load4(a.r + ld.at(ld.bg_slot(mode), b, i, j), vec, n, g);
+  float fl[4] = {1.f, 1.f, 1.f, 1.f}, dk[4] = {0.f, 0.f, 0.f, 0.f};
+  if (a.flat != nullptr) {
+    st_load4(a.flat + o, vec, n, fl);
+    st_load4(a.dark + (size_t)i * a.dark_w + j, vec, n, dk);
+  }
+  StVec<TO, 4> ov;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    float res = st_blend_px(mode, L::value(f[q]), L::value(g[q]), x[q], w[q]);
+    if (a.flat != nullptr) res = st_shade_px(res, fl[q], dk[q]);
+    ov.v[q] = st_store_px<TO>(res);
+  }
+  TO* dst = (TO*)a.out + (size_t)b * a.H * a.W + o;
+  if (vec) {
+    *(StVec<TO, 4>*)dst = ov;
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (q < n) dst[q] = ov.v[q];
+  }
+}
+
+// The blend of ONE plane on the host, from the functions above: x, f, b [H][W] float32 (f / b may be nullptr where the
+// mode does not read them), band values as they are (no loader), out [H][W] float32 or uint16.
+template <typename TO>
+inline void st_blend_host(const float* x, const float* f, const float* b, int H, int W, float t, float inv_crossover,
+                          int mode, double smoothing, const float* flat, const float* dark, int dark_w, TO* out) {
+  const size_t px = (size_t)H * W;
+  std::vector<float> w(px, 0.f);
+  if (mode != kStSingle) {
+    for (size_t k = 0; k < px; ++k) w[k] = st_weight(x[k], t, inv_crossover);
+    const int R = smoothing > 0.0 ? st_smooth_radius(smoothing) : 0;
+    if (R > 0) {
+      float taps[kStMaxR + 1];
+      st_smooth_taps(smoothing, R, taps);
+      // each pass over a line folded out to R on both sides, as the kernel's LDS tile is
+      std::vector<float> line((size_t)std::max(H, W) + 2 * R), tmp(px);
+      for (int i = 0; i < H; ++i) {
+        for (int c = -R; c < W + R; ++c) line[c + R] = w[(size_t)i * W + st_refl(c, W)];
+        for (int c = 0; c < W; ++c) st_tap_sum<1>(&line[c + R], 1, taps, R, &tmp[(size_t)i * W + c]);
+      }
+      for (int c = 0; c < W; ++c) {
+        for (int i = -R; i < H + R; ++i) line[i + R] = tmp[(size_t)st_refl(i, H) * W + c];
+        for (int i = 0; i < H; ++i) st_tap_sum<1>(&line[i + R], 1, taps, R, &w[(size_t)i * W + c]);
+      }
+    }
+  }
+  for (int i = 0; i < H; ++i)
+    for (int c = 0; c < W; ++c) {
+      const size_t k = (size_t)i * W + c;
+      float res = st_blend_px(mode, f ? f[k] : 0.f, b ? b[k] : 0.f, x[k], w[k]);
+      if (flat != nullptr) res = st_shade_px(res, flat[k], dark[(size_t)i * dark_w + c]);
+      out[k] = st_store_px<TO>(res);
+    }
+}
+
 // ---- host side: geometry of a plan and the row-filter operators ---------------------------------------------------
 constexpr int kStMaxLevels = 32;
 
@@ -493,6 +715,7 @@ struct StLevel {
 
 struct StreaksPlan {
   int H = 0, W = 0, Hp = 0, Wp = 0, L = 0, F = 0, bands = 1, B = 0;
+  int clip = 0;  // one band (bands == 1) of a clipped plane: kStFg max(x, t), kStBg min(x, t); 0: the plane itself
   float sigma[2] = {0.f, 0.f};  // band 0 (background / single), band 1 (foreground)
   float crossover = 10.f, threshold = 0.f;
   int otsu = 1;

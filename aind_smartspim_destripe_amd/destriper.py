@@ -130,7 +130,8 @@ def read_filter_save(
         return
     dtype = _target_dtype(raw_image.dtype, output_dtype)
     if streaks is not None:
-        filtered_image = fl.filter_streaks(raw_image, **streaks)
+        flat, dark = fl._resolve_shading(shadow_correction, input_path)
+        filtered_image = fl.filter_streaks(raw_image, **fl.streaks_call_options(streaks, flat, dark))
         _save_with_retries(output_path, filtered_image.astype(dtype), compression, output_format)
         return
     filtered_image = fl.filter_stripes(
@@ -144,13 +145,12 @@ def read_filter_save(
 
 
 def _streaks_options(streaks, shadow_correction):
-    """The checked ``streaks`` dict (``filtering.streaks_options``) or ``None``; the dual-band filter has no dark / flat
-    step, so it refuses a ``shadow_correction``."""
+    """The checked ``streaks`` dict (``filtering.streaks_options``) or ``None``; the dual-band filter applies a
+    ``shadow_correction`` only with ``"shading": True`` and refuses it otherwise."""
     if streaks is None:
         return None
     streaks = fl.streaks_options(streaks)
-    if shadow_correction is not None:
-        raise ValueError("streaks: the dual-band filter has no dark / flat step; shadow_correction must be None")
+    fl.streaks_shading(streaks, shadow_correction)
     return streaks
 
 
@@ -215,8 +215,10 @@ def batch_filter(
     ``streaks``: a dict ``{"sigma": (fg, bg), "level": 0, "wavelet": "db3", "crossover": 10, "threshold": -1,
     "route": "auto"}`` (defaults as in ``filtering.filter_streaks``; unknown keys raise ``TypeError``) runs the dual-band
     filter (``filtering.destripe_streaks_planes``) on every group of planes instead of the stripe filter; the two
-    parameter dicts are not read then and ``shadow_correction`` must be ``None`` (``ValueError``, before anything is
-    created).
+    parameter dicts are not read then.  Optional keys: ``"smoothing"`` (sigma of the gaussian over the blend weight,
+    0 .. 2) and ``"shading": True``, with which the ``shadow_correction`` is resolved per folder as for the stripe
+    filter and applied to the filter's result; without it ``shadow_correction`` must be ``None`` (``ValueError``,
+    before anything is created).
     """
     streaks = _streaks_options(streaks, shadow_correction)
     input_path, output_path = Path(input_path), Path(output_path)
@@ -247,8 +249,10 @@ def batch_filter(
                 want = _target_dtype(stack.dtype, output_dtype)
                 as_u16 = shaded or np.dtype(want) == np.uint16
                 if streaks is not None:
+                    flat, dark = fl._resolve_shading(shadow_correction, str(paths[ks[0]]))
                     res = fl.destripe_streaks_planes(stack, out_dtype=np.uint16 if as_u16 else np.float32,
-                                                     max_batch=min(batch, 64), device=device, **streaks)  # fmt: skip
+                                                     max_batch=min(batch, 64), device=device,
+                                                     **fl.streaks_call_options(streaks, flat, dark))  # fmt: skip
                 else:
                     res = fl.destripe_planes(
                         stack,

@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "dsx_pyramid_work_bytes", "dsx_pyramid_block_u16", "dsx_pyramid_block_ref",
     "dsx_pyramid_bricks_u16", "dsx_pyramid_bricks_ref",
     "dsx_volhist_reset", "dsx_volhist_add_device", "dsx_volhist_get", "dsx_volhist_ref",
+    "dsx_plan_streaks_opts", "dsx_streaks_blend_ref",
 ]  # fmt: skip
 
 
@@ -99,6 +100,17 @@ class _StreaksCfg(ctypes.Structure):
         ("crossover", ctypes.c_float),
         ("otsu", ctypes.c_int32),
         ("threshold", ctypes.c_float),
+    ]
+
+
+class _StreaksOpts(ctypes.Structure):
+    _fields_ = [
+        ("bands", ctypes.c_int32),
+        ("smoothing", ctypes.c_float),
+        ("flat", ctypes.c_void_p),
+        ("dark", ctypes.c_void_p),
+        ("dark_h", ctypes.c_int32),
+        ("dark_w", ctypes.c_int32),
     ]
 
 
@@ -204,6 +216,10 @@ def load_library(path=None):
     lib.dsx_plan_streaks.argtypes = [vp, i32, i32, i32, ctypes.POINTER(_StreaksCfg)]
     lib.dsx_plan_streaks_ex.argtypes = [vp, i32, i32, i32, ctypes.POINTER(_StreaksCfg), i32]
     lib.dsx_get_streaks_threshold.argtypes = [vp, i32, f32p]
+    lib.dsx_plan_streaks_opts.argtypes = [vp, i32, i32, i32, ctypes.POINTER(_StreaksCfg), i32,
+                                          ctypes.POINTER(_StreaksOpts)]  # fmt: skip
+    lib.dsx_streaks_blend_ref.argtypes = [vp, vp, vp, i32, i32, ctypes.c_float, ctypes.c_float,
+                                          ctypes.POINTER(_StreaksOpts), vp, i32]  # fmt: skip
     lib.dsx_blosc_decode.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t]
     lib.dsx_blosc_encode.argtypes = [vp, ctypes.c_size_t, i32, i32, i32, vp, ctypes.c_size_t,
                                      ctypes.POINTER(ctypes.c_size_t)]  # fmt: skip
@@ -239,6 +255,40 @@ def load_library(path=None):
 
 
 STREAKS_ROUTES = {"generic": 0, "march": 1}  # DSX_STREAKS_GENERIC, DSX_STREAKS_MARCH
+STREAKS_BANDS = {"both": 0, "fg": 1, "bg": 2}  # DSX_STREAKS_BANDS_BOTH, _FG, _BG
+STREAKS_MAX_SMOOTHING = 2.0
+
+
+def streaks_smoothing(smoothing):
+    """``smoothing`` of the blend weight as a float: 0 (none) or ``0 < s <= 2``; ``ValueError`` for anything else."""
+    try:
+        s = float(smoothing)
+    except (TypeError, ValueError):
+        raise ValueError("smoothing must be 0 or a value in (0, 2], not {!r}".format(smoothing))
+    if not (0.0 <= s <= STREAKS_MAX_SMOOTHING):  # (nan fails both comparisons)
+        raise ValueError("smoothing must be 0 or a value in (0, 2], not {!r}".format(smoothing))
+    return s
+
+
+def _shading_planes(flatfield, darkfield, out_shape):
+    """float32 flat / dark of a plan, with the checks (and messages) of ``flatfield_correction()``,
+    filtering.py:377-391: the dark is at least the plane (cropped by indexing), the flat is the plane."""
+    flat = np.ascontiguousarray(flatfield, dtype=np.float32)
+    dark = np.ascontiguousarray(darkfield, dtype=np.float32)
+    if flat.ndim != 2 or dark.ndim != 2:
+        raise ValueError("flatfield / darkfield must be 2-D planes")
+    cropped = dark[: out_shape[0], : out_shape[1]].shape
+    if cropped != out_shape:
+        raise ValueError(
+            "Please, check the shape of the darkfield. "
+            "Image: {} - Darkfield: {}".format(out_shape, cropped)
+        )
+    if flat.shape != out_shape:
+        raise ValueError(
+            "Please, check the shape of the flatfield."
+            "Image: {} - Flatfield: {}".format(out_shape, flat.shape)
+        )
+    return flat, dark
 # What "auto" resolves to where the march route applies.  The march route's rate has not been measured, so "auto" is the
 # generic route everywhere; it becomes "march" here once a same-session record (tools/bench_streaks.py with both
 # routes, README "filter_streaks") shows march ahead.  Elsewhere "auto" is the generic route in any case.
@@ -413,23 +463,7 @@ class DestripeEngine:
             raise ValueError("flatfield and darkfield must be given together")
         info = call(None, None, 0, 0)
         if flatfield is not None:
-            flat = np.ascontiguousarray(flatfield, dtype=np.float32)
-            dark = np.ascontiguousarray(darkfield, dtype=np.float32)
-            out_shape = (info.out_height, info.out_width)
-            if flat.ndim != 2 or dark.ndim != 2:
-                raise ValueError("flatfield / darkfield must be 2-D planes")
-            # same checks (and messages) as flatfield_correction(), filtering.py:377-391
-            cropped = dark[: out_shape[0], : out_shape[1]].shape
-            if cropped != out_shape:
-                raise ValueError(
-                    "Please, check the shape of the darkfield. "
-                    "Image: {} - Darkfield: {}".format(out_shape, cropped)
-                )
-            if flat.shape != out_shape:
-                raise ValueError(
-                    "Please, check the shape of the flatfield."
-                    "Image: {} - Flatfield: {}".format(out_shape, flat.shape)
-                )
+            flat, dark = _shading_planes(flatfield, darkfield, (info.out_height, info.out_width))
             info = call(flat.ctypes.data_as(ctypes.c_void_p), dark.ctypes.data_as(ctypes.c_void_p),
                         dark.shape[0], dark.shape[1])  # fmt: skip
         self.info = info
@@ -437,12 +471,31 @@ class DestripeEngine:
         return info
 
     def plan_streaks(self, height, width, sigma_fg, sigma_bg, wavelet="db3", level=0, crossover=10.0,
-                     threshold=None, max_batch=32, route="generic"):  # fmt: skip
+                     threshold=None, max_batch=32, route="generic", bands="both", smoothing=0.0, flatfield=None,
+                     darkfield=None):  # fmt: skip
         """Plan the dual-band filter (``dsx_plan_streaks_ex``); ``threshold=None``: Otsu per plane.  Replaces any plan
         of this engine; :meth:`run` / :meth:`run_device` then return ``[n, height, width]``.  ``route``: ``"generic"``
         (the per-band kernels of the filter, any wavelet and plane), ``"march"`` (the bands run through the log-space
         db3 chain; db3, even planes and levels up to the maximum only, ``ValueError`` elsewhere) or ``"auto"``
-        (``AUTO_ROUTE`` where march applies -- generic until a measurement shows march ahead -- generic elsewhere)."""
+        (``AUTO_ROUTE`` where march applies -- generic until a measurement shows march ahead -- generic elsewhere).
+
+        Options of the blend (``dsx_plan_streaks_opts``; with none given the plan is ``dsx_plan_streaks_ex``):
+        ``bands`` ``"both"``, ``"fg"`` (only the foreground band is filtered and blended with the raw plane,
+        ``sigma_bg`` is not read) or ``"bg"`` (the same for the background band); ``smoothing`` 0 or ``0 < s <= 2``, the
+        sigma of ``scipy.ndimage.gaussian_filter`` over the blend weight; ``flatfield`` / ``darkfield`` (together, shapes
+        as in :meth:`plan`): the reference's ``flatfield_correction`` of the blend result."""
+        if bands not in STREAKS_BANDS:
+            raise ValueError("bands must be 'both', 'fg' or 'bg', not {!r}".format(bands))
+        smoothing = streaks_smoothing(smoothing)
+        if (flatfield is None) != (darkfield is None):
+            raise ValueError("flatfield and darkfield must be given together")
+        flat = dark = None
+        if flatfield is not None:
+            flat, dark = _shading_planes(flatfield, darkfield, (int(height), int(width)))
+        if bands == "fg":
+            sigma_bg = sigma_fg
+        elif bands == "bg":
+            sigma_fg = sigma_bg
         route = streaks_route(route, height, width, wavelet, level)
         key = _wavelet_key({"wavelet": wavelet})
         wid = DSX_WAVELET_DB3 if key == "db3" else DSX_WAVELET_BANK
@@ -455,8 +508,11 @@ class DestripeEngine:
             self._check(rc)
         cfg = _StreaksCfg(wid, int(level or 0), float(sigma_fg), float(sigma_bg), float(crossover),
                           1 if threshold is None else 0, 0.0 if threshold is None else float(threshold))  # fmt: skip
-        rc = self._lib.dsx_plan_streaks_ex(self._ctx, int(height), int(width), int(max_batch), ctypes.byref(cfg),
-                                           STREAKS_ROUTES[route])  # fmt: skip
+        opts = _StreaksOpts(STREAKS_BANDS[bands], smoothing, None if flat is None else flat.ctypes.data,
+                            None if dark is None else dark.ctypes.data, 0 if dark is None else dark.shape[0],
+                            0 if dark is None else dark.shape[1])  # fmt: skip
+        rc = self._lib.dsx_plan_streaks_opts(self._ctx, int(height), int(width), int(max_batch), ctypes.byref(cfg),
+                                             STREAKS_ROUTES[route], ctypes.byref(opts))  # fmt: skip
         if rc == -1:
             raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
         self._check(rc)
@@ -879,6 +935,39 @@ def volhist_ref(array, hist=None):
     if rc != 0:
         raise ValueError((lib.dsx_last_error(None) or b"volhist_ref failed").decode())
     return hist
+
+
+def streaks_blend_ref(x, f, b, t, crossover=10.0, bands="both", smoothing=0.0, flatfield=None, darkfield=None,
+                      out_dtype=np.float32):
+    """Host build of the options blend of a streaks plan (``dsx_streaks_blend_ref``) over one plane: ``x`` the plane,
+    ``f`` / ``b`` the filtered foreground / background bands (``None`` for the band a one-sided ``bands`` leaves out),
+    all ``[H, W]``; the arithmetic is the kernel's own.  No device call."""
+    if bands not in STREAKS_BANDS:
+        raise ValueError("bands must be 'both', 'fg' or 'bg', not {!r}".format(bands))
+    smoothing = streaks_smoothing(smoothing)
+    if (flatfield is None) != (darkfield is None):
+        raise ValueError("flatfield and darkfield must be given together")
+    lib = load_library()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2 or x.size == 0:
+        raise ValueError("x must be one non-empty 2-D plane")
+    planes = [None if p is None else np.ascontiguousarray(p, dtype=np.float32) for p in (f, b)]
+    for p in planes:
+        if p is not None and p.shape != x.shape:
+            raise ValueError("the band planes must have the shape of x")
+    flat = dark = None
+    if flatfield is not None:
+        flat, dark = _shading_planes(flatfield, darkfield, x.shape)
+    opts = _StreaksOpts(STREAKS_BANDS[bands], smoothing, None if flat is None else flat.ctypes.data,
+                        None if dark is None else dark.ctypes.data, 0 if dark is None else dark.shape[0],
+                        0 if dark is None else dark.shape[1])  # fmt: skip
+    out = np.empty(x.shape, dtype=out_dtype)
+    rc = lib.dsx_streaks_blend_ref(x.ctypes.data, *[None if p is None else p.ctypes.data for p in planes],
+                                   x.shape[0], x.shape[1], float(t), float(crossover), ctypes.byref(opts),
+                                   out.ctypes.data, _dtype_code(out_dtype))  # fmt: skip
+    if rc != 0:
+        raise ValueError((lib.dsx_last_error(None) or b"streaks_blend_ref failed").decode())
+    return out
 
 
 def pyramid_block_ref(planes, chunks, z0s=None, bricks=None, rows=None):

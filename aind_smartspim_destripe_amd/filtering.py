@@ -306,11 +306,15 @@ def log_space_fft_filtering(
 
 
 def _streaks_params(sigma, level, wavelet, crossover, threshold):
-    """Checks of the dual-band form (every one before any device call); returns (sigma_fg, sigma_bg, level)."""
-    if isinstance(sigma, (str, bytes)) or np.ndim(sigma) != 1 or len(sigma) != 2:
+    """Checks of the dual-band form (every one before any device call); returns (sigma_fg, sigma_bg, level).  One
+    member of the pair may be ``None``: that band is not filtered (the blend takes the raw plane in its place)."""
+    if isinstance(sigma, (str, bytes)) or not isinstance(sigma, (tuple, list, np.ndarray)) or len(sigma) != 2 \
+            or any(v is not None and np.ndim(v) != 0 for v in sigma):  # fmt: skip
         raise ValueError("sigma must be a number or a pair (sigma_fg, sigma_bg)")
-    sigma_fg, sigma_bg = (float(v) for v in sigma)
-    if not (sigma_fg > 0 and sigma_bg > 0):
+    if sigma[0] is None and sigma[1] is None:
+        raise ValueError("sigma: at least one of (sigma_fg, sigma_bg) must be a number")
+    sigma_fg, sigma_bg = (None if v is None else float(v) for v in sigma)
+    if not all(v is None or v > 0 for v in (sigma_fg, sigma_bg)):
         raise ValueError("sigma must be positive")
     if not (float(crossover) > 0):
         raise ValueError("crossover must be positive")
@@ -323,11 +327,13 @@ def _streaks_params(sigma, level, wavelet, crossover, threshold):
 
 
 def _streaks_engine(shape, sigma_fg, sigma_bg, level, wavelet, crossover, threshold, max_batch, device,
-                    route="generic"):  # fmt: skip
-    """Planned streaks engine (cached per process and device); ``route`` is resolved: ``generic`` or ``march``."""
+                    route="generic", smoothing=0.0, flat=None, dark=None):  # fmt: skip
+    """Planned streaks engine (cached per process and device); ``route`` is resolved: ``generic`` or ``march``.
+    ``sigma_fg`` / ``sigma_bg``: one may be ``None`` (a one-sided plan)."""
     fixed = None if float(threshold) == -1 else float(threshold)
+    shade_key = None if flat is None else (_array_key(flat), _array_key(dark))
     key = (device, "streaks", tuple(shape), sigma_fg, sigma_bg, level, _engine._wavelet_key({"wavelet": wavelet}),
-           float(crossover), fixed, int(max_batch), route)  # fmt: skip
+           float(crossover), fixed, int(max_batch), route, float(smoothing), shade_key)  # fmt: skip
     eng = _ENGINES.get(key)
     if eng is not None:
         _ENGINES.move_to_end(key)
@@ -336,22 +342,30 @@ def _streaks_engine(shape, sigma_fg, sigma_bg, level, wavelet, crossover, thresh
         _, old = _ENGINES.popitem(last=False)
         old[0].close()
     e = _engine.DestripeEngine(device)
-    e.plan_streaks(shape[0], shape[1], sigma_fg, sigma_bg, wavelet=wavelet, level=level, crossover=crossover,
-                   threshold=fixed, max_batch=max_batch, route=route)  # fmt: skip
-    _ENGINES[key] = (e, None, None)
+    bands = "fg" if sigma_bg is None else "bg" if sigma_fg is None else "both"
+    e.plan_streaks(shape[0], shape[1], sigma_bg if sigma_fg is None else sigma_fg,
+                   sigma_fg if sigma_bg is None else sigma_bg, wavelet=wavelet, level=level, crossover=crossover,
+                   threshold=fixed, max_batch=max_batch, route=route, bands=bands, smoothing=smoothing, flatfield=flat,
+                   darkfield=dark)  # fmt: skip
+    # (the shading arrays stay referenced, so their addresses stay unique while the plan is cached)
+    _ENGINES[key] = (e, flat, dark)
     return e
 
 
 STREAKS_DEFAULTS = {"sigma": None, "level": 0, "wavelet": "db3", "crossover": 10, "threshold": -1, "route": "auto"}
+# optional keys of the ``streaks=`` dict: passed through (checked) only when present
+STREAKS_OPTIONAL = ("smoothing", "shading")
 
 
 def streaks_options(streaks):
     """The ``streaks=`` dict of the pipelines (``destripe_zarr_store``, ``destripe_zarr``, ``batch_filter``), checked
     and completed with the defaults of :func:`filter_streaks` (``route``: ``"auto"``): ``TypeError`` for an unknown key
-    or a missing ``sigma`` pair, ``ValueError`` for a bad value.  No device call."""
+    or a missing ``sigma`` pair, ``ValueError`` for a bad value.  The optional keys ``"smoothing"`` (0 or
+    ``0 < s <= 2``) and ``"shading"`` (a bool: apply the pipeline's ``shadow_correction`` to the filter's result) are
+    in the result only when they were given.  No device call."""
     if not isinstance(streaks, dict):
         raise TypeError("streaks must be a dict {'sigma': (fg, bg), ...}")
-    unknown = sorted(set(streaks) - set(STREAKS_DEFAULTS))
+    unknown = sorted(set(streaks) - set(STREAKS_DEFAULTS) - set(STREAKS_OPTIONAL))
     if unknown:
         raise TypeError("streaks got unexpected keys: {}".format(unknown))
     opt = dict(STREAKS_DEFAULTS, **streaks)
@@ -362,7 +376,31 @@ def streaks_options(streaks):
     sigma_fg, sigma_bg, opt["level"] = _streaks_params(opt["sigma"], opt["level"], opt["wavelet"], opt["crossover"],
                                                        opt["threshold"])  # fmt: skip
     opt["sigma"] = (sigma_fg, sigma_bg)
+    if "smoothing" in opt:
+        opt["smoothing"] = _engine.streaks_smoothing(opt["smoothing"])
+    if "shading" in opt:
+        if not isinstance(opt["shading"], (bool, np.bool_)):
+            raise ValueError("shading must be True or False")
+        opt["shading"] = bool(opt["shading"])
     return opt
+
+
+def streaks_call_options(streaks, flat=None, dark=None):
+    """The keyword arguments of :func:`destripe_streaks_planes` / :func:`filter_streaks` for a checked ``streaks``
+    dict: the ``"shading"`` flag becomes the resolved ``flat`` / ``dark`` planes (dropped when it is not set)."""
+    kw = {k: v for k, v in streaks.items() if k != "shading"}
+    if streaks.get("shading") and flat is not None:
+        kw["flat"], kw["dark"] = flat, dark
+    return kw
+
+
+def streaks_shading(streaks, shadow_correction):
+    """``shadow_correction`` as a streaks pipeline takes it: ``None`` when there is none, ``ValueError`` when there is
+    one and the checked ``streaks`` dict does not ask for it with ``"shading": True``."""
+    if shadow_correction is not None and not streaks.get("shading"):
+        raise ValueError("streaks: the dual-band filter has no dark / flat step without 'shading': True; "
+                         "shadow_correction must be None")  # fmt: skip
+    return shadow_correction
 
 
 def _warn_streaks_level(shape, level, wavelet):
@@ -374,7 +412,8 @@ def _warn_streaks_level(shape, level, wavelet):
         )
 
 
-def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, threshold=-1, route="generic", **params):
+def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, threshold=-1, route="generic", smoothing=0,
+                   flat=None, dark=None, **params):  # fmt: skip
     """The stripe filter under its upstream (pystripe) name, in two forms.
 
     * Scalar ``sigma``: ``log_space_fft_filtering(image, sigma=sigma, level=level, wavelet=wavelet, **params)``,
@@ -389,11 +428,18 @@ def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, thresh
       run through the marching db3 kernels and the FFT row filter of the log-space engine -- the same filter, for
       db3, planes of even height and width and levels up to the maximum; ``ValueError`` elsewhere) or ``"auto"``
       (``engine.AUTO_ROUTE`` where march applies: the generic route until a same-session measurement shows march
-      ahead; generic elsewhere).
+      ahead; generic elsewhere).  Options of this form: one member of ``sigma`` may be ``None`` -- ``(s, None)``
+      filters the foreground band only (``f w + x (1 - w)``), ``(None, s)`` the background band only
+      (``x w + b (1 - w)``); ``smoothing`` (0, or ``0 < s <= 2``) blends with
+      ``scipy.ndimage.gaussian_filter(w, smoothing)`` instead of the raw sigmoid ``w``; ``flat`` / ``dark`` (together)
+      put the result through the reference's ``flatfield_correction`` and make the return value uint16, as
+      :func:`filter_stripes` does.
     """
-    if not isinstance(sigma, (str, bytes)) and np.ndim(sigma) == 0:
-        if "crossover" in params or crossover != 10 or threshold != -1 or route != "generic":
-            raise TypeError("crossover / threshold / route belong to the dual-band form: pass sigma=(sigma_fg, sigma_bg)")
+    if sigma is not None and not isinstance(sigma, (str, bytes)) and np.ndim(sigma) == 0:
+        if ("crossover" in params or crossover != 10 or threshold != -1 or route != "generic" or smoothing != 0
+                or flat is not None or dark is not None):  # fmt: skip
+            raise TypeError("crossover / threshold / route / smoothing / flat / dark belong to the dual-band form: "
+                            "pass sigma=(sigma_fg, sigma_bg)")  # fmt: skip
         return log_space_fft_filtering(input_image=image, sigma=sigma, level=level, wavelet=wavelet, **params)
     if params:
         raise TypeError("filter_streaks got unexpected arguments: {}".format(sorted(params)))
@@ -402,17 +448,23 @@ def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, thresh
     if image.ndim != 2 or image.size == 0:
         raise ValueError("filter_streaks takes one non-empty 2-D plane; use destripe_streaks_planes for a stack")
     out = destripe_streaks_planes(image[None], (sigma_fg, sigma_bg), level=level, wavelet=wavelet, crossover=crossover,
-                                  threshold=threshold, out_dtype=np.float32, max_batch=1, route=route)  # fmt: skip
-    return out[0].astype(np.float64)
+                                  threshold=threshold, out_dtype=np.float32 if flat is None else np.uint16, max_batch=1,
+                                  route=route, smoothing=smoothing, flat=flat, dark=dark)  # fmt: skip
+    return out[0].astype(np.float64) if flat is None else out[0]
 
 
 def destripe_streaks_planes(planes, sigma, level=0, wavelet="db3", crossover=10, threshold=-1, out_dtype=np.uint16,
-                            max_batch=32, device=0, return_threshold=False, route="generic"):  # fmt: skip
+                            max_batch=32, device=0, return_threshold=False, route="generic", smoothing=0, flat=None,
+                            dark=None):  # fmt: skip
     """Batched dual-band :func:`filter_streaks` over ``planes[n, H, W]`` (uint16 or float32), every plane on its own
     (with ``threshold=-1`` each takes its own Otsu ``t``).  ``out_dtype`` uint16: clip to [0, 65535] and truncate, as
     the Zarr path stores; float32: the filter's value.  ``return_threshold``: also the per-plane ``t`` (float64).
-    ``route``: as in :func:`filter_streaks`."""
+    ``route``, a ``None`` member of ``sigma``, ``smoothing``, ``flat`` / ``dark``: as in :func:`filter_streaks`; with a
+    flat, a float32 output is the clipped value of ``flatfield_correction`` (not truncated)."""
     sigma_fg, sigma_bg, level = _streaks_params(sigma, level, wavelet, crossover, threshold)
+    smoothing = _engine.streaks_smoothing(smoothing)
+    if (flat is None) != (dark is None):
+        raise ValueError("flatfield and darkfield must be given together")
     planes = np.asarray(planes)
     if planes.ndim != 3:
         raise ValueError("planes must be [n, H, W]")
@@ -427,7 +479,7 @@ def destripe_streaks_planes(planes, sigma, level=0, wavelet="db3", crossover=10,
     n = planes.shape[0]
     max_batch = max(1, min(int(max_batch), max(n, 1)))
     eng = _streaks_engine(planes.shape[1:], sigma_fg, sigma_bg, level, wavelet, crossover, threshold, max_batch, device,
-                          route)  # fmt: skip
+                          route, smoothing, flat, dark)  # fmt: skip
     out = np.empty(planes.shape, dtype=out_dtype)
     ts = np.zeros(n, dtype=np.float64)
     for start in range(0, n, max_batch):

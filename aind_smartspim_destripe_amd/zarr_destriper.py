@@ -201,7 +201,8 @@ def execute_worker(
     """``zarr_destriper.py:253-336`` with the plane loop (``:319-327``) as one batched GPU call.
 
     ``streaks`` (the checked dict of ``fl.streaks_options``, ``route`` resolved): the planes go through the dual-band
-    filter (``fl.destripe_streaks_planes``) instead; the configs and ``shadow_correction`` are not read then.
+    filter (``fl.destripe_streaks_planes``) instead; the configs are not read then, and the ``shadow_correction`` is
+    resolved as for the stripe filter and applied when the dict says ``"shading": True``.
 
     ``data``: float32 (or uint16) ``[1, Z, Y, X]``; every plane goes through ``filter_stripes`` semantics
     with ``microscope_high_int=2500`` (``:326``); the result is assigned to
@@ -227,7 +228,9 @@ def execute_worker(
     input_tile_path = dataset_name.replace(".zarr", "")
     planes = data if data.dtype in (np.uint16, np.float32) else data.astype(np.float32)
     if streaks is not None:
-        filtered = fl.destripe_streaks_planes(planes, out_dtype=np.uint16, max_batch=max_batch, device=device, **streaks)
+        flat, dark = fl._resolve_shading(shadow_correction, input_tile_path)
+        filtered = fl.destripe_streaks_planes(planes, out_dtype=np.uint16, max_batch=max_batch, device=device,
+                                              **fl.streaks_call_options(streaks, flat, dark))  # fmt: skip
     else:
         filtered = fl.destripe_planes(
             planes,
@@ -849,13 +852,18 @@ def destripe_zarr_store(
     zlib and Blosc outputs.
 
     ``streaks``: a dict ``{"sigma": (fg, bg), "level": 0, "wavelet": "db3", "crossover": 10, "threshold": -1,
-    "route": "auto"}`` (defaults as in ``filtering.filter_streaks``; an unknown key raises ``TypeError``) runs the
+    "route": "auto"}`` (defaults as in ``filtering.filter_streaks``; an unknown key raises ``TypeError``; a member of
+    ``sigma`` may be ``None`` for a one-sided filter; optional keys ``"smoothing"``, the sigma 0 .. 2 of the gaussian
+    over the blend weight, and ``"shading"``) runs the
     dual-band filter on every plane instead of the stripe filter: the device path plans a streaks engine, the host path
     (``device_retile=False`` or a geometry that is not chunk-aligned) calls ``filtering.destripe_streaks_planes``;
     everything around the filter -- re-tiling, codecs, pyramid, ranks -- is the same.  ``cells_config`` /
-    ``no_cells_config`` may be ``None`` then; the dual-band filter has no dark / flat step, so a ``shadow_correction``
-    raises ``ValueError`` before anything is created.  ``LAST_RUN["filter"]`` is ``"stripes"`` or ``"streaks"``,
-    ``LAST_RUN["streaks_route"]`` the route taken (``None`` for the stripe filter).
+    ``no_cells_config`` may be ``None`` then.  Without ``"shading": True`` in the dict a ``shadow_correction``
+    raises ``ValueError`` before anything is created; with it the flat / dark are resolved as for the stripe filter
+    and the filter's result goes through ``flatfield_correction`` (no ``shadow_correction``: unshaded).
+    ``LAST_RUN["filter"]`` is ``"stripes"`` or ``"streaks"``, ``LAST_RUN["streaks_route"]`` the route taken,
+    ``LAST_RUN["streaks_smoothing"]`` the smoothing and ``LAST_RUN["streaks_shading"]`` whether a dark / flat step ran
+    (all ``None`` for the stripe filter).
 
     ``histogram``: a zeroed ``np.int64[65536]``; this rank's share of the level-0 voxels it writes is added to it, one
     count per value -- what the display window of the OME-NGFF metadata is taken from
@@ -873,8 +881,7 @@ def destripe_zarr_store(
         raise ValueError("histogram must be a writeable C-contiguous int64 array of {} bins".format(engine_mod.VOLHIST_BINS))
     if streaks is not None:
         streaks = fl.streaks_options(streaks)
-        if shadow_correction is not None:
-            raise ValueError("streaks: the dual-band filter has no dark / flat step; shadow_correction must be None")
+        fl.streaks_shading(streaks, shadow_correction)
     codec_mode = output_codec_mode(device_codec, compressor)  # (a wrong mode fails before anything is created)
     device_codec = codec_mode is not None
     decode_mode = device_decode_mode(device_decode)
@@ -920,7 +927,9 @@ def destripe_zarr_store(
     dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device
     LAST_RUN.update(rank=rank, world_size=world_size, z_range=(z0, z1), io_threads=int(io_threads), device=dev,
                     filter="stripes" if streaks is None else "streaks",
-                    streaks_route=None if streaks is None else streaks["route"])  # fmt: skip
+                    streaks_route=None if streaks is None else streaks["route"],
+                    streaks_smoothing=None if streaks is None else float(streaks.get("smoothing", 0.0)),
+                    streaks_shading=None if streaks is None else bool(streaks.get("shading") and shadow_correction is not None))  # fmt: skip
     # dataset_name of the reference = the tile folder (X_..._Y_....zarr), also when level "0" is opened
     name = tile_name or os.path.basename(str(dataset_path).rstrip("/"))
     n_planes, t0 = 0, time.perf_counter()
@@ -951,8 +960,10 @@ def destripe_zarr_store(
     LAST_RUN["histogram_voxels"] = None if histogram is None else 0
     if can and device_retile is not False:
         if streaks is not None:
+            flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
             eng = fl._streaks_engine(zyx[1:], *streaks["sigma"], streaks["level"], streaks["wavelet"], streaks["crossover"],
-                                     streaks["threshold"], min(block_z, 64), dev, streaks["route"])  # fmt: skip
+                                     streaks["threshold"], min(block_z, 64), dev, streaks["route"],
+                                     streaks.get("smoothing", 0.0), flatfield, darkfield)  # fmt: skip
         else:
             flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
             eng = fl.get_engine(zyx[1:], cells_config, no_cells_config, 2500, flatfield, darkfield,
@@ -1455,8 +1466,8 @@ def destripe_zarr(
     ``device_codec`` and ``io_threads``, and this call's ``device_decode`` when the output is Blosc -- level 0 is this
     run's own output; same stores; ``ValueError`` together with ``fused_pyramid``), ``streaks`` (the dict of
     :func:`destripe_zarr_store`: the dual-band filter instead of the stripe filter; ``parameters`` need no configs then,
-    and a derivatives folder that exists or a ``flatfield`` raises ``ValueError`` before anything is created -- that
-    filter has no dark / flat step), ``ome_metadata`` / ``display_window`` (rank 0 writes the group's ``.zgroup`` and
+    and, unless the dict says ``"shading": True``, a derivatives folder that exists or a ``flatfield`` raises
+    ``ValueError`` before anything is created; with it they are read as for the stripe filter), ``ome_metadata`` / ``display_window`` (rank 0 writes the group's ``.zgroup`` and
     OME-NGFF ``.zattrs`` once the levels are written -- inside :func:`compute_multiscale`, or itself on the
     ``fused_pyramid`` route; the same file on every route.  ``xyz_resolution`` is the voxel size, handed on as
     ``[z, y, x]``; ``display_window`` as in :func:`compute_multiscale`, except that ``"percentile"`` needs nothing from
@@ -1483,9 +1494,9 @@ def destripe_zarr(
     histogram = np.zeros(engine_mod.VOLHIST_BINS, np.int64) if percentile else None
     if streaks is not None:
         streaks = fl.streaks_options(streaks)
-        if flatfield is not None or os.path.exists(Path(derivatives_path)):
-            raise ValueError("streaks: the dual-band filter has no dark / flat step; give no flatfield and no "
-                             "derivatives folder")  # fmt: skip
+        if not streaks.get("shading") and (flatfield is not None or os.path.exists(Path(derivatives_path))):
+            raise ValueError("streaks: the dual-band filter has no dark / flat step without 'shading': True; give no "
+                             "flatfield and no derivatives folder")  # fmt: skip
         no_cells_config, cells_config = parameters.get("no_cells_config"), parameters.get("cells_config")
     else:
         no_cells_config = parameters["no_cells_config"]
@@ -1510,7 +1521,7 @@ def destripe_zarr(
         return {"darkfield": sc["darkfield"], "microscope_flats": None if sc["retrospective"] else sc["flatfield"],
                 "tile_config": sc["tile_config"]}  # fmt: skip
 
-    if streaks is not None:
+    if streaks is not None and not streaks.get("shading"):
         shadow_correction = {"flatfield": None, "darkfield": None}
     elif _group_broadcasts(group, world_size):
         tile_config = {}
@@ -1642,6 +1653,7 @@ def destripe_channel(
     pipelined_pyramid=False,
     ome_metadata=False,
     display_window=None,
+    streaks=None,
 ):
     """``destripe_channel`` of the reference (``zarr_destriper.py:1214-1267``), same eight parameters (the reference's
     caller passes them by keyword, ``run_capsule.py:394-403``), wired to the GPU chunk map.
@@ -1660,9 +1672,15 @@ def destripe_channel(
     production tile, ``(64, 1600, 2000)``), ``io_threads``, ``device_retile``, ``device_codec``, ``device_decode``, ``fused_pyramid``, ``pipelined_pyramid`` (:func:`destripe_zarr`).  ``world_size > 1`` needs ``group`` (anything with
     ``barrier()``): the pyramid of a tile may only be computed once EVERY rank has written its z-range.  With a
     ``distributed.RankGroup`` rank 0 alone reads the flat and dark planes of a tile and broadcasts them (RCCL).
+    ``streaks``: the dict of :func:`destripe_zarr_store`, handed to every tile's :func:`destripe_zarr`.  Every tile
+    comes with its retrospective flat here, so the dict must say ``"shading": True`` (``ValueError`` before anything is
+    created otherwise).
     """
     if world_size > 1 and group is None:
         raise ValueError("destripe_channel with world_size > 1 needs a group to order the pyramid after all ranks")
+    if streaks is not None and not fl.streaks_options(streaks).get("shading"):
+        raise ValueError("streaks: the dual-band filter has no dark / flat step without 'shading': True, and "
+                         "destripe_channel hands every tile its flat")  # fmt: skip
     output_codec_mode(device_codec, compressor)  # (a wrong string or mode fails before anything is written)
     device_decode_mode(device_decode)
     if fused_pyramid and pipelined_pyramid:
@@ -1722,6 +1740,7 @@ def destripe_channel(
             pipelined_pyramid=pipelined_pyramid,
             ome_metadata=ome_metadata,
             display_window=display_window,
+            streaks=streaks,
         )
         done[tile_path.name] = n
     return done

@@ -419,6 +419,41 @@ int dsx_plan_streaks(dsx_ctx* ctx, int height, int width, int max_batch, const d
 #define DSX_STREAKS_GENERIC 0
 #define DSX_STREAKS_MARCH 1
 int dsx_plan_streaks_ex(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_streaks_cfg* cfg, int route);
+/* Options of the blend (the three upstream pystripe forms the plain plan leaves out).  All zero == no option.
+ *   bands      DSX_STREAKS_BANDS_BOTH: out = f w + b (1 - w).  _FG: only the foreground band is filtered,
+ *              out = f w + x (1 - w); _BG: only the background band, out = x w + b (1 - w).  A one-sided plan runs ONE
+ *              band through the whole chain and does not read the other sigma of the cfg.
+ *   smoothing  0: w = sigmoid((x - t) / crossover) on the unpadded [H, W] plane.  0 < s <= 2:
+ *              w = scipy.ndimage.gaussian_filter(sigmoid, s) with that function's defaults (separable, radius
+ *              int(4 s + 0.5), taps exp(-k^2 / 2 s^2) normalised to sum 1, half-sample reflection at the border).
+ *              Anything else (negative, above 2, not finite): DSX_EINVAL.  Equal sigmas have no w: accepted, no effect.
+ *   flat/dark  host float32 planes, NULL together: flat [H, W], dark [dark_h, dark_w] with dark_h >= H and
+ *              dark_w >= W (cropped by indexing).  The float result r goes through flatfield_correction(r, flat, dark):
+ *              r > dark ? r - dark : 0, / flat, clip to [0, 65535]; uint16 output truncates, float32 output is the
+ *              clipped value.
+ * With any option set, one tiled kernel (k_st_blendx, dsx_streaks.h) does the blend on either route; with none,
+ * dsx_plan_streaks_opts IS dsx_plan_streaks_ex, byte for byte and launch for launch. */
+#define DSX_STREAKS_BANDS_BOTH 0
+#define DSX_STREAKS_BANDS_FG 1
+#define DSX_STREAKS_BANDS_BG 2
+typedef struct dsx_streaks_opts {
+  int32_t bands;      /* DSX_STREAKS_BANDS_*                                                                */
+  float smoothing;    /* 0, or 0 < s <= 2                                                                   */
+  const float* flat;  /* host, [H, W], or NULL                                                              */
+  const float* dark;  /* host, [dark_h, dark_w], NULL exactly when flat is                                  */
+  int32_t dark_h;
+  int32_t dark_w;
+} dsx_streaks_opts;
+/* opts NULL or all zero: dsx_plan_streaks_ex. */
+int dsx_plan_streaks_opts(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_streaks_cfg* cfg, int route,
+                          const dsx_streaks_opts* opts);
+/* Host build of the options blend over ONE plane, compiled from the same weight, fold, tap, blend and epilogue
+ * functions as the kernel: x, f, b float32 [H, W] (the plane and the band values f = band(max(x, t), sigma_fg),
+ * b = band(min(x, t), sigma_bg); the band a one-sided opts->bands does not read may be NULL), t, crossover and opts
+ * as above (flat / dark host planes); out [H, W] of out_dtype.  No context and no device call; the message of an
+ * error is read with dsx_last_error(NULL). */
+int dsx_streaks_blend_ref(const float* x, const float* f, const float* b, int height, int width, float t,
+                          float crossover, const dsx_streaks_opts* opts, void* out, int out_dtype);
 /* t of a plane of the last cohort of the last run (a bin centre for float32 planes, an integer for uint16). */
 int dsx_get_streaks_threshold(dsx_ctx* ctx, int plane, float* threshold);
 

@@ -3,7 +3,10 @@ planes in, uint16 planes out, db3, maximum level, Otsu per plane.  Prints one JS
 16 777 216 bytes per 2048 x 2048 plane (uint16 in + uint16 out, read and written once) against 8 TB/s.
 
     python tools/bench_streaks.py [--planes 256] [--steps 5] [--warmup 2] [--size 2048] [--max-batch 32]
-                                  [--route generic|march|auto]
+                                  [--route generic|march|auto] [--bands both|fg|bg] [--smoothing S] [--shading]
+
+--bands / --smoothing / --shading time the options of the blend (README "filter_streaks"): one filtered band, the
+gaussian over the blend weight, and a dark / flat step (a flat in [0.8, 1.2], a dark of 100).
 """
 
 import argparse
@@ -30,6 +33,9 @@ def main():
     ap.add_argument("--sigma", type=float, nargs=2, default=(64.0, 128.0))
     ap.add_argument("--crossover", type=float, default=10.0)
     ap.add_argument("--route", default="generic", choices=("generic", "march", "auto"))
+    ap.add_argument("--bands", default="both", choices=("both", "fg", "bg"))
+    ap.add_argument("--smoothing", type=float, default=0.0)
+    ap.add_argument("--shading", action="store_true")
     args = ap.parse_args()
     n, S = args.planes, args.size
     rng = np.random.default_rng(0)
@@ -38,8 +44,11 @@ def main():
     block[rng.random(block.shape) < 0.03] += 1500.0
     block = np.clip(block, 0, 65535).astype(np.uint16)
     eng = engine.DestripeEngine(0)
+    flat = (0.8 + 0.4 * rng.random((S, S))).astype(np.float32) if args.shading else None
+    dark = np.full((S, S), 100.0, np.float32) if args.shading else None
     eng.plan_streaks(S, S, args.sigma[0], args.sigma[1], wavelet="db3", level=0, crossover=args.crossover,
-                     threshold=None, max_batch=args.max_batch, route=args.route)  # fmt: skip
+                     threshold=None, max_batch=args.max_batch, route=args.route, bands=args.bands,
+                     smoothing=args.smoothing, flatfield=flat, darkfield=dark)  # fmt: skip
     plane_bytes = S * S * 2
     d_in = eng.alloc(plane_bytes * n)
     d_out = eng.alloc(plane_bytes * n)
@@ -66,6 +75,9 @@ def main():
         "value": round(rate, 2),
         "unit": "planes/s",
         "route": eng.streaks_route,
+        "bands": args.bands,
+        "smoothing": args.smoothing,
+        "shading": bool(args.shading),
         "planes": n,
         "max_batch": args.max_batch,
         "step_seconds": [round(t, 6) for t in times],

@@ -2,13 +2,14 @@
 # per-kernel device time of one dual-band streaks run (tools/bench_streaks.py, 1 timed step of STREAKS_PLANES planes,
 # default 256 x 2048^2 uint16) from a rocprofv3 kernel trace: total, launches and share of every kernel class.
 # STREAKS_ROUTE=march (with STREAKS_MAX_BATCH, default 32): the march route -- the log-space chain's kernels are counted too
+# STREAKS_ARGS: further arguments of tools/bench_streaks.py, e.g. "--smoothing 1 --shading" (the options blend k_st_blendx)
 set -o pipefail
 PLANES=${STREAKS_PLANES:-256}
 ROUTE=${STREAKS_ROUTE:-generic}
 OUT=$(mktemp -d)
 rocprofv3 --kernel-trace --output-format csv -d "$OUT" -- \
   python3 tools/bench_streaks.py --planes "$PLANES" --steps 1 --warmup 0 --route "$ROUTE" \
-  --max-batch "${STREAKS_MAX_BATCH:-32}" > /dev/null || exit $?
+  --max-batch "${STREAKS_MAX_BATCH:-32}" ${STREAKS_ARGS:-} > /dev/null || exit $?
 python3 - "$PLANES" "$OUT" "$ROUTE" <<'PY'
 import collections, csv, glob, sys
 tot, cnt = collections.Counter(), collections.Counter()
