@@ -24,6 +24,7 @@
 #include "../../include/dsx.h"
 #include "dsx_kernels.h"
 #include "dsx_retile.h"
+#include "dsx_rot90.h"
 #include "dsx_pyramid.h"
 #include "dsx_volhist.h"
 #include "dsx_wavelet.h"
@@ -191,6 +192,16 @@ struct dsx_ctx {
   float* st_flat = nullptr;       // [H][W], or nullptr: no dark / flat step
   float* st_dark = nullptr;       // [>= H][st_dark_w]
   int st_dark_w = 0;
+  // dsx_set_rotate: the next plan is made for np.rot90 of the caller's planes.  `rot`: the current plan is such a plan
+  // -- its chain (or streaks plan) holds the rotated geometry, rot_H x rot_W is the caller's plane, and the run entry
+  // points turn every plane into rot_in ahead of the chain and its result out of rot_out behind it (dsx_rot90.h).  The
+  // two buffers hold max_batch planes and are sized by the element types of the first run that needs them.
+  bool rot_next = false;
+  bool rot = false;
+  int rot_H = 0, rot_W = 0;
+  void* rot_in = nullptr;
+  void* rot_out = nullptr;
+  size_t rot_in_bytes = 0, rot_out_bytes = 0;
 };
 
 namespace {
@@ -256,6 +267,9 @@ void free_plan_buffers(dsx_ctx* c) {
   c->own_shading = false;
   fr(c->d_stage_in); c->d_stage_in = nullptr; c->stage_in_bytes = 0;
   fr(c->d_stage_out); c->d_stage_out = nullptr; c->stage_out_bytes = 0;
+  fr(c->rot_in); c->rot_in = nullptr; c->rot_in_bytes = 0;
+  fr(c->rot_out); c->rot_out = nullptr; c->rot_out_bytes = 0;
+  c->rot = false;
   c->planned = false;
 }
 
@@ -827,6 +841,56 @@ CohortView make_view(dsx_ctx* ctx, int po, hipStream_t stream, int part = 0, boo
   return v;
 }
 
+// n planes [H, W] -> [W, H] on stream s (dsx_rot90.h); dir +1: np.rot90, -1: its inverse
+void rot_planes(hipStream_t s, const void* src, void* dst, int dtype, int n, int H, int W, int dir) {
+  if (n <= 0) return;
+  if (dtype == DSX_U16) dsx::rot::rot90_launch<uint16_t>(s, src, dst, n, H, W, dir);
+  else dsx::rot::rot90_launch<float>(s, src, dst, n, H, W, dir);
+}
+
+// The rotation buffers of a rotated plan, at least need_in / need_out bytes.  Streams of an earlier run may still use
+// the buffers they replace, so the context is drained first (use_main joins the parts).
+int grow_rot(dsx_ctx* ctx, size_t need_in, size_t need_out) {
+  if (need_in <= ctx->rot_in_bytes && need_out <= ctx->rot_out_bytes) return DSX_OK;
+  DSX_HIP(hipStreamSynchronize(use_main(ctx)));
+  void** buf[2] = {&ctx->rot_in, &ctx->rot_out};
+  size_t* have[2] = {&ctx->rot_in_bytes, &ctx->rot_out_bytes};
+  const size_t need[2] = {need_in, need_out};
+  for (int k = 0; k < 2; ++k) {
+    if (need[k] <= *have[k]) continue;
+    if (*buf[k]) (void)hipFree(*buf[k]);
+    *buf[k] = nullptr;
+    ctx->workspace_bytes -= *have[k];
+    *have[k] = 0;
+    if (hipMalloc(buf[k], need[k]) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, DSX_ENOMEM, "hipMalloc (rotation buffers of a rotated plan)");
+    }
+    *have[k] = need[k];
+    ctx->workspace_bytes += need[k];
+  }
+  return DSX_OK;
+}
+
+// One part of a cohort of the log-space chain: planes [po, po + n) of the cohort.  With a rotated plan the part turns
+// its planes into its slice of rot_in ahead of its first kernel and its result out of rot_out behind its last one, both
+// on its own stream, so the parts overlap as they do without the rotation.  (A streaks plan rotates around its whole
+// cohort instead, streaks_run: the chain of its march route runs over virtual planes that are rotated already.)
+int run_part(dsx_ctx* ctx, const CohortView& v, int po, const void* d_in, int in_dtype, int n, void* d_out,
+             int out_dtype, int32_t* d_cfg_used, size_t in_plane, size_t out_plane) {
+  if (!ctx->rot || ctx->streaks) return run_cohort(ctx, v, d_in, in_dtype, n, d_out, out_dtype, d_cfg_used);
+  const dsx::Plan& p = ctx->plan;
+  char* ri = (char*)ctx->rot_in + po * in_plane;
+  char* ro = (char*)ctx->rot_out + po * out_plane;
+  rot_planes(v.stream, d_in, ri, in_dtype, n, ctx->rot_H, ctx->rot_W, +1);
+  DSX_HIP(hipGetLastError());
+  if (int rc = run_cohort(ctx, v, ri, in_dtype, n, ro, out_dtype, d_cfg_used)) return rc;
+  if (ctx->stop_after != 0) return DSX_OK;  // (no result is made)
+  rot_planes(v.stream, ro, d_out, out_dtype, n, p.Hout, p.Wout, -1);
+  DSX_HIP(hipGetLastError());
+  return DSX_OK;
+}
+
 // An unsplit cohort through the graph cache (DSX_GRAPH=1, see dsx_ctx::GraphEntry): replay of a call seen before (same
 // buffers, count and types under the current plan); first sight eager, second sight capture; a runtime that cannot
 // capture falls back to eager launches for good.
@@ -894,11 +958,14 @@ int run_cohort_graphed(dsx_ctx* ctx, const CohortView& view, hipStream_t main, c
 int run_cohort_split(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d_out, int out_dtype,
                      int32_t* d_cfg_used, size_t in_plane, size_t out_plane) {
   const int parts = dsx::cohort_parts(ctx->n_streams, nb, ctx->profiling || ctx->stop_after != 0 || ctx->stack_mode);
+  const bool rotated = ctx->rot && !ctx->streaks;
+  if (rotated)
+    if (int rc = grow_rot(ctx, in_plane * ctx->max_batch, out_plane * ctx->max_batch)) return rc;
   if (parts <= 1) {
     hipStream_t main = use_main(ctx);  // joins whatever split cohort is still running
     const CohortView view = make_view(ctx, 0, main, 0, true);
-    if (ctx->graph_mode == 0 || ctx->profiling || ctx->stop_after != 0 || ctx->ablate != 0)
-      return run_cohort(ctx, view, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
+    if (ctx->graph_mode == 0 || ctx->profiling || ctx->stop_after != 0 || ctx->ablate != 0 || rotated)  // (rotated: eager)
+      return run_part(ctx, view, 0, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used, in_plane, out_plane);
     return run_cohort_graphed(ctx, view, main, d_in, in_dtype, nb, d_out, out_dtype, d_cfg_used);
   }
   const bool no_pipe = ctx->tune.no_pipeline;
@@ -918,8 +985,9 @@ int run_cohort_split(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void*
     if (n <= 0) break;
     hipStream_t st = (i == 0) ? ctx->stream_ : ctx->aux[i];
     if (i > 0 && !same_call) DSX_HIP(hipStreamWaitEvent(st, ctx->ev_fork, 0));
-    const int rc = run_cohort(ctx, make_view(ctx, po, st, i), (const char*)d_in + po * in_plane, in_dtype, n,
-                              (char*)d_out + po * out_plane, out_dtype, d_cfg_used ? d_cfg_used + po : nullptr);
+    const int rc = run_part(ctx, make_view(ctx, po, st, i), po, (const char*)d_in + po * in_plane, in_dtype, n,
+                            (char*)d_out + po * out_plane, out_dtype, d_cfg_used ? d_cfg_used + po : nullptr, in_plane,
+                            out_plane);
     if (rc != DSX_OK) return rc;
     if (i > 0) DSX_HIP(hipEventRecord(ctx->ev_join[i], st));
   }
@@ -1182,6 +1250,18 @@ int streaks_run(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, in
     if (int rc = grow_stage(ctx, &ctx->d_stage_in, &ctx->stage_in_bytes, in_plane * B)) return rc;
     if (int rc = grow_stage(ctx, &ctx->d_stage_out, &ctx->stage_out_bytes, out_plane * B)) return rc;
   }
+  if (ctx->rot)
+    if (int rc = grow_rot(ctx, in_plane * B, out_plane * B)) return rc;
+  // A rotated plan (p holds the rotated geometry, p.H == rot_W): the cohort is turned into rot_in on the context stream,
+  // filtered there into rot_out and turned back into the caller's buffer.
+  auto cohort = [&](const void* d_src, int nb, void* d_dst) -> int {
+    if (!ctx->rot) return streaks_cohort(ctx, d_src, in_dtype, nb, d_dst, out_dtype);
+    rot_planes(use_main(ctx), d_src, ctx->rot_in, in_dtype, nb, ctx->rot_H, ctx->rot_W, +1);
+    if (int rc = streaks_cohort(ctx, ctx->rot_in, in_dtype, nb, ctx->rot_out, out_dtype)) return rc;
+    rot_planes(use_main(ctx), ctx->rot_out, d_dst, out_dtype, nb, p.H, p.W, -1);
+    DSX_HIP(hipGetLastError());
+    return DSX_OK;
+  };
   if (host) {  // a value error of an earlier asynchronous call is reported now, not wiped by this call's check
     DSX_HIP(hipStreamSynchronize(use_main(ctx)));
     if (int rc = check_sticky(ctx)) return rc;
@@ -1192,14 +1272,14 @@ int streaks_run(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, in
     char* dst = (char*)out + start * out_plane;
     if (host) {
       DSX_HIP(hipMemcpyAsync(ctx->d_stage_in, src, in_plane * nb, hipMemcpyHostToDevice, use_main(ctx)));
-      if (int rc = streaks_cohort(ctx, ctx->d_stage_in, in_dtype, nb, ctx->d_stage_out, out_dtype)) return rc;
+      if (int rc = cohort(ctx->d_stage_in, nb, ctx->d_stage_out)) return rc;
       DSX_HIP(hipMemcpyAsync(dst, ctx->d_stage_out, out_plane * nb, hipMemcpyDeviceToHost, use_main(ctx)));
       DSX_HIP(hipStreamSynchronize(use_main(ctx)));
       if (ctx->h_sticky && __atomic_exchange_n(ctx->h_sticky, 0u, __ATOMIC_ACQ_REL) != 0u)
         return fail(ctx, DSX_EVALUE, "a plane of " + std::to_string(start) + " .. " + std::to_string(start + nb - 1) +
                                          ": autodetected range of [nan, nan] is not finite (a pixel is NaN, infinite "
                                          "or <= -1)");
-    } else if (int rc = streaks_cohort(ctx, src, in_dtype, nb, dst, out_dtype)) {
+    } else if (int rc = cohort(src, nb, dst)) {
       return rc;
     }
   }
@@ -1320,6 +1400,7 @@ namespace {
 // virtual band planes).  The context's earlier plan has been freed.
 int plan_chain(dsx_ctx* ctx, int height, int width, int max_batch, bool bank, double microscope_high_int,
                const float* flat, const float* dark, int dark_h, int dark_w);
+int rotated_shading_host(dsx_ctx* ctx, const float* flat, const float* dark, int dark_h, int dark_w);
 }  // namespace
 
 int dsx_plan(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_cfg* cells_config,
@@ -1348,10 +1429,52 @@ int dsx_plan(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_cfg* 
   }
   const bool bank = src[0]->wavelet == DSX_WAVELET_BANK;
   if (bank && !ctx->wl_set) return fail(ctx, DSX_EINVAL, "DSX_WAVELET_BANK without dsx_set_wavelet");
-  return plan_chain(ctx, height, width, max_batch, bank, microscope_high_int, flat, dark, dark_h, dark_w);
+  if (!ctx->rot_next)
+    return plan_chain(ctx, height, width, max_batch, bank, microscope_high_int, flat, dark, dark_h, dark_w);
+  // dsx_set_rotate: the chain of np.rot90 of the plane; the shading planes are turned with it
+  if (int rc = plan_chain(ctx, width, height, max_batch, bank, microscope_high_int, nullptr, nullptr, 0, 0)) return rc;
+  ctx->rot = true;
+  ctx->rot_H = height;
+  ctx->rot_W = width;
+  if (flat)
+    if (int rc = rotated_shading_host(ctx, flat, dark, dark_h, dark_w)) { ctx->planned = false; return rc; }
+  return DSX_OK;
 }
 
 namespace {
+// flat [H, W] and dark [dark_h, dark_w] (cropped to [H, W] first) of the caller's orientation as np.rot90 of them:
+// [W, H] each, what the epilogue of a rotated plan indexes.
+void rotate_shading(const float* flat, const float* dark, int dark_w, int H, int W, std::vector<float>& rflat,
+                    std::vector<float>& rdark) {
+  const size_t px = (size_t)H * W;
+  std::vector<float> crop(px);
+  for (int y = 0; y < H; ++y) memcpy(crop.data() + (size_t)y * W, dark + (size_t)y * dark_w, sizeof(float) * W);
+  rflat.resize(px);
+  rdark.resize(px);
+  dsx::rot::rot90_host(flat, rflat.data(), 1, H, W, +1);
+  dsx::rot::rot90_host(crop.data(), rdark.data(), 1, H, W, +1);
+}
+
+// Shading of a rotated log-space plan from host planes in the caller's orientation: flat [Hout', Wout'] with
+// Hout' = plan.Wout, Wout' = plan.Hout (the result plane as the caller sees it), dark at least that.
+int rotated_shading_host(dsx_ctx* ctx, const float* flat, const float* dark, int dark_h, int dark_w) {
+  const dsx::Plan& p = ctx->plan;
+  const int Ho = p.Wout, Wo = p.Hout;
+  if (dark_h < Ho || dark_w < Wo) return fail(ctx, DSX_EINVAL, "Please, check the shape of the darkfield.");
+  std::vector<float> rflat, rdark;
+  rotate_shading(flat, dark, dark_w, Ho, Wo, rflat, rdark);
+  const size_t fb = sizeof(float) * (size_t)Ho * Wo;
+  DSX_HIP(hipMalloc((void**)&ctx->d_flat, fb));
+  DSX_HIP(hipMalloc((void**)&ctx->d_dark, fb));
+  ctx->own_shading = true;
+  DSX_HIP(hipMemcpy(ctx->d_flat, rflat.data(), fb, hipMemcpyHostToDevice));
+  DSX_HIP(hipMemcpy(ctx->d_dark, rdark.data(), fb, hipMemcpyHostToDevice));
+  ctx->dark_h = p.Hout;
+  ctx->dark_w = p.Wout;
+  ctx->workspace_bytes += 2 * fb;
+  return DSX_OK;
+}
+
 int plan_chain(dsx_ctx* ctx, int height, int width, int max_batch, bool bank, double microscope_high_int,
                const float* flat, const float* dark, int dark_h, int dark_w) {
   ctx->wl_len = bank ? ctx->wl_bank_len : 0;
@@ -1440,13 +1563,44 @@ int dsx_set_shading_device(dsx_ctx* ctx, const float* d_flat, const float* d_dar
   if (!ctx->planned) return fail(ctx, DSX_ENOPLAN, "dsx_plan has not been called");
   if ((d_flat == nullptr) != (d_dark == nullptr))
     return fail(ctx, DSX_EINVAL, "flatfield and darkfield must be given together");
-  if (d_flat && (dark_h < ctx->plan.Hout || dark_w < ctx->plan.Wout))
+  const bool rot = ctx->rot && !ctx->streaks;  // the caller's result plane is [plan.Wout, plan.Hout] then
+  const int Ho = rot ? ctx->plan.Wout : ctx->plan.Hout, Wo = rot ? ctx->plan.Hout : ctx->plan.Wout;
+  if (d_flat && (dark_h < Ho || dark_w < Wo))
     return fail(ctx, DSX_EINVAL, "Please, check the shape of the darkfield.");
   DSX_HIP(hipSetDevice(ctx->device));
   DSX_HIP(hipStreamSynchronize(use_main(ctx)));
   drop_graphs(ctx);  // captured final kernels carry the old shading addresses
   if (ctx->own_shading) { (void)hipFree(ctx->d_flat); (void)hipFree(ctx->d_dark); }
   ctx->own_shading = false;
+  if (rot && d_flat) {
+    // a rotated plan keeps its own np.rot90 of the planes: the dark is cropped to the plane first, then both are turned
+    ctx->d_flat = ctx->d_dark = nullptr;
+    const size_t fb = sizeof(float) * (size_t)Ho * Wo;
+    float* crop = nullptr;
+    DSX_HIP(hipMalloc((void**)&crop, fb));
+    hipError_t e = hipMalloc((void**)&ctx->d_flat, fb);
+    if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_dark, fb);
+    hipStream_t s = use_main(ctx);
+    if (e == hipSuccess)
+      e = hipMemcpy2DAsync(crop, sizeof(float) * Wo, d_dark, sizeof(float) * dark_w, sizeof(float) * Wo, Ho,
+                           hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) {
+      rot_planes(s, d_flat, ctx->d_flat, DSX_F32, 1, Ho, Wo, +1);
+      rot_planes(s, crop, ctx->d_dark, DSX_F32, 1, Ho, Wo, +1);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(crop);
+    if (e != hipSuccess) {
+      (void)hipFree(ctx->d_flat); (void)hipFree(ctx->d_dark);
+      ctx->d_flat = ctx->d_dark = nullptr;
+      return fail(ctx, DSX_EHIP, std::string("rotated shading planes: ") + hipGetErrorString(e));
+    }
+    ctx->own_shading = true;
+    ctx->dark_h = ctx->plan.Hout;
+    ctx->dark_w = ctx->plan.Wout;
+    return DSX_OK;
+  }
   ctx->d_flat = const_cast<float*>(d_flat);
   ctx->d_dark = const_cast<float*>(d_dark);
   ctx->dark_h = dark_h;
@@ -1475,6 +1629,10 @@ int dsx_plan_info(const dsx_ctx* ctx, dsx_plan_info_t* info) {
   const dsx::Plan& p = ctx->plan;
   info->height = p.H; info->width = p.W;
   info->out_height = p.Hout; info->out_width = p.Wout;
+  if (ctx->rot) {  // the caller's orientation; the level entries below stay those of the rotated chain
+    info->height = p.W; info->width = p.H;
+    info->out_height = p.Wout; info->out_width = p.Hout;
+  }
   info->levels = p.L;
   for (int l = 0; l < p.L && l < 16; ++l) {
     info->level_h[l] = p.lv[l].h;
@@ -2407,9 +2565,12 @@ int dsx_plan_streaks_ex(dsx_ctx* ctx, int height, int width, int max_batch, cons
   return dsx_plan_streaks_opts(ctx, height, width, max_batch, cfg, route, nullptr);
 }
 
-int dsx_plan_streaks_opts(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_streaks_cfg* cfg_in, int route,
-                          const dsx_streaks_opts* opts) {
+int dsx_plan_streaks_opts(dsx_ctx* ctx, int height_in, int width_in, int max_batch, const dsx_streaks_cfg* cfg_in,
+                          int route, const dsx_streaks_opts* opts) {
   if (!ctx) return DSX_EINVAL;
+  // dsx_set_rotate: everything below plans np.rot90 of the caller's plane, [width_in, height_in]
+  const bool rot = ctx->rot_next;
+  const int height = rot ? width_in : height_in, width = rot ? height_in : width_in;
   const bool has_opts = opts && (opts->bands != DSX_STREAKS_BANDS_BOTH || opts->smoothing != 0.f || opts->flat || opts->dark);
   int clip = 0;
   dsx_streaks_cfg one_sided;
@@ -2421,7 +2582,7 @@ int dsx_plan_streaks_opts(dsx_ctx* ctx, int height, int width, int max_batch, co
       return fail(ctx, DSX_EINVAL, "smoothing must be 0 or a value in (0, 2]");
     if ((opts->flat == nullptr) != (opts->dark == nullptr))
       return fail(ctx, DSX_EINVAL, "flatfield and darkfield must be given together");
-    if (opts->flat && (opts->dark_h < height || opts->dark_w < width))
+    if (opts->flat && (opts->dark_h < height_in || opts->dark_w < width_in))
       return fail(ctx, DSX_EINVAL, "Please, check the shape of the darkfield.");
     if (max_batch > 65535) return fail(ctx, DSX_EINVAL, "max_batch too large");
     if (cfg_in && opts->bands != DSX_STREAKS_BANDS_BOTH) {  // the sigma of the band that is not filtered is not read
@@ -2457,6 +2618,9 @@ int dsx_plan_streaks_opts(dsx_ctx* ctx, int height, int width, int max_batch, co
   DSX_HIP(hipStreamSynchronize(use_main(ctx)));
   free_plan_buffers(ctx);
   free_streaks(ctx);
+  ctx->rot = rot;
+  ctx->rot_H = height_in;
+  ctx->rot_W = width_in;
   dsx::st::StreaksPlan& p = ctx->sp;
   p = dsx::st::StreaksPlan();
   p.H = height; p.W = width; p.B = max_batch;
@@ -2504,12 +2668,20 @@ int dsx_plan_streaks_opts(dsx_ctx* ctx, int height, int width, int max_batch, co
     if (ctx->st_R > 0) dsx::st::st_smooth_taps((double)opts->smoothing, ctx->st_R, ctx->st_taps);
     if (opts->flat) {
       const size_t fb = sizeof(float) * (size_t)height * width;
-      const size_t db = sizeof(float) * (size_t)opts->dark_h * opts->dark_w;
+      const size_t db = rot ? fb : sizeof(float) * (size_t)opts->dark_h * opts->dark_w;
       if (int rc = alloc((void**)&ctx->st_flat, fb)) return rc;
       if (int rc = alloc((void**)&ctx->st_dark, db)) return rc;
-      DSX_HIP(hipMemcpy(ctx->st_flat, opts->flat, fb, hipMemcpyHostToDevice));
-      DSX_HIP(hipMemcpy(ctx->st_dark, opts->dark, db, hipMemcpyHostToDevice));
-      ctx->st_dark_w = opts->dark_w;
+      if (rot) {  // the planes are the caller's: dark cropped to the plane, then both turned with the plane
+        std::vector<float> rflat, rdark;
+        rotate_shading(opts->flat, opts->dark, opts->dark_w, height_in, width_in, rflat, rdark);
+        DSX_HIP(hipMemcpy(ctx->st_flat, rflat.data(), fb, hipMemcpyHostToDevice));
+        DSX_HIP(hipMemcpy(ctx->st_dark, rdark.data(), db, hipMemcpyHostToDevice));
+        ctx->st_dark_w = width;
+      } else {
+        DSX_HIP(hipMemcpy(ctx->st_flat, opts->flat, fb, hipMemcpyHostToDevice));
+        DSX_HIP(hipMemcpy(ctx->st_dark, opts->dark, db, hipMemcpyHostToDevice));
+        ctx->st_dark_w = opts->dark_w;
+      }
     }
     ctx->st_opts = true;
     return DSX_OK;
@@ -2563,6 +2735,39 @@ int dsx_plan_streaks_opts(dsx_ctx* ctx, int height, int width, int max_batch, co
   if (int rc = apply_opts()) return rc;
   ctx->streaks = true;
   ctx->last_n = 0;
+  return DSX_OK;
+}
+
+int dsx_set_rotate(dsx_ctx* ctx, int on) {
+  if (!ctx) return DSX_EINVAL;
+  ctx->rot_next = on != 0;
+  return DSX_OK;  // takes effect at the next dsx_plan / dsx_plan_streaks*
+}
+
+namespace {
+const char* rot90_args(const void* src, const void* dst, int dtype, int n, int H, int W, int dir) {
+  if (n < 0 || H < 1 || W < 1) return "rot90: n must be >= 0 and the plane at least 1 x 1";
+  if (dtype != DSX_U16 && dtype != DSX_F32) return "unknown element type";
+  if (dir != 1 && dir != -1) return "rot90: dir must be +1 or -1";
+  if (n > 0 && (!src || !dst)) return "rot90: NULL pointer";
+  if (src == dst && n > 0) return "rot90: the planes cannot be turned in place";
+  return nullptr;
+}
+}  // namespace
+
+int dsx_rot90_device(dsx_ctx* ctx, const void* d_src, void* d_dst, int dtype, int n, int H, int W, int dir) {
+  if (!ctx) return DSX_EINVAL;
+  if (const char* e = rot90_args(d_src, d_dst, dtype, n, H, W, dir)) return fail(ctx, DSX_EINVAL, e);
+  DSX_HIP(hipSetDevice(ctx->device));
+  rot_planes(use_main(ctx), d_src, d_dst, dtype, n, H, W, dir);
+  DSX_HIP(hipGetLastError());
+  return DSX_OK;
+}
+
+int dsx_rot90_ref(const void* src, void* dst, int dtype, int n, int H, int W, int dir) {
+  if (const char* e = rot90_args(src, dst, dtype, n, H, W, dir)) return fail(nullptr, DSX_EINVAL, e);
+  if (dtype == DSX_U16) dsx::rot::rot90_host((const uint16_t*)src, (uint16_t*)dst, n, H, W, dir);
+  else dsx::rot::rot90_host((const float*)src, (float*)dst, n, H, W, dir);
   return DSX_OK;
 }
 

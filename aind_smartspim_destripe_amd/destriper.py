@@ -121,9 +121,12 @@ def read_filter_save(
     output_format: Optional[str] = None,
     output_dtype: Optional[type] = None,
     streaks: Optional[dict] = None,
+    rotate: bool = False,
 ):
     """One plane: read (3 tries), ``filter_stripes`` on the GPU, ``astype`` to the source dtype (or
-    ``output_dtype``), save (``destriper.py:113-215``).  ``streaks``: the dict of :func:`batch_filter`."""
+    ``output_dtype``), save (``destriper.py:113-215``).  ``streaks``: the dict of :func:`batch_filter`.  ``rotate``:
+    as in :func:`batch_filter`."""
+    rotate = _rotate_option(rotate, streaks)
     streaks = _streaks_options(streaks, shadow_correction)
     raw_image = _read_with_retries(output_dir, input_path)
     if raw_image is None:
@@ -131,7 +134,7 @@ def read_filter_save(
     dtype = _target_dtype(raw_image.dtype, output_dtype)
     if streaks is not None:
         flat, dark = fl._resolve_shading(shadow_correction, input_path)
-        filtered_image = fl.filter_streaks(raw_image, **fl.streaks_call_options(streaks, flat, dark))
+        filtered_image = fl.filter_streaks(raw_image, **dict(fl.streaks_call_options(streaks, flat, dark), rotate=rotate))
         _save_with_retries(output_path, filtered_image.astype(dtype), compression, output_format)
         return
     filtered_image = fl.filter_stripes(
@@ -140,8 +143,18 @@ def read_filter_save(
         no_cells_config=low_int_filter_params,
         cells_config=high_int_filter_params,
         shadow_correction=shadow_correction,
+        rotate=rotate,
     )
     _save_with_retries(output_path, filtered_image.astype(dtype), compression, output_format)
+
+
+def _rotate_option(rotate, streaks):
+    """``rotate`` of the two entry points: a bool (``TypeError`` otherwise, before anything is read or created); a
+    ``"rotate"`` key of the ``streaks`` dict asks for the same thing."""
+    rotate = fl._engine.rotate_flag(rotate)
+    if isinstance(streaks, dict) and "rotate" in streaks:
+        rotate = rotate or fl._engine.rotate_flag(streaks["rotate"])
+    return rotate
 
 
 def _streaks_options(streaks, shadow_correction):
@@ -207,6 +220,7 @@ def batch_filter(
     output_dtype: Optional[type] = None,
     device: int = 0,
     streaks: Optional[dict] = None,
+    rotate: bool = False,
 ):
     """Filter every image below ``input_path`` into the same tree under ``output_path``
     (``destriper.py:267-378``).  ``workers`` = I/O threads, ``chunks`` = planes per GPU batch
@@ -219,7 +233,13 @@ def batch_filter(
     0 .. 2) and ``"shading": True``, with which the ``shadow_correction`` is resolved per folder as for the stripe
     filter and applied to the filter's result; without it ``shadow_correction`` must be ``None`` (``ValueError``,
     before anything is created).
+
+    ``rotate`` (upstream pystripe's switch of the same name): every plane is turned with ``np.rot90``, filtered and
+    turned back -- for instruments whose stripes run down the columns.  The turns run on the device inside the batched
+    call (``filtering.destripe_planes(..., rotate=True)``); anything but a bool raises ``TypeError`` before anything is
+    created.
     """
+    rotate = _rotate_option(rotate, streaks)
     streaks = _streaks_options(streaks, shadow_correction)
     input_path, output_path = Path(input_path), Path(output_path)
     error_path = os.path.join(output_path, "destripe_log.txt")
@@ -252,7 +272,8 @@ def batch_filter(
                     flat, dark = fl._resolve_shading(shadow_correction, str(paths[ks[0]]))
                     res = fl.destripe_streaks_planes(stack, out_dtype=np.uint16 if as_u16 else np.float32,
                                                      max_batch=min(batch, 64), device=device,
-                                                     **fl.streaks_call_options(streaks, flat, dark))  # fmt: skip
+                                                     **dict(fl.streaks_call_options(streaks, flat, dark),
+                                                            rotate=rotate))  # fmt: skip
                 else:
                     res = fl.destripe_planes(
                         stack,
@@ -263,6 +284,7 @@ def batch_filter(
                         out_dtype=np.uint16 if as_u16 else np.float32,
                         max_batch=min(batch, 64),
                         device=device,
+                        rotate=rotate,
                     )
                 for j, k in enumerate(ks):
                     jobs.append((outs[start + k], res[j].astype(want, copy=False)))

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "dsx_pyramid_bricks_u16", "dsx_pyramid_bricks_ref",
     "dsx_volhist_reset", "dsx_volhist_add_device", "dsx_volhist_get", "dsx_volhist_ref",
     "dsx_plan_streaks_opts", "dsx_streaks_blend_ref",
+    "dsx_set_rotate", "dsx_rot90_device", "dsx_rot90_ref",
 ]  # fmt: skip
 
 
@@ -220,6 +221,9 @@ def load_library(path=None):
                                           ctypes.POINTER(_StreaksOpts)]  # fmt: skip
     lib.dsx_streaks_blend_ref.argtypes = [vp, vp, vp, i32, i32, ctypes.c_float, ctypes.c_float,
                                           ctypes.POINTER(_StreaksOpts), vp, i32]  # fmt: skip
+    lib.dsx_set_rotate.argtypes = [vp, i32]
+    lib.dsx_rot90_device.argtypes = [vp, vp, vp] + [i32] * 5
+    lib.dsx_rot90_ref.argtypes = [vp, vp] + [i32] * 5
     lib.dsx_blosc_decode.argtypes = [vp, ctypes.c_size_t, vp, ctypes.c_size_t]
     lib.dsx_blosc_encode.argtypes = [vp, ctypes.c_size_t, i32, i32, i32, vp, ctypes.c_size_t,
                                      ctypes.POINTER(ctypes.c_size_t)]  # fmt: skip
@@ -268,6 +272,28 @@ def streaks_smoothing(smoothing):
     if not (0.0 <= s <= STREAKS_MAX_SMOOTHING):  # (nan fails both comparisons)
         raise ValueError("smoothing must be 0 or a value in (0, 2], not {!r}".format(smoothing))
     return s
+
+
+def rotate_flag(rotate):
+    """``rotate`` as the C ABI takes it; anything but a ``bool`` is a ``TypeError`` (raised before any device call)."""
+    if not isinstance(rotate, (bool, np.bool_)):
+        raise TypeError("rotate must be True or False, not {!r}".format(rotate))
+    return bool(rotate)
+
+
+def rot90_ref(planes, direction=1):
+    """``np.rot90`` (``direction=1``) or ``np.rot90(., -1)`` (``-1``) of every plane of ``planes[n, H, W]`` (uint16 /
+    float32) through ``dsx_rot90_ref``: the host build of the index map ``k_rot90`` uses.  No GPU involved."""
+    a = np.ascontiguousarray(planes)
+    if a.ndim != 3:
+        raise ValueError("planes must be [n, H, W]")
+    n, H, W = a.shape
+    out = np.empty((n, W, H), a.dtype)
+    rc = load_library().dsx_rot90_ref(a.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
+                                      _dtype_code(a.dtype), n, H, W, int(direction))  # fmt: skip
+    if rc != 0:
+        raise ValueError(load_library().dsx_last_error(None).decode())
+    return out
 
 
 def _shading_planes(flatfield, darkfield, out_shape):
@@ -434,7 +460,11 @@ class DestripeEngine:
 
     # -- plan ------------------------------------------------------------------------------------
     def plan(self, height, width, cells_config, no_cells_config, microscope_high_int=2700,
-             max_batch=32, flatfield=None, darkfield=None):  # fmt: skip
+             max_batch=32, flatfield=None, darkfield=None, rotate=False):  # fmt: skip
+        """``rotate=True`` (``dsx_set_rotate``): the plan computes ``np.rot90(F(np.rot90(x)), -1)`` per plane, ``F``
+        the plan without it -- vertical stripes.  ``height`` / ``width``, the planes of :meth:`run`, ``flatfield`` and
+        ``darkfield`` stay in the caller's orientation; ``info.level_h`` / ``level_w`` are the rotated chain's."""
+        rotate = rotate_flag(rotate)
         cells, no_cells = _as_cfg(cells_config), _as_cfg(no_cells_config)
         # Both configs go through ONE decomposition: which config a plane takes is only known once the
         # statistic fused into the level-1 analysis is (filtering.py:455-462 decides before it transforms).
@@ -447,6 +477,8 @@ class DestripeEngine:
             if rc == -1:
                 raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
             self._check(rc)
+
+        self._check(self._lib.dsx_set_rotate(self._ctx, 1 if rotate else 0))
 
         def call(flat_p, dark_p, dark_h, dark_w):
             rc = self._lib.dsx_plan(self._ctx, int(height), int(width), int(max_batch), ctypes.byref(cells),
@@ -472,7 +504,7 @@ class DestripeEngine:
 
     def plan_streaks(self, height, width, sigma_fg, sigma_bg, wavelet="db3", level=0, crossover=10.0,
                      threshold=None, max_batch=32, route="generic", bands="both", smoothing=0.0, flatfield=None,
-                     darkfield=None):  # fmt: skip
+                     darkfield=None, rotate=False):  # fmt: skip
         """Plan the dual-band filter (``dsx_plan_streaks_ex``); ``threshold=None``: Otsu per plane.  Replaces any plan
         of this engine; :meth:`run` / :meth:`run_device` then return ``[n, height, width]``.  ``route``: ``"generic"``
         (the per-band kernels of the filter, any wavelet and plane), ``"march"`` (the bands run through the log-space
@@ -483,7 +515,9 @@ class DestripeEngine:
         ``bands`` ``"both"``, ``"fg"`` (only the foreground band is filtered and blended with the raw plane,
         ``sigma_bg`` is not read) or ``"bg"`` (the same for the background band); ``smoothing`` 0 or ``0 < s <= 2``, the
         sigma of ``scipy.ndimage.gaussian_filter`` over the blend weight; ``flatfield`` / ``darkfield`` (together, shapes
-        as in :meth:`plan`): the reference's ``flatfield_correction`` of the blend result."""
+        as in :meth:`plan`): the reference's ``flatfield_correction`` of the blend result.  ``rotate``: as in
+        :meth:`plan` (the route conditions are symmetric in height and width)."""
+        rotate = rotate_flag(rotate)
         if bands not in STREAKS_BANDS:
             raise ValueError("bands must be 'both', 'fg' or 'bg', not {!r}".format(bands))
         smoothing = streaks_smoothing(smoothing)
@@ -511,6 +545,7 @@ class DestripeEngine:
         opts = _StreaksOpts(STREAKS_BANDS[bands], smoothing, None if flat is None else flat.ctypes.data,
                             None if dark is None else dark.ctypes.data, 0 if dark is None else dark.shape[0],
                             0 if dark is None else dark.shape[1])  # fmt: skip
+        self._check(self._lib.dsx_set_rotate(self._ctx, 1 if rotate else 0))
         rc = self._lib.dsx_plan_streaks_opts(self._ctx, int(height), int(width), int(max_batch), ctypes.byref(cfg),
                                              STREAKS_ROUTES[route], ctypes.byref(opts))  # fmt: skip
         if rc == -1:
@@ -858,6 +893,18 @@ class DestripeEngine:
         finally:
             for b in bufs:
                 b.free()
+
+    def rot90_device(self, d_src, d_dst, dtype, n, height, width, direction=1):
+        """``n`` planes ``[height, width]`` of ``d_src`` turned into ``[width, height]`` planes of ``d_dst``
+        (``dsx_rot90_device``): ``direction`` 1 is ``np.rot90``, -1 ``np.rot90(., -1)``.  Asynchronous on the engine
+        stream."""
+        nbytes = int(n) * int(height) * int(width) * np.dtype(dtype).itemsize
+        assert nbytes <= d_src.nbytes and nbytes <= d_dst.nbytes, "rot90_device: more planes than a buffer holds"
+        rc = self._lib.dsx_rot90_device(self._ctx, ctypes.c_void_p(d_src.ptr), ctypes.c_void_p(d_dst.ptr),
+                                        _dtype_code(dtype), int(n), int(height), int(width), int(direction))  # fmt: skip
+        if rc == -1:
+            raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
+        self._check(rc)
 
     # -- parity hooks ----------------------------------------------------------------------------
     def set_stack_mode(self, on):

@@ -216,15 +216,17 @@ def _warn_levels(shape, *cfgs):
 
 
 def get_engine(shape, cells_config, no_cells_config, microscope_high_int=2700, flatfield=None,
-               darkfield=None, max_batch=32, device=0):  # fmt: skip
-    """Planned engine for a plane geometry + config pair (cached per process and device)."""
+               darkfield=None, max_batch=32, device=0, rotate=False):  # fmt: skip
+    """Planned engine for a plane geometry + config pair (cached per process and device).  ``rotate``: the plan
+    filters vertical stripes (``DestripeEngine.plan``); ``shape`` and the shading planes stay the caller's."""
+    rotate = _engine.rotate_flag(rotate)
     shade_key = None
     if flatfield is not None:
         # keyed on the memory the planes occupy, not on the Python object: ``flatfields[brain_side]`` makes a new
         # view object per call (prospective flats, filtering.py:478), which would miss the cache every time
         shade_key = (_array_key(flatfield), _array_key(darkfield))
     key = (device, tuple(shape), _cfg_key(cells_config), _cfg_key(no_cells_config),
-           float(microscope_high_int), shade_key, int(max_batch))  # fmt: skip
+           float(microscope_high_int), shade_key, int(max_batch), rotate)  # fmt: skip
     eng = _ENGINES.get(key)
     if eng is not None:
         _ENGINES.move_to_end(key)  # least recently used entries go first
@@ -234,7 +236,7 @@ def get_engine(shape, cells_config, no_cells_config, microscope_high_int=2700, f
         old[0].close()
     e = _engine.DestripeEngine(device)
     e.plan(shape[0], shape[1], cells_config, no_cells_config, microscope_high_int, max_batch,
-           flatfield, darkfield)  # fmt: skip
+           flatfield, darkfield, rotate=rotate)  # fmt: skip
     # the shading arrays stay referenced, so their addresses stay unique while the plan is cached
     _ENGINES[key] = (e, flatfield, darkfield)
     return e
@@ -268,6 +270,8 @@ def log_space_fft_filtering(
     level: Optional[int] = 0,
     sigma: Optional[int] = 64,
     max_threshold: Optional[int] = 4,
+    *,
+    rotate: bool = False,
 ):
     """``filtering.py:139-224`` on the GPU: log -> DWT (any PyWavelets discrete wavelet but ``dmey``; ``db3``,
     the production setting, has specialised kernels) -> per-level Otsu mask, row-median
@@ -279,7 +283,11 @@ def log_space_fft_filtering(
     A 3-D ``[n, H, W]`` input is the reference's stack mode (``:182-183, 188, 210-211``): every plane is decomposed
     on its own, but each level takes ONE Otsu threshold from the coefficients of all planes (``dsx_set_stack_mode``).
     Planes that are to be filtered independently go through :func:`destripe_planes`.
+
+    ``rotate=True`` filters vertical stripes: ``np.rot90(F(np.rot90(x)), -1)`` per plane, ``F`` this call without the
+    option; the turns run on the device (``dsx_set_rotate``).
     """
+    rotate = _engine.rotate_flag(rotate)
     image = np.asarray(input_image)
     if image.ndim not in (2, 3):
         raise ValueError("log_space_fft_filtering takes a 2-D plane or a 3-D stack [n, H, W]")
@@ -293,14 +301,15 @@ def log_space_fft_filtering(
         planes = image if image.dtype in (np.uint16, np.float32) else np.stack([_as_plane_dtype(p) for p in image])
         if planes.dtype not in (np.uint16, np.float32):
             planes = planes.astype(np.float32)
-        eng = get_engine(image.shape[-2:], cfg, cfg, microscope_high_int=2700, max_batch=int(image.shape[0]))
+        eng = get_engine(image.shape[-2:], cfg, cfg, microscope_high_int=2700, max_batch=int(image.shape[0]),
+                         rotate=rotate)
         eng.set_stack_mode(True)
         try:
             out = eng.run(np.ascontiguousarray(planes), out_dtype=np.float32)
         finally:
             eng.set_stack_mode(False)
         return out.astype(np.float64)
-    eng = get_engine(image.shape, cfg, cfg, microscope_high_int=2700, max_batch=1)
+    eng = get_engine(image.shape, cfg, cfg, microscope_high_int=2700, max_batch=1, rotate=rotate)
     out = eng.run(_as_plane_dtype(image)[None], out_dtype=np.float32)[0]
     return out.astype(np.float64)
 
@@ -327,13 +336,14 @@ def _streaks_params(sigma, level, wavelet, crossover, threshold):
 
 
 def _streaks_engine(shape, sigma_fg, sigma_bg, level, wavelet, crossover, threshold, max_batch, device,
-                    route="generic", smoothing=0.0, flat=None, dark=None):  # fmt: skip
+                    route="generic", smoothing=0.0, flat=None, dark=None, rotate=False):  # fmt: skip
     """Planned streaks engine (cached per process and device); ``route`` is resolved: ``generic`` or ``march``.
-    ``sigma_fg`` / ``sigma_bg``: one may be ``None`` (a one-sided plan)."""
+    ``sigma_fg`` / ``sigma_bg``: one may be ``None`` (a one-sided plan).  ``rotate``: as in :func:`get_engine`."""
+    rotate = _engine.rotate_flag(rotate)
     fixed = None if float(threshold) == -1 else float(threshold)
     shade_key = None if flat is None else (_array_key(flat), _array_key(dark))
     key = (device, "streaks", tuple(shape), sigma_fg, sigma_bg, level, _engine._wavelet_key({"wavelet": wavelet}),
-           float(crossover), fixed, int(max_batch), route, float(smoothing), shade_key)  # fmt: skip
+           float(crossover), fixed, int(max_batch), route, float(smoothing), shade_key, rotate)  # fmt: skip
     eng = _ENGINES.get(key)
     if eng is not None:
         _ENGINES.move_to_end(key)
@@ -346,7 +356,7 @@ def _streaks_engine(shape, sigma_fg, sigma_bg, level, wavelet, crossover, thresh
     e.plan_streaks(shape[0], shape[1], sigma_bg if sigma_fg is None else sigma_fg,
                    sigma_fg if sigma_bg is None else sigma_bg, wavelet=wavelet, level=level, crossover=crossover,
                    threshold=fixed, max_batch=max_batch, route=route, bands=bands, smoothing=smoothing, flatfield=flat,
-                   darkfield=dark)  # fmt: skip
+                   darkfield=dark, rotate=rotate)  # fmt: skip
     # (the shading arrays stay referenced, so their addresses stay unique while the plan is cached)
     _ENGINES[key] = (e, flat, dark)
     return e
@@ -354,7 +364,7 @@ def _streaks_engine(shape, sigma_fg, sigma_bg, level, wavelet, crossover, thresh
 
 STREAKS_DEFAULTS = {"sigma": None, "level": 0, "wavelet": "db3", "crossover": 10, "threshold": -1, "route": "auto"}
 # optional keys of the ``streaks=`` dict: passed through (checked) only when present
-STREAKS_OPTIONAL = ("smoothing", "shading")
+STREAKS_OPTIONAL = ("smoothing", "shading", "rotate")
 
 
 def streaks_options(streaks):
@@ -362,7 +372,8 @@ def streaks_options(streaks):
     and completed with the defaults of :func:`filter_streaks` (``route``: ``"auto"``): ``TypeError`` for an unknown key
     or a missing ``sigma`` pair, ``ValueError`` for a bad value.  The optional keys ``"smoothing"`` (0 or
     ``0 < s <= 2``) and ``"shading"`` (a bool: apply the pipeline's ``shadow_correction`` to the filter's result) are
-    in the result only when they were given.  No device call."""
+    in the result only when they were given; so is ``"rotate"`` (a bool, ``TypeError`` for anything else: the filter
+    runs on ``np.rot90`` of every plane and the result is turned back -- vertical stripes).  No device call."""
     if not isinstance(streaks, dict):
         raise TypeError("streaks must be a dict {'sigma': (fg, bg), ...}")
     unknown = sorted(set(streaks) - set(STREAKS_DEFAULTS) - set(STREAKS_OPTIONAL))
@@ -382,6 +393,8 @@ def streaks_options(streaks):
         if not isinstance(opt["shading"], (bool, np.bool_)):
             raise ValueError("shading must be True or False")
         opt["shading"] = bool(opt["shading"])
+    if "rotate" in opt:
+        opt["rotate"] = _engine.rotate_flag(opt["rotate"])
     return opt
 
 
@@ -413,7 +426,7 @@ def _warn_streaks_level(shape, level, wavelet):
 
 
 def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, threshold=-1, route="generic", smoothing=0,
-                   flat=None, dark=None, **params):  # fmt: skip
+                   flat=None, dark=None, rotate=False, **params):  # fmt: skip
     """The stripe filter under its upstream (pystripe) name, in two forms.
 
     * Scalar ``sigma``: ``log_space_fft_filtering(image, sigma=sigma, level=level, wavelet=wavelet, **params)``,
@@ -434,13 +447,19 @@ def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, thresh
       ``scipy.ndimage.gaussian_filter(w, smoothing)`` instead of the raw sigmoid ``w``; ``flat`` / ``dark`` (together)
       put the result through the reference's ``flatfield_correction`` and make the return value uint16, as
       :func:`filter_stripes` does.
+
+    ``rotate=True`` (either form; upstream's ``rotate`` switch of ``read_filter_save``) filters vertical stripes:
+    ``np.rot90(F(np.rot90(image)), -1)`` with ``F`` this call without the option, the turns on the device; ``flat`` /
+    ``dark`` stay in the orientation of ``image``.
     """
+    rotate = _engine.rotate_flag(rotate)
     if sigma is not None and not isinstance(sigma, (str, bytes)) and np.ndim(sigma) == 0:
         if ("crossover" in params or crossover != 10 or threshold != -1 or route != "generic" or smoothing != 0
                 or flat is not None or dark is not None):  # fmt: skip
             raise TypeError("crossover / threshold / route / smoothing / flat / dark belong to the dual-band form: "
                             "pass sigma=(sigma_fg, sigma_bg)")  # fmt: skip
-        return log_space_fft_filtering(input_image=image, sigma=sigma, level=level, wavelet=wavelet, **params)
+        return log_space_fft_filtering(input_image=image, sigma=sigma, level=level, wavelet=wavelet, rotate=rotate,
+                                       **params)
     if params:
         raise TypeError("filter_streaks got unexpected arguments: {}".format(sorted(params)))
     sigma_fg, sigma_bg, level = _streaks_params(sigma, level, wavelet, crossover, threshold)
@@ -449,18 +468,20 @@ def filter_streaks(image, sigma=64, level=0, wavelet="db3", crossover=10, thresh
         raise ValueError("filter_streaks takes one non-empty 2-D plane; use destripe_streaks_planes for a stack")
     out = destripe_streaks_planes(image[None], (sigma_fg, sigma_bg), level=level, wavelet=wavelet, crossover=crossover,
                                   threshold=threshold, out_dtype=np.float32 if flat is None else np.uint16, max_batch=1,
-                                  route=route, smoothing=smoothing, flat=flat, dark=dark)  # fmt: skip
+                                  route=route, smoothing=smoothing, flat=flat, dark=dark, rotate=rotate)  # fmt: skip
     return out[0].astype(np.float64) if flat is None else out[0]
 
 
 def destripe_streaks_planes(planes, sigma, level=0, wavelet="db3", crossover=10, threshold=-1, out_dtype=np.uint16,
                             max_batch=32, device=0, return_threshold=False, route="generic", smoothing=0, flat=None,
-                            dark=None):  # fmt: skip
+                            dark=None, rotate=False):  # fmt: skip
     """Batched dual-band :func:`filter_streaks` over ``planes[n, H, W]`` (uint16 or float32), every plane on its own
     (with ``threshold=-1`` each takes its own Otsu ``t``).  ``out_dtype`` uint16: clip to [0, 65535] and truncate, as
     the Zarr path stores; float32: the filter's value.  ``return_threshold``: also the per-plane ``t`` (float64).
     ``route``, a ``None`` member of ``sigma``, ``smoothing``, ``flat`` / ``dark``: as in :func:`filter_streaks`; with a
-    flat, a float32 output is the clipped value of ``flatfield_correction`` (not truncated)."""
+    flat, a float32 output is the clipped value of ``flatfield_correction`` (not truncated).  ``rotate``: as in
+    :func:`filter_streaks`; ``t`` does not depend on it."""
+    rotate = _engine.rotate_flag(rotate)
     sigma_fg, sigma_bg, level = _streaks_params(sigma, level, wavelet, crossover, threshold)
     smoothing = _engine.streaks_smoothing(smoothing)
     if (flat is None) != (dark is None):
@@ -479,7 +500,7 @@ def destripe_streaks_planes(planes, sigma, level=0, wavelet="db3", crossover=10,
     n = planes.shape[0]
     max_batch = max(1, min(int(max_batch), max(n, 1)))
     eng = _streaks_engine(planes.shape[1:], sigma_fg, sigma_bg, level, wavelet, crossover, threshold, max_batch, device,
-                          route, smoothing, flat, dark)  # fmt: skip
+                          route, smoothing, flat, dark, rotate)  # fmt: skip
     out = np.empty(planes.shape, dtype=out_dtype)
     ts = np.zeros(n, dtype=np.float64)
     for start in range(0, n, max_batch):
@@ -511,13 +532,17 @@ def filter_stripes(
     cells_config: dict,
     shadow_correction: Optional[dict] = None,
     microscope_high_int: Optional[int] = 2700,
+    *,
+    rotate: bool = False,
 ) -> np.array:
     """``filtering.py:417-491`` on the GPU (one plane).
 
     The fg/bg statistic, the config choice, the filter and (if given) the dark/flat correction
     all run on the device.  Returns float64 without shading and uint16 with shading, like the
-    reference.
+    reference.  ``rotate=True``: vertical stripes, ``np.rot90(F(np.rot90(image)), -1)`` with the shading planes in the
+    orientation of ``image`` (:func:`destripe_planes`).
     """
+    rotate = _engine.rotate_flag(rotate)
     image = np.asarray(image)
     if image.ndim != 2:
         raise ValueError("filter_stripes takes one 2-D plane; use destripe_planes for a stack")
@@ -526,10 +551,11 @@ def filter_stripes(
     plane = _as_plane_dtype(image)[None]
     if _engine._wavelet_key(cells_config) != _engine._wavelet_key(no_cells_config):
         out = _destripe_planes_two_wavelets(plane, no_cells_config, cells_config, microscope_high_int, flatfield, darkfield,
-                                            np.uint16 if flatfield is not None else np.float32, 1, False, 0)[0]  # fmt: skip
+                                            np.uint16 if flatfield is not None else np.float32, 1, False, 0,
+                                            rotate)[0]  # fmt: skip
         return out if flatfield is not None else out.astype(np.float64)
     eng = get_engine(image.shape, cells_config, no_cells_config, microscope_high_int, flatfield, darkfield,
-                     max_batch=1)  # fmt: skip
+                     max_batch=1, rotate=rotate)  # fmt: skip
     if flatfield is not None:
         return eng.run(plane, out_dtype=np.uint16)[0]
     return eng.run(plane, out_dtype=np.float32)[0].astype(np.float64)
@@ -546,13 +572,20 @@ def destripe_planes(
     max_batch: int = 32,
     return_config: bool = False,
     device: int = 0,
+    rotate: bool = False,
 ):
     """Batched ``filter_stripes`` over ``planes[n, H, W]`` (uint16 or float32): every plane is
     filtered independently, exactly as the z-loop of ``execute_worker`` does
     (``zarr_destriper.py:319-327``), in cohorts of ``max_batch`` planes per launch chain.
 
     ``out_dtype`` uint16 = what the Zarr path stores (clip + truncate); float32 = ``exp(y) + 1``.
+
+    ``rotate=True`` filters vertical stripes: per plane ``np.rot90(F(np.rot90(x)), -1)``, ``F`` this call without the
+    option -- everything the filter derives from the plane shape is derived from the rotated plane, the flat and the
+    dark (cropped to the plane) are applied in the orientation of ``x``, and the config decision does not depend on
+    the orientation.  The turns run on the device, inside the launch chain (``dsx_set_rotate``).
     """
+    rotate = _engine.rotate_flag(rotate)
     planes = np.asarray(planes)
     if planes.ndim != 3:
         raise ValueError("planes must be [n, H, W]")
@@ -562,14 +595,14 @@ def destripe_planes(
         planes = np.stack([_as_plane_dtype(p) for p in planes]) if len(planes) else planes.astype(np.float32)
     if _engine._wavelet_key(cells_config) != _engine._wavelet_key(no_cells_config):
         return _destripe_planes_two_wavelets(planes, no_cells_config, cells_config, microscope_high_int, flatfield,
-                                             darkfield, out_dtype, max_batch, return_config, device)  # fmt: skip
+                                             darkfield, out_dtype, max_batch, return_config, device, rotate)  # fmt: skip
     eng = get_engine(planes.shape[1:], cells_config, no_cells_config, microscope_high_int, flatfield,
-                     darkfield, max_batch=max_batch, device=device)  # fmt: skip
+                     darkfield, max_batch=max_batch, device=device, rotate=rotate)  # fmt: skip
     return eng.run(planes, out_dtype=out_dtype, return_cfg=return_config)
 
 
 def _destripe_planes_two_wavelets(planes, no_cells_config, cells_config, microscope_high_int, flatfield, darkfield,
-                                  out_dtype, max_batch, return_config, device):
+                                  out_dtype, max_batch, return_config, device, rotate=False):
     """The two configs name DIFFERENT wavelets.  One launch chain decomposes a plane before its config is known (the
     fg/bg statistic is fused into the first kernel), so it cannot switch filter banks per plane; the reference decides
     first and decomposes afterwards (``filtering.py:459-467``).  Same order here: the statistic of every plane
@@ -579,7 +612,7 @@ def _destripe_planes_two_wavelets(planes, no_cells_config, cells_config, microsc
     cutoff = _foreground_cutoff(0.3)
     which = np.zeros(n, dtype=np.int32)
     probe = get_engine(planes.shape[1:], no_cells_config, no_cells_config, microscope_high_int, flatfield, darkfield,
-                       max_batch=max_batch, device=device)  # fmt: skip
+                       max_batch=max_batch, device=device, rotate=rotate)  # fmt: skip
     for k in range(n):
         fore, back, _ = probe.foreground_background(planes[k], cutoff, want_mask=False)
         which[k] = 1 if (fore > back and fore > microscope_high_int) else 0
@@ -589,7 +622,7 @@ def _destripe_planes_two_wavelets(planes, no_cells_config, cells_config, microsc
         if idx.size == 0:
             continue
         eng = get_engine(planes.shape[1:], cfg, cfg, microscope_high_int, flatfield, darkfield,
-                         max_batch=max_batch, device=device)  # fmt: skip
+                         max_batch=max_batch, device=device, rotate=rotate)  # fmt: skip
         res = eng.run(np.ascontiguousarray(planes[idx]), out_dtype=out_dtype)
         if out is None:
             out = np.empty((n,) + res.shape[1:], dtype=res.dtype)

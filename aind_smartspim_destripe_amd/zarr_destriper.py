@@ -197,8 +197,13 @@ def execute_worker(
     device: int = 0,
     max_batch: int = 64,
     streaks=None,
+    *,
+    rotate: bool = False,
 ):
     """``zarr_destriper.py:253-336`` with the plane loop (``:319-327``) as one batched GPU call.
+
+    ``rotate``: every plane is filtered as ``np.rot90(F(np.rot90(x)), -1)`` (vertical stripes; the turns run on the
+    device, ``fl.destripe_planes``); a ``"rotate"`` key of ``streaks`` asks for the same.
 
     ``streaks`` (the checked dict of ``fl.streaks_options``, ``route`` resolved): the planes go through the dual-band
     filter (``fl.destripe_streaks_planes``) instead; the configs are not read then, and the ``shadow_correction`` is
@@ -208,6 +213,7 @@ def execute_worker(
     with ``microscope_high_int=2500`` (``:326``); the result is assigned to
     ``output_destriped_zarr[output_slices]`` (uint16 store: truncation, ``:336``).
     """
+    rotate = engine_mod.rotate_flag(rotate)
     data = np.squeeze(data, axis=0)
     global_coord_pos, _, _ = recover_global_position(batch_super_chunk, batch_internal_slice)
     unpadded_global_slice, unpadded_local_slice = unpad_global_coords(
@@ -229,8 +235,9 @@ def execute_worker(
     planes = data if data.dtype in (np.uint16, np.float32) else data.astype(np.float32)
     if streaks is not None:
         flat, dark = fl._resolve_shading(shadow_correction, input_tile_path)
-        filtered = fl.destripe_streaks_planes(planes, out_dtype=np.uint16, max_batch=max_batch, device=device,
-                                              **fl.streaks_call_options(streaks, flat, dark))  # fmt: skip
+        kw = fl.streaks_call_options(streaks, flat, dark)
+        kw["rotate"] = rotate or engine_mod.rotate_flag(kw.get("rotate", False))
+        filtered = fl.destripe_streaks_planes(planes, out_dtype=np.uint16, max_batch=max_batch, device=device, **kw)
     else:
         filtered = fl.destripe_planes(
             planes,
@@ -242,6 +249,7 @@ def execute_worker(
             out_dtype=np.uint16,
             max_batch=max_batch,
             device=device,
+            rotate=rotate,
         )
     if filtered.shape != data.shape:
         # odd planes grow by one row / column (waverec2); the reference's assignment into
@@ -786,6 +794,7 @@ def destripe_zarr_store(
     n_levels=1,
     streaks=None,
     histogram=None,
+    rotate=False,
 ):
     """Chunk map of ``destripe_zarr`` (``zarr_destriper.py:909-1211``) over a Zarr-v2 directory store -- the engine-level
     form (explicit configs and ``shadow_correction``); :func:`destripe_zarr` is the entry point with the reference's
@@ -871,8 +880,17 @@ def destripe_zarr_store(
     every block are counted where they lie, right behind the filter (``dsx_volhist_add_device``, one more read of them);
     the host path counts what it assigns.  ``LAST_RUN["histogram_voxels"]`` is the number added (``None`` without the
     option).  Anything but a C-contiguous ``int64`` array of 65 536 bins raises ``ValueError`` before anything is created.
+
+    ``rotate``: ``True`` destripes a store whose stripes run down the columns -- every plane is filtered as
+    ``np.rot90(F(np.rot90(x)), -1)``, ``F`` the filter without the option (either filter; a ``"rotate": True`` in the
+    ``streaks`` dict asks for the same).  The engine turns the planes on the device inside its launch chain
+    (``dsx_set_rotate``), so every route -- device re-tiling, device codecs, fused pyramid, histogram, the host path --
+    runs as without it and sees planes in the store's orientation; the shading planes stay in that orientation too.
+    Anything but a bool raises ``TypeError`` before anything is created.  ``LAST_RUN["rotate"]`` is the value used.
     """
     from . import pyramid
+
+    rotate = engine_mod.rotate_flag(rotate)
 
     logger = logger or logging.getLogger("dsx.zarr")
     if histogram is not None and not (isinstance(histogram, np.ndarray) and histogram.dtype == np.int64
@@ -882,6 +900,7 @@ def destripe_zarr_store(
     if streaks is not None:
         streaks = fl.streaks_options(streaks)
         fl.streaks_shading(streaks, shadow_correction)
+        rotate = rotate or streaks.get("rotate", False)
     codec_mode = output_codec_mode(device_codec, compressor)  # (a wrong mode fails before anything is created)
     device_codec = codec_mode is not None
     decode_mode = device_decode_mode(device_decode)
@@ -926,7 +945,7 @@ def destripe_zarr_store(
         z0, z1 = z_shard(zyx[0], world_size, rank, z_chunk=output_chunks[-3])
     dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device
     LAST_RUN.update(rank=rank, world_size=world_size, z_range=(z0, z1), io_threads=int(io_threads), device=dev,
-                    filter="stripes" if streaks is None else "streaks",
+                    rotate=rotate, filter="stripes" if streaks is None else "streaks",
                     streaks_route=None if streaks is None else streaks["route"],
                     streaks_smoothing=None if streaks is None else float(streaks.get("smoothing", 0.0)),
                     streaks_shading=None if streaks is None else bool(streaks.get("shading") and shadow_correction is not None))  # fmt: skip
@@ -963,11 +982,11 @@ def destripe_zarr_store(
             flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
             eng = fl._streaks_engine(zyx[1:], *streaks["sigma"], streaks["level"], streaks["wavelet"], streaks["crossover"],
                                      streaks["threshold"], min(block_z, 64), dev, streaks["route"],
-                                     streaks.get("smoothing", 0.0), flatfield, darkfield)  # fmt: skip
+                                     streaks.get("smoothing", 0.0), flatfield, darkfield, rotate)  # fmt: skip
         else:
             flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
             eng = fl.get_engine(zyx[1:], cells_config, no_cells_config, 2500, flatfield, darkfield,
-                                max_batch=min(block_z, 64), device=dev)  # fmt: skip
+                                max_batch=min(block_z, 64), device=dev, rotate=rotate)  # fmt: skip
         blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, "runs" if codec_mode == "runs" else device_codec,
                                 device_decode, (levels, pyr_arrays) if levels else None)  # fmt: skip
         blocks.histogram = histogram is not None
@@ -994,7 +1013,7 @@ def destripe_zarr_store(
         block = src[lead + sc]
         data = block[np.newaxis].astype(np.float32) if block.dtype != np.uint16 else block[np.newaxis]
         written = execute_worker(data, sc, internal, cells_config, no_cells_config, (0, 0, 0), dst, shadow_correction,
-                                 name, logger, device=dev, streaks=streaks)  # fmt: skip
+                                 name, logger, device=dev, streaks=streaks, rotate=rotate)  # fmt: skip
         if histogram is not None:
             counts = np.bincount(written.ravel(), minlength=engine_mod.VOLHIST_BINS)
             histogram += counts
@@ -1434,6 +1453,7 @@ def destripe_zarr(
     streaks=None,
     ome_metadata=False,
     display_window=None,
+    rotate=False,
 ):
     """``destripe_zarr`` of the reference (``zarr_destriper.py:909-1211``) with its 14 parameters, on the GPU chunk map.
 
@@ -1474,9 +1494,11 @@ def destripe_zarr(
     the caller: every rank counts the voxels it writes (``destripe_zarr_store(histogram=...)``), ``group.sum_counts``
     adds the ranks' counts after the barrier, and rank 0 raises ``RuntimeError`` unless they add up to the voxels of
     level 0.  ``"percentile"`` with ``world_size > 1`` and a group without ``sum_counts`` raises ``ValueError`` before
-    anything is created.  ``LAST_RUN["display_window"]`` is the pair written, or ``None``).
+    anything is created.  ``LAST_RUN["display_window"]`` is the pair written, or ``None``), ``rotate`` (vertical stripes:
+    :func:`destripe_zarr_store`; a bool, ``TypeError`` before anything is created otherwise).
     Returns ``(planes processed by this rank, seconds)``.
     """
+    rotate = engine_mod.rotate_flag(rotate)
     output_codec_mode(device_codec, compressor)  # (a wrong string or mode fails before anything is written)
     device_decode_mode(device_decode)
     if fused_pyramid and pipelined_pyramid:
@@ -1579,6 +1601,7 @@ def destripe_zarr(
         n_levels=n_levels if fused_pyramid else 1,
         streaks=streaks,
         histogram=histogram,
+        rotate=rotate,
     )
     if group is not None and world_size > 1:
         group.barrier()  # level 0 of this tile is complete on every rank: the pyramid may read it
@@ -1654,6 +1677,7 @@ def destripe_channel(
     ome_metadata=False,
     display_window=None,
     streaks=None,
+    rotate=False,
 ):
     """``destripe_channel`` of the reference (``zarr_destriper.py:1214-1267``), same eight parameters (the reference's
     caller passes them by keyword, ``run_capsule.py:394-403``), wired to the GPU chunk map.
@@ -1674,8 +1698,10 @@ def destripe_channel(
     ``distributed.RankGroup`` rank 0 alone reads the flat and dark planes of a tile and broadcasts them (RCCL).
     ``streaks``: the dict of :func:`destripe_zarr_store`, handed to every tile's :func:`destripe_zarr`.  Every tile
     comes with its retrospective flat here, so the dict must say ``"shading": True`` (``ValueError`` before anything is
-    created otherwise).
+    created otherwise).  ``rotate``: vertical stripes, handed to every tile's :func:`destripe_zarr` (a bool,
+    ``TypeError`` before anything is created otherwise).
     """
+    rotate = engine_mod.rotate_flag(rotate)
     if world_size > 1 and group is None:
         raise ValueError("destripe_channel with world_size > 1 needs a group to order the pyramid after all ranks")
     if streaks is not None and not fl.streaks_options(streaks).get("shading"):
@@ -1741,6 +1767,7 @@ def destripe_channel(
             ome_metadata=ome_metadata,
             display_window=display_window,
             streaks=streaks,
+            rotate=rotate,
         )
         done[tile_path.name] = n
     return done

@@ -101,6 +101,26 @@ int dsx_plan_info(const dsx_ctx* ctx, dsx_plan_info_t* info);
  * correction, not the plane).  Takes effect at the next dsx_plan.                                          */
 int dsx_set_wavelet(dsx_ctx* ctx, const double* dec_lo, const double* dec_hi, const double* rec_lo,
                     const double* rec_hi, int len);
+/* Vertical stripes (pystripe's `rotate` switch of read_filter_save / batch_filter): sticky context state like the
+ * filter bank, read by the next dsx_plan / dsx_plan_streaks*.  A plan made with it on computes, per plane,
+ *     np.rot90( F(np.rot90(x)), -1 )          np.rot90(x)[i, j] == x[j, W - 1 - i], shape [W, H]
+ * with F the same plan without it: the plan takes the caller's height and width and plans the chain for
+ * (width, height) -- sigma / min(H, W), the level count, the odd-size growth and the even padding are those of the
+ * rotated plane -- and dsx_run_host / dsx_run_device take and return planes in the caller's orientation: every stream
+ * part of a cohort turns its planes ahead of its first kernel and its result back behind its last one
+ * (csrc/dsx_rot90.h), through two buffers of max_batch planes the plan owns.  flat / dark of dsx_plan,
+ * dsx_plan_streaks_opts and dsx_set_shading_device stay in the caller's orientation (the dark is cropped to the plane,
+ * then both are turned by the plan).  dsx_plan_info reports height / width / out_height / out_width of the caller's
+ * plane; level_h / level_w, dsx_get_level and dsx_get_thresholds are those of the rotated chain.  cfg_used and the
+ * streaks threshold do not depend on the orientation.  A caller's height above the row filter's width limit (36 856)
+ * is DSX_ELIMIT.  DSX_GRAPH=1 runs such a plan eagerly.  Off (the default): nothing changes, no kernel is added and no
+ * buffer is allocated. */
+int dsx_set_rotate(dsx_ctx* ctx, int on);
+/* The quarter turn on its own: n planes [H, W] -> [W, H] of dtype (DSX_U16 / DSX_F32), dir +1 == np.rot90(x),
+ * -1 == np.rot90(x, -1), per plane.  Device pointers, not in place, asynchronous on the context stream.
+ * dsx_rot90_ref: the same index map on the host (host pointers, synchronous, no context: dsx_last_error(NULL)). */
+int dsx_rot90_device(dsx_ctx* ctx, const void* d_src, void* d_dst, int dtype, int n, int H, int W, int dir);
+int dsx_rot90_ref(const void* src, void* dst, int dtype, int n, int H, int W, int dir);
 /* Same, with the shading planes already in device memory (e.g. after an RCCL broadcast). */
 int dsx_set_shading_device(dsx_ctx* ctx, const float* d_flat, const float* d_dark, int dark_h,
                            int dark_w);
