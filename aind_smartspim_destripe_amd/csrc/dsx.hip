@@ -32,6 +32,7 @@
 #include "dsx_chain.h"
 #include "dsx_io.h"
 #include "dsx_streaks.h"
+#include "dsx_lightsheet.h"
 #include "dsx_zenc_kernels.h"
 #include "dsx_lz4enc_kernels.h"
 #include "dsx_zdec_kernels.h"
@@ -202,6 +203,17 @@ struct dsx_ctx {
   void* rot_in = nullptr;
   void* rot_out = nullptr;
   size_t rot_in_bytes = 0, rot_out_bytes = 0;
+  // light-sheet background mode (dsx_plan_lightsheet): when set, dsx_run_* run this plan.  ls_H x ls_W is the plane the
+  // kernels see (the rotated one of a rotated plan); ls_q / ls_ls / ls_bg hold max_batch uint8 planes each
+  bool lightsheet = false;
+  int ls_H = 0, ls_W = 0, ls_A = 0, ls_B = 0;
+  double ls_p = 0.0;
+  float ls_lambda = 0.f;
+  uint32_t* ls_edges = nullptr;   // [kLsEdges]
+  float* ls_back = nullptr;       // [256]
+  uint8_t* ls_q = nullptr;
+  uint8_t* ls_ls = nullptr;
+  uint8_t* ls_bg = nullptr;
 };
 
 namespace {
@@ -1238,27 +1250,70 @@ int streaks_cohort(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d
   return DSX_OK;
 }
 
-// dsx_run_host (host = true: staged through the context's device buffers) / dsx_run_device of a streaks plan
-int streaks_run(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, int out_dtype, bool host) {
+// ---- light-sheet background mode (dsx_plan_lightsheet) ---------------------------------------------------------------
+void free_lightsheet(dsx_ctx* c) {
+  auto fr = [](void* p) { if (p) (void)hipFree(p); };
+  fr(c->ls_edges); c->ls_edges = nullptr;
+  fr(c->ls_back); c->ls_back = nullptr;
+  fr(c->ls_q); c->ls_q = nullptr;
+  fr(c->ls_ls); c->ls_ls = nullptr;
+  fr(c->ls_bg); c->ls_bg = nullptr;
+  c->lightsheet = false;
+}
+
+// One cohort of a light-sheet plan on the context stream: quantise, the 1 x A filter, the B x B filter with step 3
+int lightsheet_cohort(dsx_ctx* ctx, const void* d_in, int in_dtype, int nb, void* d_out, int out_dtype) {
+  using namespace dsx::ls;
+  if (in_dtype != DSX_U16) return fail(ctx, DSX_EINVAL, "the light-sheet plan takes uint16 planes only");
+  hipStream_t s = use_main(ctx);
+  const int H = ctx->ls_H, W = ctx->ls_W, A = ctx->ls_A, B = ctx->ls_B;
+  const size_t rows = (size_t)nb * H, total = rows * W;
+  const uint16_t* x = (const uint16_t*)d_in;
+  k_ls_quant<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(x, total, ctx->ls_edges, ctx->ls_q);
+  const size_t runs = rows * ((W + kLsRun - 1) / kLsRun);
+  if (A <= 255)
+    k_ls_row<uint8_t, 128><<<(unsigned)((runs + 127) / 128), 128, 0, s>>>(ctx->ls_q, ctx->ls_ls, rows, W, A, ctx->ls_p);
+  else
+    k_ls_row<uint16_t, 64><<<(unsigned)((runs + 63) / 64), 64, 0, s>>>(ctx->ls_q, ctx->ls_ls, rows, W, A, ctx->ls_p);
+  const int S = bg_strip(B);
+  const dim3 grid((unsigned)((W + S - 1) / S), (unsigned)((H + kLsRows - 1) / kLsRows), (unsigned)nb);
+  const size_t lds = bg_lds_bytes(W, B);
+  if (out_dtype == DSX_U16) {
+    DSX_HIP(raise_lds_limit<k_ls_bg<uint16_t>>());
+    k_ls_bg<uint16_t><<<grid, kLsBgThreads, lds, s>>>(x, ctx->ls_q, ctx->ls_ls, ctx->ls_bg, (uint16_t*)d_out, ctx->ls_back,
+                                                      H, W, B, S, ctx->ls_p, ctx->ls_lambda);
+  } else {
+    DSX_HIP(raise_lds_limit<k_ls_bg<float>>());
+    k_ls_bg<float><<<grid, kLsBgThreads, lds, s>>>(x, ctx->ls_q, ctx->ls_ls, ctx->ls_bg, (float*)d_out, ctx->ls_back, H, W,
+                                                   B, S, ctx->ls_p, ctx->ls_lambda);
+  }
+  DSX_HIP(hipGetLastError());
+  ctx->last_n = nb;
+  return DSX_OK;
+}
+
+// dsx_run_host (host = true: staged through the context's device buffers) / dsx_run_device of a streaks plan or a
+// light-sheet plan: planes of H x W (the plan's own, rotated, geometry), cohorts of B planes through `run_one`
+typedef int (*cohort_fn)(dsx_ctx*, const void*, int, int, void*, int);
+int cohort_run(dsx_ctx* ctx, int H, int W, int B, cohort_fn run_one, const void* in, int in_dtype, int n, void* out,
+               int out_dtype, bool host) {
   if (int rc = check_run_args(ctx, in, out, n, in_dtype, out_dtype)) return rc;
   DSX_HIP(hipSetDevice(ctx->device));
-  const dsx::st::StreaksPlan& p = ctx->sp;
-  const size_t in_plane = (size_t)p.H * p.W * elem_size(in_dtype);
-  const size_t out_plane = (size_t)p.H * p.W * elem_size(out_dtype);
-  const int B = p.B;
+  const size_t in_plane = (size_t)H * W * elem_size(in_dtype);
+  const size_t out_plane = (size_t)H * W * elem_size(out_dtype);
   if (host) {
     if (int rc = grow_stage(ctx, &ctx->d_stage_in, &ctx->stage_in_bytes, in_plane * B)) return rc;
     if (int rc = grow_stage(ctx, &ctx->d_stage_out, &ctx->stage_out_bytes, out_plane * B)) return rc;
   }
   if (ctx->rot)
     if (int rc = grow_rot(ctx, in_plane * B, out_plane * B)) return rc;
-  // A rotated plan (p holds the rotated geometry, p.H == rot_W): the cohort is turned into rot_in on the context stream,
+  // A rotated plan (H x W is the rotated geometry, H == rot_W): the cohort is turned into rot_in on the context stream,
   // filtered there into rot_out and turned back into the caller's buffer.
   auto cohort = [&](const void* d_src, int nb, void* d_dst) -> int {
-    if (!ctx->rot) return streaks_cohort(ctx, d_src, in_dtype, nb, d_dst, out_dtype);
+    if (!ctx->rot) return run_one(ctx, d_src, in_dtype, nb, d_dst, out_dtype);
     rot_planes(use_main(ctx), d_src, ctx->rot_in, in_dtype, nb, ctx->rot_H, ctx->rot_W, +1);
-    if (int rc = streaks_cohort(ctx, ctx->rot_in, in_dtype, nb, ctx->rot_out, out_dtype)) return rc;
-    rot_planes(use_main(ctx), ctx->rot_out, d_dst, out_dtype, nb, p.H, p.W, -1);
+    if (int rc = run_one(ctx, ctx->rot_in, in_dtype, nb, ctx->rot_out, out_dtype)) return rc;
+    rot_planes(use_main(ctx), ctx->rot_out, d_dst, out_dtype, nb, H, W, -1);
     DSX_HIP(hipGetLastError());
     return DSX_OK;
   };
@@ -1284,6 +1339,15 @@ int streaks_run(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, in
     }
   }
   return DSX_OK;
+}
+
+int streaks_run(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, int out_dtype, bool host) {
+  return cohort_run(ctx, ctx->sp.H, ctx->sp.W, ctx->sp.B, streaks_cohort, in, in_dtype, n, out, out_dtype, host);
+}
+
+int lightsheet_run(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, int out_dtype, bool host) {
+  if (in_dtype != DSX_U16) return fail(ctx, DSX_EINVAL, "the light-sheet plan takes uint16 planes only");
+  return cohort_run(ctx, ctx->ls_H, ctx->ls_W, ctx->max_batch, lightsheet_cohort, in, in_dtype, n, out, out_dtype, host);
 }
 
 }  // namespace
@@ -1368,6 +1432,7 @@ void dsx_destroy(dsx_ctx* ctx) {
   for (auto& r : ctx->prof) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
   free_plan_buffers(ctx);
   free_streaks(ctx);
+  free_lightsheet(ctx);
   if (ctx->t0) (void)hipEventDestroy(ctx->t0);
   if (ctx->t1) (void)hipEventDestroy(ctx->t1);
   for (int i = 1; i < dsx_ctx::kMaxStreams; ++i) {
@@ -1415,6 +1480,7 @@ int dsx_plan(dsx_ctx* ctx, int height, int width, int max_batch, const dsx_cfg* 
   DSX_HIP(hipStreamSynchronize(use_main(ctx)));
   free_plan_buffers(ctx);
   free_streaks(ctx);
+  free_lightsheet(ctx);
 
   const dsx_cfg* src[2] = {no_cells_config, cells_config};  // index 1 == cells_config
   for (int c = 0; c < 2; ++c) {
@@ -1649,6 +1715,7 @@ int dsx_run_device(dsx_ctx* ctx, const void* d_in, int in_dtype, int n, void* d_
                    int32_t* d_cfg_used) {
   if (!ctx) return DSX_EINVAL;
   if (ctx->streaks) return streaks_run(ctx, d_in, in_dtype, n, d_out, out_dtype, false);
+  if (ctx->lightsheet) return lightsheet_run(ctx, d_in, in_dtype, n, d_out, out_dtype, false);
   if (!ctx->planned) return fail(ctx, DSX_ENOPLAN, "dsx_plan has not been called");
   if (int rc = check_run_args(ctx, d_in, d_out, n, in_dtype, out_dtype)) return rc;
   DSX_HIP(hipSetDevice(ctx->device));
@@ -1679,6 +1746,7 @@ int dsx_run_host(dsx_ctx* ctx, const void* in, int in_dtype, int n, void* out, i
                  int32_t* cfg_used) {
   if (!ctx) return DSX_EINVAL;
   if (ctx->streaks) return streaks_run(ctx, in, in_dtype, n, out, out_dtype, true);
+  if (ctx->lightsheet) return lightsheet_run(ctx, in, in_dtype, n, out, out_dtype, true);
   if (!ctx->planned) return fail(ctx, DSX_ENOPLAN, "dsx_plan has not been called");
   if (int rc = check_run_args(ctx, in, out, n, in_dtype, out_dtype)) return rc;
   DSX_HIP(hipSetDevice(ctx->device));
@@ -2618,6 +2686,7 @@ int dsx_plan_streaks_opts(dsx_ctx* ctx, int height_in, int width_in, int max_bat
   DSX_HIP(hipStreamSynchronize(use_main(ctx)));
   free_plan_buffers(ctx);
   free_streaks(ctx);
+  free_lightsheet(ctx);
   ctx->rot = rot;
   ctx->rot_H = height_in;
   ctx->rot_W = width_in;
@@ -2735,6 +2804,78 @@ int dsx_plan_streaks_opts(dsx_ctx* ctx, int height_in, int width_in, int max_bat
   if (int rc = apply_opts()) return rc;
   ctx->streaks = true;
   ctx->last_n = 0;
+  return DSX_OK;
+}
+
+int dsx_plan_lightsheet(dsx_ctx* ctx, int height_in, int width_in, int max_batch, double p, int A, int B, double lambda,
+                        const uint32_t* edges, const float* back) {
+  using namespace dsx::ls;
+  if (!ctx) return DSX_EINVAL;
+  if (const char* e = lightsheet_args(height_in, width_in, p, A, B, lambda, edges, back)) return fail(ctx, DSX_EINVAL, e);
+  if (max_batch < 1 || max_batch > 65535) return fail(ctx, DSX_EINVAL, "max_batch must be in 1 .. 65535");
+  if ((size_t)height_in * width_in > ((size_t)1 << 30)) return fail(ctx, DSX_ELIMIT, "plane larger than 2^30 pixels");
+  // dsx_set_rotate: the kernels see np.rot90 of the caller's plane, [width_in, height_in]
+  const bool rot = ctx->rot_next;
+  const int height = rot ? width_in : height_in, width = rot ? height_in : width_in;
+  if ((height + kLsRows - 1) / kLsRows > 65535) return fail(ctx, DSX_ELIMIT, "plane too high for the light-sheet plan");
+  DSX_HIP(hipSetDevice(ctx->device));
+  DSX_HIP(hipStreamSynchronize(use_main(ctx)));
+  free_plan_buffers(ctx);
+  free_streaks(ctx);
+  free_lightsheet(ctx);
+  ctx->rot = rot;
+  ctx->rot_H = height_in;
+  ctx->rot_W = width_in;
+  ctx->ls_H = height; ctx->ls_W = width; ctx->ls_A = A; ctx->ls_B = B;
+  ctx->ls_p = p;
+  ctx->ls_lambda = (float)lambda;
+  ctx->max_batch = max_batch;
+  const size_t planes = (size_t)height * width * max_batch;
+  void** bufs[5] = {(void**)&ctx->ls_edges, (void**)&ctx->ls_back, (void**)&ctx->ls_q, (void**)&ctx->ls_ls, (void**)&ctx->ls_bg};
+  const size_t bytes[5] = {sizeof(uint32_t) * kLsEdges, sizeof(float) * 256, planes, planes, planes};
+  for (int k = 0; k < 5; ++k) {
+    hipError_t e = hipMalloc(bufs[k], bytes[k]);
+    if (e != hipSuccess) {
+      *bufs[k] = nullptr;
+      free_lightsheet(ctx);
+      return fail(ctx, DSX_ENOMEM, std::string("hipMalloc (light-sheet plan): ") + hipGetErrorString(e));
+    }
+  }
+  DSX_HIP(hipMemcpy(ctx->ls_edges, edges, bytes[0], hipMemcpyHostToDevice));
+  DSX_HIP(hipMemcpy(ctx->ls_back, back, bytes[1], hipMemcpyHostToDevice));
+  ctx->workspace_bytes = 3 * planes;
+  ctx->lightsheet = true;
+  ctx->last_n = 0;
+  return DSX_OK;
+}
+
+int dsx_lightsheet_ref(const void* x, int height, int width, double p, int A, int B, double lambda,
+                       const uint32_t* edges, const float* back, uint8_t* ls, uint8_t* bg, void* out, int out_dtype) {
+  using namespace dsx::ls;
+  if (const char* e = lightsheet_args(height, width, p, A, B, lambda, edges, back)) return fail(nullptr, DSX_EINVAL, e);
+  if (!x || !out) return fail(nullptr, DSX_EINVAL, "lightsheet: NULL pointer");
+  if ((uintptr_t)x & 1) return fail(nullptr, DSX_EINVAL, "lightsheet: uint16 planes must be 2-byte aligned");
+  if (out_dtype != DSX_U16 && out_dtype != DSX_F32) return fail(nullptr, DSX_EINVAL, "unknown output type");
+  const size_t n = (size_t)height * width;
+  std::vector<uint8_t> work(n * 3);
+  uint8_t* lsp = ls ? ls : work.data() + n;
+  uint8_t* bgp = bg ? bg : work.data() + 2 * n;
+  if (out_dtype == DSX_U16)
+    lightsheet_host((const uint16_t*)x, height, width, p, A, B, (float)lambda, edges, back, work.data(), lsp, bgp, (uint16_t*)out);
+  else
+    lightsheet_host((const uint16_t*)x, height, width, p, A, B, (float)lambda, edges, back, work.data(), lsp, bgp, (float*)out);
+  return DSX_OK;
+}
+
+int dsx_get_lightsheet_planes(dsx_ctx* ctx, int plane, uint8_t* ls, uint8_t* bg) {
+  if (!ctx) return DSX_EINVAL;
+  if (!ctx->lightsheet) return fail(ctx, DSX_ENOPLAN, "dsx_plan_lightsheet has not been called");
+  if (plane < 0 || plane >= ctx->last_n) return fail(ctx, DSX_EINVAL, "plane index out of range");
+  DSX_HIP(hipSetDevice(ctx->device));
+  DSX_HIP(hipStreamSynchronize(use_main(ctx)));
+  const size_t n = (size_t)ctx->ls_H * ctx->ls_W;
+  if (ls) DSX_HIP(hipMemcpy(ls, ctx->ls_ls + n * plane, n, hipMemcpyDeviceToHost));
+  if (bg) DSX_HIP(hipMemcpy(bg, ctx->ls_bg + n * plane, n, hipMemcpyDeviceToHost));
   return DSX_OK;
 }
 

@@ -122,16 +122,24 @@ def read_filter_save(
     output_dtype: Optional[type] = None,
     streaks: Optional[dict] = None,
     rotate: bool = False,
+    *,
+    lightsheet: Optional[dict] = None,
 ):
     """One plane: read (3 tries), ``filter_stripes`` on the GPU, ``astype`` to the source dtype (or
     ``output_dtype``), save (``destriper.py:113-215``).  ``streaks``: the dict of :func:`batch_filter`.  ``rotate``:
-    as in :func:`batch_filter`."""
+    as in :func:`batch_filter`.  ``lightsheet``: the dict of :func:`batch_filter`."""
     rotate = _rotate_option(rotate, streaks)
+    if lightsheet is not None:
+        lightsheet = fl.lightsheet_options(lightsheet, streaks, shadow_correction)
     streaks = _streaks_options(streaks, shadow_correction)
     raw_image = _read_with_retries(output_dir, input_path)
     if raw_image is None:
         return
     dtype = _target_dtype(raw_image.dtype, output_dtype)
+    if lightsheet is not None:
+        filtered_image = fl.correct_lightsheet(raw_image, rotate=rotate, **lightsheet)
+        _save_with_retries(output_path, filtered_image.astype(dtype), compression, output_format)
+        return
     if streaks is not None:
         flat, dark = fl._resolve_shading(shadow_correction, input_path)
         filtered_image = fl.filter_streaks(raw_image, **dict(fl.streaks_call_options(streaks, flat, dark), rotate=rotate))
@@ -221,6 +229,8 @@ def batch_filter(
     device: int = 0,
     streaks: Optional[dict] = None,
     rotate: bool = False,
+    *,
+    lightsheet: Optional[dict] = None,
 ):
     """Filter every image below ``input_path`` into the same tree under ``output_path``
     (``destriper.py:267-378``).  ``workers`` = I/O threads, ``chunks`` = planes per GPU batch
@@ -238,8 +248,16 @@ def batch_filter(
     turned back -- for instruments whose stripes run down the columns.  The turns run on the device inside the batched
     call (``filtering.destripe_planes(..., rotate=True)``); anything but a bool raises ``TypeError`` before anything is
     created.
+
+    ``lightsheet``: a dict ``{"percentile": .25, "artifact_length": 150, "background_window_size": 200,
+    "lightsheet_vs_background": 2.0}`` (every key optional; an unknown key raises ``TypeError``, a bad value
+    ``ValueError``) runs the light-sheet background mode (``filtering.correct_lightsheet_planes``) on every group of
+    planes instead of the stripe filter; the two parameter dicts are not read then.  The planes must be uint16; it
+    cannot be combined with ``streaks`` or with a ``shadow_correction`` (``ValueError``, before anything is created).
     """
     rotate = _rotate_option(rotate, streaks)
+    if lightsheet is not None:
+        lightsheet = fl.lightsheet_options(lightsheet, streaks, shadow_correction)
     streaks = _streaks_options(streaks, shadow_correction)
     input_path, output_path = Path(input_path), Path(output_path)
     error_path = os.path.join(output_path, "destripe_log.txt")
@@ -268,7 +286,10 @@ def batch_filter(
                 # source dtype: for integer sources that is the clip-free truncation the uint16 epilogue does
                 want = _target_dtype(stack.dtype, output_dtype)
                 as_u16 = shaded or np.dtype(want) == np.uint16
-                if streaks is not None:
+                if lightsheet is not None:
+                    res = fl.correct_lightsheet_planes(stack, rotate=rotate, max_batch=min(batch, 64), device=device,
+                                                       out_dtype=np.uint16 if as_u16 else np.float32, **lightsheet)
+                elif streaks is not None:
                     flat, dark = fl._resolve_shading(shadow_correction, str(paths[ks[0]]))
                     res = fl.destripe_streaks_planes(stack, out_dtype=np.uint16 if as_u16 else np.float32,
                                                      max_batch=min(batch, 64), device=device,

@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "dsx_volhist_reset", "dsx_volhist_add_device", "dsx_volhist_get", "dsx_volhist_ref",
     "dsx_plan_streaks_opts", "dsx_streaks_blend_ref",
     "dsx_set_rotate", "dsx_rot90_device", "dsx_rot90_ref",
+    "dsx_plan_lightsheet", "dsx_lightsheet_ref", "dsx_get_lightsheet_planes",
 ]  # fmt: skip
 
 
@@ -249,6 +250,10 @@ def load_library(path=None):
     lib.dsx_volhist_add_device.argtypes = [vp, vp, ctypes.c_size_t]
     lib.dsx_volhist_get.argtypes = [vp, vp]
     lib.dsx_volhist_ref.argtypes = [vp, ctypes.c_size_t, vp]
+    f64 = ctypes.c_double
+    lib.dsx_plan_lightsheet.argtypes = [vp, i32, i32, i32, f64, i32, i32, f64, vp, vp]
+    lib.dsx_lightsheet_ref.argtypes = [vp, i32, i32, f64, i32, i32, f64, vp, vp, vp, vp, vp, i32]
+    lib.dsx_get_lightsheet_planes.argtypes = [vp, i32, vp, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("dsx_destroy", "dsx_last_error"):
@@ -279,6 +284,71 @@ def rotate_flag(rotate):
     if not isinstance(rotate, (bool, np.bool_)):
         raise TypeError("rotate must be True or False, not {!r}".format(rotate))
     return bool(rotate)
+
+
+LIGHTSHEET_DEFAULTS = {"percentile": 0.25, "artifact_length": 150, "background_window_size": 200,
+                       "lightsheet_vs_background": 2.0}  # fmt: skip
+LIGHTSHEET_MAX_ARTIFACT = 1024  # kLsMaxA
+LIGHTSHEET_MAX_WINDOW = 255  # kLsMaxB: B * B fits a 16-bit count
+
+
+def lightsheet_params(percentile=0.25, artifact_length=150, background_window_size=200, lightsheet_vs_background=2.0):
+    """The four parameters of the light-sheet background mode as ``(p, A, B, lam)``, checked: ``ValueError`` for a value
+    out of range or of the wrong kind (raised before any library call)."""
+
+    def number(name, v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("lightsheet: {} must be a number, not {!r}".format(name, v))
+        return v
+
+    p = float(number("percentile", percentile))
+    if not (0.0 < p < 1.0):  # (nan fails both comparisons)
+        raise ValueError("lightsheet: percentile must lie in (0, 1), not {!r}".format(percentile))
+    sizes = []
+    for name, v, top in (("artifact_length", artifact_length, LIGHTSHEET_MAX_ARTIFACT),
+                         ("background_window_size", background_window_size, LIGHTSHEET_MAX_WINDOW)):  # fmt: skip
+        v = number(name, v)
+        if not np.isfinite(v) or int(v) != v or not (1 <= int(v) <= top):
+            raise ValueError("lightsheet: {} must be an integer in 1 .. {}, not {!r}".format(name, top, v))
+        sizes.append(int(v))
+    lam = float(number("lightsheet_vs_background", lightsheet_vs_background))
+    if not (lam > 0.0 and np.isfinite(np.float32(lam)) and np.float32(lam) > 0):
+        raise ValueError("lightsheet: lightsheet_vs_background must be positive and finite, not {!r}".format(
+            lightsheet_vs_background))  # fmt: skip
+    return p, sizes[0], sizes[1], lam
+
+
+def lightsheet_tables():
+    """``(edges, back)`` of the light-sheet mode's fixed log scale ``q = floor(255 log2(1 + x) / 16)``, made in NumPy
+    float64: ``edges[v - 1]`` (uint32, v = 1 .. 255) the smallest ``x`` with ``q(x) >= v``, and ``back[v] =
+    float32(2 ** (16 v / 255) - 1)``.  The plan, the host build and the NumPy restatement of the tests all take them."""
+    x = np.arange(65536, dtype=np.float64)
+    q = np.floor(255.0 * np.log2(1.0 + x) / 16.0).astype(np.int64)
+    edges = np.searchsorted(q, np.arange(1, 256), side="left").astype(np.uint32)
+    back = (np.exp2(16.0 * np.arange(256, dtype=np.float64) / 255.0) - 1.0).astype(np.float32)
+    return edges, back
+
+
+def lightsheet_ref(plane, percentile=0.25, artifact_length=150, background_window_size=200,
+                   lightsheet_vs_background=2.0, out_dtype=np.float32, tables=None):  # fmt: skip
+    """Host build of the light-sheet background mode over one uint16 plane (``dsx_lightsheet_ref``): returns ``(out, ls,
+    bg)``, ``out`` of ``out_dtype`` (uint16 / float32) and the two uint8 percentile planes.  No GPU involved."""
+    p, A, B, lam = lightsheet_params(percentile, artifact_length, background_window_size, lightsheet_vs_background)
+    a = np.ascontiguousarray(plane)
+    if a.ndim != 2 or a.dtype != np.uint16 or a.size == 0:
+        raise ValueError("lightsheet: the plane must be a non-empty 2-D uint16 array")
+    edges, back = lightsheet_tables() if tables is None else tables
+    edges, back = np.ascontiguousarray(edges, np.uint32), np.ascontiguousarray(back, np.float32)
+    if edges.shape != (255,) or back.shape != (256,):
+        raise ValueError("lightsheet: tables must be (255 uint32 edges, 256 float32 values)")
+    out = np.empty(a.shape, np.dtype(out_dtype))
+    ls, bg = np.empty(a.shape, np.uint8), np.empty(a.shape, np.uint8)
+    lib = load_library()
+    rc = lib.dsx_lightsheet_ref(a.ctypes.data, a.shape[0], a.shape[1], p, A, B, lam, edges.ctypes.data, back.ctypes.data,
+                                ls.ctypes.data, bg.ctypes.data, out.ctypes.data, _dtype_code(out.dtype))  # fmt: skip
+    if rc != 0:
+        raise ValueError((lib.dsx_last_error(None) or b"lightsheet_ref failed").decode())
+    return out, ls, bg
 
 
 def rot90_ref(planes, direction=1):
@@ -557,6 +627,38 @@ class DestripeEngine:
         self.info = info
         self.streaks_route = route
         return info
+
+    def plan_lightsheet(self, height, width, percentile=0.25, artifact_length=150, background_window_size=200,
+                        lightsheet_vs_background=2.0, max_batch=32, rotate=False, tables=None):  # fmt: skip
+        """Plan the light-sheet background mode (``dsx_plan_lightsheet``).  Replaces any plan of this engine;
+        :meth:`run` / :meth:`run_device` then take uint16 planes and return ``[n, height, width]`` uint16 or float32.
+        ``rotate``: as in :meth:`plan`.  ``tables``: ``(edges, back)``, by default :func:`lightsheet_tables`."""
+        rotate = rotate_flag(rotate)
+        p, A, B, lam = lightsheet_params(percentile, artifact_length, background_window_size, lightsheet_vs_background)
+        edges, back = lightsheet_tables() if tables is None else tables
+        edges, back = np.ascontiguousarray(edges, np.uint32), np.ascontiguousarray(back, np.float32)
+        if edges.shape != (255,) or back.shape != (256,):
+            raise ValueError("lightsheet: tables must be (255 uint32 edges, 256 float32 values)")
+        self._check(self._lib.dsx_set_rotate(self._ctx, 1 if rotate else 0))
+        rc = self._lib.dsx_plan_lightsheet(self._ctx, int(height), int(width), int(max_batch), p, A, B, lam,
+                                           edges.ctypes.data, back.ctypes.data)  # fmt: skip
+        if rc == -1:
+            raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
+        self._check(rc)
+        info = _PlanInfo()
+        info.height, info.width, info.out_height, info.out_width = int(height), int(width), int(height), int(width)
+        info.max_batch = int(max_batch)
+        self.info = info
+        self.streaks_route = None
+        self._ls_shape = (int(width), int(height)) if rotate else (int(height), int(width))
+        return info
+
+    def lightsheet_planes(self, plane):
+        """``(ls, bg)``: the two uint8 percentile planes of a plane of the last cohort of a light-sheet run
+        (``dsx_get_lightsheet_planes``), in the plan's own orientation (the rotated one of a ``rotate=True`` plan)."""
+        ls, bg = np.empty(self._ls_shape, np.uint8), np.empty(self._ls_shape, np.uint8)
+        self._check(self._lib.dsx_get_lightsheet_planes(self._ctx, int(plane), ls.ctypes.data, bg.ctypes.data))
+        return ls, bg
 
     def streaks_threshold(self, plane):
         """Threshold ``t`` of a plane of the last cohort of a streaks run (``dsx_get_streaks_threshold``)."""

@@ -511,6 +511,94 @@ def destripe_streaks_planes(planes, sigma, level=0, wavelet="db3", crossover=10,
     return (out, ts) if return_threshold else out
 
 
+LIGHTSHEET_DEFAULTS = dict(_engine.LIGHTSHEET_DEFAULTS)
+
+
+def lightsheet_options(lightsheet, streaks=None, shadow_correction=None):
+    """The ``lightsheet=`` dict of the pipelines (``read_filter_save``, ``batch_filter``, ``destripe_zarr_store``,
+    ``destripe_zarr``), checked and completed with the defaults of :func:`correct_lightsheet`: keys ``percentile``,
+    ``artifact_length``, ``background_window_size`` and ``lightsheet_vs_background``, all optional.  ``TypeError`` for
+    anything but a dict or for an unknown key, ``ValueError`` for a bad value, for a ``streaks`` dict given together
+    with it (one filter per run) and for a ``shadow_correction`` (this mode has no dark / flat step).  No library
+    call."""
+    if not isinstance(lightsheet, dict):
+        raise TypeError("lightsheet must be a dict {'percentile': .25, 'artifact_length': 150, ...}")
+    unknown = sorted(set(lightsheet) - set(LIGHTSHEET_DEFAULTS), key=str)
+    if unknown:
+        raise TypeError("lightsheet got unexpected keys: {}".format(unknown))
+    if streaks is not None:
+        raise ValueError("lightsheet and streaks cannot be given together: a run applies one filter")
+    if shadow_correction is not None:
+        raise ValueError("lightsheet: the light-sheet background mode has no dark / flat step; "
+                         "shadow_correction must be None")  # fmt: skip
+    opt = dict(LIGHTSHEET_DEFAULTS, **lightsheet)
+    p, A, B, lam = _engine.lightsheet_params(**opt)
+    return dict(percentile=p, artifact_length=A, background_window_size=B, lightsheet_vs_background=lam)
+
+
+def _lightsheet_engine(shape, p, A, B, lam, max_batch, device, rotate=False):
+    """Planned light-sheet engine (cached per process and device).  ``rotate``: as in :func:`get_engine`."""
+    key = (device, "lightsheet", tuple(shape), p, A, B, lam, int(max_batch), rotate)
+    eng = _ENGINES.get(key)
+    if eng is not None:
+        _ENGINES.move_to_end(key)
+        return eng[0]
+    while len(_ENGINES) >= _MAX_CACHED_PLANS:
+        _, old = _ENGINES.popitem(last=False)
+        old[0].close()
+    e = _engine.DestripeEngine(device)
+    e.plan_lightsheet(shape[0], shape[1], p, A, B, lam, max_batch=max_batch, rotate=rotate)
+    _ENGINES[key] = (e, None, None)
+    return e
+
+
+def correct_lightsheet(image, percentile=0.25, artifact_length=150, background_window_size=200,
+                       lightsheet_vs_background=2.0, rotate=False):  # fmt: skip
+    """Upstream pystripe's light-sheet background mode (``lightsheet=True``) over one uint16 plane, on the GPU
+    (``dsx_plan_lightsheet``): the additive glow a sheet leaves along x is estimated by two windowed percentile filters
+    on a fixed log scale and subtracted.
+
+    ``q = floor(255 log2(1 + x) / 16)``; ``ls`` = the ``percentile`` of ``q`` over a 1 x ``artifact_length`` window and
+    ``bg`` over a ``background_window_size`` square, both with the arithmetic of scikit-image's ``rank.percentile``
+    (windows cut at the border); back on the linear scale (``2 ** (16 v / 255) - 1``) the line estimate is the offset
+    unless it exceeds ``lightsheet_vs_background`` times the regional one, which then takes its place; the result is
+    ``max(x - offset, 0)``, float32 ``[H, W]``.  ``0 < percentile < 1``, ``artifact_length`` 1 .. 1024,
+    ``background_window_size`` 1 .. 255 (``ValueError`` elsewhere, and for a plane that is not uint16).
+    ``rotate=True``: ``np.rot90(F(np.rot90(image)), -1)``, the turns on the device.  Not verified against pystripe
+    itself (README "Light-sheet background mode")."""
+    image = np.asarray(image)
+    if image.ndim != 2:
+        raise ValueError("correct_lightsheet takes one 2-D plane; use correct_lightsheet_planes for a stack")
+    return correct_lightsheet_planes(image[None], percentile, artifact_length, background_window_size,
+                                     lightsheet_vs_background, rotate=rotate, out_dtype=np.float32, max_batch=1)[0]  # fmt: skip
+
+
+def correct_lightsheet_planes(planes, percentile=0.25, artifact_length=150, background_window_size=200,
+                              lightsheet_vs_background=2.0, rotate=False, out_dtype=np.uint16, max_batch=32, device=0):  # fmt: skip
+    """Batched :func:`correct_lightsheet` over ``planes[n, H, W]`` (uint16), every plane on its own.  ``out_dtype``
+    uint16 (the value truncated; it is in range already) or float32."""
+    rotate = _engine.rotate_flag(rotate)
+    p, A, B, lam = _engine.lightsheet_params(percentile, artifact_length, background_window_size,
+                                             lightsheet_vs_background)  # fmt: skip
+    planes = np.asarray(planes)
+    if planes.ndim != 3:
+        raise ValueError("planes must be [n, H, W]")
+    if planes.dtype != np.uint16:
+        raise ValueError("lightsheet: planes must be uint16, not {}".format(planes.dtype))
+    if planes.shape[1] == 0 or planes.shape[2] == 0:
+        raise ValueError("planes must not be empty")
+    if np.dtype(out_dtype) not in (np.dtype(np.uint16), np.dtype(np.float32)):
+        raise ValueError("lightsheet: out_dtype must be uint16 or float32")
+    n = planes.shape[0]
+    max_batch = max(1, min(int(max_batch), max(n, 1)))
+    eng = _lightsheet_engine(planes.shape[1:], p, A, B, lam, max_batch, device, rotate)
+    out = np.empty(planes.shape, dtype=out_dtype)
+    for start in range(0, n, max_batch):
+        stop = min(n, start + max_batch)
+        out[start:stop] = eng.run(np.ascontiguousarray(planes[start:stop]), out_dtype=out_dtype)
+    return out
+
+
 def _resolve_shading(shadow_correction, input_tile_path):
     if shadow_correction is None:
         return None, None

@@ -199,8 +199,12 @@ def execute_worker(
     streaks=None,
     *,
     rotate: bool = False,
+    lightsheet=None,
 ):
     """``zarr_destriper.py:253-336`` with the plane loop (``:319-327``) as one batched GPU call.
+
+    ``lightsheet`` (the checked dict of ``fl.lightsheet_options``): the uint16 planes go through the light-sheet
+    background mode (``fl.correct_lightsheet_planes``) instead; configs and ``shadow_correction`` are not read then.
 
     ``rotate``: every plane is filtered as ``np.rot90(F(np.rot90(x)), -1)`` (vertical stripes; the turns run on the
     device, ``fl.destripe_planes``); a ``"rotate"`` key of ``streaks`` asks for the same.
@@ -233,7 +237,10 @@ def execute_worker(
 
     input_tile_path = dataset_name.replace(".zarr", "")
     planes = data if data.dtype in (np.uint16, np.float32) else data.astype(np.float32)
-    if streaks is not None:
+    if lightsheet is not None:
+        filtered = fl.correct_lightsheet_planes(data, rotate=rotate, out_dtype=np.uint16, max_batch=max_batch,
+                                                device=device, **lightsheet)  # fmt: skip
+    elif streaks is not None:
         flat, dark = fl._resolve_shading(shadow_correction, input_tile_path)
         kw = fl.streaks_call_options(streaks, flat, dark)
         kw["rotate"] = rotate or engine_mod.rotate_flag(kw.get("rotate", False))
@@ -795,6 +802,7 @@ def destripe_zarr_store(
     streaks=None,
     histogram=None,
     rotate=False,
+    lightsheet=None,
 ):
     """Chunk map of ``destripe_zarr`` (``zarr_destriper.py:909-1211``) over a Zarr-v2 directory store -- the engine-level
     form (explicit configs and ``shadow_correction``); :func:`destripe_zarr` is the entry point with the reference's
@@ -887,6 +895,14 @@ def destripe_zarr_store(
     (``dsx_set_rotate``), so every route -- device re-tiling, device codecs, fused pyramid, histogram, the host path --
     runs as without it and sees planes in the store's orientation; the shading planes stay in that orientation too.
     Anything but a bool raises ``TypeError`` before anything is created.  ``LAST_RUN["rotate"]`` is the value used.
+
+    ``lightsheet``: a dict ``{"percentile": .25, "artifact_length": 150, "background_window_size": 200,
+    "lightsheet_vs_background": 2.0}`` (every key optional) runs the light-sheet background mode
+    (``filtering.correct_lightsheet``) on every plane instead of the stripe filter: the device path plans a light-sheet
+    engine, the host path calls ``filtering.correct_lightsheet_planes``; everything around the filter is the same and
+    the configs may be ``None``.  An unknown key raises ``TypeError``; a bad value, a ``streaks`` dict or a
+    ``shadow_correction`` given with it, or an input that is not uint16 raise ``ValueError``, all before anything is
+    created.  ``LAST_RUN["filter"]`` is ``"lightsheet"`` then.
     """
     from . import pyramid
 
@@ -897,6 +913,8 @@ def destripe_zarr_store(
                                       and histogram.shape == (engine_mod.VOLHIST_BINS,)
                                       and histogram.flags["C_CONTIGUOUS"] and histogram.flags["WRITEABLE"]):  # fmt: skip
         raise ValueError("histogram must be a writeable C-contiguous int64 array of {} bins".format(engine_mod.VOLHIST_BINS))
+    if lightsheet is not None:
+        lightsheet = fl.lightsheet_options(lightsheet, streaks, shadow_correction)
     if streaks is not None:
         streaks = fl.streaks_options(streaks)
         fl.streaks_shading(streaks, shadow_correction)
@@ -910,6 +928,8 @@ def destripe_zarr_store(
     zyx = src.shape[-3:]
     if prediction_chunksize[1] < zyx[1] or prediction_chunksize[2] < zyx[2]:
         raise ValueError("blocks must cover whole planes: the stripe filter is a per-plane operation")
+    if lightsheet is not None and src.dtype != np.uint16:
+        raise ValueError("lightsheet: the store must be uint16, not {}".format(src.dtype))
     if streaks is not None:  # ("march" on an odd plane or another wavelet fails here, before anything is created)
         streaks["route"] = engine_mod.streaks_route(streaks["route"], zyx[1], zyx[2], streaks["wavelet"],
                                                     streaks["level"])  # fmt: skip
@@ -945,7 +965,7 @@ def destripe_zarr_store(
         z0, z1 = z_shard(zyx[0], world_size, rank, z_chunk=output_chunks[-3])
     dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device
     LAST_RUN.update(rank=rank, world_size=world_size, z_range=(z0, z1), io_threads=int(io_threads), device=dev,
-                    rotate=rotate, filter="stripes" if streaks is None else "streaks",
+                    rotate=rotate, filter="lightsheet" if lightsheet is not None else "stripes" if streaks is None else "streaks",
                     streaks_route=None if streaks is None else streaks["route"],
                     streaks_smoothing=None if streaks is None else float(streaks.get("smoothing", 0.0)),
                     streaks_shading=None if streaks is None else bool(streaks.get("shading") and shadow_correction is not None))  # fmt: skip
@@ -978,7 +998,11 @@ def destripe_zarr_store(
                     device_decode_mode=decode_mode, decode_routes=None, fused_pyramid=bool(levels), pyramid_levels=[lv.level for lv in levels])  # fmt: skip
     LAST_RUN["histogram_voxels"] = None if histogram is None else 0
     if can and device_retile is not False:
-        if streaks is not None:
+        if lightsheet is not None:
+            eng = fl._lightsheet_engine(zyx[1:], lightsheet["percentile"], lightsheet["artifact_length"],
+                                        lightsheet["background_window_size"], lightsheet["lightsheet_vs_background"],
+                                        min(block_z, 64), dev, rotate)  # fmt: skip
+        elif streaks is not None:
             flatfield, darkfield = fl._resolve_shading(shadow_correction, name.replace(".zarr", ""))
             eng = fl._streaks_engine(zyx[1:], *streaks["sigma"], streaks["level"], streaks["wavelet"], streaks["crossover"],
                                      streaks["threshold"], min(block_z, 64), dev, streaks["route"],
@@ -1013,7 +1037,7 @@ def destripe_zarr_store(
         block = src[lead + sc]
         data = block[np.newaxis].astype(np.float32) if block.dtype != np.uint16 else block[np.newaxis]
         written = execute_worker(data, sc, internal, cells_config, no_cells_config, (0, 0, 0), dst, shadow_correction,
-                                 name, logger, device=dev, streaks=streaks, rotate=rotate)  # fmt: skip
+                                 name, logger, device=dev, streaks=streaks, rotate=rotate, lightsheet=lightsheet)  # fmt: skip
         if histogram is not None:
             counts = np.bincount(written.ravel(), minlength=engine_mod.VOLHIST_BINS)
             histogram += counts
@@ -1454,6 +1478,7 @@ def destripe_zarr(
     ome_metadata=False,
     display_window=None,
     rotate=False,
+    lightsheet=None,
 ):
     """``destripe_zarr`` of the reference (``zarr_destriper.py:909-1211``) with its 14 parameters, on the GPU chunk map.
 
@@ -1495,7 +1520,10 @@ def destripe_zarr(
     adds the ranks' counts after the barrier, and rank 0 raises ``RuntimeError`` unless they add up to the voxels of
     level 0.  ``"percentile"`` with ``world_size > 1`` and a group without ``sum_counts`` raises ``ValueError`` before
     anything is created.  ``LAST_RUN["display_window"]`` is the pair written, or ``None``), ``rotate`` (vertical stripes:
-    :func:`destripe_zarr_store`; a bool, ``TypeError`` before anything is created otherwise).
+    :func:`destripe_zarr_store`; a bool, ``TypeError`` before anything is created otherwise), ``lightsheet`` (the dict
+    of :func:`destripe_zarr_store`: the light-sheet background mode instead of the stripe filter; ``parameters`` need no
+    configs then; together with ``streaks``, a ``flatfield`` or a derivatives folder that exists it raises
+    ``ValueError`` before anything is created -- the mode has no dark / flat step).
     Returns ``(planes processed by this rank, seconds)``.
     """
     rotate = engine_mod.rotate_flag(rotate)
@@ -1514,7 +1542,11 @@ def destripe_zarr(
         raise ValueError("display_window=\"percentile\" with world_size > 1 needs a group with sum_counts "
                          "(distributed.RankGroup): the ranks' voxel counts must be added")  # fmt: skip
     histogram = np.zeros(engine_mod.VOLHIST_BINS, np.int64) if percentile else None
-    if streaks is not None:
+    if lightsheet is not None:
+        shaded = flatfield is not None or os.path.exists(Path(derivatives_path))
+        lightsheet = fl.lightsheet_options(lightsheet, streaks, True if shaded else None)
+        no_cells_config, cells_config = parameters.get("no_cells_config"), parameters.get("cells_config")
+    elif streaks is not None:
         streaks = fl.streaks_options(streaks)
         if not streaks.get("shading") and (flatfield is not None or os.path.exists(Path(derivatives_path))):
             raise ValueError("streaks: the dual-band filter has no dark / flat step without 'shading': True; give no "
@@ -1543,7 +1575,7 @@ def destripe_zarr(
         return {"darkfield": sc["darkfield"], "microscope_flats": None if sc["retrospective"] else sc["flatfield"],
                 "tile_config": sc["tile_config"]}  # fmt: skip
 
-    if streaks is not None and not streaks.get("shading"):
+    if lightsheet is not None or (streaks is not None and not streaks.get("shading")):
         shadow_correction = {"flatfield": None, "darkfield": None}
     elif _group_broadcasts(group, world_size):
         tile_config = {}
@@ -1602,6 +1634,7 @@ def destripe_zarr(
         streaks=streaks,
         histogram=histogram,
         rotate=rotate,
+        lightsheet=lightsheet,
     )
     if group is not None and world_size > 1:
         group.barrier()  # level 0 of this tile is complete on every rank: the pyramid may read it

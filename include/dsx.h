@@ -477,6 +477,26 @@ int dsx_streaks_blend_ref(const float* x, const float* f, const float* b, int he
 /* t of a plane of the last cohort of the last run (a bin centre for float32 planes, an integer for uint16). */
 int dsx_get_streaks_threshold(dsx_ctx* ctx, int plane, float* threshold);
 
+/* ---- light-sheet background mode (csrc/dsx_lightsheet.h; DESIGN.md "Light-sheet background mode") -----------------
+ * Per uint16 plane x[height, width], stripes along x:
+ *   q      = number of edges[v] <= x        (edges: 255 non-decreasing values, edges[v - 1] = smallest x with q >= v)
+ *   P(h,w) = the windowed percentile of scikit-image's rank.percentile(q, ones((h, w)), p0 = p): rows i - h/2 ..
+ *            i - h/2 + h - 1, columns j - w/2 .. j - w/2 + w - 1, only the n pixels inside the plane counted, the
+ *            smallest v with #{q <= v} >= floor(p n) + 1 (p n in float64)
+ *   L = back[P(1, A)], G = back[P(B, B)];  offset = L <= (float)lambda * G ? L : G;  out = max((float)x - offset, 0)
+ * 0 < p < 1, 1 <= A <= 1024, 1 <= B <= 255, lambda > 0; edges and back (256 float32) are host tables and are copied.
+ * The plan replaces any other and serves dsx_run_host / dsx_run_device: uint16 in, uint16 (truncated) or float32 out,
+ * anything else DSX_EINVAL; cfg_used is not written.  It honours dsx_set_rotate. */
+int dsx_plan_lightsheet(dsx_ctx* ctx, int height, int width, int max_batch, double p, int A, int B, double lambda,
+                        const uint32_t* edges, const float* back);
+/* The host build of the same arithmetic over ONE plane (host pointers, no context, no device call): out [H, W] of
+ * out_dtype; ls and bg (uint8 [H, W], the two percentile planes) may be NULL.  dsx_last_error(NULL) has the message. */
+int dsx_lightsheet_ref(const void* x, int height, int width, double p, int A, int B, double lambda,
+                       const uint32_t* edges, const float* back, uint8_t* ls, uint8_t* bg, void* out, int out_dtype);
+/* Debug hook: the ls and bg planes (uint8 [h, w] each, of the plan's own -- with dsx_set_rotate the rotated --
+ * orientation; either may be NULL) of plane `plane` of the last cohort of the last run.  Synchronises. */
+int dsx_get_lightsheet_planes(dsx_ctx* ctx, int plane, uint8_t* ls, uint8_t* bg);
+
 /* ---- parity / debug hooks (state of the LAST cohort of the last run) ----------------------- */
 /* Per plane of the last cohort: fore/back means and chosen config (filtering.py:459-462). */
 int dsx_get_stats(dsx_ctx* ctx, int plane, double* fore_mean, double* back_mean,
