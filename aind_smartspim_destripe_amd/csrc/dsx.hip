@@ -4,7 +4,8 @@
 // HIP streams; no host synchronisation inside) -- run_cohort and its stages; what is fused and every grid, block and
 // LDS size is decided by dsx_chain.h:
 //   k_zero3  ->  k_fwd_march<fused: levels 1 + 2>, k_fwd_march per level from 3  ->  k_hist (one launch per stream)
-//   ->  k_otsu  ->  k_rowfilter (level 2), k_rowfilter_multi (the coarse levels in one launch)
+//   ->  k_otsu  ->  k_rowfilter (level 2), k_rowfilter_pack (the coarse levels in one launch, several row pairs per
+//       wave; DSX_NO_ROW_PACK=1: k_rowfilter_multi, one pair per wave)
 //   ->  k_inv_march per level down to 3  ->  k_rowfinal (level-1 row filter + levels 2 and 1 of the synthesis + finish)
 // An unsplit cohort runs the wide levels' k_hist and k_rowfilter on a helper stream beside the coarse levels' launches.
 // Planes the fused kernels do not take (widths that are no multiple of 4 / 8, float32, other FFT plans) fall back piece
@@ -170,6 +171,7 @@ struct dsx_ctx {
   unsigned long long graph_clock = 0;
   int graph_mode = 0;  // DSX_GRAPH=1 turns graphs on; back to 0 when a capture fails on this runtime
   unsigned long long graph_launches = 0, graph_captures = 0;
+  unsigned long long row_pack_launches = 0;  // k_rowfilter_pack launches enqueued (dsx_row_pack_launches)
   // dual-band filter (dsx_plan_streaks): when set, dsx_run_* run this plan instead of the log-space one
   bool streaks = false;
   dsx::st::StreaksPlan sp;
@@ -391,6 +393,23 @@ hipError_t launch_rowfilter_multi(const dsx::RowMultiArgs& a_in, const int* npai
   for (int i = 0; i < a.nlev; ++i) M[i] = a.lv[i].M;
   const dsx::RowLaunch g = dsx::row_multi_launch(a.nlev, npairs, M, a.blk_end);
   hipLaunchKernelGGL(dsx::k_rowfilter_multi<6>, dim3(g.grid_x, nb), dim3(64 * g.wpb), g.lds, s, a);
+  return hipGetLastError();
+}
+
+// ... with several row pairs per wave (k_rowfilter_pack): pack factor per level and geometry from dsx_chain.h
+hipError_t launch_rowfilter_pack(const DsxTuning& t, const dsx::RowMultiArgs& m, const int* npairs, int nb, hipStream_t s) {
+  if (hipError_t e = raise_lds_limit<dsx::k_rowfilter_pack<6>>()) return e;
+  dsx::RowPackArgs a;
+  memset(&a, 0, sizeof(a));
+  a.nlev = m.nlev;
+  int M[dsx::kRowMultiMax];
+  for (int i = 0; i < m.nlev; ++i) {
+    a.lv[i] = m.lv[i];
+    M[i] = m.lv[i].M;
+    a.pack[i] = dsx::row_pack_factor(t, m.lv[i].M, m.lv[i].npass, m.lv[i].radix);
+  }
+  const dsx::RowLaunch g = dsx::row_pack_launch(t, a.nlev, npairs, M, a.pack, a.blk_end);
+  hipLaunchKernelGGL(dsx::k_rowfilter_pack<6>, dim3(g.grid_x, nb), dim3(64 * g.wpb), g.lds, s, a);
   return hipGetLastError();
 }
 
@@ -660,9 +679,15 @@ int stage_rowfilters(const Chain& c, dsx::RowArgs* row1) {
     LaunchScope ls(ctx, KC_ROW);
     DSX_HIP(dispatch_rowfilter(ctx->tune, a, npairs, c.nb, rs));
   }
+  int multi_waves = 0;  // per plane, one row pair per wave
+  for (int i = 0; i < multi.nlev; ++i) multi_waves += multi_pairs[i];
   if (multi.nlev == 1) {
     LaunchScope ls(ctx, KC_ROW);
     DSX_HIP(dispatch_rowfilter(ctx->tune, multi.lv[0], multi_pairs[0], c.nb, s));
+  } else if (dsx::row_pack_runs(ctx->tune, multi.nlev, (long long)c.nb * multi_waves, ctx->cus)) {
+    LaunchScope ls(ctx, KC_ROW);
+    DSX_HIP(launch_rowfilter_pack(ctx->tune, multi, multi_pairs, c.nb, s));
+    ++ctx->row_pack_launches;
   } else if (multi.nlev > 1) {
     LaunchScope ls(ctx, KC_ROW);
     DSX_HIP(launch_rowfilter_multi(multi, multi_pairs, c.nb, s));
@@ -1678,6 +1703,12 @@ int dsx_graph_stats(const dsx_ctx* ctx, uint64_t* launches, uint64_t* captures) 
   if (!ctx || !launches || !captures) return DSX_EINVAL;
   *launches = ctx->graph_launches;
   *captures = ctx->graph_captures;
+  return DSX_OK;
+}
+
+int dsx_row_pack_launches(const dsx_ctx* ctx, uint64_t* launches) {
+  if (!ctx || !launches) return DSX_EINVAL;
+  *launches = ctx->row_pack_launches;
   return DSX_OK;
 }
 

@@ -20,7 +20,9 @@ constexpr int kMarchOut = (kMarchCols - 4) / 2;  // 126 coefficient columns per 
 constexpr int kFuseOut = (kMarchOut - 4) / 2;    // 61 level-2 columns per wave of the fused kernel
 constexpr int kHistWaves = 8;  // waves per block: they share one 32 KB counter array (LDS is what the 4-stream mix runs short of)
 constexpr int kRowMaxWaves = 8;  // waves (row pairs) per block; they share one twiddle table
-constexpr int kRowMultiMax = 8;  // levels one k_rowfilter_multi launch carries
+constexpr int kRowMultiMax = 8;  // levels one k_rowfilter_multi / k_rowfilter_pack launch carries
+constexpr int kRowPackMax = 4;     // row pairs one wave of k_rowfilter_pack owns, at most
+constexpr int kRowPackValues = 18; // complex values a lane holds in a joint pass of k_rowfilter_pack (the CPL = 18 class)
 constexpr int kWideThreads = 512;
 constexpr int kWideCpl = 36;                              // complex values per lane
 constexpr int kWideMaxLen = kWideThreads * kWideCpl;      // 18 432: transform lengths the kernel takes
@@ -68,6 +70,10 @@ struct DsxTuning {
   int fwd_wpb = 8, inv_wpb = 8;  // DSX_FWD_WPB / DSX_INV_WPB: waves per block of the fused march kernels (4 or 8)
   bool no_row_multi = false;  // DSX_NO_ROW_MULTI: one row-filter launch per coarse level
   int row_multi_alone = 48;   // DSX_ROW_MULTI_ALONE: largest unsplit cohort that takes the merged coarse row filter
+  bool no_row_pack = false;   // DSX_NO_ROW_PACK: k_rowfilter_multi (one row pair per wave) for the merged launch (same bits)
+  int row_pack = 0;           // DSX_ROW_PACK: row pairs per wave of k_rowfilter_pack (0 = chosen per level by the cost model)
+  int row_pack_wpb = 4;       // DSX_ROW_PACK_WPB: waves per block of k_rowfilter_pack (4 or 8)
+  int row_pack_fill = 16;     // DSX_ROW_PACK_FILL: waves per CU (one pair each) from which the merged launch is packed
   int helper = -1;            // DSX_HELPER: -1 = helper stream for unsplit cohorts only, 0 / 1 = never / always
   bool no_pipeline = false;   // DSX_NO_PIPELINE: join the sub-cohort streams at every call
 #ifdef DSX_DIAG
@@ -98,6 +104,10 @@ inline void read_tuning(DsxTuning& t) {
   t.inv_wpb = env_int("DSX_INV_WPB", 8) == 4 ? 4 : 8;
   t.no_row_multi = env_int("DSX_NO_ROW_MULTI", 0) != 0;
   t.row_multi_alone = std::max(0, env_int("DSX_ROW_MULTI_ALONE", 48));
+  t.no_row_pack = env_int("DSX_NO_ROW_PACK", 0) != 0;
+  t.row_pack = std::max(0, std::min(env_int("DSX_ROW_PACK", 0), (int)kRowPackMax));
+  t.row_pack_wpb = env_int("DSX_ROW_PACK_WPB", 4) == 8 ? 8 : 4;
+  t.row_pack_fill = std::max(0, env_int("DSX_ROW_PACK_FILL", 16));
   t.helper = getenv("DSX_HELPER") ? (env_int("DSX_HELPER", 0) != 0 ? 1 : 0) : -1;
   t.no_pipeline = env_int("DSX_NO_PIPELINE", 0) != 0;
 #ifdef DSX_DIAG
@@ -418,6 +428,94 @@ inline RowLaunch row_multi_launch(int nlev, const int* npairs, const int* M, int
     max_m = std::max(max_m, M[i]);
   }
   return {wpb, (size_t)max_m * (wpb + 1) * kC32Bytes, blocks};
+}
+
+// ---- the merged coarse launch with SEVERAL row pairs per wave (k_rowfilter_pack) -----------------------------------------
+// One wave per row pair leaves most lanes of a short row's passes idle: a pass of radix R over M values has M / R
+// butterflies, one per lane (M = 260: 20, 52 and 65 of 64 lanes; M = 36: 6 and 6).  A wave of the packed kernel owns P
+// consecutive pairs and runs every pass jointly over the P row buffers: virtual butterfly v = lane + 64 i < P M / R.
+
+// v -> (pair, butterfly) without a division: off = pair * stride, b = v - pair * n; for 0 <= v < kRowPackMax * n
+inline DSX_CHAIN_HD void row_pack_split(int v, int n, int stride, int& off, int& b) {
+  off = 0;
+  b = v;
+  for (int j = 1; j < kRowPackMax; ++j) {
+    if (b >= n) {
+      b -= n;
+      off += stride;
+    }
+  }
+}
+
+// a pass list the joint passes take: register butterflies only (a generic pass runs pair by pair)
+inline bool row_pack_reg_passes(int npass, const int* radix) {
+  for (int i = 0; i < npass; ++i) {
+    bool reg = false;
+    for (int q : kRegRadix) reg = reg || (q == radix[i]);
+    if (!reg) return false;
+  }
+  return true;
+}
+
+// modelled cost of the passes of one transform per row pair, P pairs per wave (pass_cost of dsx_plan.h with the rounds
+// counted over the P buffers together)
+inline double row_pack_cost(int M, int npass, const int* radix, int P) {
+  double c = 0;
+  for (int i = 0; i < npass; ++i) c += 60.0 + round_cost(radix[i]) * (double)((P * (M / radix[i]) + 63) / 64);
+  return c / P;
+}
+
+// registers: a lane never holds more than kRowPackValues complex values in a pass; LDS: the twiddle table and P row
+// buffers per wave, with 16 waves (16 / wpb blocks) on a CU
+inline bool row_pack_fits(int M, int npass, const int* radix, int P, int wpb) {
+  for (int i = 0; i < npass; ++i) {
+    const int R = radix[i];
+    if (P * (M / R) > 64 * ((kRowPackValues + R - 1) / R)) return false;
+  }
+  return (size_t)(16 / wpb) * (size_t)(1 + wpb * P) * M * kC32Bytes <= kLdsLimit;
+}
+
+// Row pairs per wave for a level: the P <= kRowPackMax of least modelled cost within both bounds (the smaller one on a
+// tie); DSX_ROW_PACK = n: the largest P <= n within the bounds.  Measured at M = 260, where the model separates
+// P = 3 from P = 4 by 6 % only: profiles/row_pack_bench.txt.
+inline int row_pack_factor(const DsxTuning& t, int M, int npass, const int* radix) {
+  if (!row_pack_reg_passes(npass, radix)) return 1;
+  int best = 1;
+  double best_cost = row_pack_cost(M, npass, radix, 1);
+  for (int P = 2; P <= kRowPackMax; ++P) {
+    if (!row_pack_fits(M, npass, radix, P, t.row_pack_wpb)) break;
+    if (t.row_pack > 0) {
+      if (P <= t.row_pack) best = P;
+      continue;
+    }
+    const double c = row_pack_cost(M, npass, radix, P);
+    if (c < best_cost) { best_cost = c; best = P; }
+  }
+  return t.row_pack == 1 ? 1 : best;
+}
+
+// The merged launch goes to k_rowfilter_pack (DSX_NO_ROW_PACK=1: k_rowfilter_multi); a single level runs its own kernel.
+// waves: what the launch has with one pair per wave (planes x row pairs of its levels).  Packing trades parallelism for
+// lane use, and a launch that does not fill the chip once (16 waves on each of the cus compute units) has idle SIMDs, not
+// idle lanes, to give away: its waves would only run 3-4 x as long.  Measured on 2048^2 planes, latency per call: 1 plane
+// 250 -> 264 us, 8 planes 313 -> 326 us packed, 16 planes (4224 waves on 256 CUs) even (profiles/row_pack_bench.txt).
+// Those launches keep one pair per wave; DSX_ROW_PACK_FILL = 0 packs whatever the size.
+inline bool row_pack_runs(const DsxTuning& t, int nlev, long long waves, int cus) {
+  return !t.no_row_pack && nlev >= 2 && waves >= (long long)t.row_pack_fill * cus;
+}
+
+// k_rowfilter_pack: wpb waves per block, pack[i] row pairs per wave of level i; blk_end as in row_multi_launch
+inline RowLaunch row_pack_launch(const DsxTuning& t, int nlev, const int* npairs, const int* M, const int* pack, int* blk_end) {
+  const int wpb = t.row_pack_wpb;
+  int blocks = 0;
+  size_t lds = kC32Bytes;
+  for (int i = 0; i < nlev; ++i) {
+    const int per_block = wpb * pack[i];
+    blocks += (npairs[i] + per_block - 1) / per_block;
+    blk_end[i] = blocks;
+    lds = std::max(lds, (size_t)(1 + wpb * pack[i]) * M[i] * kC32Bytes);
+  }
+  return {wpb, lds, blocks};
 }
 
 }  // namespace dsx

@@ -1872,6 +1872,426 @@ __global__ __launch_bounds__(64 * kRowMaxWaves, row_waves_per_simd<CPL>()) void 
                                           bx * (blockDim.x >> 6) + wave, blockIdx.y);
 }
 
+// ---- the merged coarse launch with SEVERAL row pairs per wave ------------------------------------------------------------
+// k_rowfilter_multi gives a wave to every row pair whatever the row length: levels 3 ... 8 of a 2048^2 plane are 264 pairs,
+// as many waves as level 2 runs for three times the data, and a pass of a short transform leaves most lanes idle (M / R
+// butterflies, one per lane: 20, 52, 65 of 64 at M = 260, 6 and 6 at M = 36).  Here a wave owns P <= kRowPackMax consecutive
+// pairs of one level and one plane (P per level from the host: dsx::row_pack_factor) and pays the fixed costs -- load
+// latency, twiddle staging and its barrier, the dependent steps of the median loop, two fences per pass -- once for all
+// of them.  The arithmetic of every row is that of rf_pair_body, operation for operation: same results, bit for bit.
+
+// One pass over the P_live row buffers of a wave jointly: virtual butterfly v = lane + 64 i < nlive * (M / R) is butterfly
+// b of buffer p (dsx::row_pack_split); the butterflies themselves are those of fft_pass.  The host keeps
+// P * (M / R) <= 64 * ceil(kRowPackValues / R), so MAXB rounds reach them all.
+template <int R>
+__device__ __forceinline__ void fft_pass_pack(float2* buf, const float2* tw, int M, int s, float inv_s, int lane, int nlive) {
+  constexpr int MAXB = (kRowPackValues + R - 1) / R;
+  const int nb = M / R;
+  const int total = nlive * nb;
+  const bool unit_tw = (s * R == M);
+  dsx_c32 v[MAXB][R];
+#pragma unroll
+  for (int i = 0; i < MAXB; ++i) {
+    const int vi = lane + kWave * i;
+    if (vi < total) {
+      int off, b;
+      row_pack_split(vi, nb, M, off, b);
+      dsx_bfly_load<R>((const dsx_c32*)buf + off, b, nb, v[i]);
+    }
+  }
+  wave_sync();
+#pragma unroll
+  for (int i = 0; i < MAXB; ++i) {
+    const int vi = lane + kWave * i;
+    if (vi < total) {
+      int off, b;
+      row_pack_split(vi, nb, M, off, b);
+      dsx_bfly_store<R>((dsx_c32*)buf + off, (const dsx_c32*)tw, b, s, inv_s, v[i], unit_tw);
+    }
+    __builtin_amdgcn_sched_barrier(0);  // (see fft_pass)
+  }
+  wave_sync();
+}
+
+// the passes of RowArgs over the nlive row buffers of a wave (fft_run for one buffer)
+template <int CPL>
+__device__ __forceinline__ void fft_run_pack(float2* buf, const float2* tw, const RowArgs& a, int lane_in, int nlive) {
+  int s = 1;
+  for (int pi = 0; pi < a.npass; ++pi) {
+    const int R = a.radix[pi];
+    const float inv_s = 1.0f / (float)s;
+    int lane = lane_in, M = a.M;
+    asm volatile("" : "+v"(lane), "+s"(M));  // (see fft_run)
+    switch (R) {
+      case 2: fft_pass_pack<2>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 3: fft_pass_pack<3>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 4: fft_pass_pack<4>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 5: fft_pass_pack<5>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 6: fft_pass_pack<6>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 8: fft_pass_pack<8>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 9: fft_pass_pack<9>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 10: fft_pass_pack<10>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 12: fft_pass_pack<12>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 15: fft_pass_pack<15>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 16: fft_pass_pack<16>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 20: fft_pass_pack<20>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 25: fft_pass_pack<25>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 7: fft_pass_pack<7>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 11: fft_pass_pack<11>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 13: fft_pass_pack<13>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 17: fft_pass_pack<17>(buf, tw, M, s, inv_s, lane, nlive); break;
+      case 19: fft_pass_pack<19>(buf, tw, M, s, inv_s, lane, nlive); break;
+      default:  // a prime factor without a register butterfly: buffer by buffer (the host packs such levels with P = 1)
+        for (int p = 0; p < nlive; ++p) fft_pass_generic<CPL, WaveGroup>(buf + p * M, tw, M, s, inv_s, R, lane);
+        break;
+    }
+    s *= R;
+  }
+}
+
+// P row pairs (pair0 ... pair0 + P - 1, those below the level's pair count are live) of one level and plane per wave.
+// buf: P row buffers of M complex values.  Like rf_pair_body the function contains ONE block-wide barrier that every wave
+// of the block reaches, and returns on every path.
+template <int CPL>
+__device__ __forceinline__ void rf_pack_body(const RowArgs& a, float2* s_tw, float2* buf, int tid, int nthreads, int lane,
+                                             int pair0, int P, int plane) {
+  constexpr int PM = kRowPackMax;
+  const int M = a.M, N = a.w, K = a.K;
+  const bool halo = K > 0;
+  const int npairs = (a.h + 1) >> 1;
+  const int nlive = max(0, min(P, npairs - pair0));  // the live pairs of a wave are its first nlive
+  const int cfg = a.cfg[plane];
+  float* const row0 = a.ws + plane * a.ws_plane_stride + a.da_off + (long long)(2 * pair0) * a.ld;
+  auto rowa_of = [&](int p) { return row0 + (long long)(2 * p) * a.ld; };
+  auto has_b_of = [&](int p) { return 2 * (pair0 + p) + 1 < a.h; };
+
+  constexpr int GV = RowSlots<CPL>::GV;
+  constexpr int E = RowSlots<CPL>::E;
+  typedef typename SlotMask<E>::type mask_t;
+  const int gf = N >> 8;
+  const int tail0 = gf << 8;
+  const int nt = (N - tail0 + 63) >> 6;
+  const int tn = tail0 + lane;
+
+  if (a.lvl >= a.lvl_active[cfg]) {  // this config does not filter this level: Delta = 0 (block-uniform)
+    for (int p = 0; p < nlive; ++p) {
+      float* rowa = rowa_of(p);
+      const bool has_b = has_b_of(p);
+      for (int n = 4 * lane; n < N; n += 4 * kWave) {
+        *(float4*)(rowa + n) = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (has_b) *(float4*)(rowa + a.ld + n) = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+    return;
+  }
+  const float thr = a.thr[(long long)plane * a.L + a.lvl];
+
+  // ---- the row loads of all pairs, THEN the twiddles and the barrier ---------------------------------------------------
+  float4 ra4[PM][GV > 0 ? GV : 1], rb4[PM][GV > 0 ? GV : 1];
+  float rta[PM][4], rtb[PM][4];
+#pragma unroll
+  for (int p = 0; p < PM; ++p) {
+    const float* rowa = rowa_of(p);
+    const float* rowb = rowa + a.ld;
+    const bool live = p < nlive, has_b = has_b_of(p);
+#pragma unroll
+    for (int g = 0; g < GV; ++g) {
+      ra4[p][g] = make_float4(0.f, 0.f, 0.f, 0.f);
+      rb4[p][g] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (live && g < gf) {
+        ra4[p][g] = *(const float4*)(rowa + 256 * g + 4 * lane);
+        if (has_b) rb4[p][g] = *(const float4*)(rowb + 256 * g + 4 * lane);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      rta[p][k] = 0.f;
+      rtb[p][k] = 0.f;
+      if (live && k < nt && tn + 64 * k < N) {
+        rta[p][k] = rowa[tn + 64 * k];
+        if (has_b) rtb[p][k] = rowb[tn + 64 * k];
+      }
+    }
+  }
+  for (int i = tid; i < M; i += nthreads) s_tw[i] = a.tw[i];
+  __syncthreads();  // the only block-wide barrier
+  if (nlive == 0) return;
+
+  // ---- mask and background per pair (rf_pair_body) ---------------------------------------------------------------------
+  float va[PM][E], vb[PM][E];
+  mask_t maska[PM], maskb[PM];
+#pragma unroll
+  for (int p = 0; p < PM; ++p) {
+    maska[p] = 0;
+    maskb[p] = 0;
+    if (p < nlive) {
+      auto take = [&](int e, float xa, float xb, bool valid) {
+        const bool ma = valid && fabsf(xa) > thr, mb = valid && fabsf(xb) > thr;
+        if (ma) maska[p] |= ((mask_t)1 << e);
+        if (mb) maskb[p] |= ((mask_t)1 << e);
+        va[p][e] = valid ? (ma ? 0.f : xa) : __builtin_huge_valf();
+        vb[p][e] = valid ? (mb ? 0.f : xb) : __builtin_huge_valf();
+      };
+#pragma unroll
+      for (int g = 0; g < GV; ++g) {
+        if (g < gf) {
+          take(4 * g + 0, ra4[p][g].x, rb4[p][g].x, true);
+          take(4 * g + 1, ra4[p][g].y, rb4[p][g].y, true);
+          take(4 * g + 2, ra4[p][g].z, rb4[p][g].z, true);
+          take(4 * g + 3, ra4[p][g].w, rb4[p][g].w, true);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k < nt) take(4 * GV + k, rta[p][k], rtb[p][k], tn + 64 * k < N);
+      }
+      if (!has_b_of(p)) {  // odd row count: the partner row is all zeros
+        for_slots<GV>(gf, nt, [&](int e) { if (vb[p][e] != __builtin_huge_valf()) vb[p][e] = 0.f; });
+      }
+    }
+  }
+
+  // ---- exact row medians: the bracketing of rf_pair_body for all 2 P rows in ONE lockstep loop ------------------------
+  // Row r = 2 p (row a of pair p) / 2 p + 1 (row b) keeps its bracket state in LANE r of ordinary vector registers:
+  // where rf_pair_body updates two wave-uniform states one after the other -- every float operation of them a trip from
+  // the scalar to the vector unit and back -- one run of vector instructions here steps every row at once.  Per step and
+  // row the probe goes out through v_readlane, the compares of the row's values against it are counted through the
+  // ballot masks as before, and the count comes back into lane r (one select).  The rows stay independent, a
+  // finished row keeps stepping (C(lo) <= k < C(hi) holds on), and the result, an order statistic, does not depend on
+  // which values were probed.  Rows without a masked entry never use their median and take no part.
+  float meda[PM], medb[PM];
+#pragma unroll
+  for (int p = 0; p < PM; ++p) meda[p] = medb[p] = 0.f;
+  unsigned need = 0u;  // bit r: row r has masked entries (wave-uniform)
+#pragma unroll
+  for (int p = 0; p < PM; ++p) {
+    if (p < nlive) {
+      if (__ballot(maska[p] != (mask_t)0) != 0ull) need |= 1u << (2 * p);
+      if (__ballot(maskb[p] != (mask_t)0) != 0ull) need |= 2u << (2 * p);
+    }
+  }
+  if (need != 0u && !DSX_ABL(a, 1)) {
+    const unsigned k1 = (unsigned)(N - 1) >> 1;
+    const bool even = (N & 1) == 0;
+    // C(t) of every row that takes part, t and the result per lane (lane r: row r)
+    auto count_rows = [&](float t, bool le) -> unsigned {
+      int c = 0;
+      const int tb = (int)as_u32(t);
+#pragma unroll
+      for (int p = 0; p < PM; ++p) {
+        if (((need >> (2 * p)) & 3u) != 0u) {
+          const float ta = as_f32((unsigned)__builtin_amdgcn_readlane(tb, 2 * p));
+          const float tbv = as_f32((unsigned)__builtin_amdgcn_readlane(tb, 2 * p + 1));
+          unsigned ca = 0, cb = 0;
+          for_slots<GV>(gf, nt, [&](int e) {
+            ca += (unsigned)__popcll(__ballot(le ? (va[p][e] <= ta) : (va[p][e] < ta)));
+            cb += (unsigned)__popcll(__ballot(le ? (vb[p][e] <= tbv) : (vb[p][e] < tbv)));
+          });
+          c = (lane == 2 * p) ? (int)ca : c;
+          c = (lane == 2 * p + 1) ? (int)cb : c;
+        }
+      }
+      return (unsigned)c;
+    };
+    const float target = (float)k1 + 0.5f;
+    const float thr_up = as_f32(as_u32(thr) + 1u);  // next float above thr (thr >= 0): C(thr_up) = N
+    float lo, hi, flo, fhi;
+    unsigned clo, chi;
+    int last = 0;
+    const bool mine = lane < 2 * PM && ((need >> (lane & (2 * PM - 1))) & 1u) != 0u;
+    bool adj = !mine;  // lanes without a row are finished from the start (their state steps along, unread)
+    {
+      const unsigned lt = count_rows(0.f, false), le = count_rows(0.f, true);
+      if (k1 < lt) {            // the statistic is negative
+        lo = -thr; clo = 0u; hi = 0.f; chi = lt;
+      } else if (k1 < le) {     // inside the zero spike: [0, denorm_min) holds the value 0 only
+        lo = 0.f; clo = lt; hi = as_f32(1u); chi = le; adj = true;
+      } else {                  // positive: C(denorm_min) = #{x <= 0}
+        lo = as_f32(1u); clo = le; hi = thr_up; chi = (unsigned)N;
+      }
+      flo = (float)clo - target;
+      fhi = (float)chi - target;
+    }
+    for (int it = 0; it < 256; ++it) {
+      const bool fin = adj || chi - clo <= 1u;
+      if (__ballot(!fin) == 0ull) break;
+      float tt = (lo * fhi - hi * flo) * __builtin_amdgcn_rcpf(fhi - flo);
+      if ((it & 7) == 7 || !(tt > lo && tt < hi)) {
+        const unsigned kl = f32_key(lo), kh = f32_key(hi);
+        if (kh - kl <= 1u) adj = true;
+        tt = key_f32(kl + ((kh - kl) >> 1));
+      }
+      const unsigned cr = count_rows(tt, false);
+      const float f = (float)cr - target;
+      if (cr <= k1) {
+        lo = tt; clo = cr; flo = f;
+        if (last == 1) fhi *= 0.5f;
+        last = 1;
+      } else {
+        hi = tt; chi = cr; fhi = f;
+        if (last == 2) flo *= 0.5f;
+        last = 2;
+      }
+    }
+    // s_k = min{x >= lo};  even N: s_{k+1} = s_k if more than k + 1 values lie below hi, else min{x >= hi}
+    const int lo_b = (int)as_u32(lo), hi_b = (int)as_u32(hi);
+#pragma unroll
+    for (int p = 0; p < PM; ++p) {
+      if (((need >> (2 * p)) & 3u) != 0u) {
+        float lo_r[2], hi_r[2];
+        unsigned chi_r[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          lo_r[r] = as_f32((unsigned)__builtin_amdgcn_readlane(lo_b, 2 * p + r));
+          hi_r[r] = as_f32((unsigned)__builtin_amdgcn_readlane(hi_b, 2 * p + r));
+          chi_r[r] = (unsigned)__builtin_amdgcn_readlane((int)chi, 2 * p + r);
+        }
+        float m_lo[2] = {__builtin_huge_valf(), __builtin_huge_valf()}, m_hi[2] = {__builtin_huge_valf(), __builtin_huge_valf()};
+        for_slots<GV>(gf, nt, [&](int e) {
+          m_lo[0] = min_no_nan(m_lo[0], va[p][e] >= lo_r[0] ? va[p][e] : __builtin_huge_valf());
+          m_lo[1] = min_no_nan(m_lo[1], vb[p][e] >= lo_r[1] ? vb[p][e] : __builtin_huge_valf());
+          if (even) {
+            m_hi[0] = min_no_nan(m_hi[0], va[p][e] >= hi_r[0] ? va[p][e] : __builtin_huge_valf());
+            m_hi[1] = min_no_nan(m_hi[1], vb[p][e] >= hi_r[1] ? vb[p][e] : __builtin_huge_valf());
+          }
+        });
+        float sk[2], sk1[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          sk[r] = wave_min_no_nan(m_lo[r]);
+          sk1[r] = sk[r];
+          if (even) {
+            const float nxt = wave_min_no_nan(m_hi[r]);
+            sk1[r] = (k1 + 1u < chi_r[r]) ? sk[r] : nxt;
+          }
+        }
+        meda[p] = even ? 0.5f * (sk[0] + sk1[0]) : sk[0];
+        medb[p] = even ? 0.5f * (sk[1] + sk1[1]) : sk[1];
+      }
+    }
+  }
+  // (wave-uniform medians pinned into VGPRs: see rf_pair_body)
+#pragma unroll
+  for (int p = 0; p < PM; ++p) asm volatile("" : "+v"(meda[p]), "+v"(medb[p]));
+
+  // ---- in-painted rows -> the pair's complex buffer (rf_pair_body) -----------------------------------------------------
+#pragma unroll
+  for (int p = 0; p < PM; ++p) {
+    if (p < nlive) {
+      float2* const bp = buf + p * M;
+      for_slots<GV>(gf, nt, [&](int e) {
+        const int n = (e < 4 * GV) ? 256 * (e >> 2) + 4 * lane + (e & 3) : tn + 64 * (e - 4 * GV);
+        if (e < 4 * GV || n < N) {
+          const float xa = bit_select(slot_mask(maska[p], e), meda[p], va[p][e]);
+          const float xb = bit_select(slot_mask(maskb[p], e), medb[p], vb[p][e]);
+          const float2 z = make_float2(xa, xb);
+          bp[K + n] = z;
+          if (halo) {
+            if (n <= K) bp[K + N + n] = z;
+            if (n >= N - K) bp[n - (N - K)] = z;
+          }
+        }
+      });
+      if (halo) {
+        for (int m = N + 2 * K + 1 + lane; m < M; m += kWave) bp[m] = make_float2(0.f, 0.f);
+      }
+    }
+  }
+  wave_sync();
+
+  if (!DSX_ABL(a, 2)) fft_run_pack<CPL>(buf, s_tw, a, lane, nlive);
+
+  // ---- V[k] = G1[k] U[k] + G2[k] U[M - k] over the nlive * (kcut + 1) bin pairs of the wave (rf_pair_body) ---------------
+  if (!DSX_ABL(a, 4)) {
+    const float2* g1 = a.g[cfg];
+    const float2* g2 = g1 + M;
+    const int kcut = a.kcut[cfg];
+    const int n1 = kcut + 1;
+    for (int vi = lane; vi < nlive * n1; vi += kWave) {
+      int off, k;
+      row_pack_split(vi, n1, M, off, k);
+      float2* const bp = buf + off;
+      const int kr = (k == 0) ? 0 : M - k;
+      const float2 u = bp[k], ur = bp[kr];
+      const float ga = g1[k].x;
+      const float2 gb = g2[k];
+      const float2 v = make_float2(ga * u.x + gb.x * ur.x - gb.y * ur.y, ga * u.y + gb.x * ur.y + gb.y * ur.x);
+      const float2 vr = make_float2(ga * ur.x + gb.x * u.x + gb.y * u.y, ga * ur.y + gb.x * u.y - gb.y * u.x);
+      bp[k] = make_float2(v.y, v.x);
+      if (kr != k) bp[kr] = make_float2(vr.y, vr.x);
+    }
+    // beyond the band limit of the low-pass the product is an exact zero
+    const int nz = M - 2 * kcut - 1;
+    for (int vi = lane; vi < nlive * nz; vi += kWave) {
+      int off, k;
+      row_pack_split(vi, nz, M, off, k);
+      buf[off + kcut + 1 + k] = make_float2(0.f, 0.f);
+    }
+    wave_sync();
+  }
+
+  if (!DSX_ABL(a, 2)) fft_run_pack<CPL>(buf, s_tw, a, lane, nlive);
+
+  // ---- Delta = -(1 - mask) LP per pair (rf_pair_body) ------------------------------------------------------------------
+#pragma unroll
+  for (int p = 0; p < PM; ++p) {
+    if (p < nlive) {
+      const float2* const bp = buf + p * M;
+      float* rowa = rowa_of(p);
+      float* rowb = rowa + a.ld;
+      const bool has_b = has_b_of(p);
+      const mask_t ma = opaque_mask(maska[p]), mb = opaque_mask(maskb[p]);
+#pragma unroll
+      for (int g = 0; g < GV; ++g) {
+        if (g < gf) {
+          const int nb0 = 256 * g + 4 * lane;
+          float da_[4], db_[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int e = 4 * g + i;
+            const float2 y = bp[K + nb0 + i];
+            da_[i] = bit_select(slot_mask(ma, e), 0.f, -y.y * a.inv_M);
+            db_[i] = bit_select(slot_mask(mb, e), 0.f, -y.x * a.inv_M);
+          }
+          const dsx_f4 oa = {da_[0], da_[1], da_[2], da_[3]}, ob = {db_[0], db_[1], db_[2], db_[3]};
+          __builtin_nontemporal_store(oa, (dsx_f4*)(rowa + nb0));
+          if (has_b) __builtin_nontemporal_store(ob, (dsx_f4*)(rowb + nb0));
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int n = tn + 64 * k;
+        if (k < nt && n < N) {
+          const int e = 4 * GV + k;
+          const float2 y = bp[K + n];
+          rowa[n] = bit_select(slot_mask(ma, e), 0.f, -y.y * a.inv_M);
+          if (has_b) rowb[n] = bit_select(slot_mask(mb, e), 0.f, -y.x * a.inv_M);
+        }
+      }
+    }
+  }
+}
+
+struct RowPackArgs {
+  int nlev;
+  int blk_end[kRowMultiMax];  // cumulative block counts
+  int pack[kRowMultiMax];     // row pairs per wave of the level
+  RowArgs lv[kRowMultiMax];
+};
+
+template <int CPL>
+__global__ __launch_bounds__(64 * kRowMaxWaves, row_waves_per_simd<CPL>()) void k_rowfilter_pack(RowPackArgs args) {
+  extern __shared__ __attribute__((aligned(16))) float2 dsx_smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wpb = blockDim.x >> 6;
+  int ent = 0;
+  while (ent + 1 < args.nlev && (int)blockIdx.x >= args.blk_end[ent]) ++ent;  // block-uniform, scalar unit
+  const RowArgs& a = args.lv[ent];
+  const int P = args.pack[ent];
+  const int bx = (int)blockIdx.x - (ent > 0 ? args.blk_end[ent - 1] : 0);
+  rf_pack_body<CPL>(a, dsx_smem, dsx_smem + (long long)a.M * (1 + wave * P), tid, blockDim.x, lane, (bx * wpb + wave) * P, P,
+                    blockIdx.y);
+}
+
 // ---- K4w: the row filter for rows longer than one wave holds (levels wider than 64 x 36 = 2 304 coefficients: planes
 // wider than ~4 600 pixels; round 3) -------------------------------------------------------------------------------
 // One BLOCK of kWideThreads lanes per pair of rows; the complex row buffer fills the block's LDS (up to 144 KiB), the

@@ -145,6 +145,9 @@ int dsx_sync(dsx_ctx* ctx);
  * kernel launches.  Off by default: measured 5-8 % slower than eager launches on ROCm 7.2.
  * Counters for tests / diagnosis.                                                                           */
 int dsx_graph_stats(const dsx_ctx* ctx, uint64_t* launches, uint64_t* captures);
+/* Launches of the packed coarse row filter (k_rowfilter_pack: several row pairs per wave) this context has enqueued;
+ * 0 throughout with DSX_NO_ROW_PACK=1.  Counter for tests / diagnosis.                                         */
+int dsx_row_pack_launches(const dsx_ctx* ctx, uint64_t* launches);
 
 /* ---- device memory + timing helpers for host programs without a GPU array library --------- */
 int dsx_malloc(dsx_ctx* ctx, size_t bytes, void** d_ptr);

@@ -34,7 +34,8 @@ CHAIN_KERNELS = ("k_zero3", "k_fwd_march", "k_fwd_gen", "k_hist", "k_otsu", "k_r
                  "k_inv_gen")
 SWITCHES = ("DSX_SEG_MIN_ROWS", "DSX_MARCH_WAVES", "DSX_FWD_WPB", "DSX_INV_WPB", "DSX_ROW_WPB", "DSX_HIST_ROWS", "DSX_STREAMS",
             "DSX_HELPER", "DSX_NO_QUANT", "DSX_NO_ROW_MULTI", "DSX_ROW_MULTI_ALONE", "DSX_NO_PAIR", "DSX_NO_FUSE",
-            "DSX_NO_FUSE_INV", "DSX_NO_FUSE_RF", "DSX_FUSE_RF_WIDE", "DSX_NO_PIPELINE", "DSX_GRAPH", "DSX_PRIO")
+            "DSX_NO_FUSE_INV", "DSX_NO_FUSE_RF", "DSX_FUSE_RF_WIDE", "DSX_NO_PIPELINE", "DSX_GRAPH", "DSX_PRIO",
+            "DSX_NO_ROW_PACK", "DSX_ROW_PACK", "DSX_ROW_PACK_WPB", "DSX_ROW_PACK_FILL")
 
 
 def _case(name, H, W, n, in_dt="uint16", out_dt="uint16", env=None, **kw):

@@ -6,7 +6,7 @@ near-threshold mask decisions are forced into the oracle).  usage: python tools/
 kernels, on small planes down to a few pixels, the oracle running on the same filter bank;
 "geometry": every case ALSO draws the launch-geometry switches of the library -- DSX_SEG_MIN_ROWS, DSX_MARCH_WAVES,
 DSX_FWD_WPB / DSX_INV_WPB, DSX_ROW_WPB, DSX_HIST_ROWS, DSX_STREAMS, DSX_HELPER, DSX_NO_QUANT, DSX_NO_ROW_MULTI,
-DSX_ROW_MULTI_ALONE, DSX_NO_PAIR, DSX_NO_FUSE, DSX_NO_FUSE_INV, DSX_NO_FUSE_RF, DSX_FUSE_RF_WIDE, DSX_NO_PIPELINE, DSX_GRAPH,
+DSX_ROW_MULTI_ALONE, DSX_NO_ROW_PACK, DSX_ROW_PACK_FILL, DSX_NO_PAIR, DSX_NO_FUSE, DSX_NO_FUSE_INV, DSX_NO_FUSE_RF, DSX_FUSE_RF_WIDE, DSX_NO_PIPELINE, DSX_GRAPH,
 DSX_PRIO: each moves
 segment boundaries, block heights or the launch chain, none may move a result -- on a fresh context per case (dsx_init
 reads them per context), with big multi-stream batches three times as often)
@@ -42,6 +42,8 @@ GEOMETRY = {  # switch -> values a case draws from (None = unset: the library's 
     "DSX_GRAPH": [None, None, None, 1],
     "DSX_FUSE_RF_WIDE": [None, None, 1],           # k_rowfinal for the embedded plans of 2000- / 1800-wide planes (off by default)
     "DSX_PRIO": [None, None, None, "0,-1,0,-1", "-1,0,1,0"],  # HIP stream priorities of the sub-cohort streams
+    "DSX_NO_ROW_PACK": [None, None, 1],            # k_rowfilter_multi instead of k_rowfilter_pack for the merged coarse launch
+    "DSX_ROW_PACK_FILL": [None, 0, 0],             # 0: the merged launch is packed whatever its size (the default packs full launches only)
 }
 
 
