@@ -2088,15 +2088,16 @@ int dsx_volhist_ref(const void* vox, size_t n, uint64_t* hist) {
 namespace {
 // Checks the per-level geometry and fills the kernels' view of it; n_out = levels with a non-empty share.
 const char* pyramid_levels(int Z, int H, int W, int n_levels, const dsx_pyramid_level* levels, void* const* bricks,
-                           dsx::pyr::Level* out, int* n_out) {
+                           dsx::pyr::Level* out, int* n_out, const dsx::pyr::Scale& f = dsx::pyr::Scale{2, 2, 2}) {
   *n_out = 0;
+  if (!dsx::pyr::scale_ok(f)) return "pyramid: every scale factor is 1 or 2, and not all are 1";
   if (Z <= 0 || H <= 0 || W <= 0) return "pyramid: the block must not be empty";
   if (n_levels < 1 || n_levels > dsx::pyr::kMaxLevels) return "pyramid: n_levels out of range";
   if (n_levels > 1 && (!levels || !bricks)) return "pyramid: level table is NULL";
   for (int l = 1; l < n_levels; ++l) {
     const dsx_pyramid_level& g = levels[l - 1];
     dsx::pyr::Level& o = out[l - 1];
-    o.Z = dsx::pyr::extent(Z, l); o.H = dsx::pyr::extent(H, l); o.W = dsx::pyr::extent(W, l);
+    o.Z = dsx::pyr::extent(Z, l, f.fz); o.H = dsx::pyr::extent(H, l, f.fy); o.W = dsx::pyr::extent(W, l, f.fx);
     if (o.Z <= 0 || o.H <= 0 || o.W <= 0) break;
     if (!bricks[l - 1]) return "pyramid: brick buffer is NULL";
     if (g.cz <= 0 || g.cy <= 0 || g.cx <= 0 || g.rows <= 0 || g.z0 < 0) return "pyramid: shapes must be positive";
@@ -2111,32 +2112,100 @@ const char* pyramid_levels(int Z, int H, int W, int n_levels, const dsx_pyramid_
 }  // namespace
 
 int dsx_pyramid_work_bytes(int Z, int H, int W, int n_levels, size_t* bytes) {
-  if (!bytes || Z < 0 || H < 0 || W < 0 || n_levels < 1 || n_levels > dsx::pyr::kMaxLevels) return DSX_EINVAL;
-  *bytes = dsx::pyr::work_bytes(Z, H, W, n_levels);
+  return dsx_pyramid_work_bytes_scale(Z, H, W, 2, 2, 2, n_levels, bytes);
+}
+
+int dsx_pyramid_work_bytes_scale(int Z, int H, int W, int fz, int fy, int fx, int n_levels, size_t* bytes) {
+  const dsx::pyr::Scale f = {fz, fy, fx};
+  if (!bytes || Z < 0 || H < 0 || W < 0 || n_levels < 1 || n_levels > dsx::pyr::kMaxLevels || !dsx::pyr::scale_ok(f))
+    return DSX_EINVAL;
+  *bytes = dsx::pyr::work_bytes(Z, H, W, n_levels, f);
   return DSX_OK;
 }
 
 int dsx_pyramid_block_ref(const void* planes, int Z, int H, int W, int n_levels, const dsx_pyramid_level* levels,
                           void* const* bricks) {
+  return dsx_pyramid_block_scale_ref(planes, Z, H, W, 2, 2, 2, n_levels, levels, bricks);
+}
+
+int dsx_pyramid_block_scale_ref(const void* planes, int Z, int H, int W, int fz, int fy, int fx, int n_levels,
+                                const dsx_pyramid_level* levels, void* const* bricks) {
   if (!planes) return DSX_EINVAL;
+  const dsx::pyr::Scale f = {fz, fy, fx};
   dsx::pyr::Level lv[dsx::pyr::kMaxLevels] = {};
   int n = 0;
-  if (const char* e = pyramid_levels(Z, H, W, n_levels, levels, bricks, lv, &n)) return fail(nullptr, DSX_EINVAL, e);
+  if (const char* e = pyramid_levels(Z, H, W, n_levels, levels, bricks, lv, &n, f)) return fail(nullptr, DSX_EINVAL, e);
   for (int l = 1; l <= n; ++l)
     if (levels[l - 1].zero) memset(lv[l - 1].bricks, 0, (size_t)levels[l - 1].rows * dsx::pyr::row_elems(lv[l - 1]) * 2);
-  dsx::pyr::pyramid_block_host((const uint16_t*)planes, H, W, n + 1, lv);
+  dsx::pyr::pyramid_block_host((const uint16_t*)planes, H, W, n + 1, lv, f);
   return DSX_OK;
 }
 
 namespace {
+// One level step with a window other than 2 x 2 x 2 (k_pyramid_step): the vector body when every access of a thread is
+// whole and aligned, the tail body otherwise.  The caller has checked the scale and the 65535 limits of the grid.
+void pyramid_step(const dsx::pyr::Scale& f, bool bricks, hipStream_t s, const dsx::PyrStepArgs& a) {
+  const int n = 8 / f.fx;  // output voxels of a thread
+  const void* src = bricks ? (const void*)a.bsrc.bricks : (const void*)a.src;
+  const bool vec = a.X % 8 == 0 && (uintptr_t)src % 16 == 0 && (!bricks || a.bsrc.cx % 8 == 0) &&
+                   (!a.out.bricks || (a.out.cx % n == 0 && (uintptr_t)a.out.bricks % (2 * n) == 0)) &&
+                   (uintptr_t)a.dense % (2 * n) == 0;
+  const dim3 grid(((a.out.W + n - 1) / n + 255) / 256, a.out.H, a.out.Z);
+  switch ((f.fz - 1) * 4 + (f.fy - 1) * 2 + (f.fx - 1)) {
+    case 1: dsx::launch_pyramid_step<1, 1, 2>(vec, bricks, grid, s, a); break;
+    case 2: dsx::launch_pyramid_step<1, 2, 1>(vec, bricks, grid, s, a); break;
+    case 3: dsx::launch_pyramid_step<1, 2, 2>(vec, bricks, grid, s, a); break;
+    case 4: dsx::launch_pyramid_step<2, 1, 1>(vec, bricks, grid, s, a); break;
+    case 5: dsx::launch_pyramid_step<2, 1, 2>(vec, bricks, grid, s, a); break;
+    default: dsx::launch_pyramid_step<2, 2, 1>(vec, bricks, grid, s, a); break;
+  }
+}
+
+// The levels of a block with a scale other than (2, 2, 2): one step per level, level l from the dense level l - 1 in
+// the work buffer (level 1 from the block itself, dense or in chunk order).
+int pyramid_run_steps(dsx_ctx* ctx, const void* d_src, const dsx::pyr::BrickSrc* bs, int H, int W, const dsx::pyr::Scale& f,
+                      int n, const dsx::pyr::Level* lv, void* d_work, hipStream_t s) {
+  uint8_t* work = (uint8_t*)d_work;
+  const uint16_t* prev = (const uint16_t*)d_src;
+  int Y = H, X = W;
+  for (int l = 1; l <= n; ++l) {
+    dsx::PyrStepArgs b = {};
+    const bool bricks = l == 1 && bs;
+    if (bricks) b.bsrc = *bs;
+    else b.src = prev;
+    b.Y = Y; b.X = X;
+    b.out = lv[l - 1];
+    b.dense = l < n ? (uint16_t*)work : nullptr;
+    pyramid_step(f, bricks, s, b);
+    DSX_HIP(hipGetLastError());
+    prev = b.dense; Y = b.out.H; X = b.out.W;
+    work += ((size_t)b.out.Z * b.out.H * b.out.W * 2 + 15) & ~(size_t)15;
+  }
+  return DSX_OK;
+}
+
 // bs == nullptr: d_src is the dense block (k_pyramid_block); otherwise the block in chunk order (k_pyramid_bricks).
 int pyramid_run(dsx_ctx* ctx, const void* d_src, const dsx::pyr::BrickSrc* bs, int Z, int H, int W, int n_levels,
-                const dsx_pyramid_level* levels, void* const* d_bricks, void* d_work, size_t work_bytes) {
+                const dsx_pyramid_level* levels, void* const* d_bricks, void* d_work, size_t work_bytes,
+                const dsx::pyr::Scale& f) {
   namespace p = dsx::pyr;
   p::Level lv[p::kMaxLevels] = {};
   int n = 0;
-  if (const char* e = pyramid_levels(Z, H, W, n_levels, levels, d_bricks, lv, &n)) return fail(ctx, DSX_EINVAL, e);
+  if (const char* e = pyramid_levels(Z, H, W, n_levels, levels, d_bricks, lv, &n, f)) return fail(ctx, DSX_EINVAL, e);
   if (n == 0) return DSX_OK;
+  if (!p::scale_is_2(f)) {
+    if (n > 1 && (!d_work || work_bytes < p::work_bytes(Z, H, W, n + 1, f) || (uintptr_t)d_work % 16))
+      return fail(ctx, DSX_EINVAL, "pyramid: the work buffer is smaller than dsx_pyramid_work_bytes_scale");
+    for (int l = 1; l <= n; ++l)
+      if (lv[l - 1].H > 65535 || lv[l - 1].Z > 65535)
+        return fail(ctx, DSX_ELIMIT, "pyramid: more than 65535 rows or planes of a level per call");
+    DSX_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = use_main(ctx);
+    for (int l = 1; l <= n; ++l)
+      if (levels[l - 1].zero)
+        DSX_HIP(hipMemsetAsync(lv[l - 1].bricks, 0, (size_t)levels[l - 1].rows * p::row_elems(lv[l - 1]) * 2, s));
+    return pyramid_run_steps(ctx, d_src, bs, H, W, f, n, lv, d_work, s);
+  }
   if (n > 2 && (!d_work || work_bytes < p::work_bytes(Z, H, W, n + 1) || (uintptr_t)d_work % 16))
     return fail(ctx, DSX_EINVAL, "pyramid: the work buffer is smaller than dsx_pyramid_work_bytes");
   if ((lv[0].H + 1) / 2 > 65535 || (lv[0].Z + 1) / 2 > 65535)
@@ -2190,30 +2259,69 @@ const char* brick_src(const void* bricks, int H, int W, int cz, int cy, int cx, 
 
 int dsx_pyramid_block_u16(dsx_ctx* ctx, const void* d_planes, int Z, int H, int W, int n_levels,
                           const dsx_pyramid_level* levels, void* const* d_bricks, void* d_work, size_t work_bytes) {
+  return dsx_pyramid_block_scale_u16(ctx, d_planes, Z, H, W, 2, 2, 2, n_levels, levels, d_bricks, d_work, work_bytes);
+}
+
+int dsx_pyramid_block_scale_u16(dsx_ctx* ctx, const void* d_planes, int Z, int H, int W, int fz, int fy, int fx,
+                                int n_levels, const dsx_pyramid_level* levels, void* const* d_bricks, void* d_work,
+                                size_t work_bytes) {
   if (!ctx || !d_planes) return DSX_EINVAL;
-  return pyramid_run(ctx, d_planes, nullptr, Z, H, W, n_levels, levels, d_bricks, d_work, work_bytes);
+  return pyramid_run(ctx, d_planes, nullptr, Z, H, W, n_levels, levels, d_bricks, d_work, work_bytes,
+                     dsx::pyr::Scale{fz, fy, fx});
 }
 
 int dsx_pyramid_bricks_u16(dsx_ctx* ctx, const void* d_src_bricks, int Z, int H, int W, int src_cz, int src_cy,
                            int src_cx, int n_levels, const dsx_pyramid_level* levels, void* const* d_bricks,
                            void* d_work, size_t work_bytes) {
+  return dsx_pyramid_bricks_scale_u16(ctx, d_src_bricks, Z, H, W, src_cz, src_cy, src_cx, 2, 2, 2, n_levels, levels,
+                                      d_bricks, d_work, work_bytes);
+}
+
+int dsx_pyramid_bricks_scale_u16(dsx_ctx* ctx, const void* d_src_bricks, int Z, int H, int W, int src_cz, int src_cy,
+                                 int src_cx, int fz, int fy, int fx, int n_levels, const dsx_pyramid_level* levels,
+                                 void* const* d_bricks, void* d_work, size_t work_bytes) {
   if (!ctx || !d_src_bricks) return DSX_EINVAL;
   dsx::pyr::BrickSrc bs = {};
   if (const char* e = brick_src(d_src_bricks, H, W, src_cz, src_cy, src_cx, &bs)) return fail(ctx, DSX_EINVAL, e);
-  return pyramid_run(ctx, d_src_bricks, &bs, Z, H, W, n_levels, levels, d_bricks, d_work, work_bytes);
+  return pyramid_run(ctx, d_src_bricks, &bs, Z, H, W, n_levels, levels, d_bricks, d_work, work_bytes,
+                     dsx::pyr::Scale{fz, fy, fx});
 }
 
 int dsx_pyramid_bricks_ref(const void* src_bricks, int Z, int H, int W, int src_cz, int src_cy, int src_cx,
                            int n_levels, const dsx_pyramid_level* levels, void* const* bricks) {
+  return dsx_pyramid_bricks_scale_ref(src_bricks, Z, H, W, src_cz, src_cy, src_cx, 2, 2, 2, n_levels, levels, bricks);
+}
+
+int dsx_pyramid_bricks_scale_ref(const void* src_bricks, int Z, int H, int W, int src_cz, int src_cy, int src_cx, int fz,
+                                 int fy, int fx, int n_levels, const dsx_pyramid_level* levels, void* const* bricks) {
   if (!src_bricks) return DSX_EINVAL;
+  const dsx::pyr::Scale f = {fz, fy, fx};
   dsx::pyr::BrickSrc bs = {};
   if (const char* e = brick_src(src_bricks, H, W, src_cz, src_cy, src_cx, &bs)) return fail(nullptr, DSX_EINVAL, e);
   dsx::pyr::Level lv[dsx::pyr::kMaxLevels] = {};
   int n = 0;
-  if (const char* e = pyramid_levels(Z, H, W, n_levels, levels, bricks, lv, &n)) return fail(nullptr, DSX_EINVAL, e);
+  if (const char* e = pyramid_levels(Z, H, W, n_levels, levels, bricks, lv, &n, f)) return fail(nullptr, DSX_EINVAL, e);
   for (int l = 1; l <= n; ++l)
     if (levels[l - 1].zero) memset(lv[l - 1].bricks, 0, (size_t)levels[l - 1].rows * dsx::pyr::row_elems(lv[l - 1]) * 2);
-  dsx::pyr::pyramid_bricks_host(bs, Z, H, W, n + 1, lv);
+  dsx::pyr::pyramid_bricks_host(bs, Z, H, W, n + 1, lv, f);
+  return DSX_OK;
+}
+
+int dsx_downsample_u16(dsx_ctx* ctx, const void* d_src, void* d_dst, int Z, int Y, int X, int fz, int fy, int fx) {
+  namespace p = dsx::pyr;
+  const p::Scale f = {fz, fy, fx};
+  if (!ctx || !d_src || !d_dst) return DSX_EINVAL;
+  if (!p::scale_ok(f)) return fail(ctx, DSX_EINVAL, "downsample: every scale factor is 1 or 2, and not all are 1");
+  if (p::scale_is_2(f)) return dsx_downsample2_u16(ctx, d_src, d_dst, Z, Y, X);
+  if (Z < fz || Y < fy || X < fx) return fail(ctx, DSX_EINVAL, "downsample: an axis is shorter than its scale factor");
+  dsx::PyrStepArgs a = {};
+  a.src = (const uint16_t*)d_src; a.Y = Y; a.X = X;
+  a.out.Z = Z / fz; a.out.H = Y / fy; a.out.W = X / fx;
+  a.dense = (uint16_t*)d_dst;
+  if (a.out.H > 65535 || a.out.Z > 65535) return fail(ctx, DSX_ELIMIT, "downsample: more than 65535 rows or planes");
+  DSX_HIP(hipSetDevice(ctx->device));
+  pyramid_step(f, false, use_main(ctx), a);
+  DSX_HIP(hipGetLastError());
   return DSX_OK;
 }
 

@@ -9,6 +9,9 @@
 //       of a finished store: a decoded level-0 block), without k_bricks_to_planes in front.
 //   k_pyramid_level : one further level (>= 3; under 0.2 % of the bytes) from the dense previous one: 2 x 2 x 2 mean,
 //       brick-order store, dense copy for the next level.
+//   k_pyramid_step<FZ, FY, FX> : one level of a pyramid with another window (factor 1 or 2 per axis, anisotropic
+//       volumes: compute_pyramid(scale_axis=...), compute_multiscale(scale_factor=...)) from the previous one, dense or
+//       in chunk order; one launch per level, every level >= 1 but the last also left dense.
 //
 // Pure HBM streaming like dsx_retile.h: 16-byte loads per lane, row / plane indices from blockIdx, non-temporal
 // accesses, no LDS.  A thread of k_pyramid_block owns 4 planes x 4 rows x 8 columns of level 0 = 2 x 2 x 4 level-1
@@ -208,6 +211,83 @@ __global__ __launch_bounds__(256) void k_pyramid_level(PyrLevelArgs a) {
   const uint16_t v = (uint16_t)pyr::mean8(t);
   a.out.bricks[pyr::brick_offset(a.out, a.out.z0 + z, y, x)] = v;
   if (a.dense) a.dense[((size_t)z * a.out.H + y) * a.out.W + x] = v;
+}
+
+struct PyrStepArgs {
+  const uint16_t* src;  // BRICKS == false: the dense previous level [..][Y][X]
+  pyr::BrickSrc bsrc;   // BRICKS == true: the previous level (level 0 of a block) in chunk order
+  int Y, X;             // rows / columns of the previous level
+  pyr::Level out;       // this level; out.bricks may be NULL when only the dense copy is wanted
+  uint16_t* dense;      // nullable: this level dense [out.Z][out.H][out.W], for the next one
+};
+
+// One level of a pyramid with an FZ x FY x FX window (a pyr::Scale other than 2 x 2 x 2) from the previous one: mean,
+// brick-order store at out.z0, dense copy for the next level.  A thread owns 8 source columns of FZ planes x FY rows
+// (one 16-byte load each) = N = 8 / FX output voxels of one row (one 8- or 16-byte store).
+// grid: (ceil(ceil(out.W / N) / 256), out.H, out.Z).
+// VEC == true needs X % 8 == 0, out.cx % N == 0, a 16-byte aligned source (bsrc.cx % 8 == 0 for bricks) and 2 N-byte
+// aligned outputs; otherwise scalar accesses with per-voxel bounds (the tail body).
+template <int FZ, int FY, int FX, bool VEC, bool BRICKS>
+__global__ __launch_bounds__(256) void k_pyramid_step(PyrStepArgs a) {
+  constexpr int N = 8 / FX;
+  constexpr int SHIFT = (FZ - 1) + (FY - 1) + (FX - 1);
+  const int x = (blockIdx.x * 256 + threadIdx.x) * N;
+  if (x >= a.out.W) return;
+  const int y = blockIdx.y, z = blockIdx.z;
+  const size_t dense_at = ((size_t)z * a.out.H + y) * a.out.W + x;
+  if (VEC) {
+    uint32_t s[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) s[i] = 0;
+    const size_t col = BRICKS ? pyr::src_col(a.bsrc, FX * x) : (size_t)(FX * x);
+#pragma unroll
+    for (int dz = 0; dz < FZ; ++dz) {
+#pragma unroll
+      for (int dy = 0; dy < FY; ++dy) {
+        const int zs = FZ * z + dz, ys = FY * y + dy;
+        const uint16_t* p = BRICKS ? a.bsrc.bricks + pyr::src_plane(a.bsrc, zs) + pyr::src_row(a.bsrc, ys) + col
+                                   : a.src + ((size_t)zs * a.Y + ys) * a.X + col;
+        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+        if constexpr (FX == 2) {
+          s[0] += pair_sum(v.x); s[1] += pair_sum(v.y); s[2] += pair_sum(v.z); s[3] += pair_sum(v.w);
+        } else {
+          s[0] += v.x & 0xffffu; s[1] += v.x >> 16; s[2] += v.y & 0xffffu; s[3] += v.y >> 16;
+          s[4] += v.z & 0xffffu; s[5] += v.z >> 16; s[6] += v.w & 0xffffu; s[7] += v.w >> 16;
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) s[i] = pyr::window_mean(s[i], SHIFT);
+    using V = typename U16Vec<N>::type;
+    V o;
+    o.x = s[0] | (s[1] << 16);
+    o.y = s[2] | (s[3] << 16);
+    if constexpr (N == 8) {
+      o.z = s[4] | (s[5] << 16);
+      o.w = s[6] | (s[7] << 16);
+    }
+    if (a.out.bricks)
+      __builtin_nontemporal_store(o, reinterpret_cast<V*>(a.out.bricks + pyr::brick_offset(a.out, a.out.z0 + z, y, x)));
+    if (a.dense) __builtin_nontemporal_store(o, reinterpret_cast<V*>(a.dense + dense_at));
+  } else {
+    const pyr::DenseAt dense = {a.src, (size_t)a.Y * a.X, (size_t)a.X};
+    const pyr::BrickAt bricks = {a.bsrc};
+    for (int i = 0; i < N && x + i < a.out.W; ++i) {
+      const uint32_t t = BRICKS ? pyr::window_sum(bricks, z, y, x + i, FZ, FY, FX) : pyr::window_sum(dense, z, y, x + i, FZ, FY, FX);
+      const uint16_t v = (uint16_t)pyr::window_mean(t, SHIFT);
+      if (a.out.bricks) a.out.bricks[pyr::brick_offset(a.out, a.out.z0 + z, y, x + i)] = v;
+      if (a.dense) a.dense[dense_at + i] = v;
+    }
+  }
+}
+
+// The body of k_pyramid_step<FZ, FY, FX> that the geometry allows (dsx.hip decides `vec`).
+template <int FZ, int FY, int FX>
+inline void launch_pyramid_step(bool vec, bool bricks, const dim3& grid, hipStream_t s, const PyrStepArgs& a) {
+  if (vec && bricks) hipLaunchKernelGGL((k_pyramid_step<FZ, FY, FX, true, true>), grid, dim3(256), 0, s, a);
+  else if (vec) hipLaunchKernelGGL((k_pyramid_step<FZ, FY, FX, true, false>), grid, dim3(256), 0, s, a);
+  else if (bricks) hipLaunchKernelGGL((k_pyramid_step<FZ, FY, FX, false, true>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((k_pyramid_step<FZ, FY, FX, false, false>), grid, dim3(256), 0, s, a);
 }
 
 }  // namespace dsx

@@ -57,6 +57,8 @@ EXPORTED_SYMBOLS = [
     "dsx_io_read_zlib_chunks", "dsx_io_write_chunks_blosc_lz4", "dsx_blosc_encode_lz4",
     "dsx_pyramid_work_bytes", "dsx_pyramid_block_u16", "dsx_pyramid_block_ref",
     "dsx_pyramid_bricks_u16", "dsx_pyramid_bricks_ref",
+    "dsx_downsample_u16", "dsx_pyramid_work_bytes_scale", "dsx_pyramid_block_scale_u16", "dsx_pyramid_block_scale_ref",
+    "dsx_pyramid_bricks_scale_u16", "dsx_pyramid_bricks_scale_ref",
     "dsx_volhist_reset", "dsx_volhist_add_device", "dsx_volhist_get", "dsx_volhist_ref",
     "dsx_plan_streaks_opts", "dsx_streaks_blend_ref",
     "dsx_set_rotate", "dsx_rot90_device", "dsx_rot90_ref",
@@ -248,6 +250,15 @@ def load_library(path=None):
     lib.dsx_pyramid_bricks_u16.argtypes = [vp, vp] + [i32] * 7 + [ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp), vp,
                                                                   ctypes.c_size_t]  # fmt: skip
     lib.dsx_pyramid_bricks_ref.argtypes = [vp] + [i32] * 7 + [ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp)]
+    # the same with a scale factor per axis (fz, fy, fx in front of n_levels)
+    lib.dsx_downsample_u16.argtypes = [vp, vp, vp] + [i32] * 6
+    lib.dsx_pyramid_work_bytes_scale.argtypes = [i32] * 7 + [ctypes.POINTER(ctypes.c_size_t)]
+    lib.dsx_pyramid_block_scale_u16.argtypes = [vp, vp] + [i32] * 7 + [ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp),
+                                                                       vp, ctypes.c_size_t]  # fmt: skip
+    lib.dsx_pyramid_block_scale_ref.argtypes = [vp] + [i32] * 7 + [ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp)]
+    lib.dsx_pyramid_bricks_scale_u16.argtypes = [vp, vp] + [i32] * 10 + [ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp),
+                                                                         vp, ctypes.c_size_t]  # fmt: skip
+    lib.dsx_pyramid_bricks_scale_ref.argtypes = [vp] + [i32] * 10 + [ctypes.POINTER(_PyramidLevel), ctypes.POINTER(vp)]
     lib.dsx_volhist_reset.argtypes = [vp]
     lib.dsx_volhist_add_device.argtypes = [vp, vp, ctypes.c_size_t]
     lib.dsx_volhist_get.argtypes = [vp, vp]
@@ -883,49 +894,61 @@ class DestripeEngine:
                                                        ctypes.c_void_p(d_bricks.ptr), *map(int, zyx),
                                                        *map(int, brick), int(z0)))  # fmt: skip
 
-    def downsample2(self, d_src, d_dst, zyx):
-        """One 2x2x2 windowed-mean pyramid level, uint16 (``zarr_destriper.py:365-407``)."""
-        rc = self._lib.dsx_downsample2_u16(self._ctx, ctypes.c_void_p(d_src.ptr), ctypes.c_void_p(d_dst.ptr),
-                                           *map(int, zyx))  # fmt: skip
+    def downsample2(self, d_src, d_dst, zyx, scale=(2, 2, 2)):
+        """One windowed-mean pyramid level, uint16 (``zarr_destriper.py:365-407``): ``zyx`` -> ``zyx // scale``, the
+        window ``scale`` = 1 or 2 per axis (``dsx_downsample_u16``; 2 x 2 x 2 is ``dsx_downsample2_u16``)."""
+        scale = pyramid_scale(scale)
+        assert d_src.nbytes >= int(np.prod(zyx)) * 2, "downsample source buffer too small"
+        assert d_dst.nbytes >= int(np.prod([n // f for n, f in zip(zyx, scale)])) * 2, "downsample buffer too small"
+        rc = self._lib.dsx_downsample_u16(self._ctx, ctypes.c_void_p(d_src.ptr), ctypes.c_void_p(d_dst.ptr),
+                                          *map(int, zyx), *scale)  # fmt: skip
         if rc == -1:
             raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
         self._check(rc)
 
-    def pyramid_block(self, d_planes, zyx, chunks, d_bricks, z0s=None, zero=None, rows=None, d_work=None):
+    def pyramid_block(self, d_planes, zyx, chunks, d_bricks, z0s=None, zero=None, rows=None, d_work=None, scale=(2, 2, 2)):
         """Pyramid levels ``1 .. len(chunks)`` of the dense uint16 block ``d_planes`` (``zyx``), each stored in chunk
-        order into ``d_bricks[l - 1]`` (``dsx_pyramid_block_u16``; ``zarr_destriper.py:365-407, 746-782``).
+        order into ``d_bricks[l - 1]`` (``dsx_pyramid_block_scale_u16``; ``zarr_destriper.py:365-407, 746-782``).
 
         ``chunks[l - 1]``: the level's (clamped) chunk shape; ``z0s[l - 1]``: first plane of the block's share inside the
         level's brick grid (default 0); ``zero[l - 1]``: zero the level's buffer first (default True); ``rows[l - 1]``:
         chunk rows the buffer holds (default: what the share needs).  ``d_work``: ``pyramid_work_bytes`` bytes when there
-        are more than two levels.  Asynchronous on the engine stream."""
-        table = _pyramid_table(zyx, chunks, z0s, zero, rows)
+        are more than two levels (more than one with a ``scale`` other than 2 x 2 x 2).  ``scale``: the window per axis,
+        1 or 2 each.  Asynchronous on the engine stream."""
+        scale = pyramid_scale(scale)
+        table = _pyramid_table(zyx, chunks, z0s, zero, rows, scale)
         n = len(chunks)
+        assert d_planes.nbytes >= int(np.prod(zyx)) * 2, "pyramid source buffer too small"
+        assert n < 2 or scale == (2, 2, 2) or (d_work is not None and d_work.nbytes >= pyramid_work_bytes(zyx, n + 1, scale))
         for lv, g, b in zip(range(1, n + 1), table, d_bricks):
-            assert b.nbytes >= pyramid_level_elems(zyx, lv, (g.cz, g.cy, g.cx), g.rows) * 2, "pyramid brick buffer too small"
+            assert b.nbytes >= pyramid_level_elems(zyx, lv, (g.cz, g.cy, g.cx), g.rows, scale) * 2, "pyramid brick buffer too small"
         ptrs = (ctypes.c_void_p * max(n, 1))(*[b.ptr for b in d_bricks])
-        rc = self._lib.dsx_pyramid_block_u16(self._ctx, ctypes.c_void_p(d_planes.ptr), *map(int, zyx), n + 1, table, ptrs,
-                                             ctypes.c_void_p(d_work.ptr) if d_work is not None else None,
-                                             d_work.nbytes if d_work is not None else 0)  # fmt: skip
+        rc = self._lib.dsx_pyramid_block_scale_u16(self._ctx, ctypes.c_void_p(d_planes.ptr), *map(int, zyx), *scale, n + 1,
+                                                   table, ptrs,
+                                                   ctypes.c_void_p(d_work.ptr) if d_work is not None else None,
+                                                   d_work.nbytes if d_work is not None else 0)  # fmt: skip
         if rc == -1:
             raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
         self._check(rc)
 
-    def pyramid_bricks(self, d_src, zyx, src_chunk, chunks, d_bricks, z0s=None, zero=None, rows=None, d_work=None):
-        """:meth:`pyramid_block` for a block that is still in chunk order (``dsx_pyramid_bricks_u16``;
+    def pyramid_bricks(self, d_src, zyx, src_chunk, chunks, d_bricks, z0s=None, zero=None, rows=None, d_work=None,
+                       scale=(2, 2, 2)):  # fmt: skip
+        """:meth:`pyramid_block` for a block that is still in chunk order (``dsx_pyramid_bricks_scale_u16``;
         ``zarr_destriper.py:365-407, 746-782``): ``d_src`` holds the uint16 bricks ``[nbz, nby, nbx] + src_chunk`` of
         the block ``zyx``, which starts on a source chunk boundary; positions outside ``zyx`` are never read.  Every
         other argument as in :meth:`pyramid_block`.  Asynchronous on the engine stream."""
-        table = _pyramid_table(zyx, chunks, z0s, zero, rows)
+        scale = pyramid_scale(scale)
+        table = _pyramid_table(zyx, chunks, z0s, zero, rows, scale)
         n = len(chunks)
         assert d_src.nbytes >= src_brick_elems(zyx, src_chunk) * 2, "pyramid source brick buffer too small"
+        assert n < 2 or scale == (2, 2, 2) or (d_work is not None and d_work.nbytes >= pyramid_work_bytes(zyx, n + 1, scale))
         for lv, g, b in zip(range(1, n + 1), table, d_bricks):
-            assert b.nbytes >= pyramid_level_elems(zyx, lv, (g.cz, g.cy, g.cx), g.rows) * 2, "pyramid brick buffer too small"
+            assert b.nbytes >= pyramid_level_elems(zyx, lv, (g.cz, g.cy, g.cx), g.rows, scale) * 2, "pyramid brick buffer too small"
         ptrs = (ctypes.c_void_p * max(n, 1))(*[b.ptr for b in d_bricks])
-        rc = self._lib.dsx_pyramid_bricks_u16(self._ctx, ctypes.c_void_p(d_src.ptr), *map(int, zyx), *map(int, src_chunk),
-                                              n + 1, table, ptrs,
-                                              ctypes.c_void_p(d_work.ptr) if d_work is not None else None,
-                                              d_work.nbytes if d_work is not None else 0)  # fmt: skip
+        rc = self._lib.dsx_pyramid_bricks_scale_u16(self._ctx, ctypes.c_void_p(d_src.ptr), *map(int, zyx),
+                                                    *map(int, src_chunk), *scale, n + 1, table, ptrs,
+                                                    ctypes.c_void_p(d_work.ptr) if d_work is not None else None,
+                                                    d_work.nbytes if d_work is not None else 0)  # fmt: skip
         if rc == -1:
             raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
         self._check(rc)
@@ -1041,22 +1064,40 @@ class DestripeEngine:
         return out
 
 
-def _pyramid_table(zyx, chunks, z0s, zero, rows):
+def pyramid_scale(scale):
+    """``(fz, fy, fx)`` of a pyramid as ints: each 1 or 2, not all 1 (what the kernels of ``csrc/dsx_pyramid.h`` take);
+    ``ValueError`` otherwise."""
+    try:
+        f = tuple(int(s) for s in scale)
+        exact = all(s == v for s, v in zip(scale, f))
+    except (TypeError, ValueError):
+        f, exact = (), False
+    if len(f) != 3 or not exact or any(v not in (1, 2) for v in f) or f == (1, 1, 1):
+        raise ValueError("only scale factors of 1 or 2 per axis (not all 1) are implemented, not {!r}".format(scale))
+    return f
+
+
+def pyramid_extent(n, level, factor):
+    """Extent of an axis of ``n`` voxels at pyramid level ``level``: halved per level with factor 2, kept with 1."""
+    return int(n) >> level if int(factor) == 2 else int(n)
+
+
+def _pyramid_table(zyx, chunks, z0s, zero, rows, scale=(2, 2, 2)):
     n = len(chunks)
     table = (_PyramidLevel * max(n, 1))()
     for i, ck in enumerate(chunks):
         z0 = int(z0s[i]) if z0s is not None else 0
-        share = int(zyx[0]) >> (i + 1)
+        share = pyramid_extent(zyx[0], i + 1, scale[0])
         need = max(1, -(-(z0 + share) // int(ck[0])))
         table[i] = _PyramidLevel(int(ck[0]), int(ck[1]), int(ck[2]), int(rows[i]) if rows is not None else need, z0,
                                  1 if zero is None or zero[i] else 0)  # fmt: skip
     return table
 
 
-def pyramid_level_elems(zyx, level, chunk, rows=1):
+def pyramid_level_elems(zyx, level, chunk, rows=1, scale=(2, 2, 2)):
     """uint16 elements of ``rows`` chunk rows of pyramid level ``level`` of a ``[.., H, W]`` volume in chunk order."""
-    nby = -(-(int(zyx[1]) >> level) // int(chunk[1]))
-    nbx = -(-(int(zyx[2]) >> level) // int(chunk[2]))
+    nby = -(-pyramid_extent(zyx[1], level, scale[1]) // int(chunk[1]))
+    nbx = -(-pyramid_extent(zyx[2], level, scale[2]) // int(chunk[2]))
     return int(rows) * nby * nbx * int(chunk[0]) * int(chunk[1]) * int(chunk[2])
 
 
@@ -1068,11 +1109,11 @@ def src_brick_elems(zyx, src_chunk):
     return n
 
 
-def pyramid_work_bytes(zyx, n_levels):
+def pyramid_work_bytes(zyx, n_levels, scale=(2, 2, 2)):
     """Bytes of the work buffer :meth:`DestripeEngine.pyramid_block` needs for ``n_levels`` levels (level 0 counted)."""
     lib = load_library()
     n = ctypes.c_size_t(0)
-    if lib.dsx_pyramid_work_bytes(*map(int, zyx), int(n_levels), ctypes.byref(n)) != 0:
+    if lib.dsx_pyramid_work_bytes_scale(*map(int, zyx), *pyramid_scale(scale), int(n_levels), ctypes.byref(n)) != 0:
         raise ValueError("pyramid_work_bytes: bad geometry {} / {} levels".format(tuple(zyx), n_levels))
     return int(n.value)
 
@@ -1127,20 +1168,22 @@ def streaks_blend_ref(x, f, b, t, crossover=10.0, bands="both", smoothing=0.0, f
     return out
 
 
-def pyramid_block_ref(planes, chunks, z0s=None, bricks=None, rows=None):
+def pyramid_block_ref(planes, chunks, z0s=None, bricks=None, rows=None, scale=(2, 2, 2)):
     """Host build of :meth:`DestripeEngine.pyramid_block` (``dsx_pyramid_block_ref``): ``planes`` uint16 ``[Z, H, W]``
     -> one uint16 array ``[rows, nby, nbx, cz, cy, cx]`` per level ``1 .. len(chunks)``.  ``bricks``: arrays of an
-    earlier call to write into (a chunk row filled by several blocks); fresh zeroed ones otherwise."""
+    earlier call to write into (a chunk row filled by several blocks); fresh zeroed ones otherwise.  ``scale``: the window
+    per axis, 1 or 2 each (``dsx_pyramid_block_scale_ref``)."""
     lib = load_library()
+    scale = pyramid_scale(scale)
     a = np.ascontiguousarray(planes)
     if a.dtype != np.uint16 or a.ndim != 3:
         raise ValueError("the pyramid kernels take uint16 [Z, H, W] blocks")
-    table = _pyramid_table(a.shape, chunks, z0s, [bricks is None] * len(chunks), rows)
+    table = _pyramid_table(a.shape, chunks, z0s, [bricks is None] * len(chunks), rows, scale)
     out = []
     for i, ck in enumerate(chunks):
         g = table[i]
-        shape = (g.rows, -(-(a.shape[1] >> (i + 1)) // g.cy) if a.shape[1] >> (i + 1) else 0,
-                 -(-(a.shape[2] >> (i + 1)) // g.cx) if a.shape[2] >> (i + 1) else 0, g.cz, g.cy, g.cx)  # fmt: skip
+        shape = (g.rows, -(-pyramid_extent(a.shape[1], i + 1, scale[1]) // g.cy),
+                 -(-pyramid_extent(a.shape[2], i + 1, scale[2]) // g.cx), g.cz, g.cy, g.cx)  # fmt: skip
         if bricks is None:
             out.append(np.zeros(shape, np.uint16))
         else:
@@ -1150,18 +1193,20 @@ def pyramid_block_ref(planes, chunks, z0s=None, bricks=None, rows=None):
             out.append(b)
     n = len(chunks)
     ptrs = (ctypes.c_void_p * max(n, 1))(*[o.ctypes.data for o in out])  # (a level with an empty share is not touched)
-    rc = lib.dsx_pyramid_block_ref(a.ctypes.data_as(ctypes.c_void_p), *a.shape, n + 1, table, ptrs)
+    rc = lib.dsx_pyramid_block_scale_ref(a.ctypes.data_as(ctypes.c_void_p), *a.shape, *scale, n + 1, table, ptrs)
     if rc != 0:
         raise ValueError((lib.dsx_last_error(None) or b"pyramid_block_ref failed").decode())
     return out
 
 
-def pyramid_bricks_ref(bricks, zyx, src_chunk, chunks, z0s=None, bricks_out=None, rows=None):
+def pyramid_bricks_ref(bricks, zyx, src_chunk, chunks, z0s=None, bricks_out=None, rows=None, scale=(2, 2, 2)):
     """Host build of :meth:`DestripeEngine.pyramid_bricks` (``dsx_pyramid_bricks_ref``): ``bricks`` uint16
     ``[nbz, nby, nbx] + src_chunk`` holding the block ``zyx`` -> one uint16 array ``[rows, nby, nbx, cz, cy, cx]`` per
     level ``1 .. len(chunks)``, the bytes :func:`pyramid_block_ref` gives for the dense block.  ``bricks_out``: arrays of
-    an earlier call to write into; fresh zeroed ones otherwise."""
+    an earlier call to write into; fresh zeroed ones otherwise.  ``scale``: the window per axis, 1 or 2 each
+    (``dsx_pyramid_bricks_scale_ref``)."""
     lib = load_library()
+    scale = pyramid_scale(scale)
     a = np.ascontiguousarray(bricks)
     zyx, src_chunk = tuple(int(v) for v in zyx), tuple(int(v) for v in src_chunk)
     if a.dtype != np.uint16 or len(zyx) != 3 or len(src_chunk) != 3 or min(src_chunk) <= 0:
@@ -1169,12 +1214,12 @@ def pyramid_bricks_ref(bricks, zyx, src_chunk, chunks, z0s=None, bricks_out=None
     if a.size != src_brick_elems(zyx, src_chunk):
         raise ValueError("a {} block in chunks {} has {} voxels, not {}".format(zyx, src_chunk,
                                                                                src_brick_elems(zyx, src_chunk), a.size))  # fmt: skip
-    table = _pyramid_table(zyx, chunks, z0s, [bricks_out is None] * len(chunks), rows)
+    table = _pyramid_table(zyx, chunks, z0s, [bricks_out is None] * len(chunks), rows, scale)
     out = []
     for i, ck in enumerate(chunks):
         g = table[i]
-        shape = (g.rows, -(-(zyx[1] >> (i + 1)) // g.cy) if zyx[1] >> (i + 1) else 0,
-                 -(-(zyx[2] >> (i + 1)) // g.cx) if zyx[2] >> (i + 1) else 0, g.cz, g.cy, g.cx)  # fmt: skip
+        shape = (g.rows, -(-pyramid_extent(zyx[1], i + 1, scale[1]) // g.cy),
+                 -(-pyramid_extent(zyx[2], i + 1, scale[2]) // g.cx), g.cz, g.cy, g.cx)  # fmt: skip
         if bricks_out is None:
             out.append(np.zeros(shape, np.uint16))
         else:
@@ -1184,7 +1229,7 @@ def pyramid_bricks_ref(bricks, zyx, src_chunk, chunks, z0s=None, bricks_out=None
             out.append(b)
     n = len(chunks)
     ptrs = (ctypes.c_void_p * max(n, 1))(*[o.ctypes.data for o in out])
-    rc = lib.dsx_pyramid_bricks_ref(a.ctypes.data_as(ctypes.c_void_p), *zyx, *src_chunk, n + 1, table, ptrs)
+    rc = lib.dsx_pyramid_bricks_scale_ref(a.ctypes.data_as(ctypes.c_void_p), *zyx, *src_chunk, *scale, n + 1, table, ptrs)
     if rc != 0:
         raise ValueError((lib.dsx_last_error(None) or b"pyramid_bricks_ref failed").decode())
     return out

@@ -6,6 +6,10 @@ level loop of ``compute_multiscale`` (``:677-794``): ``xarray_multiscale.multisc
 is the 2 x 2 x 2 windowed mean of the previous one, truncated back to uint16 -- without the dask
 ``LocalCluster`` (``:689-697``): one HIP kernel per level (``dsx_downsample2_u16``), the volume stays in HBM
 between levels.  No CPU fallback.
+
+The window is a parameter as in the reference (``scale_axis`` / ``scale_factor``): 1 or 2 per spatial axis, not all 1
+(:func:`_check_scale`), so an anisotropic volume can reduce only its fine axes, e.g. ``(1, 2, 2)``.  ``(2, 2, 2)`` runs
+the kernels named here; any other scale runs ``k_pyramid_step<FZ, FY, FX>`` once per level on every route.
 """
 
 import itertools
@@ -22,9 +26,33 @@ from .mini_zarr import MiniZarrArray
 
 
 def _check_scale(scale_axis):
-    scale = [int(s) for s in scale_axis]
-    if len(scale) < 3 or any(s != 1 for s in scale[:-3]) or scale[-3:] != [2, 2, 2]:
-        raise ValueError("only scale factors (.., 2, 2, 2) are implemented (production setting, zarr_destriper.py:1176)")
+    """``(fz, fy, fx)`` of ``scale_axis`` (``compute_pyramid``) / ``(1, 1) + scale_factor`` (``compute_multiscale``):
+    1 or 2 per spatial axis, not all 1, behind unit leading axes; ``ValueError`` otherwise."""
+    try:
+        scale = list(scale_axis)
+        lead_ok = len(scale) >= 3 and all(s == 1 for s in scale[:-3])
+    except TypeError:
+        scale, lead_ok = [], False
+    if not lead_ok:
+        raise ValueError("only scale factors (.., fz, fy, fx) behind unit leading axes are implemented, not {!r}"
+                         .format(scale_axis))  # fmt: skip
+    return _engine.pyramid_scale(scale[-3:])
+
+
+def check_scale_factor(scale_factor):
+    """``(fz, fy, fx)`` of a ``scale_factor`` of ``compute_multiscale``: three factors, :func:`_check_scale`'s rules."""
+    try:
+        axes = (1, 1) + tuple(scale_factor)
+    except TypeError:
+        axes = ()
+    if len(axes) != 5:
+        raise ValueError("only scale factors (fz, fy, fx) are implemented, not {!r}".format(scale_factor))
+    return _check_scale(axes)
+
+
+def _window(scale, level):
+    """Level-0 planes under one plane of level ``level``."""
+    return int(scale[0]) ** int(level)
 
 
 # ---- the pyramid fused into the destripe pass (zarr_destriper.destripe_zarr_store(pyramid_group=...)) -----------------
@@ -35,40 +63,43 @@ FusedLevel = namedtuple("FusedLevel", "level shape chunks")
 BlockShare = namedtuple("BlockShare", "level row offset planes first flush")
 
 
-def fused_levels(zyx, chunks, n_levels):
-    """Levels ``1 .. n_levels - 1`` as :func:`write_pyramid_levels` writes them: shape ``n // 2`` of the previous
-    level, chunks ``min(c, n)``, stopping at a source level with an axis shorter than 2."""
+def fused_levels(zyx, chunks, n_levels, scale=(2, 2, 2)):
+    """Levels ``1 .. n_levels - 1`` as :func:`write_pyramid_levels` writes them: shape ``n // f`` of the previous
+    level per axis (``f`` of ``scale``), chunks ``min(c, n)``, stopping at a source level with an axis shorter than its
+    factor."""
     levels, cur = [], tuple(int(n) for n in zyx)
     for i in range(1, int(n_levels)):
-        if min(cur) < 2:
+        if any(n < f for n, f in zip(cur, scale)):
             break
-        cur = tuple(n // 2 for n in cur)
+        cur = tuple(n // f for n, f in zip(cur, scale))
         levels.append(FusedLevel(i, cur, tuple(min(int(c), n) for c, n in zip(tuple(chunks)[-3:], cur))))
     return levels
 
 
-def fused_z_chunk(z_chunk, levels):
+def fused_z_chunk(z_chunk, levels, scale=(2, 2, 2)):
     """z alignment of the rank shards: one chunk row of the deepest level, in level-0 planes
-    (``cz << (levels written - 1)``), so that every chunk of every level is written by exactly one rank."""
-    return int(z_chunk) << len(levels)
+    (``cz << (levels written - 1)``; ``cz * fz ** levels`` in general, so the plain output z chunk when z is not
+    reduced), so that every chunk of every level is written by exactly one rank."""
+    return int(z_chunk) * _window(scale, len(levels))
 
 
-def fused_z_range(n_slices, world_size, rank, z_chunk, levels):
-    return z_shard(n_slices, world_size, rank, z_chunk=fused_z_chunk(z_chunk, levels))
+def fused_z_range(n_slices, world_size, rank, z_chunk, levels, scale=(2, 2, 2)):
+    return z_shard(n_slices, world_size, rank, z_chunk=fused_z_chunk(z_chunk, levels, scale))
 
 
-def fused_check_blocks(levels, block_z):
+def fused_check_blocks(levels, block_z, scale=(2, 2, 2)):
     """``ValueError`` unless z blocks of ``block_z`` planes hold whole windows of every level and fill whole chunk rows."""
-    if levels and block_z % (1 << len(levels)):
-        raise ValueError("fused_pyramid needs z blocks of a multiple of {} planes (2 x 2 x 2 windows of {} levels), "
-                         "not {}".format(1 << len(levels), len(levels), block_z))  # fmt: skip
+    if levels and block_z % _window(scale, len(levels)):
+        raise ValueError("fused_pyramid needs z blocks of a multiple of {} planes ({} x {} x {} windows of {} levels), "
+                         "not {}".format(_window(scale, len(levels)), *scale, len(levels), block_z))  # fmt: skip
     for lv in levels:
-        if lv.shape[0] > lv.chunks[0] and (lv.chunks[0] << lv.level) % block_z:
+        row = lv.chunks[0] * _window(scale, lv.level)
+        if lv.shape[0] > lv.chunks[0] and row % block_z:
             raise ValueError("fused_pyramid needs z blocks that fill whole chunk rows of every level: {} planes do not "
-                             "divide the {} of a level-{} chunk row".format(block_z, lv.chunks[0] << lv.level, lv.level))  # fmt: skip
+                             "divide the {} of a level-{} chunk row".format(block_z, row, lv.level))  # fmt: skip
 
 
-def fused_schedule(levels, z_start, z_stop, block_z):
+def fused_schedule(levels, z_start, z_stop, block_z, scale=(2, 2, 2)):
     """What every z block of ``[z_start, z_stop)`` (a :func:`fused_z_range`) gives to every level:
     ``[((z0, z1), [BlockShare per level])]``.  A chunk row leaves (``flush``) with the block that completes it, or with
     the last block of the range when it holds anything."""
@@ -77,7 +108,8 @@ def fused_schedule(levels, z_start, z_stop, block_z):
     for z0 in starts:
         z1, shares = min(z0 + block_z, z_stop), []
         for i, lv in enumerate(levels):
-            p0, n, cz = z0 >> lv.level, (min(z0 + block_z, z_stop) - z0) >> lv.level, lv.chunks[0]
+            w = _window(scale, lv.level)
+            p0, n, cz = z0 // w, (min(z0 + block_z, z_stop) - z0) // w, lv.chunks[0]
             row, off = divmod(p0, cz)
             if n and off + n > cz:
                 raise ValueError("a z block straddles a level-{} chunk row (fused_check_blocks)".format(lv.level))
@@ -90,23 +122,23 @@ def fused_schedule(levels, z_start, z_stop, block_z):
     return out
 
 
-def pipelined_block_z(src_cz, levels):
+def pipelined_block_z(src_cz, levels, scale=(2, 2, 2)):
     """z block of the pipelined stand-alone pyramid: the smallest multiple of the source z chunk ``src_cz`` (blocks are
     whole source chunks) that :func:`fused_check_blocks` accepts.  The first condition there holds from
-    ``lcm(src_cz, 2^levels) <= src_cz << levels`` on, and a block the chunk rows refuse has no multiple they accept, so
-    the search is bounded; ``ValueError`` when it finds nothing."""
+    ``lcm(src_cz, 2^levels) <= src_cz << levels`` on (``fz ** levels`` for 2 in general), and a block the chunk rows
+    refuse has no multiple they accept, so the search is bounded; ``ValueError`` when it finds nothing."""
     src_cz = int(src_cz)
     if src_cz <= 0:
         raise ValueError("the source z chunk must be positive, not {}".format(src_cz))
-    for m in range(1, (1 << len(levels)) + 1):
+    for m in range(1, _window(scale, len(levels)) + 1):
         try:
-            fused_check_blocks(levels, m * src_cz)
+            fused_check_blocks(levels, m * src_cz, scale)
         except ValueError:
             continue
         return m * src_cz
-    raise ValueError("pipelined pyramid: no z block of whole source chunks ({} planes each) holds whole 2 x 2 x 2 windows "
+    raise ValueError("pipelined pyramid: no z block of whole source chunks ({} planes each) holds whole {} x {} x {} windows "
                      "of {} levels and fills whole chunk rows of every level (z chunks {})".format(
-                         src_cz, len(levels), [lv.chunks[0] for lv in levels]))  # fmt: skip
+                         src_cz, *scale, len(levels), [lv.chunks[0] for lv in levels]))  # fmt: skip
 
 
 def compute_pyramid(data, n_lvls, scale_axis, chunks="auto", device=0, engine=None):
@@ -114,8 +146,16 @@ def compute_pyramid(data, n_lvls, scale_axis, chunks="auto", device=0, engine=No
 
     ``data``: uint16 with the spatial axes last (``[Z, Y, X]`` up to ``[1, 1, Z, Y, X]``; leading axes must be
     singletons); ``chunks`` is accepted for signature parity and ignored (dense arrays come back).
+
+    ``scale_axis``: :func:`_check_scale`'s factors with ``fy == fx`` -- ``(2, 2, 2)``, ``(1, 2, 2)``, ``(2, 1, 1)``: the
+    pixel of a plane is square, so this in-memory entry point reduces y and x together or not at all, and it goes on
+    refusing a window such as ``(2, 2, 1)`` as it always did (``ValueError`` before a device is touched).  The store
+    routes (:func:`write_pyramid_levels`, the fused pass) take every scale of :func:`_check_scale`.
     """
-    _check_scale(scale_axis)
+    scale = _check_scale(scale_axis)
+    if scale[1] != scale[2]:
+        raise ValueError("only scale factors that reduce y and x alike (fy == fx) are implemented by compute_pyramid, "
+                         "not {!r}".format(scale_axis))  # fmt: skip
     vol = np.asarray(data)
     if vol.dtype != np.uint16:
         raise ValueError("the pyramid kernel takes uint16 volumes (what the destriped Zarr stores)")
@@ -131,12 +171,12 @@ def compute_pyramid(data, n_lvls, scale_axis, chunks="auto", device=0, engine=No
         bufs.append(d_prev)
         d_prev.upload(np.ascontiguousarray(vol))
         for _ in range(1, int(n_lvls)):
-            if min(zyx) < 2:
+            if any(n < f for n, f in zip(zyx, scale)):
                 break
-            nxt = tuple(n // 2 for n in zyx)
+            nxt = tuple(n // f for n, f in zip(zyx, scale))
             d_next = eng.alloc(max(int(np.prod(nxt)) * 2, 16))
             bufs.append(d_next)
-            eng.downsample2(d_prev, d_next, zyx)
+            eng.downsample2(d_prev, d_next, zyx, scale)
             levels.append(d_next.download(nxt, np.uint16).reshape(lead + nxt))
             d_prev, zyx = d_next, nxt
     finally:
@@ -159,7 +199,8 @@ def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_leve
     The volume is streamed in z-slabs (a 34 GB channel does not fit one allocation, nor host RAM twice):
     a slab of ``2 * output z-chunk`` source planes is read, reduced by one ``dsx_downsample2_u16`` launch
     and written as whole output chunks; the 2 x 2 x 2 windows never straddle a slab because slabs start
-    at even planes.
+    at even planes.  ``scale_factor`` ``(fz, fy, fx)``, 1 or 2 each and not all 1, is the window of every level on
+    both routes (a slab is then ``fz * output z-chunk`` planes and level ``i`` is ``previous // factor`` per axis).
 
     ``pipelined=True``: the same arrays, chunk files and voxels from ONE software-pipelined pass over level 0
     (:class:`_PipelinedPyramid`): level 0 is read block by block on ``io_threads`` native threads straight into pinned
@@ -170,10 +211,11 @@ def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_leve
     Blosc-zstd uint16 output with byte shuffle, and ``pipelined``.  ``slab_planes`` is ignored then.
     :data:`LAST_PYRAMID` holds what the call did.
     """
-    _check_scale((1,) * 2 + tuple(scale_factor))
+    scale = check_scale_factor(scale_factor)
+    fz, fy, fx = scale
     if pipelined:
         return _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, device, device_codec, device_decode,
-                                io_threads)  # fmt: skip
+                                io_threads, scale)  # fmt: skip
     if device_codec is not False or device_decode is not False:
         raise ValueError("device_codec / device_decode need pipelined=True: the slab route of write_pyramid_levels has no "
                          "device codecs")  # fmt: skip
@@ -187,26 +229,26 @@ def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_leve
             if src.dtype != np.uint16 or any(n != 1 for n in src.shape[:-3]):
                 raise ValueError("the pyramid kernel takes uint16 volumes with singleton leading axes")
             Z, Y, X = src.shape[-3:]
-            if min(Z, Y, X) < 2:
+            if Z < fz or Y < fy or X < fx:
                 break
-            out_zyx = (Z // 2, Y // 2, X // 2)
+            out_zyx = (Z // fz, Y // fy, X // fx)
             lead = src.shape[:-3]
             out_shape = lead + out_zyx
             ck = tuple(min(c, n) for c, n in zip(tuple(chunks)[-len(out_shape):], out_shape))
             dst = MiniZarrArray.create(os.path.join(group_path, str(i)), out_shape, ck, np.uint16,
                                        compressor=compressor, dimension_separator="/")  # fmt: skip
-            slab = int(slab_planes) if slab_planes else 2 * ck[-3]
-            slab += slab & 1
+            slab = int(slab_planes) if slab_planes else fz * ck[-3]
+            slab += -slab % fz
             d_src = eng.alloc(slab * Y * X * 2)
-            d_dst = eng.alloc(max((slab // 2) * out_zyx[1] * out_zyx[2] * 2, 16))
+            d_dst = eng.alloc(max((slab // fz) * out_zyx[1] * out_zyx[2] * 2, 16))
             try:
                 lead_idx = (0,) * len(lead)
-                for z in range(0, 2 * out_zyx[0], slab):
-                    n = min(slab, 2 * out_zyx[0] - z)  # even: an odd trailing plane is cropped
+                for z in range(0, fz * out_zyx[0], slab):
+                    n = min(slab, fz * out_zyx[0] - z)  # whole windows: an odd trailing plane is cropped
                     d_src.upload(src[lead_idx + (slice(z, z + n),)])
-                    eng.downsample2(d_src, d_dst, (n, Y, X))
-                    out = d_dst.download((n // 2,) + out_zyx[1:], np.uint16)
-                    dst[lead_idx + (slice(z // 2, z // 2 + n // 2),)] = out
+                    eng.downsample2(d_src, d_dst, (n, Y, X), scale)
+                    out = d_dst.download((n // fz,) + out_zyx[1:], np.uint16)
+                    dst[lead_idx + (slice(z // fz, z // fz + n // fz),)] = out
             finally:
                 d_src.free()
                 d_dst.free()
@@ -216,13 +258,13 @@ def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_leve
         eng.close()
     LAST_PYRAMID.clear()
     LAST_PYRAMID.update(route="slabs", block_z=None, levels=list(range(1, len(shapes) + 1)), decode_routes=None, read_s=None,
-                        write_s=None, upload_bytes=None, download_bytes=None, seconds=time.perf_counter() - t_start)  # fmt: skip
+                        scale=scale, write_s=None, upload_bytes=None, download_bytes=None, seconds=time.perf_counter() - t_start)  # fmt: skip
     return shapes
 
 
 # ---- the stand-alone pyramid in one pipelined pass (write_pyramid_levels(pipelined=True)) ----------------------------
 # What the last write_pyramid_levels call of this process did: route ("pipelined" / "slabs"), block_z, levels,
-# decode_routes ({"device", "host", "fill"}: level-0 chunks by where they were decoded), read_s / write_s (time inside
+# scale ((fz, fy, fx)), decode_routes ({"device", "host", "fill"}: level-0 chunks by where they were decoded), read_s / write_s (time inside
 # the I/O stages), upload_bytes / download_bytes over the host link, seconds.  The slab route fills route, levels, seconds.
 LAST_PYRAMID = {}
 
@@ -256,8 +298,9 @@ class _PipelinedPyramid:
 
     N_BUF = 2
 
-    def __init__(self, eng, src, levels, arrays, block_z, io_threads, codec_mode=None, decode_mode=None):
+    def __init__(self, eng, src, levels, arrays, block_z, io_threads, codec_mode=None, decode_mode=None, scale=(2, 2, 2)):
         self.eng, self.src, self.levels, self.arrays, self.block_z = eng, src, levels, arrays, int(block_z)
+        self.scale = tuple(scale)
         self.codec_mode, self.decode_mode, self.io_threads = codec_mode, decode_mode, int(io_threads)
         self.zyx = tuple(int(n) for n in src.shape[-3:])
         self.ci = tuple(int(c) for c in src.chunks[-3:])
@@ -300,7 +343,7 @@ class _PipelinedPyramid:
                 self.offsets.append([self._host(8 * (ny * nx + 1)).array((ny * nx + 1,), np.int64) for _ in R])
             else:
                 self.stage_row.append([self._host(ny * nx * brick * 2).array((ny, nx, brick), np.uint16) for _ in R])
-        work = _engine.pyramid_work_bytes((self.block_z, H, W), len(levels) + 1)
+        work = _engine.pyramid_work_bytes((self.block_z, H, W), len(levels) + 1, self.scale)
         self.d_work = self._dev(work) if work else None
         self.cur, self.flushes = [0] * len(levels), [[] for _ in R]
         self.timing = {"read_s": 0.0, "write_s": 0.0, "upload_bytes": 0, "download_bytes": 0,
@@ -409,7 +452,8 @@ class _PipelinedPyramid:
         eng.stream_wait(C, D)  # (lands before the kernel:) after the downloads enqueued so far
         eng.pyramid_bricks(self.d_src[k], (z1 - z0, H, W), self.ci, [lv.chunks for lv in self.levels],
                            [self.d_row[i][cur[i]] for i in range(len(shares))], z0s=[s.offset for s in shares],
-                           zero=[s.first for s in shares], rows=[1] * len(shares), d_work=self.d_work)  # fmt: skip
+                           zero=[s.first for s in shares], rows=[1] * len(shares), d_work=self.d_work,
+                           **({} if self.scale == (2, 2, 2) else {"scale": self.scale}))  # (the default: the call as it always was)
         flushes = []
         for i, s in enumerate(shares):
             if not s.flush:
@@ -468,7 +512,7 @@ class _PipelinedPyramid:
 
     def run(self):
         """All blocks of level 0 through the pipeline; returns the number of blocks."""
-        sched = fused_schedule(self.levels, 0, self.zyx[0], self.block_z)
+        sched = fused_schedule(self.levels, 0, self.zyx[0], self.block_z, self.scale)
         nb, N = len(sched), self.N_BUF
         self.cur = [0] * len(self.levels)
         reader = ThreadPoolExecutor(max_workers=1)  # stage drivers: one read and one write in flight,
@@ -499,7 +543,8 @@ class _PipelinedPyramid:
         return nb
 
 
-def _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, device, device_codec, device_decode, io_threads):
+def _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, device, device_codec, device_decode, io_threads,
+                     scale=(2, 2, 2)):  # fmt: skip
     from . import zarr_destriper as zd
 
     t_start = time.perf_counter()
@@ -511,8 +556,8 @@ def _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, devi
     if decode_mode is not None and not zd.device_decode_input_ok(src, decode_mode):
         raise ValueError("device_decode needs a Blosc uint16 input, not {!r} {}".format(src.compressor, src.dtype))
     zyx, lead = tuple(src.shape[-3:]), tuple(src.shape[:-3])
-    levels = fused_levels(zyx, chunks, n_levels)
-    block_z = pipelined_block_z(src.chunks[-3], levels) if levels else None
+    levels = fused_levels(zyx, chunks, n_levels, scale)
+    block_z = pipelined_block_z(src.chunks[-3], levels, scale) if levels else None
     arrays, shapes = [], []
     for lv in levels:  # created as the slab route creates them
         out_shape = lead + lv.shape
@@ -529,13 +574,13 @@ def _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, devi
     if io_threads is None:
         io_threads = zd.default_io_threads(1)
     LAST_PYRAMID.clear()
-    LAST_PYRAMID.update(route="pipelined", block_z=block_z, levels=[lv.level for lv in levels], decode_routes=None,
+    LAST_PYRAMID.update(route="pipelined", block_z=block_z, levels=[lv.level for lv in levels], decode_routes=None, scale=scale,
                         read_s=0.0, write_s=0.0, upload_bytes=0, download_bytes=0, seconds=None)  # fmt: skip
     if levels:
         eng = _engine.DestripeEngine(device)
         pipe = None
         try:
-            pipe = _PipelinedPyramid(eng, src, levels, arrays, block_z, io_threads, codec_mode, decode_mode)
+            pipe = _PipelinedPyramid(eng, src, levels, arrays, block_z, io_threads, codec_mode, decode_mode, scale)
             try:
                 pipe.run()
             finally:

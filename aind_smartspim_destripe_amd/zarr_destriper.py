@@ -320,7 +320,9 @@ class _DeviceBlocks:
 
     N_BUF = 2
 
-    def __init__(self, eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False, pyr=None):
+    def __init__(self, eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False, pyr=None,
+                 pyr_scale=(2, 2, 2)):  # fmt: skip
+        self.pyr_scale = tuple(pyr_scale)
         self.eng, self.src, self.dst, self.zyx, self.block_z = eng, src, dst, zyx, block_z
         self.pyr_levels, self.pyr_arrays = pyr if pyr else ([], [])
         self.ci, self.co = tuple(src.chunks[-3:]), tuple(dst.chunks[-3:])
@@ -394,7 +396,7 @@ class _DeviceBlocks:
             else:
                 self.h_row.append([eng.alloc_host(row_bytes) for _ in range(self.N_BUF)])
                 self.stage_row.append([h.array((ny, nx, brick), np.uint16) for h in self.h_row[-1]])
-        work = engine_mod.pyramid_work_bytes((block_z, H, W), len(self.pyr_levels) + 1) if self.pyr_levels else 0
+        work = engine_mod.pyramid_work_bytes((block_z, H, W), len(self.pyr_levels) + 1, self.pyr_scale) if self.pyr_levels else 0
         self.d_work = eng.alloc(work) if work else None
         if self.pyr_levels:
             self.pyr_bufs = [b for per_level in (self.d_row + self.h_row + self.d_pframes + self.d_poffsets + self.h_pframes
@@ -562,7 +564,8 @@ class _DeviceBlocks:
         cur = self.pyr_cur
         eng.pyramid_block(self.d_out, (z1 - z0, H, W), [lv.chunks for lv in self.pyr_levels],
                           [self.d_row[i][cur[i]] for i in range(len(shares))], z0s=[s.offset for s in shares],
-                          zero=[s.first for s in shares], rows=[1] * len(shares), d_work=self.d_work)  # fmt: skip
+                          zero=[s.first for s in shares], rows=[1] * len(shares), d_work=self.d_work,
+                          **({} if self.pyr_scale == (2, 2, 2) else {"scale": self.pyr_scale}))  # fmt: skip
         flushes = []
         for i, (s, lv) in enumerate(zip(shares, self.pyr_levels)):
             if not s.flush:
@@ -614,7 +617,7 @@ class _DeviceBlocks:
         if self.pyr_levels:
             from . import pyramid
 
-            self.pyr_schedule = dict(pyramid.fused_schedule(self.pyr_levels, z_start, z_stop, self.block_z))
+            self.pyr_schedule = dict(pyramid.fused_schedule(self.pyr_levels, z_start, z_stop, self.block_z, self.pyr_scale))
             self.pyr_cur = [0] * len(self.pyr_levels)
         reader = ThreadPoolExecutor(max_workers=1)   # stage drivers: one read and one write in flight,
         writer = ThreadPoolExecutor(max_workers=1)   # each fanning its chunks out over the I/O pool
@@ -733,12 +736,14 @@ def device_decode_mode(device_decode):
     return "zstd" if device_decode else None
 
 
-def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False, pyr=None):
+def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False, device_decode=False, pyr=None,
+                   pyr_scale=(2, 2, 2)):  # fmt: skip
     """Staging buffers for this geometry, reused from the previous tile when nothing but the stores changed
     (a channel is tens of tiles of one shape, ``zarr_destriper.py:1231``)."""
     key = (id(eng), tuple(zyx[1:]), tuple(src.chunks[-3:]), tuple(dst.chunks[-3:]), int(block_z),
            output_codec_mode(device_codec, dst),  # (a zstd and an LZ4 output of one geometry differ here only)
-           device_decode_mode(device_decode), tuple((lv.level, lv.shape[1:], lv.chunks) for lv in (pyr[0] if pyr else ())))  # fmt: skip
+           device_decode_mode(device_decode), tuple((lv.level, lv.shape[1:], lv.chunks) for lv in (pyr[0] if pyr else ())),
+           tuple(pyr_scale) if pyr else None)  # fmt: skip
     cached = _BLOCKS.get("blocks")
     if cached is not None and cached[0] == key and cached[1].eng._ctx is not None:
         blocks = cached[1]
@@ -751,7 +756,7 @@ def _device_blocks(eng, src, dst, zyx, block_z, io_threads, device_codec=False, 
             cached[1].close()
         except Exception:  # the engine of the cached buffers may be gone already
             pass
-    blocks = _DeviceBlocks(eng, src, dst, zyx, block_z, io_threads, device_codec, device_decode, pyr)
+    blocks = _DeviceBlocks(eng, src, dst, zyx, block_z, io_threads, device_codec, device_decode, pyr, pyr_scale)
     _BLOCKS["blocks"] = (key, blocks)
     return blocks
 
@@ -799,6 +804,7 @@ def destripe_zarr_store(
     device_decode=False,
     pyramid_group=None,
     n_levels=1,
+    scale_factor=(2, 2, 2),
     streaks=None,
     histogram=None,
     rotate=False,
@@ -866,7 +872,11 @@ def destripe_zarr_store(
     range, which is then aligned to one chunk row of the deepest level (``output z chunk << (levels written - 1)``).
     Needs the device re-tiling path and z blocks that hold whole 2 x 2 x 2 windows of every level and fill whole chunk
     rows; anything else raises ``ValueError``.  Works with ``device_codec`` / ``device_decode`` on or off and with raw,
-    zlib and Blosc outputs.
+    zlib and Blosc outputs.  ``scale_factor`` ``(fz, fy, fx)``, 1 or 2 each and not all 1, is the window of the levels
+    (an anisotropic volume reduces only its fine axes, e.g. ``(1, 2, 2)``); the z range of a rank is aligned to
+    ``output z chunk * fz ** (levels written)`` planes, the plain output z chunk when z is not reduced, and z blocks hold
+    whole ``fz``-windows of every level.  Anything else raises ``ValueError`` before anything is created.
+    ``LAST_RUN["pyramid_scale"]`` is the scale of the levels written, ``None`` without a pyramid.
 
     ``streaks``: a dict ``{"sigma": (fg, bg), "level": 0, "wavelet": "db3", "crossover": 10, "threshold": -1,
     "route": "auto"}`` (defaults as in ``filtering.filter_streaks``; an unknown key raises ``TypeError``; a member of
@@ -907,6 +917,7 @@ def destripe_zarr_store(
     from . import pyramid
 
     rotate = engine_mod.rotate_flag(rotate)
+    scale = pyramid.check_scale_factor(scale_factor)
 
     logger = logger or logging.getLogger("dsx.zarr")
     if histogram is not None and not (isinstance(histogram, np.ndarray) and histogram.dtype == np.int64
@@ -936,7 +947,7 @@ def destripe_zarr_store(
     out_shape = (1,) * (5 - len(src.shape)) + tuple(src.shape)
     out_chunks = tuple(output_chunks)[-len(out_shape):]
     fused = pyramid_group is not None and int(n_levels) > 1
-    levels = pyramid.fused_levels(zyx, out_chunks, n_levels) if fused else []
+    levels = pyramid.fused_levels(zyx, out_chunks, n_levels, scale) if fused else []
     lead = out_shape[:-3]
     level_arrays = [(os.path.join(str(pyramid_group), str(lv.level)), lead + lv.shape, (1,) * len(lead) + lv.chunks)
                     for lv in levels]  # fmt: skip
@@ -960,7 +971,7 @@ def destripe_zarr_store(
     dst = open_created(output_path, out_shape, out_chunks)
     pyr_arrays = [open_created(*a) for a in level_arrays]
     if levels:  # every chunk of every level written by one rank: shards of whole chunk rows of the deepest level
-        z0, z1 = pyramid.fused_z_range(zyx[0], world_size, rank, output_chunks[-3], levels)
+        z0, z1 = pyramid.fused_z_range(zyx[0], world_size, rank, output_chunks[-3], levels, scale)
     else:
         z0, z1 = z_shard(zyx[0], world_size, rank, z_chunk=output_chunks[-3])
     dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device
@@ -993,7 +1004,8 @@ def destripe_zarr_store(
         if not can or device_retile is False:
             raise ValueError("fused_pyramid needs the device re-tiling path (a uint16 store, even planes and "
                              "output-chunk-aligned z blocks)")  # fmt: skip
-        pyramid.fused_check_blocks(levels, block_z)
+        pyramid.fused_check_blocks(levels, block_z, scale)
+    LAST_RUN.update(pyramid_scale=scale if levels else None)
     LAST_RUN.update(device_codec=device_codec, device_codec_mode=codec_mode, device_decode=bool(device_decode),
                     device_decode_mode=decode_mode, decode_routes=None, fused_pyramid=bool(levels), pyramid_levels=[lv.level for lv in levels])  # fmt: skip
     LAST_RUN["histogram_voxels"] = None if histogram is None else 0
@@ -1012,7 +1024,7 @@ def destripe_zarr_store(
             eng = fl.get_engine(zyx[1:], cells_config, no_cells_config, 2500, flatfield, darkfield,
                                 max_batch=min(block_z, 64), device=dev, rotate=rotate)  # fmt: skip
         blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, "runs" if codec_mode == "runs" else device_codec,
-                                device_decode, (levels, pyr_arrays) if levels else None)  # fmt: skip
+                                device_decode, (levels, pyr_arrays) if levels else None, scale)  # fmt: skip
         blocks.histogram = histogram is not None
         if histogram is not None:
             eng.volhist_reset()
@@ -1426,10 +1438,15 @@ def compute_multiscale(
     ``device_decode`` / ``device_codec`` (as in :func:`destripe_zarr_store`: ``False``, ``True``, ``"any"``, ``"full"`` / ``"runs"``)
     then decode level 0 and encode the levels on the GPU; without ``pipelined`` they raise ``ValueError``.
     ``pyramid.LAST_PYRAMID`` holds what the call did.
+
+    ``scale_factor`` ``(fz, fy, fx)``: 1 or 2 per axis, not all 1 -- ``[2, 2, 2]`` in production (``:1176``), e.g.
+    ``[1, 2, 2]`` for a volume whose z step is coarser than its pixel; level ``l`` is ``previous // factor`` per axis.
+    Every route takes it; anything else raises ``ValueError`` before anything is written.
     """
     from . import pyramid
 
     del n_workers, threads_per_worker
+    pyramid.check_scale_factor(scale_factor)  # (a scale the kernels do not take fails before anything is written)
     window = _check_ome_options(ome_metadata, display_window, histogram, voxel_size, image_name)
     level0 = getattr(output_zarr, "path", output_zarr)
     group_path = getattr(zarr_group, "path", zarr_group)
@@ -1479,6 +1496,7 @@ def destripe_zarr(
     display_window=None,
     rotate=False,
     lightsheet=None,
+    scale_factor=None,
 ):
     """``destripe_zarr`` of the reference (``zarr_destriper.py:909-1211``) with its 14 parameters, on the GPU chunk map.
 
@@ -1523,10 +1541,16 @@ def destripe_zarr(
     :func:`destripe_zarr_store`; a bool, ``TypeError`` before anything is created otherwise), ``lightsheet`` (the dict
     of :func:`destripe_zarr_store`: the light-sheet background mode instead of the stripe filter; ``parameters`` need no
     configs then; together with ``streaks``, a ``flatfield`` or a derivatives folder that exists it raises
-    ``ValueError`` before anything is created -- the mode has no dark / flat step).
+    ``ValueError`` before anything is created -- the mode has no dark / flat step), ``scale_factor`` (``(fz, fy, fx)`` of
+    the pyramid, 1 or 2 each and not all 1; ``None`` = the reference's ``[2, 2, 2]``, ``:1176``; it goes to the fused
+    route, to rank 0's :func:`compute_multiscale` and to the metadata; anything else raises ``ValueError`` before
+    anything is created.  ``LAST_RUN["pyramid_scale"]`` is the scale used).
     Returns ``(planes processed by this rank, seconds)``.
     """
+    from . import pyramid
+
     rotate = engine_mod.rotate_flag(rotate)
+    scale_factor = list(pyramid.check_scale_factor([2, 2, 2] if scale_factor is None else scale_factor))
     output_codec_mode(device_codec, compressor)  # (a wrong string or mode fails before anything is written)
     device_decode_mode(device_decode)
     if fused_pyramid and pipelined_pyramid:
@@ -1605,11 +1629,6 @@ def destripe_zarr(
         # flatfield_correction dereferences the dark plane (filtering.py:371-377): nothing to correct with
         raise ValueError(f"No darkfield for the shading correction: {derivatives_path} does not exist")
     level0 = output_destriped_zarr.joinpath("0")
-    scale_factor = [2, 2, 2]
-    if fused_pyramid:
-        from . import pyramid
-
-        pyramid._check_scale([1, 1] + scale_factor)
     n_planes, seconds = destripe_zarr_store(
         str(src),
         str(level0),
@@ -1631,6 +1650,7 @@ def destripe_zarr(
         device_decode=device_decode,
         pyramid_group=str(output_destriped_zarr) if fused_pyramid else None,
         n_levels=n_levels if fused_pyramid else 1,
+        scale_factor=scale_factor,
         streaks=streaks,
         histogram=histogram,
         rotate=rotate,
@@ -1650,6 +1670,7 @@ def destripe_zarr(
     elif ome_metadata:
         ome_kw = dict(ome_metadata=True, display_window=display_window)
     LAST_RUN["display_window"] = window
+    LAST_RUN["pyramid_scale"] = tuple(scale_factor) if n_levels > 1 else None
     if rank == 0 and ome_metadata and (fused_pyramid or n_levels <= 1):  # compute_multiscale is not called: the same file
         _write_group_metadata(str(output_destriped_zarr), str(level0), dataset_name, n_levels, scale_factor, voxel_size,
                               window)  # fmt: skip
@@ -1711,6 +1732,7 @@ def destripe_channel(
     display_window=None,
     streaks=None,
     rotate=False,
+    scale_factor=None,
 ):
     """``destripe_channel`` of the reference (``zarr_destriper.py:1214-1267``), same eight parameters (the reference's
     caller passes them by keyword, ``run_capsule.py:394-403``), wired to the GPU chunk map.
@@ -1732,9 +1754,14 @@ def destripe_channel(
     ``streaks``: the dict of :func:`destripe_zarr_store`, handed to every tile's :func:`destripe_zarr`.  Every tile
     comes with its retrospective flat here, so the dict must say ``"shading": True`` (``ValueError`` before anything is
     created otherwise).  ``rotate``: vertical stripes, handed to every tile's :func:`destripe_zarr` (a bool,
-    ``TypeError`` before anything is created otherwise).
+    ``TypeError`` before anything is created otherwise).  ``scale_factor``: the pyramid's ``(fz, fy, fx)``, handed to
+    every tile's :func:`destripe_zarr` (``None`` = ``[2, 2, 2]``; ``ValueError`` before anything is created otherwise).
     """
+    from . import pyramid
+
     rotate = engine_mod.rotate_flag(rotate)
+    if scale_factor is not None:
+        pyramid.check_scale_factor(scale_factor)
     if world_size > 1 and group is None:
         raise ValueError("destripe_channel with world_size > 1 needs a group to order the pyramid after all ranks")
     if streaks is not None and not fl.streaks_options(streaks).get("shading"):
@@ -1801,6 +1828,7 @@ def destripe_channel(
             display_window=display_window,
             streaks=streaks,
             rotate=rotate,
+            scale_factor=scale_factor,
         )
         done[tile_path.name] = n
     return done

@@ -235,6 +235,26 @@ int dsx_pyramid_bricks_u16(dsx_ctx* ctx, const void* d_src_bricks, int Z, int H,
                            void* d_work, size_t work_bytes);
 int dsx_pyramid_bricks_ref(const void* src_bricks, int Z, int H, int W, int src_cz, int src_cy, int src_cx,
                            int n_levels, const dsx_pyramid_level* levels, void* const* bricks);
+/* The same calls with a scale factor per axis (compute_pyramid(scale_axis=...), compute_multiscale(scale_factor=...),
+ * zarr_destriper.py:365-407, 677-794), for anisotropic volumes: fz, fy, fx are 1 or 2 each and not all 1, anything else
+ * is DSX_EINVAL.  Level l has the extent of level l - 1 divided by the factor per axis (trailing voxels cropped), every
+ * voxel floor(sum of the fz x fy x fx window of the TRUNCATED previous level / (fz fy fx)); an axis with factor 1 keeps
+ * its extent.  A block's plane 0 lies at a multiple of fz^(n_levels - 1).  With (2, 2, 2) each call IS the one above.
+ * With any other scale every level is one kernel from the dense previous level, so d_work holds the dense levels
+ * 1 .. n_levels - 2 (dsx_pyramid_work_bytes_scale) and is needed from two levels on; more than 65535 rows or planes of
+ * a level is DSX_ELIMIT.  dsx_downsample_u16: one dense level, [Z,Y,X] -> [Z/fz,Y/fy,X/fx]. */
+int dsx_downsample_u16(dsx_ctx* ctx, const void* d_src, void* d_dst, int Z, int Y, int X, int fz, int fy, int fx);
+int dsx_pyramid_work_bytes_scale(int Z, int H, int W, int fz, int fy, int fx, int n_levels, size_t* bytes);
+int dsx_pyramid_block_scale_u16(dsx_ctx* ctx, const void* d_planes, int Z, int H, int W, int fz, int fy, int fx,
+                                int n_levels, const dsx_pyramid_level* levels, void* const* d_bricks, void* d_work,
+                                size_t work_bytes);
+int dsx_pyramid_block_scale_ref(const void* planes, int Z, int H, int W, int fz, int fy, int fx, int n_levels,
+                                const dsx_pyramid_level* levels, void* const* bricks);
+int dsx_pyramid_bricks_scale_u16(dsx_ctx* ctx, const void* d_src_bricks, int Z, int H, int W, int src_cz, int src_cy,
+                                 int src_cx, int fz, int fy, int fx, int n_levels, const dsx_pyramid_level* levels,
+                                 void* const* d_bricks, void* d_work, size_t work_bytes);
+int dsx_pyramid_bricks_scale_ref(const void* src_bricks, int Z, int H, int W, int src_cz, int src_cy, int src_cx, int fz,
+                                 int fy, int fx, int n_levels, const dsx_pyramid_level* levels, void* const* bricks);
 
 /* Exact histogram of the uint16 voxels a pass writes, for the display window of the OME-NGFF metadata: the reference
  * says the window should be da.percentile(image_data, (0.1, 95)) and hard-codes (0.0, 350.0) because of the cost

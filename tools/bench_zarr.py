@@ -6,7 +6,7 @@ download) into another store.  Prints one JSON line; the roofline of this path i
 
     bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode|device-decode-any|device-decode-all]
                   [lz4|blosc-zlib|blosc-blosclz|plain-zlib] [pyramid|fused-pyramid|pipelined-pyramid] [lz4-out] [read-back]
-                  [streaks|streaks-generic|streaks-march] [ome-percentile]
+                  [streaks|streaks-generic|streaks-march] [ome-percentile] [scale-FZ-FY-FX]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
 line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
@@ -35,6 +35,8 @@ the same route, bit for bit (no CPU oracle pass).
 (destripe_zarr_store(histogram=...)), takes the display window from the counts (display_window_from_histogram) and, with
 a pyramid word (the output is then a group), writes .zgroup / .zattrs (write_ome_ngff_metadata), all inside the timed
 seconds; the line reports the window and the voxels counted under "ome", and a count other than N * 2048 * 2048 fails the run.
+`scale-FZ-FY-FX` (with a pyramid word): the pyramid's scale factor per axis, 1 or 2 each, e.g. `scale-1-2-2` for a volume
+whose z step is coarser than its pixel (scale_factor of destripe_zarr_store / compute_multiscale); the default is 2-2-2.
 `pyramid`: after the timed level-0 pass, compute_multiscale(n_levels=3) on the store is timed too (the two-pass route);
 `fused-pyramid`: level 0 and levels 1-2 in one destripe_zarr_store call (pyramid_group / n_levels);
 `pipelined-pyramid`: level 0 is timed as without a pyramid word, then compute_multiscale(pipelined=True, n_levels=3) with the
@@ -62,6 +64,7 @@ lz4_out, read_back = "lz4-out" in sys.argv[3:], "read-back" in sys.argv[3:]
 streaks = ([{"sigma": (64.0, 128.0), "route": r} for w, r in (("streaks", "auto"), ("streaks-generic", "generic"),
                                                                ("streaks-march", "march")) if w in sys.argv[3:]] + [None])[0]
 ome = "ome-percentile" in sys.argv[3:]
+scale = ([[int(f) for f in w.split("-")[1:]] for w in sys.argv[3:] if w.startswith("scale-")] + [[2, 2, 2]])[0]
 if (lz4_out or read_back) and codec != "blosc":
     sys.exit("lz4-out / read-back: a Blosc store")
 out_codec = {"id": "blosc", "cname": "lz4", "clevel": 5, "shuffle": 1, "blocksize": 0} if lz4_out else codec
@@ -110,7 +113,7 @@ try:
     res = {}
     group = os.path.join(root, "out.zarr")
     level0 = os.path.join(group, "0") if two_pass or fused or pipelined else group
-    for name, kw in (("overlapped", {"pyramid_group": group, "n_levels": 3} if fused else {}),):
+    for name, kw in (("overlapped", {"pyramid_group": group, "n_levels": 3, "scale_factor": scale} if fused else {}),):
         for rep in range(2):  # second pass: plan + pinned buffers exist, page cache warm
             t0 = time.perf_counter()
             hist = np.zeros(65536, np.int64) if ome else None
@@ -122,7 +125,7 @@ try:
             if ome:
                 window = zd.display_window_from_histogram(hist)
                 if level0 != group:
-                    zd.write_ome_ngff_metadata(group, MiniZarrArray.open(level0), "bench", 3, [2, 2, 2], [2.0, 1.8, 1.8],
+                    zd.write_ome_ngff_metadata(group, MiniZarrArray.open(level0), "bench", 3, scale, [2.0, 1.8, 1.8],
                                                channel_names=["bench"], channel_colors=[zd.REFERENCE_CHANNEL_COLOR],
                                                channel_minmax=[(0, 65535)], channel_startend=[window])
             res[name] = {"planes": planes, "seconds": round(time.perf_counter() - t0, 3)}
@@ -143,16 +146,16 @@ try:
         if pipelined:  # one pipelined device pass over the finished level 0 (compute_multiscale(pipelined=True))
             from aind_smartspim_destripe_amd import pyramid
             t0 = time.perf_counter()
-            zd.compute_multiscale(level0, group, [2, 2, 2], 1, None, "bench", n_levels=3, compressor=out_codec, device=0,
+            zd.compute_multiscale(level0, group, scale, 1, None, "bench", n_levels=3, compressor=out_codec, device=0,
                                   pipelined=True, device_codec=device_codec, io_threads=16,
                                   device_decode=device_decode if codec == "blosc" else False)
             pyramid_s = time.perf_counter() - t0
             pyr["pipelined"] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in pyramid.LAST_PYRAMID.items()}
         if two_pass:  # the route destripe_zarr takes by default: rank 0 reads level 0 back and writes the levels
             t0 = time.perf_counter()
-            zd.compute_multiscale(level0, group, [2, 2, 2], 1, None, "bench", n_levels=3, compressor=out_codec, device=0)
+            zd.compute_multiscale(level0, group, scale, 1, None, "bench", n_levels=3, compressor=out_codec, device=0)
             pyramid_s = time.perf_counter() - t0
-        pyr = {**pyr, "route": "fused" if fused else ("pipelined" if pipelined else "two-pass"), "level0_s": round(secs, 3), "pyramid_s": round(pyramid_s, 3),
+        pyr = {**pyr, "scale": scale, "route": "fused" if fused else ("pipelined" if pipelined else "two-pass"), "level0_s": round(secs, 3), "pyramid_s": round(pyramid_s, 3),
                "total_s": round(secs + pyramid_s, 3), "pyramid_download_bytes": int(timing["pyramid_download_bytes"])}
     up, down = int(timing["upload_bytes"]), int(timing["download_bytes"])
     link = {"upload_bytes": up, "download_bytes": down,
@@ -183,11 +186,11 @@ try:
         shutil.rmtree(os.path.join(root, "back.zarr"), ignore_errors=True)
     if pyr:
         from oracle import format_oracle as fo
-        want = fo.pyramid(out[0, 0, 0:8], 3)
+        want = fo.pyramid(out[0, 0, 0:8], 3, scale)
         pyr["levels"], pyr["verified"] = {}, True
         for lvl in (1, 2):
             arr = MiniZarrArray.open(os.path.join(group, str(lvl)))
-            pyr["verified"] = pyr["verified"] and bool(np.array_equal(arr[0, 0, 0 : 8 >> lvl], want[lvl]))
+            pyr["verified"] = pyr["verified"] and bool(np.array_equal(arr[0, 0, 0 : want[lvl].shape[0]], want[lvl]))
             info = {"shape": list(arr.shape), "chunks": list(arr.chunks),
                     "bytes_written": sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(arr.path)
                                          for f in fs if not f.startswith("."))}
