@@ -28,6 +28,7 @@
 #include "dsx_rot90.h"
 #include "dsx_pyramid.h"
 #include "dsx_volhist.h"
+#include "dsx_project.h"
 #include "dsx_wavelet.h"
 #include "dsx_plan.h"
 #include "dsx_chain.h"
@@ -2081,6 +2082,70 @@ int dsx_volhist_ref(const void* vox, size_t n, uint64_t* hist) {
   if (!vox || !hist) return fail(nullptr, DSX_EINVAL, "volhist: NULL pointer");
   if ((uintptr_t)vox & 1) return fail(nullptr, DSX_EINVAL, "volhist: uint16 voxels must be 2-byte aligned");
   dsx::vh::volhist_host((const uint16_t*)vox, n, hist);
+  return DSX_OK;
+}
+
+/* ---- QC projections of the volume a pass reads and writes (dsx_project.h) ------------------------------------------ */
+namespace {
+// The argument rules both builds share; nullptr when the call may run.
+const char* project_args(const void* planes, int Z, int H, int W, const dsx_projection* p, int z_off, int* code) {
+  *code = DSX_EINVAL;
+  if (Z < 0 || H <= 0 || W <= 0 || z_off < 0) return "project: Z >= 0, H > 0, W > 0 and z_off >= 0";
+  if (H > dsx::pj::kPjMaxExtent || W > dsx::pj::kPjMaxExtent || Z > dsx::pj::kPjMaxExtent) {
+    *code = DSX_ELIMIT;
+    return "project: more than 65536 rows, columns or planes in one call";
+  }
+  if (Z == 0) return nullptr;
+  if (!planes || !p || !p->max_z || !p->sum_z || !p->max_y || !p->sum_y || !p->max_x || !p->sum_x)
+    return "project: NULL pointer";
+  if ((uintptr_t)planes & 1) return "project: uint16 voxels must be 2-byte aligned";
+  return nullptr;
+}
+}  // namespace
+
+int dsx_project_work_bytes(int Z, int H, int W, size_t* bytes) {
+  if (!bytes || Z < 0 || H <= 0 || W <= 0) return DSX_EINVAL;
+  if (H > dsx::pj::kPjMaxExtent || W > dsx::pj::kPjMaxExtent || Z > dsx::pj::kPjMaxExtent) return DSX_ELIMIT;
+  *bytes = dsx::pj::work_bytes(Z, H, W);
+  return DSX_OK;
+}
+
+int dsx_project_u16_device(dsx_ctx* ctx, const void* d_planes, int Z, int H, int W, const dsx_projection* p, int z_off,
+                           int first, void* d_work) {
+  namespace pj = dsx::pj;
+  if (!ctx) return DSX_EINVAL;
+  int code = 0;
+  if (const char* e = project_args(d_planes, Z, H, W, p, z_off, &code)) return fail(ctx, code, e);
+  if (Z == 0) return DSX_OK;
+  if (!d_work) return fail(ctx, DSX_EINVAL, "project: the work buffer is NULL (dsx_project_work_bytes)");
+  if ((uintptr_t)d_work & 3) return fail(ctx, DSX_EINVAL, "project: the work buffer must be 4-byte aligned");
+  const pj::Partials part = pj::partials(d_work, Z, H, W);
+  const int S = pj::strips(W), T = pj::tiles(H);
+  const bool vec = W % 8 == 0 && (((uintptr_t)d_planes | (uintptr_t)p->max_z | (uintptr_t)p->sum_z) & 15) == 0;
+  DSX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = use_main(ctx);
+  const dim3 grid((unsigned)S, (unsigned)T);
+  if (vec)
+    hipLaunchKernelGGL(pj::k_project_u16<true>, grid, dim3(pj::kPjThreads), 0, s, (const uint16_t*)d_planes, Z, H, W,
+                       p->max_z, (unsigned long long*)p->sum_z, first, part);
+  else
+    hipLaunchKernelGGL(pj::k_project_u16<false>, grid, dim3(pj::kPjThreads), 0, s, (const uint16_t*)d_planes, Z, H, W,
+                       p->max_z, (unsigned long long*)p->sum_z, first, part);
+  DSX_HIP(hipGetLastError());
+  const size_t n = (size_t)Z * ((size_t)W + H);
+  const unsigned fold = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)8 * ctx->cus);
+  hipLaunchKernelGGL(pj::k_project_fold, dim3(fold), dim3(256), 0, s, Z, H, W, S, T, part, p->max_y, p->sum_y, p->max_x,
+                     p->sum_x, z_off);
+  DSX_HIP(hipGetLastError());
+  return DSX_OK;
+}
+
+int dsx_project_u16_ref(const void* planes, int Z, int H, int W, const dsx_projection* p, int z_off, int first) {
+  int code = 0;
+  if (const char* e = project_args(planes, Z, H, W, p, z_off, &code)) return fail(nullptr, code, e);
+  if (Z == 0) return DSX_OK;
+  const dsx::pj::Outputs o = {p->max_z, p->sum_z, p->max_y, p->sum_y, p->max_x, p->sum_x};
+  dsx::pj::project_host((const uint16_t*)planes, Z, H, W, o, z_off, first != 0);
   return DSX_OK;
 }
 

@@ -285,6 +285,35 @@ class RankGroup:
             total += row.reshape(mine.shape)
         return total
 
+    def reduce_array(self, array, op):
+        """Element-wise ``"sum"`` or ``"max"`` of every rank's integer array (any integer dtype and shape, the same on
+        all ranks) on every rank, through the rendezvous directory whatever the transport, as :meth:`sum_counts` travels.
+        Integers in the array's own dtype: exact (a sum wraps as the dtype does; the callers' bounds keep it from that).
+        The projections of a tile (``projections.VolumeProjections.merge``) are some tens of MB per rank, once per tile.
+        One rank, or an inactive group, returns the input."""
+        if op not in ("sum", "max"):
+            raise ValueError("reduce_array: op is \"sum\" or \"max\", not {!r}".format(op))
+        mine = np.ascontiguousarray(array)
+        if mine.dtype.kind not in "iu":
+            raise ValueError("reduce_array takes integer arrays, not {}".format(mine.dtype))
+        if not self.active:
+            return mine
+        self._seq += 1
+        self.rdzv.put("ra.{}.{}".format(self._seq, self.rank), mine.tobytes())
+        total = None
+        for r in range(self.world):
+            raw = self.rdzv.get("ra.{}.{}".format(self._seq, r))
+            if len(raw) != mine.nbytes:
+                raise ValueError("reduce_array: rank {} sent {} bytes, this rank {}".format(r, len(raw), mine.nbytes))
+            row = np.frombuffer(raw, dtype=mine.dtype).reshape(mine.shape)
+            if total is None:
+                total = row.copy()
+            elif op == "sum":
+                total += row
+            else:
+                np.maximum(total, row, out=total)
+        return total
+
     def broadcast_array(self, array, dtype, shape, root=0):
         """A NumPy array held by ``root`` (``array`` is ignored elsewhere) -> a host copy on every rank.
 

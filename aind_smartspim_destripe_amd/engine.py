@@ -34,6 +34,11 @@ TASK_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<u4"), ("dst
 
 COMM_ID_BYTES = 128
 VOLHIST_BINS = 65536  # one bin per uint16 value (dsx_volhist_*)
+PROJECT_MAX_EXTENT = 65536  # rows, columns, and planes of one call (dsx_project_*: the uint32 sums)
+# the six projections of a uint16 volume [Z, H, W] (dsx_projection, in the order of its members): name, dtype, the two
+# axes of zyx that are left
+PROJECTION_ARRAYS = (("max_z", np.uint16, (1, 2)), ("sum_z", np.uint64, (1, 2)), ("max_y", np.uint16, (0, 2)),
+                     ("sum_y", np.uint32, (0, 2)), ("max_x", np.uint16, (0, 1)), ("sum_x", np.uint32, (0, 1)))  # fmt: skip
 _ERRORS = {-1: "DSX_EINVAL", -2: "DSX_ENOPLAN", -3: "DSX_EHIP", -4: "DSX_ENOMEM", -5: "DSX_ELIMIT",
            -6: "DSX_ECOMM", -7: "DSX_EIO", -8: "DSX_EVALUE"}  # fmt: skip
 
@@ -60,6 +65,7 @@ EXPORTED_SYMBOLS = [
     "dsx_downsample_u16", "dsx_pyramid_work_bytes_scale", "dsx_pyramid_block_scale_u16", "dsx_pyramid_block_scale_ref",
     "dsx_pyramid_bricks_scale_u16", "dsx_pyramid_bricks_scale_ref",
     "dsx_volhist_reset", "dsx_volhist_add_device", "dsx_volhist_get", "dsx_volhist_ref",
+    "dsx_project_work_bytes", "dsx_project_u16_device", "dsx_project_u16_ref",
     "dsx_plan_streaks_opts", "dsx_streaks_blend_ref",
     "dsx_set_rotate", "dsx_rot90_device", "dsx_rot90_ref",
     "dsx_plan_lightsheet", "dsx_lightsheet_ref", "dsx_get_lightsheet_planes",
@@ -121,6 +127,10 @@ class _StreaksOpts(ctypes.Structure):
 
 class _PyramidLevel(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("cz", "cy", "cx", "rows", "z0", "zero")]
+
+
+class _Projection(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in PROJECTION_ARRAYS]
 
 
 class _PlanInfo(ctypes.Structure):
@@ -263,6 +273,9 @@ def load_library(path=None):
     lib.dsx_volhist_add_device.argtypes = [vp, vp, ctypes.c_size_t]
     lib.dsx_volhist_get.argtypes = [vp, vp]
     lib.dsx_volhist_ref.argtypes = [vp, ctypes.c_size_t, vp]
+    lib.dsx_project_work_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    lib.dsx_project_u16_device.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(_Projection), i32, i32, vp]
+    lib.dsx_project_u16_ref.argtypes = [vp, i32, i32, i32, ctypes.POINTER(_Projection), i32, i32]
     f64 = ctypes.c_double
     lib.dsx_plan_lightsheet.argtypes = [vp, i32, i32, i32, f64, i32, i32, f64, vp, vp]
     lib.dsx_lightsheet_ref.argtypes = [vp, i32, i32, f64, i32, i32, f64, vp, vp, vp, vp, vp, i32]
@@ -972,6 +985,58 @@ class DestripeEngine:
         self._check(self._lib.dsx_volhist_get(self._ctx, out.ctypes.data_as(ctypes.c_void_p)))
         return out.astype(np.int64)
 
+    # -- QC projections of the volume a pass reads and writes --------------------------------------
+    def alloc_projection(self, zyx):
+        """Six zeroed device arrays for the projections of a ``zyx`` volume: ``{name: DeviceBuffer}`` for
+        :meth:`project` (``PROJECTION_ARRAYS``); the caller frees them."""
+        bufs = {}
+        for name, shape, dtype in projection_shapes(zyx):
+            bufs[name] = self.alloc(max(int(np.prod(shape)) * np.dtype(dtype).itemsize, 16))
+            bufs[name].upload(np.zeros(shape, dtype))
+        return bufs
+
+    def project(self, d_planes, zyx, bufs, z_off=0, first=True, d_work=None):
+        """Maximum and sum projections of the ``zyx[0]`` dense uint16 planes ``[H, W]`` at a :class:`DeviceBuffer` or a
+        device address, one read of them (``dsx_project_u16_device``): rows ``z_off .. z_off + Z - 1`` of the device
+        arrays ``max_y`` / ``sum_y`` ``[., W]`` and ``max_x`` / ``sum_x`` ``[., H]`` of ``bufs`` are written; ``max_z`` /
+        ``sum_z`` ``[H, W]`` are overwritten when ``first`` and combined otherwise.  ``d_work``:
+        :func:`project_work_bytes` bytes, reusable by the next call; without one the call allocates its own and waits.
+        More than 65 536 rows, columns or planes is a ``ValueError`` before any launch.  Asynchronous on the engine
+        stream."""
+        Z, H, W = _project_geometry(zyx)
+        z_off = int(z_off)
+        if z_off < 0:
+            raise ValueError("project: z_off must not be negative")
+        ptr = getattr(d_planes, "ptr", d_planes)
+        nbytes = getattr(d_planes, "nbytes", None)
+        assert nbytes is None or 2 * Z * H * W <= nbytes, "project: more voxels than the buffer holds"
+        for name, shape, dtype in projection_shapes((z_off + Z, H, W)):
+            assert bufs[name].nbytes >= int(np.prod(shape)) * np.dtype(dtype).itemsize, "project: {} is too small".format(name)
+        if Z == 0:
+            return
+        need = project_work_bytes((Z, H, W))
+        own = self.alloc(need) if d_work is None else None
+        work = own if d_work is None else d_work
+        assert work.nbytes >= need, "project: the work buffer is smaller than project_work_bytes"
+        table = _Projection(*[bufs[name].ptr for name, _, _ in PROJECTION_ARRAYS])
+        try:
+            rc = self._lib.dsx_project_u16_device(self._ctx, ctypes.c_void_p(ptr), Z, H, W, ctypes.byref(table), z_off,
+                                                  1 if first else 0, ctypes.c_void_p(work.ptr))  # fmt: skip
+            if rc in (-1, -5):
+                raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
+            self._check(rc)
+            if own is not None:
+                self.sync()
+        finally:
+            if own is not None:
+                own.free()
+
+    def projection_get(self, bufs, zyx):
+        """The six arrays of ``bufs`` (``zyx``: the volume they were allocated for) on the host, ``{name: array}``;
+        waits for the engine stream."""
+        self.sync()
+        return {name: bufs[name].download(shape, dtype) for name, shape, dtype in projection_shapes(zyx)}
+
     def foreground_background(self, image, cutoff, want_mask=True):
         """``(fore_mean, back_mean, mask uint8)`` of a host image (uint16 / float32, any shape)."""
         a = np.ascontiguousarray(image)
@@ -1133,6 +1198,65 @@ def volhist_ref(array, hist=None):
     if rc != 0:
         raise ValueError((lib.dsx_last_error(None) or b"volhist_ref failed").decode())
     return hist
+
+
+def _project_geometry(zyx):
+    try:
+        Z, H, W = (int(n) for n in zyx)
+    except (TypeError, ValueError):
+        raise ValueError("projections: zyx is (Z, H, W), not {!r}".format(zyx))
+    if Z < 0 or H <= 0 or W <= 0:
+        raise ValueError("projections: Z >= 0, H > 0 and W > 0, not {!r}".format(tuple(zyx)))
+    if max(Z, H, W) > PROJECT_MAX_EXTENT:
+        raise ValueError("projections: more than {} rows, columns or planes of one call ({!r}); the uint32 sums could "
+                         "overflow".format(PROJECT_MAX_EXTENT, tuple(zyx)))  # fmt: skip
+    return Z, H, W
+
+
+def projection_shapes(zyx):
+    """``(name, shape, dtype)`` of the six projections of a ``zyx`` volume, in the order of ``dsx_projection``."""
+    zyx = tuple(int(n) for n in zyx)
+    return [(name, (zyx[axes[0]], zyx[axes[1]]), np.dtype(dtype)) for name, dtype, axes in PROJECTION_ARRAYS]
+
+
+def project_work_bytes(zyx):
+    """Bytes of the work buffer :meth:`DestripeEngine.project` needs for one call of ``zyx`` (``dsx_project_work_bytes``)."""
+    Z, H, W = _project_geometry(zyx)
+    n = ctypes.c_size_t(0)
+    if load_library().dsx_project_work_bytes(Z, H, W, ctypes.byref(n)) != 0:
+        raise ValueError("project_work_bytes: bad geometry {}".format((Z, H, W)))
+    return int(n.value)
+
+
+def project_ref(planes, acc=None, z_off=0):
+    """Host build of the projections (``dsx_project_u16_ref``): ``planes`` is uint16 ``[Z, H, W]``.  Without ``acc`` the
+    six arrays of that volume are returned as ``{name: array}`` (``PROJECTION_ARRAYS``).  With ``acc`` (such a dict for a
+    volume of at least ``z_off + Z`` planes, zeros where nothing was added yet) the planes are rows ``z_off ..`` of it:
+    those rows of the y / x arrays are written, the z arrays are combined; ``acc`` is returned."""
+    lib = load_library()
+    a = np.ascontiguousarray(planes)
+    if a.dtype != np.uint16 or a.ndim != 3:
+        raise ValueError("the projections take a uint16 [Z, H, W] array, got {} {}".format(a.dtype, a.shape))
+    Z, H, W = _project_geometry(a.shape)
+    z_off = int(z_off)
+    if z_off < 0:
+        raise ValueError("project_ref: z_off must not be negative")
+    first = acc is None
+    if first:
+        if z_off:
+            raise ValueError("project_ref: z_off needs the arrays it counts in (acc)")
+        acc = {name: np.zeros(shape, dtype) for name, shape, dtype in projection_shapes(a.shape)}
+    else:
+        for name, shape, dtype in projection_shapes((z_off + Z, H, W)):
+            arr = acc.get(name) if isinstance(acc, dict) else None
+            if not (isinstance(arr, np.ndarray) and arr.dtype == dtype and arr.ndim == 2 and arr.shape[1] == shape[1]
+                    and (arr.shape[0] == H if name.endswith("_z") else arr.shape[0] >= shape[0]) and arr.flags["C_CONTIGUOUS"] and arr.flags["WRITEABLE"]):  # fmt: skip
+                raise ValueError("project_ref: acc[{!r}] must be a C-contiguous {} array of at least {}".format(name, dtype, shape))
+    table = _Projection(*[acc[name].ctypes.data for name, _, _ in PROJECTION_ARRAYS])
+    rc = lib.dsx_project_u16_ref(a.ctypes.data_as(ctypes.c_void_p), Z, H, W, ctypes.byref(table), z_off, 1 if first else 0)
+    if rc != 0:
+        raise ValueError((lib.dsx_last_error(None) or b"project_ref failed").decode())
+    return acc
 
 
 def streaks_blend_ref(x, f, b, t, crossover=10.0, bands="both", smoothing=0.0, flatfield=None, darkfield=None,

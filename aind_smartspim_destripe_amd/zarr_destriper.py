@@ -405,6 +405,9 @@ class _DeviceBlocks:
         self.io_threads = int(io_threads)
         self.timing = _new_timing()
         self.histogram = False  # destripe_zarr_store(histogram=...): count every block's filtered planes (volhist_add)
+        # destripe_zarr_store(projections=...): {"output" / "input": device arrays of the rank's z range}, its first
+        # plane and the work buffer of one block (eng.project); owned by the call, not by the cached buffers
+        self.proj, self.proj_z0, self.proj_work = None, 0, None
 
     def close(self):
         for b in (self.pyr_bufs + self.d_bricks_in + self.d_bricks_out + [self.d_planes, self.d_out] + self.h_in + self.h_out
@@ -520,6 +523,11 @@ class _DeviceBlocks:
         eng.run_device(self.d_planes, np.uint16, Z, self.d_out, np.uint16, None)
         if self.histogram:                # the block's real planes, where every later stage reads them
             eng.volhist_add(self.d_out, Z * H * W)
+        if self.proj is not None:         # one more read of the planes, into rows z0 - proj_z0 .. of the rank's arrays
+            for key, d in (("output", self.d_out), ("input", self.d_planes)):
+                if key in self.proj:
+                    eng.project(d, (Z, H, W), self.proj[key], z_off=z0 - self.proj_z0, first=z0 == self.proj_z0,
+                                d_work=self.proj_work)  # fmt: skip
 
     def _submit_out(self, z0, z1, k):
         """Compute(b) from planes_to_bricks on, and download(b): once pinned output buffer k has been written out."""
@@ -809,6 +817,7 @@ def destripe_zarr_store(
     histogram=None,
     rotate=False,
     lightsheet=None,
+    projections=None,
 ):
     """Chunk map of ``destripe_zarr`` (``zarr_destriper.py:909-1211``) over a Zarr-v2 directory store -- the engine-level
     form (explicit configs and ``shadow_correction``); :func:`destripe_zarr` is the entry point with the reference's
@@ -913,11 +922,23 @@ def destripe_zarr_store(
     the configs may be ``None``.  An unknown key raises ``TypeError``; a bad value, a ``streaks`` dict or a
     ``shadow_correction`` given with it, or an input that is not uint16 raise ``ValueError``, all before anything is
     created.  ``LAST_RUN["filter"]`` is ``"lightsheet"`` then.
+
+    ``projections``: a dict ``{"output": projections.VolumeProjections}`` or ``{"output": ..., "input": ...}``, built by
+    the caller for the array's full ``zyx`` like ``histogram``; the maximum and sum projections of this rank's planes
+    are added to it -- of the level-0 voxels it writes, and with ``"input"`` of the voxels it read (``projections.py``:
+    MIPs, and the row sums before and after the filter whose ratio is the stripe gain).  On the device path
+    ``dsx_project_u16_device`` runs right behind the filter on the planes where they lie, into device arrays of the
+    rank's z range that are downloaded once after the last block; the host path projects what it reads and what it
+    assigns (``dsx_project_u16_ref``).  No existing launch and no output byte changes.  ``LAST_RUN["projections"]`` is
+    ``None``, ``"output"`` or ``"both"``, ``LAST_RUN["projection_planes"]`` the planes added (``None`` without the
+    option).  A wrong key, type or shape and a store that is not uint16 raise ``ValueError`` before anything is created.
     """
+    from . import projections as proj_mod
     from . import pyramid
 
     rotate = engine_mod.rotate_flag(rotate)
     scale = pyramid.check_scale_factor(scale_factor)
+    proj_mode = proj_mod.check_store_option(projections)
 
     logger = logger or logging.getLogger("dsx.zarr")
     if histogram is not None and not (isinstance(histogram, np.ndarray) and histogram.dtype == np.int64
@@ -941,6 +962,10 @@ def destripe_zarr_store(
         raise ValueError("blocks must cover whole planes: the stripe filter is a per-plane operation")
     if lightsheet is not None and src.dtype != np.uint16:
         raise ValueError("lightsheet: the store must be uint16, not {}".format(src.dtype))
+    if proj_mode is not None:
+        proj_mod.check_store_option(projections, zyx)
+        if src.dtype != np.uint16:
+            raise ValueError("projections: the store must be uint16, not {}".format(src.dtype))
     if streaks is not None:  # ("march" on an odd plane or another wavelet fails here, before anything is created)
         streaks["route"] = engine_mod.streaks_route(streaks["route"], zyx[1], zyx[2], streaks["wavelet"],
                                                     streaks["level"])  # fmt: skip
@@ -1009,6 +1034,7 @@ def destripe_zarr_store(
     LAST_RUN.update(device_codec=device_codec, device_codec_mode=codec_mode, device_decode=bool(device_decode),
                     device_decode_mode=decode_mode, decode_routes=None, fused_pyramid=bool(levels), pyramid_levels=[lv.level for lv in levels])  # fmt: skip
     LAST_RUN["histogram_voxels"] = None if histogram is None else 0
+    LAST_RUN.update(projections=proj_mode, projection_planes=None if proj_mode is None else 0)
     if can and device_retile is not False:
         if lightsheet is not None:
             eng = fl._lightsheet_engine(zyx[1:], lightsheet["percentile"], lightsheet["artifact_length"],
@@ -1028,11 +1054,29 @@ def destripe_zarr_store(
         blocks.histogram = histogram is not None
         if histogram is not None:
             eng.volhist_reset()
+        rank_zyx = (z1 - z0,) + tuple(zyx[1:])
+        blocks.proj = None
         try:
-            n_planes = blocks.run_range(z0, z1)
+            if proj_mode is not None:
+                blocks.proj, blocks.proj_z0 = {}, z0
+                for key in projections:
+                    blocks.proj[key] = eng.alloc_projection(rank_zyx)
+                blocks.proj_work = eng.alloc(engine_mod.project_work_bytes((min(block_z, z1 - z0),) + tuple(zyx[1:])))
+            try:
+                n_planes = blocks.run_range(z0, z1)
+            finally:
+                LAST_RUN["decode_routes"] = dict(blocks.timing["decode_routes"])
+            eng.sync()
+            if proj_mode is not None:  # one download per array, after the last block
+                for key, bufs in blocks.proj.items():
+                    projections[key].add_projected(z0, eng.projection_get(bufs, rank_zyx))
+                LAST_RUN["projection_planes"] = z1 - z0
         finally:
-            LAST_RUN["decode_routes"] = dict(blocks.timing["decode_routes"])
-        eng.sync()
+            if blocks.proj is not None:
+                for b in [b for bufs in blocks.proj.values() for b in bufs.values()] + [blocks.proj_work]:
+                    if b is not None:
+                        b.free()
+                blocks.proj, blocks.proj_work = None, None
         if histogram is not None:
             counts = eng.volhist_get()
             histogram += counts
@@ -1054,6 +1098,11 @@ def destripe_zarr_store(
             counts = np.bincount(written.ravel(), minlength=engine_mod.VOLHIST_BINS)
             histogram += counts
             LAST_RUN["histogram_voxels"] += int(counts.sum())
+        if proj_mode is not None:
+            projections["output"].add(sc[0].start, written.reshape((-1,) + written.shape[-2:]))
+            if "input" in projections:
+                projections["input"].add(sc[0].start, block)
+            LAST_RUN["projection_planes"] += block.shape[0]
         n_planes += block.shape[0]
     dt = time.perf_counter() - t0
     logger.info("rank %d: %d planes z[%d:%d) in %.2f s", rank, n_planes, z0, z1, dt)
@@ -1497,6 +1546,7 @@ def destripe_zarr(
     rotate=False,
     lightsheet=None,
     scale_factor=None,
+    qc_projections=None,
 ):
     """``destripe_zarr`` of the reference (``zarr_destriper.py:909-1211``) with its 14 parameters, on the GPU chunk map.
 
@@ -1513,9 +1563,9 @@ def destripe_zarr(
       (:func:`load_shadow_correction`: ``DarkMaster_cropped.tif``, retrospective flat if given, else the
       normalised microscope flats + tile config); no derivatives folder and no flat = no shading correction.
     * ``n_workers``: ``ValueError`` when above the CPU limit, like ``:977-978``; otherwise unused -- so are
-      ``target_size_mb``, ``batch_size``, ``super_chunksize`` (sizing of the reference's data loader, ``:1041-1057``),
-      ``results_folder`` (log file and resource plots, ``:980, 1202-1211``): loader and logging are out of scope (SURVEY
-      section 2.1).  ``xyz_resolution`` (OME-NGFF voxel size, ``:1181-1185``) is used with ``ome_metadata=True``.
+      ``target_size_mb``, ``batch_size``, ``super_chunksize`` (sizing of the reference's data loader, ``:1041-1057``):
+      the loader is out of scope.  ``results_folder`` (log file and resource plots, ``:980,
+      1202-1211``): no log file or resource plot is written; with ``qc_projections`` the QC files of the tile go there.  ``xyz_resolution`` (OME-NGFF voxel size, ``:1181-1185``) is used with ``ome_metadata=True``.
     * ``lazy_callback_fn``: applied by the reference's loader to the lazy array (``:1052``); ``None`` in production
       (``:1266``).  Anything else raises ``NotImplementedError`` -- silently skipping a transform would change the data.
 
@@ -1544,12 +1594,23 @@ def destripe_zarr(
     ``ValueError`` before anything is created -- the mode has no dark / flat step), ``scale_factor`` (``(fz, fy, fx)`` of
     the pyramid, 1 or 2 each and not all 1; ``None`` = the reference's ``[2, 2, 2]``, ``:1176``; it goes to the fused
     route, to rank 0's :func:`compute_multiscale` and to the metadata; anything else raises ``ValueError`` before
-    anything is created.  ``LAST_RUN["pyramid_scale"]`` is the scale used).
+    anything is created.  ``LAST_RUN["pyramid_scale"]`` is the scale used), ``qc_projections`` (``None``, ``"output"``
+    or ``"both"``: every rank collects the maximum and sum projections of the planes it writes -- with ``"both"`` also
+    of the planes it read -- in the pass itself (``destripe_zarr_store(projections=...)``), ``group.reduce_array``
+    merges the ranks' arrays after the barrier, and rank 0 writes ``<tile>_projections.npz`` and the three
+    ``<tile>_mip_{z,y,x}.tif`` into ``results_folder`` (``projections.write_qc``; ``"both"`` adds the input's arrays and
+    the stripe gain).  Any other value, and ``world_size > 1`` with a group without ``reduce_array``, raise
+    ``ValueError`` before anything is created).
     Returns ``(planes processed by this rank, seconds)``.
     """
+    from . import projections as proj_mod
     from . import pyramid
 
     rotate = engine_mod.rotate_flag(rotate)
+    proj_mod.check_qc_mode(qc_projections)
+    if qc_projections is not None and world_size > 1 and not hasattr(group, "reduce_array"):
+        raise ValueError("qc_projections with world_size > 1 needs a group with reduce_array (distributed.RankGroup): "
+                         "the ranks' projections must be merged")  # fmt: skip
     scale_factor = list(pyramid.check_scale_factor([2, 2, 2] if scale_factor is None else scale_factor))
     output_codec_mode(device_codec, compressor)  # (a wrong string or mode fails before anything is written)
     device_decode_mode(device_decode)
@@ -1584,7 +1645,7 @@ def destripe_zarr(
         raise ValueError(f"Provided workers {n_workers} > current workers {co_cpus}")
     if lazy_callback_fn is not None:
         raise NotImplementedError("lazy_callback_fn: the GPU chunk map reads the store as it is (production passes None)")
-    del target_size_mb, batch_size, super_chunksize, results_folder
+    del target_size_mb, batch_size, super_chunksize
     logger = logger or logging.getLogger("dsx.zarr")
     logger.info(f"Processing dataset {dataset_path}")
     dataset_path = Path(dataset_path)
@@ -1629,6 +1690,10 @@ def destripe_zarr(
         # flatfield_correction dereferences the dark plane (filtering.py:371-377): nothing to correct with
         raise ValueError(f"No darkfield for the shading correction: {derivatives_path} does not exist")
     level0 = output_destriped_zarr.joinpath("0")
+    qc = None
+    if qc_projections is not None:  # (a volume the projections do not take fails here, before anything is created)
+        src_zyx = MiniZarrArray.open(str(src)).shape[-3:]
+        qc = {key: proj_mod.VolumeProjections(src_zyx) for key in (("output", "input") if qc_projections == "both" else ("output",))}
     n_planes, seconds = destripe_zarr_store(
         str(src),
         str(level0),
@@ -1655,9 +1720,16 @@ def destripe_zarr(
         histogram=histogram,
         rotate=rotate,
         lightsheet=lightsheet,
+        projections=qc,
     )
     if group is not None and world_size > 1:
         group.barrier()  # level 0 of this tile is complete on every rank: the pyramid may read it
+    if qc is not None:
+        for p in qc.values():
+            p.merge(group if world_size > 1 else None)
+        if rank == 0:
+            proj_mod.write_qc(results_folder, dataset_name.replace(".zarr", ""), qc["output"], qc.get("input"),
+                              rotate=bool(LAST_RUN.get("rotate", rotate)))  # fmt: skip
     window, ome_kw = fixed_window, {}
     if percentile:
         total = group.sum_counts(histogram) if world_size > 1 else histogram
@@ -1733,6 +1805,7 @@ def destripe_channel(
     streaks=None,
     rotate=False,
     scale_factor=None,
+    qc_projections=None,
 ):
     """``destripe_channel`` of the reference (``zarr_destriper.py:1214-1267``), same eight parameters (the reference's
     caller passes them by keyword, ``run_capsule.py:394-403``), wired to the GPU chunk map.
@@ -1756,10 +1829,18 @@ def destripe_channel(
     created otherwise).  ``rotate``: vertical stripes, handed to every tile's :func:`destripe_zarr` (a bool,
     ``TypeError`` before anything is created otherwise).  ``scale_factor``: the pyramid's ``(fz, fy, fx)``, handed to
     every tile's :func:`destripe_zarr` (``None`` = ``[2, 2, 2]``; ``ValueError`` before anything is created otherwise).
+    ``qc_projections``: ``None``, ``"output"`` or ``"both"``, handed to every tile's :func:`destripe_zarr`, which leaves
+    the tile's QC files in ``results_folder`` (``ValueError`` before anything is created for any other value, and with
+    ``world_size > 1`` for a group without ``reduce_array``).
     """
+    from . import projections as proj_mod
     from . import pyramid
 
     rotate = engine_mod.rotate_flag(rotate)
+    proj_mod.check_qc_mode(qc_projections)
+    if qc_projections is not None and world_size > 1 and not hasattr(group, "reduce_array"):
+        raise ValueError("qc_projections with world_size > 1 needs a group with reduce_array (distributed.RankGroup): "
+                         "the ranks' projections must be merged")  # fmt: skip
     if scale_factor is not None:
         pyramid.check_scale_factor(scale_factor)
     if world_size > 1 and group is None:
@@ -1829,6 +1910,7 @@ def destripe_channel(
             streaks=streaks,
             rotate=rotate,
             scale_factor=scale_factor,
+            qc_projections=qc_projections,
         )
         done[tile_path.name] = n
     return done

@@ -272,6 +272,29 @@ int dsx_volhist_get(dsx_ctx* ctx, uint64_t* hist);
 /* zarr_destriper.py:722-726: the host build -- adds the counts of n host voxels into hist (65 536 bins). */
 int dsx_volhist_ref(const void* vox, size_t n, uint64_t* hist);
 
+/* QC projections of a pass: the three maximum-intensity projections of a uint16 volume and the three sum projections,
+ * whose row sums before and after the filter are the stripe signature and what became of it (csrc/dsx_project.h).  The
+ * reference leaves only a resource plot in its results folder (zarr_destriper.py:1202-1211).  A volume v[., H, W]
+ * arrives in z blocks: planes = Z dense planes (2-byte aligned), which are rows z_off .. z_off + Z - 1 of the volume.
+ *   max_z uint16 [H, W], sum_z uint64 [H, W]: over z -- overwritten when first != 0, combined with their content otherwise
+ *   max_y uint16 [., W], sum_y uint32 [., W]: over y -- rows z_off .. z_off + Z - 1 are written, no other row is touched
+ *   max_x uint16 [., H], sum_x uint32 [., H]: over x -- likewise
+ * All integers, exact, independent of the order of the blocks.  H, W > 0, Z >= 0, z_off >= 0, anything else is
+ * DSX_EINVAL; H, W or Z above 65 536 is DSX_ELIMIT (the uint32 sums); Z == 0 is a no-op; with Z > 0 a NULL planes
+ * pointer, table, table member or work buffer and an odd planes pointer are DSX_EINVAL, all before anything is launched.
+ * dsx_project_u16_device: device pointers, one read of the planes, asynchronous on the context stream; d_work holds
+ * dsx_project_work_bytes(Z, H, W) bytes (4-byte aligned) and may be reused by the next call on the stream.
+ * dsx_project_u16_ref: the host build of the same arithmetic (host pointers, synchronous, no work buffer). */
+typedef struct dsx_projection {
+  uint16_t* max_z; uint64_t* sum_z;
+  uint16_t* max_y; uint32_t* sum_y;
+  uint16_t* max_x; uint32_t* sum_x;
+} dsx_projection;
+int dsx_project_work_bytes(int Z, int H, int W, size_t* bytes);
+int dsx_project_u16_device(dsx_ctx* ctx, const void* d_planes, int Z, int H, int W, const dsx_projection* p, int z_off,
+                           int first, void* d_work);
+int dsx_project_u16_ref(const void* planes, int Z, int H, int W, const dsx_projection* p, int z_off, int first);
+
 /* Host side of the chunk map: n Zarr chunk files <-> memory (normally the pinned staging buffers) on
  * `threads` native threads -- what zarr / numcodecs do under the reference's worker processes
  * (zarr_destriper.py:336, 1042-1074).  codec: raw chunks, zlib streams, or Blosc frames -- the production

@@ -6,7 +6,7 @@ download) into another store.  Prints one JSON line; the roofline of this path i
 
     bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode|device-decode-any|device-decode-all]
                   [lz4|blosc-zlib|blosc-blosclz|plain-zlib] [pyramid|fused-pyramid|pipelined-pyramid] [lz4-out] [read-back]
-                  [streaks|streaks-generic|streaks-march] [ome-percentile] [scale-FZ-FY-FX]
+                  [streaks|streaks-generic|streaks-march] [ome-percentile] [scale-FZ-FY-FX] [projections|projections-both]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
 line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
@@ -35,6 +35,9 @@ the same route, bit for bit (no CPU oracle pass).
 (destripe_zarr_store(histogram=...)), takes the display window from the counts (display_window_from_histogram) and, with
 a pyramid word (the output is then a group), writes .zgroup / .zattrs (write_ome_ngff_metadata), all inside the timed
 seconds; the line reports the window and the voxels counted under "ome", and a count other than N * 2048 * 2048 fails the run.
+`projections`: every timed pass collects the QC projections of the planes it writes (destripe_zarr_store(projections=
+{"output": ...}); `projections-both`: of the planes it read as well), inside the timed seconds; the line reports the mode and
+the planes added under "projections", and the rows of the picked planes are held to NumPy (a mismatch fails the run).
 `scale-FZ-FY-FX` (with a pyramid word): the pyramid's scale factor per axis, 1 or 2 each, e.g. `scale-1-2-2` for a volume
 whose z step is coarser than its pixel (scale_factor of destripe_zarr_store / compute_multiscale); the default is 2-2-2.
 `pyramid`: after the timed level-0 pass, compute_multiscale(n_levels=3) on the store is timed too (the two-pass route);
@@ -64,6 +67,7 @@ lz4_out, read_back = "lz4-out" in sys.argv[3:], "read-back" in sys.argv[3:]
 streaks = ([{"sigma": (64.0, 128.0), "route": r} for w, r in (("streaks", "auto"), ("streaks-generic", "generic"),
                                                                ("streaks-march", "march")) if w in sys.argv[3:]] + [None])[0]
 ome = "ome-percentile" in sys.argv[3:]
+proj_keys = ("output", "input") if "projections-both" in sys.argv[3:] else ("output",) if "projections" in sys.argv[3:] else ()
 scale = ([[int(f) for f in w.split("-")[1:]] for w in sys.argv[3:] if w.startswith("scale-")] + [[2, 2, 2]])[0]
 if (lz4_out or read_back) and codec != "blosc":
     sys.exit("lz4-out / read-back: a Blosc store")
@@ -117,6 +121,10 @@ try:
         for rep in range(2):  # second pass: plan + pinned buffers exist, page cache warm
             t0 = time.perf_counter()
             hist = np.zeros(65536, np.int64) if ome else None
+            if proj_keys:
+                from aind_smartspim_destripe_amd import projections as pj
+                proj = {key: pj.VolumeProjections((n, H, W)) for key in proj_keys}
+                kw = {**kw, "projections": proj}
             planes, dt = zd.destripe_zarr_store(os.path.join(root, "in.zarr"), level0, synth.CELLS_CONFIG,
                                           synth.NO_CELLS_CONFIG, None, prediction_chunksize=(64, H, W),
                                           output_chunks=(1, 1, 64, 128, 128), device=0, device_retile=True, io_threads=16, compressor=out_codec,
@@ -214,11 +222,21 @@ try:
     if ome and int(hist.sum()) != n * H * W:
         verified = False
         print("histogram counted", int(hist.sum()), "voxels of", n * H * W, file=sys.stderr)
+    proj_info = {}
+    if proj_keys:
+        proj_info = {"projections": {"mode": zd.LAST_RUN["projections"], "planes": zd.LAST_RUN["projection_planes"]}}
+        verified = verified and all(p.added.all() for p in proj.values())
     for b in blocks:
         z0, z1 = 64 * b, min(64 * b + 64, n)
         for z in stream_part_picks(64, z0, z1):
             plane_in = src[0, 0, z]
             got = out[0, 0, z]
+            for key, plane in (("output", got), ("input", plane_in)):
+                if key in proj_keys:
+                    want = pj.project_volume(plane[None])
+                    if not all(np.array_equal(proj[key].arrays[k][z], want[k][0]) for k in ("max_y", "sum_y", "max_x", "sum_x")):
+                        verified = False
+                        print("projection mismatch", key, z, file=sys.stderr)
             if streaks is not None:
                 alone = fl.destripe_streaks_planes(plane_in[None], streaks["sigma"], route=zd.LAST_RUN["streaks_route"],
                                                    out_dtype=np.uint16, max_batch=1)[0]
@@ -243,7 +261,7 @@ try:
                       "roofline": {"bound": "host link", "peak_planes_per_s": 3750, "frac": round(v / 3750.0, 3)},
                       "read_s": round(timing["read_s"], 3), "write_s": round(timing["write_s"], 3), "host_link": link,
                       "plane0_checksum": chk, "verified": verified,
-                      "filter": zd.LAST_RUN.get("filter"), "streaks_route": zd.LAST_RUN.get("streaks_route"), **decode, **sizes, **ome_info, **({"pyramid": pyr} if pyr else {}),
+                      "filter": zd.LAST_RUN.get("filter"), "streaks_route": zd.LAST_RUN.get("streaks_route"), **decode, **sizes, **ome_info, **proj_info, **({"pyramid": pyr} if pyr else {}),
                       "verification": {"planes_bit_identical_to_single_plane_runs": checked,
                                        "planes_against_the_cpu_oracle": oracle_checked, "blocks": blocks}}))
     if not verified or not pyr.get("verified", True):
