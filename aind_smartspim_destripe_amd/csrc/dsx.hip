@@ -27,6 +27,7 @@
 #include "dsx_retile.h"
 #include "dsx_rot90.h"
 #include "dsx_pyramid.h"
+#include "dsx_stackrank.h"
 #include "dsx_volhist.h"
 #include "dsx_project.h"
 #include "dsx_wavelet.h"
@@ -2082,6 +2083,58 @@ int dsx_volhist_ref(const void* vox, size_t n, uint64_t* hist) {
   if (!vox || !hist) return fail(nullptr, DSX_EINVAL, "volhist: NULL pointer");
   if ((uintptr_t)vox & 1) return fail(nullptr, DSX_EINVAL, "volhist: uint16 voxels must be 2-byte aligned");
   dsx::vh::volhist_host((const uint16_t*)vox, n, hist);
+  return DSX_OK;
+}
+
+/* ---- per-pixel order statistics of a plane stack (dsx_stackrank.h): the samples of flatfield_estimation.py -------- */
+extern "C++" {
+namespace {
+template <int NQ>
+hipError_t launch_stack_rank(const dsx::sr::Geometry& g, int tp_log2, hipStream_t s, const uint16_t* planes, int n, size_t P,
+                             unsigned lo, unsigned range, const dsx::sr::Quantiles& qs, uint16_t* out, uint16_t* valid,
+                             int vec) {
+  namespace sr = dsx::sr;
+  if (hipError_t e = raise_lds_limit<sr::k_stack_rank_u16<NQ>>(sr::kSrTileLimit + sr::kSrPartBytes)) return e;
+  hipLaunchKernelGGL(sr::k_stack_rank_u16<NQ>, dim3((unsigned)g.grid), dim3(sr::kSrThreads), g.lds_bytes, s, planes, n, P, lo,
+                     range, qs, out, valid, tp_log2, vec);
+  return hipGetLastError();
+}
+}  // namespace
+}  // extern "C++"
+
+int dsx_stack_rank_u16_device(dsx_ctx* ctx, const void* d_planes, int n, size_t plane_elems, int lo, int hi,
+                              const int* q_milli, int n_q, void* d_out, void* d_valid) {
+  namespace sr = dsx::sr;
+  if (!ctx) return DSX_EINVAL;
+  if (const char* why = sr::check_args(d_planes, n, plane_elems, lo, hi, q_milli, n_q, d_out)) return fail(ctx, DSX_EINVAL, why);
+  if (((uintptr_t)d_out | (uintptr_t)d_valid) & 1) return fail(ctx, DSX_EINVAL, "stack_rank: uint16 results must be 2-byte aligned");
+  const sr::Geometry g = sr::geometry(n, plane_elems);
+  const int tp_log2 = g.tp == 256 ? 8 : g.tp == 128 ? 7 : 6;
+  const int vec = plane_elems % 8 == 0 && (uintptr_t)d_planes % 16 == 0;
+  sr::Quantiles qs = {};
+  for (int i = 0; i < n_q; ++i) qs.q[i] = q_milli[i];
+  const uint16_t* x = (const uint16_t*)d_planes;
+  uint16_t *o = (uint16_t*)d_out, *v = (uint16_t*)d_valid;
+  const unsigned ulo = (unsigned)lo, range = (unsigned)(hi - lo);
+  DSX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = use_main(ctx);
+  hipError_t e = hipSuccess;
+  switch (n_q) {
+    case 1: e = launch_stack_rank<1>(g, tp_log2, s, x, n, plane_elems, ulo, range, qs, o, v, vec); break;
+    case 2: e = launch_stack_rank<2>(g, tp_log2, s, x, n, plane_elems, ulo, range, qs, o, v, vec); break;
+    case 3: e = launch_stack_rank<3>(g, tp_log2, s, x, n, plane_elems, ulo, range, qs, o, v, vec); break;
+    default: e = launch_stack_rank<4>(g, tp_log2, s, x, n, plane_elems, ulo, range, qs, o, v, vec); break;
+  }
+  DSX_HIP(e);
+  return DSX_OK;
+}
+
+int dsx_stack_rank_u16_ref(const void* planes, int n, size_t plane_elems, int lo, int hi, const int* q_milli, int n_q,
+                           void* out, void* valid) {
+  namespace sr = dsx::sr;
+  if (const char* why = sr::check_args(planes, n, plane_elems, lo, hi, q_milli, n_q, out)) return fail(nullptr, DSX_EINVAL, why);
+  if (((uintptr_t)out | (uintptr_t)valid) & 1) return fail(nullptr, DSX_EINVAL, "stack_rank: uint16 results must be 2-byte aligned");
+  sr::stack_rank_host((const uint16_t*)planes, n, plane_elems, lo, hi, q_milli, n_q, (uint16_t*)out, (uint16_t*)valid);
   return DSX_OK;
 }
 

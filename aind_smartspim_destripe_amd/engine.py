@@ -34,6 +34,9 @@ TASK_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<u4"), ("dst
 
 COMM_ID_BYTES = 128
 VOLHIST_BINS = 65536  # one bin per uint16 value (dsx_volhist_*)
+STACK_RANK_MAX_PLANES = 512  # planes, quantiles and elements per plane of one dsx_stack_rank_u16_* call
+STACK_RANK_MAX_QUANTILES = 4
+STACK_RANK_MAX_ELEMS = (1 << 31) - 1
 PROJECT_MAX_EXTENT = 65536  # rows, columns, and planes of one call (dsx_project_*: the uint32 sums)
 # the six projections of a uint16 volume [Z, H, W] (dsx_projection, in the order of its members): name, dtype, the two
 # axes of zyx that are left
@@ -65,6 +68,7 @@ EXPORTED_SYMBOLS = [
     "dsx_downsample_u16", "dsx_pyramid_work_bytes_scale", "dsx_pyramid_block_scale_u16", "dsx_pyramid_block_scale_ref",
     "dsx_pyramid_bricks_scale_u16", "dsx_pyramid_bricks_scale_ref",
     "dsx_volhist_reset", "dsx_volhist_add_device", "dsx_volhist_get", "dsx_volhist_ref",
+    "dsx_stack_rank_u16_device", "dsx_stack_rank_u16_ref",
     "dsx_project_work_bytes", "dsx_project_u16_device", "dsx_project_u16_ref",
     "dsx_plan_streaks_opts", "dsx_streaks_blend_ref",
     "dsx_set_rotate", "dsx_rot90_device", "dsx_rot90_ref",
@@ -273,6 +277,9 @@ def load_library(path=None):
     lib.dsx_volhist_add_device.argtypes = [vp, vp, ctypes.c_size_t]
     lib.dsx_volhist_get.argtypes = [vp, vp]
     lib.dsx_volhist_ref.argtypes = [vp, ctypes.c_size_t, vp]
+    i32p = ctypes.POINTER(ctypes.c_int)
+    lib.dsx_stack_rank_u16_device.argtypes = [vp, vp, i32, ctypes.c_size_t, i32, i32, i32p, i32, vp, vp]
+    lib.dsx_stack_rank_u16_ref.argtypes = [vp, i32, ctypes.c_size_t, i32, i32, i32p, i32, vp, vp]
     lib.dsx_project_work_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     lib.dsx_project_u16_device.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(_Projection), i32, i32, vp]
     lib.dsx_project_u16_ref.argtypes = [vp, i32, i32, i32, ctypes.POINTER(_Projection), i32, i32]
@@ -985,6 +992,35 @@ class DestripeEngine:
         self._check(self._lib.dsx_volhist_get(self._ctx, out.ctypes.data_as(ctypes.c_void_p)))
         return out.astype(np.int64)
 
+    # -- per-pixel order statistics of a plane stack (the samples of flatfield_estimation.py) ------
+    def stack_rank(self, d_planes, n, plane_elems, q_milli, valid_range=(0, 65535), d_out=None, d_valid=None):
+        """Per-pixel quantiles of ``n`` dense uint16 planes of ``plane_elems`` elements at a :class:`DeviceBuffer` or a
+        device address (``dsx_stack_rank_u16_device``; ``flatfield_estimation.py:43-50``), one read of the stack.  Per
+        pixel only the values inside ``valid_range = (lo, hi)`` count, ``m`` of them; quantile ``q`` of ``q_milli``
+        (per-mille, up to 4) is the ``(q * (m - 1)) // 1000``-th smallest of them, 0 where ``m == 0``.  Results go to
+        ``d_out`` (uint16 ``[len(q_milli), plane_elems]``) and ``d_valid`` (uint16 ``[plane_elems]``, the counts
+        ``m``); buffers that are not given are allocated, and the caller frees them.  Returns ``(d_out, d_valid)``.  A
+        value outside the limits is a ``ValueError`` before any launch.  Asynchronous on the engine stream."""
+        n, plane_elems, q, lo, hi = stack_rank_args(n, plane_elems, q_milli, valid_range)
+        ptr = getattr(d_planes, "ptr", d_planes)
+        nbytes = getattr(d_planes, "nbytes", None)
+        assert nbytes is None or 2 * n * plane_elems <= nbytes, "stack_rank: more planes than the buffer holds"
+        if d_out is None:
+            d_out = self.alloc(max(2 * len(q) * plane_elems, 16))
+        if d_valid is None:
+            d_valid = self.alloc(max(2 * plane_elems, 16))
+        for buf, need in ((d_out, 2 * len(q) * plane_elems), (d_valid, 2 * plane_elems)):
+            held = getattr(buf, "nbytes", None)
+            assert held is None or need <= held, "stack_rank: a result buffer is too small"
+        rc = self._lib.dsx_stack_rank_u16_device(self._ctx, ctypes.c_void_p(ptr), n, plane_elems, lo, hi,
+                                                 (ctypes.c_int * len(q))(*q), len(q),
+                                                 ctypes.c_void_p(getattr(d_out, "ptr", d_out)),
+                                                 ctypes.c_void_p(getattr(d_valid, "ptr", d_valid)))  # fmt: skip
+        if rc == -1:
+            raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
+        self._check(rc)
+        return d_out, d_valid
+
     # -- QC projections of the volume a pass reads and writes --------------------------------------
     def alloc_projection(self, zyx):
         """Six zeroed device arrays for the projections of a ``zyx`` volume: ``{name: DeviceBuffer}`` for
@@ -1198,6 +1234,57 @@ def volhist_ref(array, hist=None):
     if rc != 0:
         raise ValueError((lib.dsx_last_error(None) or b"volhist_ref failed").decode())
     return hist
+
+
+def stack_rank_args(n, plane_elems, q_milli, valid_range):
+    """``(n, plane_elems, [q, ...], lo, hi)`` of a stack-rank call as ints, inside the limits of ``include/dsx.h``;
+    ``ValueError`` otherwise (raised before any library call)."""
+
+    def whole(name, v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("stack_rank: {} must be an integer, not {!r}".format(name, v))
+        return int(v)
+
+    n, plane_elems = whole("n", n), whole("plane_elems", plane_elems)
+    if not (1 <= n <= STACK_RANK_MAX_PLANES):
+        raise ValueError("stack_rank: 1 <= n <= {} planes, not {}".format(STACK_RANK_MAX_PLANES, n))
+    if not (1 <= plane_elems <= STACK_RANK_MAX_ELEMS):
+        raise ValueError("stack_rank: 1 <= plane_elems < 2^31, not {}".format(plane_elems))
+    try:
+        q = [whole("a quantile", v) for v in q_milli]
+    except TypeError:
+        raise ValueError("stack_rank: q_milli is a sequence of per-mille quantiles, not {!r}".format(q_milli)) from None
+    if not (1 <= len(q) <= STACK_RANK_MAX_QUANTILES):
+        raise ValueError("stack_rank: 1 <= len(q_milli) <= {}, not {}".format(STACK_RANK_MAX_QUANTILES, len(q)))
+    if any(not (0 <= v <= 1000) for v in q):
+        raise ValueError("stack_rank: a quantile is per-mille, 0 <= q <= 1000, not {!r}".format(q))
+    try:
+        lo, hi = valid_range
+    except (TypeError, ValueError):
+        raise ValueError("stack_rank: valid_range is (lo, hi), not {!r}".format(valid_range)) from None
+    lo, hi = whole("lo", lo), whole("hi", hi)
+    if not (0 <= lo <= hi <= 65535):
+        raise ValueError("stack_rank: 0 <= lo <= hi <= 65535, not {!r}".format((lo, hi)))
+    return n, plane_elems, q, lo, hi
+
+
+def stack_rank_ref(stack, q_milli, valid_range=(0, 65535)):
+    """Host build of :meth:`DestripeEngine.stack_rank` (``dsx_stack_rank_u16_ref``): ``stack`` is uint16 ``[n, ...]``,
+    one plane per leading index.  Returns ``(out, valid)``: uint16 ``[len(q_milli), ...]`` and uint16 ``[...]``.  No GPU
+    involved."""
+    lib = load_library()
+    a = np.ascontiguousarray(stack)
+    if a.dtype != np.uint16 or a.ndim < 2:
+        raise ValueError("stack_rank takes a uint16 stack [n, ...], got {} {}".format(a.dtype, a.shape))
+    plane_shape = a.shape[1:]
+    n, P, q, lo, hi = stack_rank_args(a.shape[0], int(np.prod(plane_shape)), q_milli, valid_range)
+    out = np.empty((len(q),) + plane_shape, np.uint16)
+    valid = np.empty(plane_shape, np.uint16)
+    rc = lib.dsx_stack_rank_u16_ref(a.ctypes.data_as(ctypes.c_void_p), n, P, lo, hi, (ctypes.c_int * len(q))(*q), len(q),
+                                    out.ctypes.data_as(ctypes.c_void_p), valid.ctypes.data_as(ctypes.c_void_p))  # fmt: skip
+    if rc != 0:
+        raise ValueError((lib.dsx_last_error(None) or b"stack_rank_ref failed").decode())
+    return out, valid
 
 
 def _project_geometry(zyx):

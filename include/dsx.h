@@ -272,6 +272,25 @@ int dsx_volhist_get(dsx_ctx* ctx, uint64_t* hist);
 /* zarr_destriper.py:722-726: the host build -- adds the counts of n host voxels into hist (65 536 bins). */
 int dsx_volhist_ref(const void* vox, size_t n, uint64_t* hist);
 
+/* Per-pixel order statistics of a stack of uint16 planes (csrc/dsx_stackrank.h): what this project's estimator of the
+ * retrospective flat fields needs from the device.  The reference fits them with BaSiC over destriped sample tiles
+ * (flatfield_estimation.py:15-52, 125-196); here the destriped samples lie in device memory behind the filter and the
+ * flat is a smoothed per-pixel quantile of them (aind_smartspim_destripe_amd/flatfield_estimation.py).
+ *   planes: n dense planes of plane_elems uint16 each (2-byte aligned; plane_elems may be odd)
+ *   per pixel p: V = the x[j, p] with lo <= x <= hi, m = |V|; valid[p] = m (valid may be NULL);
+ *   out[i, p] = the k-th smallest element of V, 0-based, k = (q_milli[i] * (m - 1)) / 1000 in integer arithmetic,
+ *   and 0 where m == 0.  out is uint16 [n_q][plane_elems].
+ * 1 <= n <= 512, 1 <= n_q <= 4, 1 <= plane_elems < 2^31, 0 <= lo <= hi <= 65535, 0 <= q_milli[i] <= 1000, non-NULL
+ * planes, q_milli and out: anything else is DSX_EINVAL, before anything is launched.  Integers only: the two builds agree
+ * exactly. */
+/* flatfield_estimation.py:43-50: device pointers, the stack is read once; asynchronous on the context stream. */
+int dsx_stack_rank_u16_device(dsx_ctx* ctx, const void* d_planes, int n, size_t plane_elems, int lo, int hi,
+                              const int* q_milli, int n_q, void* d_out /* u16 [n_q][plane_elems] */,
+                              void* d_valid /* u16 [plane_elems], may be NULL */);
+/* flatfield_estimation.py:43-50: the host build, plain C++ (host pointers, synchronous). */
+int dsx_stack_rank_u16_ref(const void* planes, int n, size_t plane_elems, int lo, int hi, const int* q_milli, int n_q,
+                           void* out, void* valid);
+
 /* QC projections of a pass: the three maximum-intensity projections of a uint16 volume and the three sum projections,
  * whose row sums before and after the filter are the stripe signature and what became of it (csrc/dsx_project.h).  The
  * reference leaves only a resource plot in its results folder (zarr_destriper.py:1202-1211).  A volume v[., H, W]
