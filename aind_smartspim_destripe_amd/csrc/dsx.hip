@@ -28,6 +28,7 @@
 #include "dsx_rot90.h"
 #include "dsx_pyramid.h"
 #include "dsx_stackrank.h"
+#include "dsx_smooth.h"
 #include "dsx_volhist.h"
 #include "dsx_project.h"
 #include "dsx_wavelet.h"
@@ -2135,6 +2136,113 @@ int dsx_stack_rank_u16_ref(const void* planes, int n, size_t plane_elems, int lo
   if (const char* why = sr::check_args(planes, n, plane_elems, lo, hi, q_milli, n_q, out)) return fail(nullptr, DSX_EINVAL, why);
   if (((uintptr_t)out | (uintptr_t)valid) & 1) return fail(nullptr, DSX_EINVAL, "stack_rank: uint16 results must be 2-byte aligned");
   sr::stack_rank_host((const uint16_t*)planes, n, plane_elems, lo, hi, q_milli, n_q, (uint16_t*)out, (uint16_t*)valid);
+  return DSX_OK;
+}
+
+/* ---- the finish of a retrospective flat (dsx_smooth.h): fill, Gaussian, mean -- flatfield_estimation.py:15-52 ---------- */
+extern "C++" {
+namespace {
+dsx::sm::Taps smooth_taps(const double* taps, int radius) {
+  dsx::sm::Taps t = {};
+  for (int k = 0; k <= radius; ++k) t.t[k] = taps[k];
+  return t;
+}
+
+// The two passes on stream s: in -> tmp along axis 0, tmp -> out along axis 1 (arguments as check_smooth passed them).
+hipError_t launch_smooth(hipStream_t s, const double* in, int H, int W, const dsx::sm::Taps& t, int r, double* tmp, double* out) {
+  namespace sm = dsx::sm;
+  const sm::Geometry g = sm::geometry(H, W, r);
+  if (hipError_t e = raise_lds_limit<sm::k_sm_col>(sm::kSmMaxLds)) return e;
+  if (hipError_t e = raise_lds_limit<sm::k_sm_row>(sm::kSmMaxLds)) return e;
+  const int vec_col = W % 2 == 0 && (uintptr_t)in % 16 == 0, vec_row = W % 2 == 0 && (uintptr_t)tmp % 16 == 0;
+  hipLaunchKernelGGL(sm::k_sm_col, dim3(g.col_bx * g.col_by), dim3(sm::kSmThreads), g.col_lds, s, in, tmp, H, W, r, g.col_bx, t,
+                     vec_col);
+  hipLaunchKernelGGL(sm::k_sm_row, dim3(g.row_bx * g.row_by), dim3(sm::kSmThreads), g.row_lds, s, (const double*)tmp, out, H, W,
+                     r, g.row_bx, t, vec_row);
+  return hipGetLastError();
+}
+}  // namespace
+}  // extern "C++"
+
+int dsx_gauss_smooth_f64_device(dsx_ctx* ctx, const void* d_in, int H, int W, const double* taps, int radius, void* d_tmp,
+                                void* d_out) {
+  namespace sm = dsx::sm;
+  if (!ctx) return DSX_EINVAL;
+  if (const char* why = sm::check_smooth(d_in, H, W, taps, radius, d_tmp, d_out)) return fail(ctx, DSX_EINVAL, why);
+  DSX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = use_main(ctx);
+  DSX_HIP(launch_smooth(s, (const double*)d_in, H, W, smooth_taps(taps, radius), radius, (double*)d_tmp, (double*)d_out));
+  return DSX_OK;
+}
+
+int dsx_gauss_smooth_f64_ref(const void* in, int H, int W, const double* taps, int radius, void* tmp, void* out) {
+  namespace sm = dsx::sm;
+  if (const char* why = sm::check_smooth(in, H, W, taps, radius, tmp, out)) return fail(nullptr, DSX_EINVAL, why);
+  sm::smooth_host((const double*)in, H, W, taps, radius, (double*)tmp, (double*)out);
+  return DSX_OK;
+}
+
+int dsx_flat_finish_work_bytes(int H, int W, size_t* bytes) {
+  namespace sm = dsx::sm;
+  if (!bytes || H < 1 || W < 1 || (long long)H * W > sm::kSmMaxElems)
+    return fail(nullptr, DSX_EINVAL, "flat_finish_work_bytes: 1 <= H, W and H * W < 2^31");
+  *bytes = sm::work_layout(H, W).bytes;
+  return DSX_OK;
+}
+
+int dsx_flat_finish_device(dsx_ctx* ctx, const void* d_rank, const void* d_valid, int Hs, int Ws, int H, int W, int n_q,
+                           const double* taps, int radius, double floor, void* d_flat, void* d_dark, void* d_work) {
+  namespace sm = dsx::sm;
+  if (!ctx) return DSX_EINVAL;
+  if (const char* why = sm::check_finish(d_rank, d_valid, Hs, Ws, H, W, n_q, taps, radius, floor, d_flat, d_dark))
+    return fail(ctx, DSX_EINVAL, why);
+  if (!d_work || (uintptr_t)d_work % 16) return fail(ctx, DSX_EINVAL, "flat_finish: the work buffer must be 16-byte aligned");
+  const sm::Work w = sm::work_layout(H, W);
+  char* base = (char*)d_work;
+  unsigned* hist = (unsigned*)(base + w.hist);
+  sm::Scalars* scal = (sm::Scalars*)(base + w.scal);
+  double *part = (double*)(base + w.part), *a = (double*)(base + w.a), *tmp = (double*)(base + w.tmp);
+  const sm::Taps t = smooth_taps(taps, radius);
+  const int N = H * W;
+  const unsigned cover = (unsigned)(((long long)N + sm::kSmThreads - 1) / sm::kSmThreads);
+  const unsigned hist_grid = cover < 512u ? cover : 512u;  // two blocks of 64 KiB LDS per CU
+  DSX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = use_main(ctx);
+  for (int q = 0; q < n_q; ++q) {
+    const uint16_t* R = (const uint16_t*)d_rank + (size_t)q * (size_t)Hs * (size_t)Ws;
+    DSX_HIP(hipMemsetAsync(hist, 0, (size_t)sm::kSmBins * sizeof(unsigned), s));
+    hipLaunchKernelGGL(sm::k_sm_hist, dim3(hist_grid), dim3(sm::kSmThreads), 0, s, R, (const uint16_t*)d_valid, Ws, W, N, hist);
+    hipLaunchKernelGGL(sm::k_sm_median, dim3(1), dim3(sm::kSmThreads), 0, s, (const unsigned*)hist, scal);
+    hipLaunchKernelGGL(sm::k_sm_fill, dim3(cover), dim3(sm::kSmThreads), 0, s, R, (const uint16_t*)d_valid, Ws, W, N,
+                       (const sm::Scalars*)scal, a);
+    DSX_HIP(hipGetLastError());
+    DSX_HIP(launch_smooth(s, a, H, W, t, radius, tmp, a));
+    if (q == 0) {
+      hipLaunchKernelGGL(sm::k_sm_partial, dim3(sm::kSmMeanLanes / sm::kSmThreads), dim3(sm::kSmThreads), 0, s, (const double*)a,
+                         N, part);
+      hipLaunchKernelGGL(sm::k_sm_mean, dim3(1), dim3(sm::kSmThreads), 0, s, (const double*)part, N, scal);
+      hipLaunchKernelGGL(sm::k_sm_norm, dim3(cover), dim3(sm::kSmThreads), 0, s, (const double*)a, N, (const sm::Scalars*)scal,
+                         floor, (float*)d_flat);
+    } else {
+      hipLaunchKernelGGL(sm::k_sm_f32, dim3(cover), dim3(sm::kSmThreads), 0, s, (const double*)a, N, (float*)d_dark);
+    }
+    DSX_HIP(hipGetLastError());
+  }
+  unsigned long long seen = 0;  // the one read of the chain: the status
+  DSX_HIP(hipMemcpyAsync(&seen, &scal->seen, sizeof(seen), hipMemcpyDeviceToHost, s));
+  DSX_HIP(hipStreamSynchronize(s));
+  if (!seen) return fail(ctx, DSX_EVALUE, "flat_finish: no pixel of the image is seen (valid is 0 everywhere)");
+  return DSX_OK;
+}
+
+int dsx_flat_finish_ref(const void* rank, const void* valid, int Hs, int Ws, int H, int W, int n_q, const double* taps,
+                        int radius, double floor, void* flat, void* dark) {
+  namespace sm = dsx::sm;
+  if (const char* why = sm::check_finish(rank, valid, Hs, Ws, H, W, n_q, taps, radius, floor, flat, dark))
+    return fail(nullptr, DSX_EINVAL, why);
+  if (!sm::flat_finish_host((const uint16_t*)rank, (const uint16_t*)valid, Hs, Ws, H, W, n_q, taps, radius, floor, (float*)flat,
+                            (float*)dark))
+    return fail(nullptr, DSX_EVALUE, "flat_finish: no pixel of the image is seen (valid is 0 everywhere)");
   return DSX_OK;
 }
 

@@ -37,6 +37,9 @@ VOLHIST_BINS = 65536  # one bin per uint16 value (dsx_volhist_*)
 STACK_RANK_MAX_PLANES = 512  # planes, quantiles and elements per plane of one dsx_stack_rank_u16_* call
 STACK_RANK_MAX_QUANTILES = 4
 STACK_RANK_MAX_ELEMS = (1 << 31) - 1
+GAUSS_MAX_SIGMA = 64.0  # dsx_gauss_smooth_f64_* / dsx_flat_finish_*: radius int(4 sigma + 0.5) <= 256
+GAUSS_MAX_RADIUS = 256
+FLAT_FINISH_MAX_ELEMS = (1 << 31) - 1  # H * W of one plane
 PROJECT_MAX_EXTENT = 65536  # rows, columns, and planes of one call (dsx_project_*: the uint32 sums)
 # the six projections of a uint16 volume [Z, H, W] (dsx_projection, in the order of its members): name, dtype, the two
 # axes of zyx that are left
@@ -69,6 +72,8 @@ EXPORTED_SYMBOLS = [
     "dsx_pyramid_bricks_scale_u16", "dsx_pyramid_bricks_scale_ref",
     "dsx_volhist_reset", "dsx_volhist_add_device", "dsx_volhist_get", "dsx_volhist_ref",
     "dsx_stack_rank_u16_device", "dsx_stack_rank_u16_ref",
+    "dsx_gauss_smooth_f64_device", "dsx_gauss_smooth_f64_ref",
+    "dsx_flat_finish_work_bytes", "dsx_flat_finish_device", "dsx_flat_finish_ref",
     "dsx_project_work_bytes", "dsx_project_u16_device", "dsx_project_u16_ref",
     "dsx_plan_streaks_opts", "dsx_streaks_blend_ref",
     "dsx_set_rotate", "dsx_rot90_device", "dsx_rot90_ref",
@@ -280,6 +285,12 @@ def load_library(path=None):
     i32p = ctypes.POINTER(ctypes.c_int)
     lib.dsx_stack_rank_u16_device.argtypes = [vp, vp, i32, ctypes.c_size_t, i32, i32, i32p, i32, vp, vp]
     lib.dsx_stack_rank_u16_ref.argtypes = [vp, i32, ctypes.c_size_t, i32, i32, i32p, i32, vp, vp]
+    f64, f64p = ctypes.c_double, ctypes.POINTER(ctypes.c_double)
+    lib.dsx_gauss_smooth_f64_device.argtypes = [vp, vp, i32, i32, f64p, i32, vp, vp]
+    lib.dsx_gauss_smooth_f64_ref.argtypes = [vp, i32, i32, f64p, i32, vp, vp]
+    lib.dsx_flat_finish_work_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    lib.dsx_flat_finish_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f64p, i32, f64, vp, vp, vp]
+    lib.dsx_flat_finish_ref.argtypes = [vp, vp, i32, i32, i32, i32, i32, f64p, i32, f64, vp, vp]
     lib.dsx_project_work_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     lib.dsx_project_u16_device.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(_Projection), i32, i32, vp]
     lib.dsx_project_u16_ref.argtypes = [vp, i32, i32, i32, ctypes.POINTER(_Projection), i32, i32]
@@ -1021,6 +1032,72 @@ class DestripeEngine:
         self._check(rc)
         return d_out, d_valid
 
+    # -- the finish of a retrospective flat: fill, Gaussian, mean (csrc/dsx_smooth.h) ---------------
+    def gauss_smooth(self, d_in, shape, taps, d_tmp=None, d_out=None, radius=None):
+        """The two Gaussian passes of the native finish on a float64 plane ``shape = (H, W)`` at a
+        :class:`DeviceBuffer` or a device address (``dsx_gauss_smooth_f64_device``; ``flatfield_estimation.py:15-52``):
+        axis 0, then axis 1, ``acc = t_0 a[i]; acc = fma(t_k, a[m(i - k)] + a[m(i + k)], acc)`` with the symmetric fold
+        ``m``.  ``taps``: :func:`gauss_taps` or any ``t_0 .. t_r``, ``r <= 256`` (a ``radius`` that is given must be that ``r``).  ``d_out`` may be ``d_in``; ``d_tmp``
+        is a third plane.  Buffers that are not given are allocated and the caller frees them.  Returns
+        ``(d_out, d_tmp)``.  ``ValueError`` before any launch for arguments outside the limits.  Asynchronous on the
+        engine stream."""
+        H, W, t = smooth_args(shape, taps, radius)
+        need = 8 * H * W
+        if d_tmp is None:
+            d_tmp = self.alloc(max(need, 16))
+        if d_out is None:
+            d_out = self.alloc(max(need, 16))
+        for buf in (d_in, d_tmp, d_out):
+            held = getattr(buf, "nbytes", None)
+            assert held is None or need <= held, "gauss_smooth: a buffer is too small"
+        rc = self._lib.dsx_gauss_smooth_f64_device(self._ctx, ctypes.c_void_p(getattr(d_in, "ptr", d_in)), H, W,
+                                                   t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(t) - 1,
+                                                   ctypes.c_void_p(getattr(d_tmp, "ptr", d_tmp)),
+                                                   ctypes.c_void_p(getattr(d_out, "ptr", d_out)))  # fmt: skip
+        if rc == -1:
+            raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
+        self._check(rc)
+        return d_out, d_tmp
+
+    def flat_finish(self, d_rank, d_valid, stored_shape, shape, n_q, taps, floor, d_flat=None, d_dark=None, d_work=None,
+                    radius=None):
+        """The native finish of a flat on the device (``dsx_flat_finish_device``; ``flatfield_estimation.py:15-52``):
+        from the rank planes ``d_rank`` (uint16 ``[n_q, Hs, Ws]``: flat, then dark) and ``d_valid`` (uint16
+        ``[Hs, Ws]``) of :meth:`stack_rank`, over the top-left ``shape = (H, W)`` of ``stored_shape = (Hs, Ws)``: the
+        unseen pixels take the median of the seen ones, the plane is smoothed as :meth:`gauss_smooth` does,
+        ``flat = float32(max(S / mean, floor))`` with the mean summed in 4096 strided lanes, ``dark = float32(S_dark)``.
+        Results go to ``d_flat`` / ``d_dark`` (float32 ``[H, W]``); buffers that are not given are allocated (the work
+        buffer is freed here, the results are the caller's).  Returns ``(d_flat, d_dark)``, ``d_dark`` ``None`` when
+        ``n_q == 1``.  :class:`NoSeenPixel` (a ``ValueError``) when ``valid`` is 0 all over the image; ``ValueError``
+        before any launch for arguments outside the limits.  Returns after the chain has run."""
+        Hs, Ws, H, W, n_q, t, floor = flat_finish_args(stored_shape, shape, n_q, taps, floor, radius)
+        for buf, need in ((d_rank, 2 * n_q * Hs * Ws), (d_valid, 2 * Hs * Ws)):
+            held = getattr(buf, "nbytes", None)
+            assert held is None or need <= held, "flat_finish: the rank planes do not fit their buffer"
+        own_work = d_work is None
+        if own_work:
+            d_work = self.alloc(flat_finish_work_bytes((H, W)))
+        try:
+            if d_flat is None:
+                d_flat = self.alloc(max(4 * H * W, 16))
+            if d_dark is None and n_q == 2:
+                d_dark = self.alloc(max(4 * H * W, 16))
+            rc = self._lib.dsx_flat_finish_device(self._ctx, ctypes.c_void_p(getattr(d_rank, "ptr", d_rank)),
+                                                  ctypes.c_void_p(getattr(d_valid, "ptr", d_valid)), Hs, Ws, H, W, n_q,
+                                                  t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(t) - 1, floor,
+                                                  ctypes.c_void_p(getattr(d_flat, "ptr", d_flat)),
+                                                  ctypes.c_void_p(getattr(d_dark, "ptr", d_dark)) if n_q == 2 else None,
+                                                  ctypes.c_void_p(getattr(d_work, "ptr", d_work)))  # fmt: skip
+        finally:
+            if own_work:
+                d_work.free()
+        if rc == -1:
+            raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
+        if rc == -8:
+            raise NoSeenPixel(self._lib.dsx_last_error(self._ctx).decode())
+        self._check(rc)
+        return d_flat, (d_dark if n_q == 2 else None)
+
     # -- QC projections of the volume a pass reads and writes --------------------------------------
     def alloc_projection(self, zyx):
         """Six zeroed device arrays for the projections of a ``zyx`` volume: ``{name: DeviceBuffer}`` for
@@ -1285,6 +1362,122 @@ def stack_rank_ref(stack, q_milli, valid_range=(0, 65535)):
     if rc != 0:
         raise ValueError((lib.dsx_last_error(None) or b"stack_rank_ref failed").decode())
     return out, valid
+
+
+class NoSeenPixel(ValueError):
+    """``dsx_flat_finish_*`` found ``valid == 0`` all over the image (``DSX_EVALUE``)."""
+
+
+def gauss_taps(sigma):
+    """``(radius, taps)`` of the native finish for a Gaussian of ``sigma`` pixels: ``radius = int(4 sigma + 0.5)`` and
+    the centre and right half ``t_0 .. t_r`` (float64) of the taps ``flatfield_estimation.gaussian_smooth`` uses --
+    ``exp(-0.5 / sigma^2 x^2)`` over ``x = -r .. r`` divided by its sum; that array is symmetric.  ``sigma == 0`` gives
+    ``(0, [1.0])``.  ``0 <= sigma <= 64``, ``ValueError`` otherwise."""
+    if isinstance(sigma, (bool, np.bool_)) or not isinstance(sigma, (int, float, np.integer, np.floating)):
+        raise ValueError("gauss_taps: sigma must be a number, not {!r}".format(sigma))
+    sigma = float(sigma)
+    if not (0.0 <= sigma <= GAUSS_MAX_SIGMA):
+        raise ValueError("gauss_taps: the native finish takes 0 <= sigma <= {}, not {!r}".format(GAUSS_MAX_SIGMA, sigma))
+    if sigma == 0.0:
+        return 0, np.ones(1, np.float64)
+    radius = int(4.0 * sigma + 0.5)
+    x = np.arange(-radius, radius + 1, dtype=np.float64)
+    taps = np.exp(-0.5 / (sigma * sigma) * x * x)
+    taps /= taps.sum()
+    return radius, np.ascontiguousarray(taps[radius:])
+
+
+def _whole_extent(what, v):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+        raise ValueError("{} must be an integer >= 1, not {!r}".format(what, v))
+    return int(v)
+
+
+def smooth_args(shape, taps, radius=None):
+    """``(H, W, taps float64 [r + 1])`` of a smoothing call inside the limits of ``include/dsx.h``; ``ValueError``
+    otherwise (raised before any library call).  The radius is ``len(taps) - 1``; a ``radius`` that is given must say
+    the same."""
+    try:
+        H, W = shape
+    except (TypeError, ValueError):
+        raise ValueError("gauss_smooth: shape is (H, W), not {!r}".format(shape)) from None
+    H, W = _whole_extent("gauss_smooth: H", H), _whole_extent("gauss_smooth: W", W)
+    if H * W > FLAT_FINISH_MAX_ELEMS:
+        raise ValueError("gauss_smooth: H * W < 2^31, not {} x {}".format(H, W))
+    t = np.ascontiguousarray(taps, dtype=np.float64)
+    if t.ndim != 1 or not (1 <= t.size <= GAUSS_MAX_RADIUS + 1) or not np.all(np.isfinite(t)):
+        raise ValueError("gauss_smooth: taps are t_0 .. t_r, finite, 0 <= r <= {}".format(GAUSS_MAX_RADIUS))
+    if radius is not None and (isinstance(radius, (bool, np.bool_)) or radius != t.size - 1):
+        raise ValueError("gauss_smooth: radius {!r} and {} taps disagree (taps are t_0 .. t_radius)".format(radius, t.size))
+    return H, W, t
+
+
+def flat_finish_args(stored_shape, shape, n_q, taps, floor, radius=None):
+    """``(Hs, Ws, H, W, n_q, taps, floor)`` of a finish call inside the limits of ``include/dsx.h``; ``ValueError``
+    otherwise (raised before any library call)."""
+    H, W, t = smooth_args(shape, taps, radius)
+    try:
+        Hs, Ws = stored_shape
+    except (TypeError, ValueError):
+        raise ValueError("flat_finish: stored_shape is (Hs, Ws), not {!r}".format(stored_shape)) from None
+    Hs, Ws = _whole_extent("flat_finish: Hs", Hs), _whole_extent("flat_finish: Ws", Ws)
+    if Hs < H or Ws < W or Hs * Ws > FLAT_FINISH_MAX_ELEMS:
+        raise ValueError("flat_finish: the image {} must be the top-left crop of the stored planes {}, Hs * Ws < 2^31".format((H, W), (Hs, Ws)))
+    if isinstance(n_q, (bool, np.bool_)) or n_q not in (1, 2):
+        raise ValueError("flat_finish: n_q is 1 (flat) or 2 (flat, dark), not {!r}".format(n_q))
+    if isinstance(floor, (bool, np.bool_)) or not isinstance(floor, (int, float, np.integer, np.floating)) or not (0.0 < float(floor) < 1e300):
+        raise ValueError("flat_finish: floor must be positive and finite, not {!r}".format(floor))
+    return Hs, Ws, H, W, int(n_q), t, float(floor)
+
+
+def flat_finish_work_bytes(shape):
+    """Bytes of the work buffer of :meth:`DestripeEngine.flat_finish` for an image ``(H, W)``."""
+    H, W, _ = smooth_args(shape, [1.0])
+    n = ctypes.c_size_t()
+    if load_library().dsx_flat_finish_work_bytes(H, W, ctypes.byref(n)) != 0:
+        raise ValueError("flat_finish_work_bytes: bad shape {!r}".format(shape))
+    return int(n.value)
+
+
+def gauss_smooth_ref(plane, taps, radius=None):
+    """Host build of :meth:`DestripeEngine.gauss_smooth` (``dsx_gauss_smooth_f64_ref``): a float64 plane ``[H, W]`` and
+    taps ``t_0 .. t_r``; returns the smoothed float64 plane.  No GPU involved."""
+    lib = load_library()
+    a = np.ascontiguousarray(plane)
+    if a.dtype != np.float64 or a.ndim != 2:
+        raise ValueError("gauss_smooth takes one float64 plane [H, W], got {} {}".format(a.dtype, a.shape))
+    H, W, t = smooth_args(a.shape, taps, radius)
+    tmp, out = np.empty_like(a), np.empty_like(a)
+    vp = ctypes.c_void_p
+    rc = lib.dsx_gauss_smooth_f64_ref(a.ctypes.data_as(vp), H, W, t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                      len(t) - 1, tmp.ctypes.data_as(vp), out.ctypes.data_as(vp))  # fmt: skip
+    if rc != 0:
+        raise ValueError((lib.dsx_last_error(None) or b"gauss_smooth_ref failed").decode())
+    return out
+
+
+def flat_finish_ref(rank, valid, shape, taps, floor, radius=None):
+    """Host build of :meth:`DestripeEngine.flat_finish` (``dsx_flat_finish_ref``): ``rank`` uint16 ``[n_q, Hs, Ws]``
+    (flat, then dark), ``valid`` uint16 ``[Hs, Ws]``, the image ``shape = (H, W)`` their top-left crop.  Returns
+    ``(flat, dark)`` as float32 ``[H, W]``, ``dark`` ``None`` when ``n_q == 1``.  :class:`NoSeenPixel` when ``valid`` is 0
+    all over the image.  No GPU involved."""
+    lib = load_library()
+    R, v = np.ascontiguousarray(rank), np.ascontiguousarray(valid)
+    if R.dtype != np.uint16 or R.ndim != 3 or v.dtype != np.uint16 or v.shape != R.shape[1:]:
+        raise ValueError("flat_finish takes uint16 rank planes [n_q, Hs, Ws] and valid [Hs, Ws], got {} {} and {} {}".format(
+            R.dtype, R.shape, v.dtype, v.shape))  # fmt: skip
+    Hs, Ws, H, W, n_q, t, floor = flat_finish_args(R.shape[1:], shape, R.shape[0], taps, floor, radius)
+    flat = np.empty((H, W), np.float32)
+    dark = np.empty((H, W), np.float32) if n_q == 2 else None
+    vp = ctypes.c_void_p
+    rc = lib.dsx_flat_finish_ref(R.ctypes.data_as(vp), v.ctypes.data_as(vp), Hs, Ws, H, W, n_q,
+                                 t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(t) - 1, floor,
+                                 flat.ctypes.data_as(vp), dark.ctypes.data_as(vp) if n_q == 2 else None)  # fmt: skip
+    if rc == -8:
+        raise NoSeenPixel((lib.dsx_last_error(None) or b"").decode())
+    if rc != 0:
+        raise ValueError((lib.dsx_last_error(None) or b"flat_finish_ref failed").decode())
+    return flat, dark
 
 
 def _project_geometry(zyx):

@@ -4,12 +4,14 @@ The reference destripes sample tiles, fits a flat / dark / baseline to them with
 ``unify_fields``.  BaSiC is NOT restated here and nothing below imitates it.  The estimator of this module is stated by
 formulas (:func:`estimate_fields`): a per-pixel quantile of the destriped sample planes -- one order statistic per pixel
 across the stack, taken where the planes lie, in device memory (``csrc/dsx_stackrank.h``, integer-exact) -- followed by a
-Gaussian smoothing and a normalisation of that one plane on the host.  ``unify_fields`` is plain NumPy in the reference
-and is mirrored exactly.  Not verified against BaSiCPy: it is not installed where this was built.
+Gaussian smoothing and a normalisation of that one plane: in NumPy on the host (``finish="numpy"``, the default), or
+where the rank planes lie (``finish="native"``: ``csrc/dsx_smooth.h``, a float64 contract that the device kernels and a
+host build meet bit for bit).  ``unify_fields`` is plain NumPy in the reference and is mirrored exactly.  Not verified
+against BaSiCPy: it is not installed where this was built.
 
 Left out: BaSiC itself, fitting weights (``mask``), a per-image baseline (zeros are returned; ``flatfield_correction``
-treats ``None`` and zeros alike), more than 512 planes per stack, dtypes other than uint16, several ranks, a device
-smoothing kernel.
+treats ``None`` and zeros alike), more than 512 planes per stack, dtypes other than uint16, several ranks, a sigma
+above 64 on the native finish.
 """
 
 import os
@@ -25,9 +27,13 @@ from .mini_zarr import MiniZarrArray
 from .readers import imread
 
 MAX_PLANES = _engine.STACK_RANK_MAX_PLANES
-ESTIMATOR_OPTIONS = ("flat_quantile", "dark_quantile", "valid_range", "smoothing", "floor", "device")
+ESTIMATOR_OPTIONS = ("flat_quantile", "dark_quantile", "valid_range", "smoothing", "floor", "device", "finish")
+FINISH_ROUTES = ("numpy", "native")
 # what the last estimate_channel_flats of this process ran: planes per side, valid range, quantiles, seconds per stage
+# "finish": the route of the finish and the seconds of the rank and the finish steps, summed over the sides
 LAST_ESTIMATE = {}
+# what the last estimate_fields of this process ran: {"finish": route, "seconds": {"rank", "finish"}}
+LAST_FIELDS = {}
 
 
 class DeviceStack:
@@ -55,7 +61,8 @@ def quantile_milli(q, name="quantile"):
     return k
 
 
-def _estimator_options(flat_quantile=0.5, dark_quantile=None, valid_range=(0, 65535), smoothing=32.0, floor=0.1, device=0):
+def _estimator_options(flat_quantile=0.5, dark_quantile=None, valid_range=(0, 65535), smoothing=32.0, floor=0.1, device=0,
+                       finish="numpy"):
     """The options of :func:`estimate_fields`, checked (``ValueError``), before any library call."""
     qf = quantile_milli(flat_quantile, "flat_quantile")
     qd = None if dark_quantile is None else quantile_milli(dark_quantile, "dark_quantile")
@@ -73,8 +80,13 @@ def _estimator_options(flat_quantile=0.5, dark_quantile=None, valid_range=(0, 65
         raise ValueError("floor must be positive and finite, not {!r}".format(floor))
     if isinstance(device, (bool, np.bool_)) or not isinstance(device, (int, np.integer)) or device < 0:
         raise ValueError("device must be a GPU index, not {!r}".format(device))
+    if not isinstance(finish, str) or finish not in FINISH_ROUTES:
+        raise ValueError("finish must be one of {}, not {!r}".format(list(FINISH_ROUTES), finish))
+    if finish == "native" and smoothing > _engine.GAUSS_MAX_SIGMA:
+        raise ValueError("finish='native' takes a smoothing of at most {} pixels, not {!r}: use finish='numpy'".format(
+            _engine.GAUSS_MAX_SIGMA, smoothing))  # fmt: skip
     return {"flat_quantile": qf, "dark_quantile": qd, "valid_range": (lo, hi), "smoothing": smoothing, "floor": floor,
-            "device": int(device)}  # fmt: skip
+            "device": int(device), "finish": finish}  # fmt: skip
 
 
 def _check_option_names(options):
@@ -133,8 +145,40 @@ def _rank_planes(stack, q_milli, valid_range):
     return R, valid, a.shape[0]
 
 
+def _native_fields(stack, q_milli, opt):
+    """Rank and native finish: ``(flat, dark, valid, n, seconds of the rank step, seconds of the finish)``.  A
+    :class:`DeviceStack` is ranked and finished on the device and only ``flat``, ``dark`` and ``valid`` are downloaded; a
+    host array goes through the two host builds."""
+    _, taps = _engine.gauss_taps(opt["smoothing"])
+    if isinstance(stack, DeviceStack):
+        eng = stack.engine
+        Hs, Ws = stack.stored_shape
+        H, W = stack.shape
+        t0 = time.perf_counter()
+        d_out, d_valid = eng.stack_rank(stack.d_planes, stack.n, Hs * Ws, q_milli, opt["valid_range"])
+        d_flat = d_dark = None
+        try:
+            eng.sync()
+            t1 = time.perf_counter()
+            d_flat, d_dark = eng.flat_finish(d_out, d_valid, (Hs, Ws), (H, W), len(q_milli), taps, opt["floor"])
+            t2 = time.perf_counter()
+            flat = d_flat.download((H, W), np.float32)
+            dark = None if d_dark is None else d_dark.download((H, W), np.float32)
+            valid = np.ascontiguousarray(d_valid.download((Hs, Ws), np.uint16)[:H, :W])
+        finally:
+            for d in (d_out, d_valid, d_flat, d_dark):
+                if d is not None:
+                    d.free()
+        return flat, dark, valid, stack.n, t1 - t0, t2 - t1
+    t0 = time.perf_counter()
+    R, valid, n = _rank_planes(stack, q_milli, opt["valid_range"])
+    t1 = time.perf_counter()
+    flat, dark = _engine.flat_finish_ref(R, valid, valid.shape, taps, opt["floor"])
+    return flat, dark, valid, n, t1 - t0, time.perf_counter() - t1
+
+
 def estimate_fields(stack_or_device_stack, *, flat_quantile=0.5, dark_quantile=None, valid_range=(0, 65535),
-                    smoothing=32.0, floor=0.1, device=0):  # fmt: skip
+                    smoothing=32.0, floor=0.1, device=0, finish="numpy"):  # fmt: skip
     """Flat (and dark) field of a stack of destriped uint16 planes ``[n, H, W]``, ``n <= 512``.
 
     1. ``R_flat`` (and ``R_dark``): per pixel the ``flat_quantile`` (``dark_quantile``) of the values inside
@@ -148,10 +192,28 @@ def estimate_fields(stack_or_device_stack, *, flat_quantile=0.5, dark_quantile=N
     4. ``flatfield = float32(max(S / mean(S), floor))``; ``darkfield = float32(G(R_dark))`` when asked for, else ``None``.
     5. ``baseline``: float32 zeros ``[n]`` (BaSiC's per-image baseline is left out).
 
+    ``finish``: who runs steps 2 to 4.  ``"numpy"`` (the default): the lines above, in NumPy on the host.  ``"native"``:
+    the native finish of ``include/dsx.h`` -- the same steps with every float64 operation fixed (explicit fused
+    multiply-adds over the taps' centre and right half, the mean summed in 4096 strided lanes), ``smoothing <= 64``; on
+    the device, behind the rank kernel, for a :class:`DeviceStack` (only ``flat``, ``dark`` and ``valid`` are
+    downloaded), and by the host build of the same contract for a host array: the two agree bit for bit, and differ
+    from ``"numpy"`` by at most one float32 spacing.  :data:`LAST_FIELDS` records the route and the seconds of the rank
+    and the finish steps.
+
     Returns ``{"flatfield", "darkfield", "baseline", "valid"}``."""
-    opt = _estimator_options(flat_quantile, dark_quantile, valid_range, smoothing, floor, device)
+    opt = _estimator_options(flat_quantile, dark_quantile, valid_range, smoothing, floor, device, finish)
     q = [opt["flat_quantile"]] + ([] if opt["dark_quantile"] is None else [opt["dark_quantile"]])
+    if opt["finish"] == "native":
+        try:
+            flat, dark, valid, n, t_rank, t_finish = _native_fields(stack_or_device_stack, q, opt)
+        except _engine.NoSeenPixel:
+            raise ValueError("estimate_fields: no pixel has a value inside valid_range {}".format(opt["valid_range"])) from None
+        LAST_FIELDS.clear()
+        LAST_FIELDS.update({"finish": "native", "seconds": {"rank": t_rank, "finish": t_finish}})
+        return {"flatfield": flat, "darkfield": dark, "baseline": np.zeros(n, np.float32), "valid": valid}
+    t0 = time.perf_counter()
     R, valid, n = _rank_planes(stack_or_device_stack, q, opt["valid_range"])
+    t1 = time.perf_counter()
     seen = valid > 0
     if not seen.any():
         raise ValueError("estimate_fields: no pixel has a value inside valid_range {}".format(opt["valid_range"]))
@@ -164,6 +226,8 @@ def estimate_fields(stack_or_device_stack, *, flat_quantile=0.5, dark_quantile=N
     S = planes[0]
     flat = np.maximum(S / S.mean(), opt["floor"]).astype(np.float32)
     dark = planes[1].astype(np.float32) if len(planes) > 1 else None
+    LAST_FIELDS.clear()
+    LAST_FIELDS.update({"finish": "numpy", "seconds": {"rank": t1 - t0, "finish": time.perf_counter() - t1}})
     return {"flatfield": flat, "darkfield": dark, "baseline": np.zeros(n, np.float32), "valid": valid}
 
 
@@ -370,6 +434,7 @@ def estimate_channel_flats(zarr_dataset_path, channel_name, laser_tiles, paramet
 
     os.makedirs(output_folder, exist_ok=True)
     seconds = {"read": 0.0, "destripe": 0.0, "estimate": 0.0, "write": 0.0}
+    finish_seconds = {"rank": 0.0, "finish": 0.0}
     paths = []
     eng = _engine.DestripeEngine(opt["device"])
     try:
@@ -397,6 +462,8 @@ def estimate_channel_flats(zarr_dataset_path, channel_name, laser_tiles, paramet
                 t0 = time.perf_counter()
                 res = estimate_fields(DeviceStack(eng, d_stack, n, (Hs, Ws), (H, W)), **estimator_options)
                 seconds["estimate"] += time.perf_counter() - t0
+                for step in finish_seconds:
+                    finish_seconds[step] += LAST_FIELDS["seconds"][step]
             finally:
                 d_in.free()
                 d_stack.free()
@@ -411,5 +478,6 @@ def estimate_channel_flats(zarr_dataset_path, channel_name, laser_tiles, paramet
     LAST_ESTIMATE.update({"planes": {side: plans[side][2] for side in sides}, "valid_range": opt["valid_range"],
                           "quantiles": {"flat": opt["flat_quantile"] / 1000.0,
                                         "dark": None if opt["dark_quantile"] is None else opt["dark_quantile"] / 1000.0},
-                          "seconds": seconds, "paths": list(paths)})  # fmt: skip
+                          "seconds": seconds, "paths": list(paths),
+                          "finish": {"route": opt["finish"], "seconds": finish_seconds}})  # fmt: skip
     return paths

@@ -291,6 +291,43 @@ int dsx_stack_rank_u16_device(dsx_ctx* ctx, const void* d_planes, int n, size_t 
 int dsx_stack_rank_u16_ref(const void* planes, int n, size_t plane_elems, int lo, int hi, const int* q_milli, int n_q,
                            void* out, void* valid);
 
+/* The finish of a retrospective flat on the device (csrc/dsx_smooth.h): what flatfield_estimation.py of this project does
+ * to the rank planes of dsx_stack_rank_u16_* -- a masked median fill, scipy's Gaussian and a division by the mean -- where
+ * those planes lie.  It stands in for the BaSiC fit of the reference (flatfield_estimation.py:15-52).  The contract
+ * ("native finish") fixes every float64 operation, so the device and the host build agree bit for bit:
+ *   taps   radius r and t_0 .. t_r, the centre and the right half of the normalised, symmetric Gaussian (0 <= r <= 256)
+ *   fold   m(j): j' = j mod 2n, non-negative; m = j' if j' < n else 2n - 1 - j'      (np.pad(mode="symmetric"))
+ *   smooth along an axis of length n: acc = t_0 * a[i]; for k = 1 .. r: acc = fma(t_k, a[m(i - k)] + a[m(i + k)], acc);
+ *          axis 0 first, then axis 1
+ *   fill   per rank plane, over the H x W top-left crop of the stored Hs x Ws plane: seen = valid > 0; fill = the median
+ *          of R[seen] (the middle value, or the mean of the two middle values: exact from a 65 536-bin count);
+ *          a[y, x] = seen ? double(R) : fill
+ *   mean   S = the smoothed flat plane, row-major, N = H * W: p_j = the sum of S[i] over i = j (mod 4096) in increasing
+ *          i from 0.0; mean = (p_0 + p_1 + ... + p_4095, left to right) / N
+ *   result flat = float32(q < floor ? floor : q), q = S / mean (IEEE division); dark = float32(S_dark) when n_q == 2
+ * 1 <= H, W, H * W < 2^31 (and Hs >= H, Ws >= W, Hs * Ws < 2^31), 0 <= radius <= 256, n_q 1 or 2, floor positive and
+ * finite, non-NULL aligned pointers: anything else is DSX_EINVAL before anything is launched. */
+/* flatfield_estimation.py:15-52 (the smoothing of this project's estimator): the two passes alone on float64 [H][W]
+ * device planes; d_tmp is a third plane of that size, d_out may be d_in.  Asynchronous on the context stream. */
+int dsx_gauss_smooth_f64_device(dsx_ctx* ctx, const void* d_in, int H, int W, const double* taps /* host, [radius + 1] */,
+                                int radius, void* d_tmp, void* d_out);
+/* flatfield_estimation.py:15-52: the host build of the two passes, plain C++ (host pointers, synchronous). */
+int dsx_gauss_smooth_f64_ref(const void* in, int H, int W, const double* taps, int radius, void* tmp, void* out);
+/* Bytes of the work buffer dsx_flat_finish_device takes for an H x W image. */
+int dsx_flat_finish_work_bytes(int H, int W, size_t* bytes);
+/* flatfield_estimation.py:15-52: fill, smooth, mean and result of the contract above, from d_rank (uint16
+ * [n_q][Hs * Ws]: flat, then dark) and d_valid (uint16 [Hs * Ws]) to d_flat (float32 [H][W]) and d_dark (float32 [H][W];
+ * not touched and may be NULL when n_q == 1).  d_work: dsx_flat_finish_work_bytes bytes, 16-byte aligned.  The launches
+ * run on the context stream with no host round trip between them; the call then reads the seen count once and returns
+ * DSX_EVALUE when no pixel of the image is seen (the results then hold nothing of use). */
+int dsx_flat_finish_device(dsx_ctx* ctx, const void* d_rank, const void* d_valid, int Hs, int Ws, int H, int W, int n_q,
+                           const double* taps /* host, [radius + 1] */, int radius, double floor, void* d_flat, void* d_dark,
+                           void* d_work);
+/* flatfield_estimation.py:15-52: the host build of the finish, plain C++ (host pointers; DSX_EVALUE as above, with
+ * nothing written). */
+int dsx_flat_finish_ref(const void* rank, const void* valid, int Hs, int Ws, int H, int W, int n_q, const double* taps,
+                        int radius, double floor, void* flat, void* dark);
+
 /* QC projections of a pass: the three maximum-intensity projections of a uint16 volume and the three sum projections,
  * whose row sums before and after the filter are the stripe signature and what became of it (csrc/dsx_project.h).  The
  * reference leaves only a resource plot in its results folder (zarr_destriper.py:1202-1211).  A volume v[., H, W]
