@@ -31,6 +31,7 @@
 #include "dsx_smooth.h"
 #include "dsx_volhist.h"
 #include "dsx_project.h"
+#include "dsx_digest.h"
 #include "dsx_wavelet.h"
 #include "dsx_plan.h"
 #include "dsx_chain.h"
@@ -2307,6 +2308,52 @@ int dsx_project_u16_ref(const void* planes, int Z, int H, int W, const dsx_proje
   if (Z == 0) return DSX_OK;
   const dsx::pj::Outputs o = {p->max_z, p->sum_z, p->max_y, p->sum_y, p->max_x, p->sum_x};
   dsx::pj::project_host((const uint16_t*)planes, Z, H, W, o, z_off, first != 0);
+  return DSX_OK;
+}
+
+/* ---- per-chunk content digests of bricks in chunk order (dsx_digest.h): the manifest of a store pass -------------- */
+namespace {
+const char* digest_args(const void* bricks, int n0, int n1, int n2, int c0, int c1, int c2, int v0, int v1, int v2,
+                        const void* out) {
+  if (const char* e = dsx::dg::check_geometry(n0, n1, n2, c0, c1, c2, v0, v1, v2)) return e;
+  if (!bricks || !out) return "digest: NULL pointer";
+  if ((uintptr_t)bricks & 1) return "digest: uint16 voxels must be 2-byte aligned";
+  if ((uintptr_t)out & 7) return "digest: the records must be 8-byte aligned";
+  return nullptr;
+}
+}  // namespace
+
+int dsx_brick_digest_u16_device(dsx_ctx* ctx, const void* d_bricks, int n0, int n1, int n2, int c0, int c1, int c2, int v0,
+                                int v1, int v2, void* d_out, int stream_id) {
+  namespace dg = dsx::dg;
+  if (!ctx) return DSX_EINVAL;
+  if (!stream_id_ok(stream_id)) return fail(ctx, DSX_EINVAL, "digest: unknown stream id");
+  if (const char* e = digest_args(d_bricks, n0, n1, n2, c0, c1, c2, v0, v1, v2, d_out)) return fail(ctx, DSX_EINVAL, e);
+  const int64_t bricks = (int64_t)n0 * n1 * n2;
+  const dg::Geometry g = dg::geometry(bricks, c0, c1, c2);
+  dg::DigestArgs a;
+  a.bricks = (const uint16_t*)d_bricks;
+  a.out = (unsigned long long*)d_out;
+  a.n1 = n1; a.n2 = n2;
+  a.c0 = c0; a.c1 = c1; a.c2 = c2;
+  a.v0 = v0; a.v1 = v1; a.v2 = v2;
+  a.lx_log2 = 0;
+  while ((1 << a.lx_log2) < g.lx) ++a.lx_log2;
+  a.segs = (unsigned)g.segs;
+  DSX_HIP(hipSetDevice(ctx->device));
+  hipStream_t s = pick_stream(ctx, stream_id);
+  DSX_HIP(hipMemsetAsync(d_out, 0, (size_t)bricks * dg::kDgRecord * 8, s));
+  const bool vec = c2 % 8 == 0 && ((uintptr_t)d_bricks & 15) == 0;
+  if (vec) hipLaunchKernelGGL(dg::k_brick_digest_u16<true>, dim3((unsigned)g.grid), dim3(dg::kDgThreads), 0, s, a);
+  else hipLaunchKernelGGL(dg::k_brick_digest_u16<false>, dim3((unsigned)g.grid), dim3(dg::kDgThreads), 0, s, a);
+  DSX_HIP(hipGetLastError());
+  return DSX_OK;
+}
+
+int dsx_brick_digest_u16_ref(const void* bricks, int n0, int n1, int n2, int c0, int c1, int c2, int v0, int v1, int v2,
+                             void* out) {
+  if (const char* e = digest_args(bricks, n0, n1, n2, c0, c1, c2, v0, v1, v2, out)) return fail(nullptr, DSX_EINVAL, e);
+  dsx::dg::grid_digest_host((const uint16_t*)bricks, n0, n1, n2, c0, c1, c2, v0, v1, v2, (uint64_t*)out);
   return DSX_OK;
 }
 

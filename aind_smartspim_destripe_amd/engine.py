@@ -34,6 +34,9 @@ TASK_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<u4"), ("dst
 
 COMM_ID_BYTES = 128
 VOLHIST_BINS = 65536  # one bin per uint16 value (dsx_volhist_*)
+# one record of dsx_brick_digest_u16_*: the valid voxels of a chunk, their sum and their weighted sum (mod 2^64)
+DIGEST_DTYPE = np.dtype([("count", "<u8"), ("sum", "<u8"), ("wsum", "<u8")])
+DIGEST_MAX_BRICK = 1 << 31  # voxels per brick
 STACK_RANK_MAX_PLANES = 512  # planes, quantiles and elements per plane of one dsx_stack_rank_u16_* call
 STACK_RANK_MAX_QUANTILES = 4
 STACK_RANK_MAX_ELEMS = (1 << 31) - 1
@@ -75,6 +78,7 @@ EXPORTED_SYMBOLS = [
     "dsx_gauss_smooth_f64_device", "dsx_gauss_smooth_f64_ref",
     "dsx_flat_finish_work_bytes", "dsx_flat_finish_device", "dsx_flat_finish_ref",
     "dsx_project_work_bytes", "dsx_project_u16_device", "dsx_project_u16_ref",
+    "dsx_brick_digest_u16_device", "dsx_brick_digest_u16_ref",
     "dsx_plan_streaks_opts", "dsx_streaks_blend_ref",
     "dsx_set_rotate", "dsx_rot90_device", "dsx_rot90_ref",
     "dsx_plan_lightsheet", "dsx_lightsheet_ref", "dsx_get_lightsheet_planes",
@@ -294,6 +298,8 @@ def load_library(path=None):
     lib.dsx_project_work_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     lib.dsx_project_u16_device.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(_Projection), i32, i32, vp]
     lib.dsx_project_u16_ref.argtypes = [vp, i32, i32, i32, ctypes.POINTER(_Projection), i32, i32]
+    lib.dsx_brick_digest_u16_device.argtypes = [vp, vp] + [i32] * 9 + [vp, i32]
+    lib.dsx_brick_digest_u16_ref.argtypes = [vp] + [i32] * 9 + [vp]
     f64 = ctypes.c_double
     lib.dsx_plan_lightsheet.argtypes = [vp, i32, i32, i32, f64, i32, i32, f64, vp, vp]
     lib.dsx_lightsheet_ref.argtypes = [vp, i32, i32, f64, i32, i32, f64, vp, vp, vp, vp, vp, i32]
@@ -1150,6 +1156,29 @@ class DestripeEngine:
         self.sync()
         return {name: bufs[name].download(shape, dtype) for name, shape, dtype in projection_shapes(zyx)}
 
+    # -- per-chunk content digests of bricks in chunk order (the manifest of a store pass) -------
+    def brick_digest(self, d_bricks, grid, chunks, valid, d_out, stream=STREAM_COMPUTE, offset=0):
+        """Records of the ``grid = (n0, n1, n2)`` bricks of ``chunks = (c0, c1, c2)`` uint16 voxels that lie back to back
+        at a :class:`DeviceBuffer` or a device address (``dsx_brick_digest_u16_device``; ``csrc/dsx_digest.h``);
+        ``valid = (v0, v1, v2)`` are the voxels the buffer covers from its chunk-aligned origin.  ``d_out`` receives
+        ``prod(grid)`` records of :data:`DIGEST_DTYPE`, from byte ``offset`` on.  What the kernel does not take is a
+        ``ValueError`` before any launch.  Asynchronous on ``stream``; never waits."""
+        n, c, v = digest_geometry(grid, chunks, valid)
+        ptr = getattr(d_bricks, "ptr", d_bricks)
+        nbytes = getattr(d_bricks, "nbytes", None)
+        bricks = n[0] * n[1] * n[2]
+        if nbytes is not None and 2 * bricks * c[0] * c[1] * c[2] > nbytes:
+            raise ValueError("brick_digest: {} bricks of {} voxels do not fit a buffer of {} bytes".format(bricks, c, nbytes))
+        offset = int(offset)
+        if offset < 0 or offset % 8 or offset + bricks * DIGEST_DTYPE.itemsize > d_out.nbytes:
+            raise ValueError("brick_digest: {} records at byte {} do not fit d_out ({} bytes; the offset a multiple of 8)"
+                             .format(bricks, offset, d_out.nbytes))  # fmt: skip
+        rc = self._lib.dsx_brick_digest_u16_device(self._ctx, ctypes.c_void_p(ptr), *n, *c, *v,
+                                                   ctypes.c_void_p(d_out.ptr + offset), int(stream))  # fmt: skip
+        if rc == -1:
+            raise ValueError(self._lib.dsx_last_error(self._ctx).decode())
+        self._check(rc)
+
     def foreground_background(self, image, cutoff, want_mask=True):
         """``(fore_mean, back_mean, mask uint8)`` of a host image (uint16 / float32, any shape)."""
         a = np.ascontiguousarray(image)
@@ -1537,6 +1566,41 @@ def project_ref(planes, acc=None, z_off=0):
     if rc != 0:
         raise ValueError((lib.dsx_last_error(None) or b"project_ref failed").decode())
     return acc
+
+
+def digest_geometry(grid, chunks, valid):
+    """``(grid, chunks, valid)`` of a digest call as three int triples; ``ValueError`` for what is no such geometry."""
+    out = []
+    for name, t in (("grid", grid), ("chunks", chunks), ("valid", valid)):
+        t = tuple(int(x) for x in t)
+        if len(t) != 3 or any(x < 1 or x >= 1 << 31 for x in t):
+            raise ValueError("digest: {} must be three positive int32 values, got {}".format(name, t))
+        out.append(t)
+    return out
+
+
+def brick_digest_ref(bricks, grid, chunks, valid):
+    """Host build of the chunk digests (``dsx_brick_digest_u16_ref``): ``bricks`` holds ``prod(grid)`` bricks of
+    ``chunks`` uint16 voxels back to back (any shape of that many elements; a view that starts at an odd element is
+    fine), ``valid`` the voxels they cover along each axis.  Returns ``prod(grid)`` records of :data:`DIGEST_DTYPE`."""
+    lib = load_library()
+    n, c, v = digest_geometry(grid, chunks, valid)
+    a = np.asarray(bricks)
+    if a.dtype != np.uint16:
+        raise ValueError("the digest takes uint16 voxels, got {}".format(a.dtype))
+    if not a.flags["C_CONTIGUOUS"]:
+        a = np.ascontiguousarray(a)
+    count = n[0] * n[1] * n[2]
+    out = np.zeros(count, DIGEST_DTYPE)
+    brick = c[0] * c[1] * c[2]
+    if brick > DIGEST_MAX_BRICK:
+        raise ValueError("digest: a brick holds more than 2^31 voxels")
+    if a.size < count * brick:
+        raise ValueError("digest: {} voxels given, the grid holds {}".format(a.size, count * brick))
+    rc = lib.dsx_brick_digest_u16_ref(a.ctypes.data_as(ctypes.c_void_p), *n, *c, *v, out.ctypes.data_as(ctypes.c_void_p))
+    if rc != 0:
+        raise ValueError((lib.dsx_last_error(None) or b"brick_digest_ref failed").decode())
+    return out
 
 
 def streaks_blend_ref(x, f, b, t, crossover=10.0, bands="both", smoothing=0.0, flatfield=None, darkfield=None,

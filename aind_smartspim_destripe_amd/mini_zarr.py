@@ -22,6 +22,11 @@ import numpy as np
 CODEC_RAW, CODEC_ZLIB, CODEC_BLOSC = 0, 1, 2  # DSX_CODEC_* of include/dsx.h
 # numcodecs.Blosc(cname="zstd", clevel=3, shuffle=Blosc.SHUFFLE).get_config(), zarr_destriper.py:1066-1074
 BLOSC_ZSTD = {"id": "blosc", "cname": "zstd", "clevel": 3, "shuffle": 1, "blocksize": 0}
+# The digest manifest of an array (csrc/dsx_digest.h, integrity.py): two files in the array's folder that Zarr readers
+# ignore.  The JSON names the geometry the records belong to; the binary file holds one record (count, sum, wsum: three
+# little-endian uint64) per chunk in C order of the chunk grid, zero-filled at creation: count == 0 is "not recorded".
+DIGEST_JSON, DIGEST_BIN = ".dsxdigest.json", ".dsxdigest.bin"
+DIGEST_FORMAT, DIGEST_ALGORITHM, DIGEST_RECORD_BYTES = 1, "dsx-sm64-rowcol", 24
 
 
 def _native():
@@ -65,6 +70,20 @@ def blosc_encode(raw, typesize, clevel=3, shuffle=True, cname="zstd"):
     return out.raw[: n.value]
 
 
+def digest_grid_of(shape, chunks, dtype):
+    """The chunk grid ``(g0, g1, g2)`` a digest manifest covers: a uint16 array whose last three axes are ``(Z, Y, X)``
+    and whose leading axes have length 1 with chunk 1.  Anything else is a ``ValueError``."""
+    shape, chunks = tuple(int(x) for x in shape), tuple(int(x) for x in chunks)
+    if np.dtype(dtype) != np.uint16:
+        raise ValueError("digests cover uint16 arrays, not {}".format(np.dtype(dtype)))
+    if len(shape) < 3 or len(chunks) != len(shape) or any(n != 1 or c != 1 for n, c in zip(shape[:-3], chunks[:-3])):
+        raise ValueError("digests need (Z, Y, X) as the last three axes and leading axes of length 1 with chunk 1, "
+                         "got shape {} chunks {}".format(shape, chunks))  # fmt: skip
+    if any(n < 1 or c < 1 for n, c in zip(shape[-3:], chunks[-3:])):
+        raise ValueError("digests need a non-empty array, got shape {} chunks {}".format(shape, chunks))
+    return tuple(-(-n // c) for n, c in zip(shape[-3:], chunks[-3:]))
+
+
 class MiniZarrArray:
     def __init__(self, path, meta):
         self.path = str(path)
@@ -92,6 +111,7 @@ class MiniZarrArray:
             raise NotImplementedError("only C-order arrays without filters are supported")
         self.ndim = len(self.shape)
         self._dirs_made = set()
+        self.digest_grid = self._load_manifest()  # (g0, g1, g2) of an array that keeps a digest manifest, else None
 
     @property
     def codec(self):
@@ -144,10 +164,21 @@ class MiniZarrArray:
 
     @classmethod
     def create(cls, path, shape, chunks, dtype, compressor=None, dimension_separator="/", fill_value=0,
-               overwrite=True):  # fmt: skip
+               overwrite=True, digests=False):  # fmt: skip
+        """``digests``: keep a digest manifest next to the chunks (``.dsxdigest.json`` / ``.dsxdigest.bin``): one record
+        per chunk, kept truthful by every write through this class and filled by the store pass from the device.  Needs
+        a uint16 array whose leading axes (all but the last three) have length 1 and chunk 1, else ``ValueError``.  A
+        manifest left by an earlier array at ``path`` is removed whenever the array is (re)created."""
+        if digests:
+            digest_grid_of(shape, chunks, dtype)  # (refuses what the digest does not cover before anything is touched)
         os.makedirs(path, exist_ok=True)
         if not overwrite and os.path.exists(os.path.join(path, ".zarray")):
             raise FileExistsError(path)
+        for name in (DIGEST_JSON, DIGEST_BIN):  # an overwritten store never keeps an old manifest
+            try:
+                os.remove(os.path.join(path, name))
+            except FileNotFoundError:
+                pass
         comp = cls._compressor_meta(compressor)
         meta = {
             "zarr_format": 2,
@@ -163,6 +194,15 @@ class MiniZarrArray:
         # written to a temporary name and renamed: a concurrent reader (another rank polling for the array)
         # sees the metadata either whole or not at all
         tmp = os.path.join(path, ".zarray.tmp.{}".format(os.getpid()))
+        if digests:  # before .zarray appears: a rank that sees the array sees its manifest
+            grid = digest_grid_of(shape, chunks, dtype)
+            with open(os.path.join(path, DIGEST_BIN), "wb") as f:
+                f.truncate(grid[0] * grid[1] * grid[2] * DIGEST_RECORD_BYTES)
+            with open(tmp, "w") as f:
+                json.dump({"format": DIGEST_FORMAT, "algorithm": DIGEST_ALGORITHM, "shape": list(shape),
+                           "chunks": list(chunks), "dtype": np.dtype(dtype).str, "fill_value": fill_value,
+                           "grid": list(grid)}, f)  # fmt: skip
+            os.replace(tmp, os.path.join(path, DIGEST_JSON))
         with open(tmp, "w") as f:
             json.dump(meta, f)
         os.replace(tmp, os.path.join(path, ".zarray"))
@@ -182,6 +222,74 @@ class MiniZarrArray:
         if ok and compressor is not Ellipsis:
             ok = self.compressor_meta == self._compressor_meta(compressor)
         return ok
+
+    # -- digest manifest ----------------------------------------------------------------------
+    def _load_manifest(self):
+        """The chunk grid of this array's manifest, or ``None``: no manifest, or one of another array (which a reader
+        must not trust; ``create`` removes it)."""
+        try:
+            with open(os.path.join(self.path, DIGEST_JSON)) as f:
+                man = json.load(f)
+        except (FileNotFoundError, ValueError):
+            return None
+        try:
+            grid = digest_grid_of(self.shape, self.chunks, self.dtype)
+        except ValueError:
+            return None
+        same = (man.get("format") == DIGEST_FORMAT and man.get("algorithm") == DIGEST_ALGORITHM
+                and tuple(man.get("shape", ())) == self.shape and tuple(man.get("chunks", ())) == self.chunks
+                and man.get("dtype") == self.dtype.str and tuple(man.get("grid", ())) == grid
+                and (man.get("fill_value", 0) or 0) == self.fill_value)  # fmt: skip
+        return grid if same and os.path.exists(os.path.join(self.path, DIGEST_BIN)) else None
+
+    def digest_extents(self, idx3):
+        """Valid extents of the chunk at grid position ``idx3`` (last three axes): the part inside the array."""
+        return tuple(min(c, n - g * c) for c, n, g in zip(self.chunks[-3:], self.shape[-3:], idx3))
+
+    def digest_records(self):
+        """The manifest's records: ``engine.DIGEST_DTYPE[g0 * g1 * g2]`` in C order of the chunk grid (a copy);
+        ``count == 0`` marks a chunk nobody recorded.  ``ValueError`` when the array keeps no manifest."""
+        from . import engine
+
+        if self.digest_grid is None:
+            raise ValueError("{} keeps no digest manifest".format(self.path))
+        n = int(np.prod(self.digest_grid))
+        rec = np.fromfile(os.path.join(self.path, DIGEST_BIN), dtype=engine.DIGEST_DTYPE)
+        if rec.size != n:
+            raise ValueError("{}: {} records, the chunk grid has {}".format(os.path.join(self.path, DIGEST_BIN), rec.size, n))
+        return rec
+
+    def set_digest_records(self, first_chunk_row, records):
+        """Store the records of whole chunk rows (a row: the ``g1 * g2`` chunks of one z position) from chunk row
+        ``first_chunk_row`` on: one contiguous byte range of the file, so writers of disjoint rows -- the blocks of a
+        pass, the ranks of a job -- never touch each other's bytes and nothing is merged."""
+        from . import engine
+
+        if self.digest_grid is None:
+            raise ValueError("{} keeps no digest manifest".format(self.path))
+        rec = np.ascontiguousarray(records, dtype=engine.DIGEST_DTYPE).reshape(-1)
+        row = self.digest_grid[1] * self.digest_grid[2]
+        first = int(first_chunk_row)
+        if first < 0 or rec.size % row or first + rec.size // row > self.digest_grid[0]:
+            raise ValueError("digest records: {} records from chunk row {} do not fit the grid {}".format(
+                rec.size, first, self.digest_grid))  # fmt: skip
+        self._put_records(first * row, rec)
+
+    def _put_records(self, first_chunk, rec):
+        fd = os.open(os.path.join(self.path, DIGEST_BIN), os.O_WRONLY)
+        try:
+            os.pwrite(fd, rec.tobytes(), first_chunk * DIGEST_RECORD_BYTES)
+        finally:
+            os.close(fd)
+
+    def _record_chunk(self, idx, block):
+        """(an array with a manifest) The record of the chunk ``block`` about to be stored at ``idx``, host build."""
+        from . import engine
+
+        idx3 = tuple(int(i) for i in idx[-3:])
+        rec = engine.brick_digest_ref(block, (1, 1, 1), self.chunks[-3:], self.digest_extents(idx3))
+        g = self.digest_grid
+        self._put_records((idx3[0] * g[1] + idx3[1]) * g[2] + idx3[2], rec)
 
     # -- chunk io -----------------------------------------------------------------------------
     def _chunk_path(self, idx):
@@ -224,11 +332,13 @@ class MiniZarrArray:
         if d not in self._dirs_made:
             os.makedirs(d, exist_ok=True)
             self._dirs_made.add(d)
-        raw = memoryview(np.ascontiguousarray(block, dtype=self.dtype)).cast("B")
-        raw = self._encode(raw)
+        block = np.ascontiguousarray(block, dtype=self.dtype)
+        raw = self._encode(memoryview(block).cast("B"))
         with open(p + ".tmp", "wb", buffering=0) as f:
             f.write(raw)
         os.replace(p + ".tmp", p)
+        if self.digest_grid is not None:  # the manifest stays truthful whoever writes the chunk
+            self._record_chunk(idx, block)
 
     # -- slicing ------------------------------------------------------------------------------
     def _normalize(self, key):

@@ -189,7 +189,7 @@ def compute_pyramid(data, n_lvls, scale_axis, chunks="auto", device=0, engine=No
 
 def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_levels=3, chunks=(1, 1, 64, 128, 128),
                        compressor="blosc", device=0, slab_planes=None, pipelined=False, device_codec=False,
-                       device_decode=False, io_threads=None):  # fmt: skip
+                       device_decode=False, io_threads=None, digests=False):  # fmt: skip
     """Level loop of ``compute_multiscale`` (``zarr_destriper.py:746-782``) over Zarr-v2 directory stores
     (``zarr_destriper.compute_multiscale`` is the entry point with the reference's signature and calls this):
     writes ``<group_path>/<i>`` for ``i = 1 .. n_levels - 1`` (uint16, ``"/"`` separator), every level from the
@@ -210,12 +210,17 @@ def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_leve
     Blosc decode of level 0 and the Blosc-zstd encode of the levels to the GPU; they need a Blosc uint16 input / a
     Blosc-zstd uint16 output with byte shuffle, and ``pipelined``.  ``slab_planes`` is ignored then.
     :data:`LAST_PYRAMID` holds what the call did.
+
+    ``digests``: every level is created with a digest manifest (``MiniZarrArray.create(digests=True)``).  The slab route
+    fills it through the array's own writes (the host build); the pipelined route digests every finished chunk row on
+    the device where it lies (``dsx_brick_digest_u16_device``, behind the pyramid kernel and before the encoder) and
+    the writer of the row stores its records.  Off: no launch, allocation or file differs.
     """
     scale = check_scale_factor(scale_factor)
     fz, fy, fx = scale
     if pipelined:
         return _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, device, device_codec, device_decode,
-                                io_threads, scale)  # fmt: skip
+                                io_threads, scale, bool(digests))  # fmt: skip
     if device_codec is not False or device_decode is not False:
         raise ValueError("device_codec / device_decode need pipelined=True: the slab route of write_pyramid_levels has no "
                          "device codecs")  # fmt: skip
@@ -236,7 +241,7 @@ def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_leve
             out_shape = lead + out_zyx
             ck = tuple(min(c, n) for c, n in zip(tuple(chunks)[-len(out_shape):], out_shape))
             dst = MiniZarrArray.create(os.path.join(group_path, str(i)), out_shape, ck, np.uint16,
-                                       compressor=compressor, dimension_separator="/")  # fmt: skip
+                                       compressor=compressor, dimension_separator="/", digests=bool(digests))  # fmt: skip
             slab = int(slab_planes) if slab_planes else fz * ck[-3]
             slab += -slab % fz
             d_src = eng.alloc(slab * Y * X * 2)
@@ -258,14 +263,16 @@ def write_pyramid_levels(level0_path, group_path, scale_factor=(2, 2, 2), n_leve
         eng.close()
     LAST_PYRAMID.clear()
     LAST_PYRAMID.update(route="slabs", block_z=None, levels=list(range(1, len(shapes) + 1)), decode_routes=None, read_s=None,
-                        scale=scale, write_s=None, upload_bytes=None, download_bytes=None, seconds=time.perf_counter() - t_start)  # fmt: skip
+                        scale=scale, write_s=None, upload_bytes=None, download_bytes=None, seconds=time.perf_counter() - t_start,
+                        digests=bool(digests))  # fmt: skip
     return shapes
 
 
 # ---- the stand-alone pyramid in one pipelined pass (write_pyramid_levels(pipelined=True)) ----------------------------
 # What the last write_pyramid_levels call of this process did: route ("pipelined" / "slabs"), block_z, levels,
 # scale ((fz, fy, fx)), decode_routes ({"device", "host", "fill"}: level-0 chunks by where they were decoded), read_s / write_s (time inside
-# the I/O stages), upload_bytes / download_bytes over the host link, seconds.  The slab route fills route, levels, seconds.
+# the I/O stages), upload_bytes / download_bytes over the host link, seconds, digests (were manifests written).  The slab
+# route fills route, levels, seconds, digests.
 LAST_PYRAMID = {}
 
 
@@ -298,8 +305,10 @@ class _PipelinedPyramid:
 
     N_BUF = 2
 
-    def __init__(self, eng, src, levels, arrays, block_z, io_threads, codec_mode=None, decode_mode=None, scale=(2, 2, 2)):
+    def __init__(self, eng, src, levels, arrays, block_z, io_threads, codec_mode=None, decode_mode=None, scale=(2, 2, 2),
+                 digests=False):  # fmt: skip
         self.eng, self.src, self.levels, self.arrays, self.block_z = eng, src, levels, arrays, int(block_z)
+        self.digests = bool(digests)
         self.scale = tuple(scale)
         self.codec_mode, self.decode_mode, self.io_threads = codec_mode, decode_mode, int(io_threads)
         self.zyx = tuple(int(n) for n in src.shape[-3:])
@@ -343,6 +352,13 @@ class _PipelinedPyramid:
                 self.offsets.append([self._host(8 * (ny * nx + 1)).array((ny * nx + 1,), np.int64) for _ in R])
             else:
                 self.stage_row.append([self._host(ny * nx * brick * 2).array((ny, nx, brick), np.uint16) for _ in R])
+        # digests: one record per chunk of a row, taken on the device and carried to the row's writer with its offsets
+        self.d_dig, self.dig = [], []
+        if self.digests:
+            rec = _engine.DIGEST_DTYPE
+            for ny, nx, _ in self.grid:
+                self.d_dig.append([self._dev(ny * nx * rec.itemsize) for _ in R])
+                self.dig.append([self._host(ny * nx * rec.itemsize).array((ny * nx,), rec) for _ in R])
         work = _engine.pyramid_work_bytes((self.block_z, H, W), len(levels) + 1, self.scale)
         self.d_work = self._dev(work) if work else None
         self.cur, self.flushes = [0] * len(levels), [[] for _ in R]
@@ -416,8 +432,15 @@ class _PipelinedPyramid:
                 self.eng.io_write_chunks(paths, [self.stage_row[i][j][y, x] for y, x in idx], threads=self.io_threads,
                                          zlib_level=-1 if comp is None else int(comp[1]),
                                          blosc=arr.blosc_write_params() if comp and comp[0] == "blosc" else None)  # fmt: skip
+            if self.digests:  # behind the chunk files they describe
+                self._write_digests(flushes)
         finally:
             self.timing["write_s"] += time.perf_counter() - t0
+
+    def _write_digests(self, flushes):
+        """(digests) The records of the rows that left with a block, each into its own range of its level's manifest."""
+        for i, j, row in flushes:
+            self.arrays[i].set_digest_records(row, self.dig[i][j])
 
     # -- device stages (asynchronous) ----------------------------------------------------------
     def _submit_in(self, k, nbz):
@@ -459,6 +482,10 @@ class _PipelinedPyramid:
             if not s.flush:
                 continue
             j = cur[i]
+            if self.digests:  # the finished row where it lies, before the encoder reads it
+                lv = self.levels[i]
+                eng.brick_digest(self.d_row[i][j], (1,) + self.grid[i][:2], lv.chunks,
+                                 (min(lv.chunks[0], lv.shape[0] - s.row * lv.chunks[0]),) + tuple(lv.shape[1:]), self.d_dig[i][j])
             if self.codec_mode is not None:
                 ny, nx, brick = self.grid[i]
                 eng.blosc_encode_device(self.d_row[i][j], ny * nx, brick * 2, self.d_frames[i][j], self.d_offsets[i][j],
@@ -473,6 +500,9 @@ class _PipelinedPyramid:
             else:
                 eng.copy_d2h_async(self.stage_row[i][j], self.d_row[i][j], D)
                 self.timing["download_bytes"] += self.stage_row[i][j].nbytes
+            if self.digests:
+                eng.copy_d2h_async(self.dig[i][j], self.d_dig[i][j], D)
+                self.timing["download_bytes"] += self.dig[i][j].nbytes
         eng.event_record(self.N_BUF + k, D)  # the rows (or their frame offsets) and the statuses of block b are here
 
     def _fetch_frames(self, k):
@@ -544,7 +574,7 @@ class _PipelinedPyramid:
 
 
 def _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, device, device_codec, device_decode, io_threads,
-                     scale=(2, 2, 2)):  # fmt: skip
+                     scale=(2, 2, 2), digests=False):  # fmt: skip
     from . import zarr_destriper as zd
 
     t_start = time.perf_counter()
@@ -565,7 +595,7 @@ def _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, devi
         if len(ck) != len(out_shape) or ck[-3:] != lv.chunks:
             raise ValueError("chunks {} do not cover the axes of a level of shape {}".format(tuple(chunks), out_shape))
         arrays.append(MiniZarrArray.create(os.path.join(group_path, str(lv.level)), out_shape, ck, np.uint16,
-                                           compressor=compressor, dimension_separator="/"))  # fmt: skip
+                                           compressor=compressor, dimension_separator="/", digests=digests))  # fmt: skip
         shapes.append(out_shape)
     if codec_mode is not None and arrays:
         if not zd.device_codec_output_ok(arrays[0]):
@@ -575,12 +605,12 @@ def _write_pipelined(level0_path, group_path, n_levels, chunks, compressor, devi
         io_threads = zd.default_io_threads(1)
     LAST_PYRAMID.clear()
     LAST_PYRAMID.update(route="pipelined", block_z=block_z, levels=[lv.level for lv in levels], decode_routes=None, scale=scale,
-                        read_s=0.0, write_s=0.0, upload_bytes=0, download_bytes=0, seconds=None)  # fmt: skip
+                        read_s=0.0, write_s=0.0, upload_bytes=0, download_bytes=0, seconds=None, digests=bool(digests))  # fmt: skip
     if levels:
         eng = _engine.DestripeEngine(device)
         pipe = None
         try:
-            pipe = _PipelinedPyramid(eng, src, levels, arrays, block_z, io_threads, codec_mode, decode_mode, scale)
+            pipe = _PipelinedPyramid(eng, src, levels, arrays, block_z, io_threads, codec_mode, decode_mode, scale, digests)
             try:
                 pipe.run()
             finally:

@@ -408,9 +408,31 @@ class _DeviceBlocks:
         # destripe_zarr_store(projections=...): {"output" / "input": device arrays of the rank's z range}, its first
         # plane and the work buffer of one block (eng.project); owned by the call, not by the cached buffers
         self.proj, self.proj_z0, self.proj_work = None, 0, None
+        # destripe_zarr_store(digests=True): one record per output chunk of a block and per chunk of a pyramid row, taken
+        # on the device behind the re-tiling / pyramid kernel (brick_digest) and carried to the block's writer with the
+        # frame offsets (or the bricks).  Allocated by the first call that asks (enable_digests), kept with the buffers.
+        self.digests = False
+        self.dig_bufs, self.d_dig, self.dig, self.d_pdig, self.pdig = [], [], [], [], []
+
+    def enable_digests(self, on):
+        self.digests = bool(on)
+        if not on or self.dig_bufs:
+            return
+        eng, rec, R = self.eng, engine_mod.DIGEST_DTYPE, range(self.N_BUF)
+
+        def pair(n):
+            d, h = [eng.alloc(n * rec.itemsize) for _ in R], [eng.alloc_host(n * rec.itemsize) for _ in R]
+            self.dig_bufs += d + h
+            return d, [b.array((n,), rec) for b in h]
+
+        self.d_dig, self.dig = pair(int(np.prod(self.go)))
+        for lv in self.pyr_levels:
+            d, h = pair(-(-lv.shape[1] // lv.chunks[1]) * -(-lv.shape[2] // lv.chunks[2]))
+            self.d_pdig.append(d)
+            self.pdig.append(h)
 
     def close(self):
-        for b in (self.pyr_bufs + self.d_bricks_in + self.d_bricks_out + [self.d_planes, self.d_out] + self.h_in + self.h_out
+        for b in (self.dig_bufs + self.pyr_bufs + self.d_bricks_in + self.d_bricks_out + [self.d_planes, self.d_out] + self.h_in + self.h_out
                   + self.d_frames + self.d_offsets + self.h_frames + self.h_offsets + self.h_packed + self.h_tasks
                   + self.h_status + self.d_packed + self.d_tasks + self.d_status):
             b.free()
@@ -457,11 +479,13 @@ class _DeviceBlocks:
                 frames, offs = self.pframes[i][j], self.poffsets[i][j]
                 self.eng.io_write_chunks(paths, [frames[offs[c] : offs[c + 1]] for c in range(len(idx))],
                                          threads=self.io_threads, zlib_level=-1)  # fmt: skip
-                continue
-            comp = arr.compressor
-            self.eng.io_write_chunks(paths, [self.stage_row[i][j][y, x] for y, x in idx], threads=self.io_threads,
-                                     zlib_level=-1 if comp is None else int(comp[1]),
-                                     blosc=arr.blosc_write_params() if comp and comp[0] == "blosc" else None)  # fmt: skip
+            else:
+                comp = arr.compressor
+                self.eng.io_write_chunks(paths, [self.stage_row[i][j][y, x] for y, x in idx], threads=self.io_threads,
+                                         zlib_level=-1 if comp is None else int(comp[1]),
+                                         blosc=arr.blosc_write_params() if comp and comp[0] == "blosc" else None)  # fmt: skip
+            if self.digests:  # the row's records into its own range of the level's manifest, behind its chunk files
+                arr.set_digest_records(row, self.pdig[i][j])
 
     def _write(self, z0, z1, k, flushes=()):
         """Compress / store the output bricks of planes ``[z0, z1)`` from pinned buffer ``k`` (and the pyramid rows that
@@ -469,6 +493,9 @@ class _DeviceBlocks:
         t0 = time.perf_counter()
         try:
             self._write_level0(z0, z1, k)
+            if self.digests:  # a z block's chunks are one contiguous range of the manifest
+                n = -(-(z1 - z0) // self.co[0]) * self.go[1] * self.go[2]
+                self.dst.set_digest_records(z0 // self.co[0], self.dig[k][:n])
             self._write_rows(flushes)
         finally:
             self.timing["write_s"] += time.perf_counter() - t0
@@ -536,8 +563,10 @@ class _DeviceBlocks:
         eng, (_, H, W), Z = self.eng, self.zyx, z1 - z0
         eng.stream_wait(C, D)             # (the wait lands before planes_to_bricks:) after download(b - 2 .. b - 1)
         eng.planes_to_bricks(self.d_out, self.d_bricks_out[k], (Z, H, W), self.co, 0)
-        flushes = self.pyr_flushes[k] = self._submit_pyramid(z0, z1)
         nbo = -(-Z // self.co[0])
+        if self.digests:                  # the bricks where the encoder / the download reads them
+            eng.brick_digest(self.d_bricks_out[k], (nbo, self.go[1], self.go[2]), self.co, (Z, H, W), self.d_dig[k])
+        flushes = self.pyr_flushes[k] = self._submit_pyramid(z0, z1)
         if self.device_codec:
             n_chunks = nbo * self.go[1] * self.go[2]
             eng.blosc_encode_device(self.d_bricks_out[k], n_chunks, self.out_brick * 2, self.d_frames[k],
@@ -547,6 +576,7 @@ class _DeviceBlocks:
             eng.copy_d2h_async(self.offsets[k][: n_chunks + 1], self.d_offsets[k], D)
             for i, j, _ in flushes:
                 eng.copy_d2h_async(self.poffsets[i][j], self.d_poffsets[i][j], D)
+            self._download_digests(k, n_chunks, flushes)
             eng.event_record(self.N_BUF + k, D)  # the frame offsets of block b (and of its rows) are here once this has passed
             return
         eng.stream_wait(D, C)             # download(b) after compute(b)
@@ -555,7 +585,20 @@ class _DeviceBlocks:
         for i, j, _ in flushes:
             eng.copy_d2h_async(self.stage_row[i][j], self.d_row[i][j], D)
             self._count_pyramid(self.stage_row[i][j].nbytes)
+        self._download_digests(k, nbo * self.go[1] * self.go[2], flushes)
         eng.event_record(self.N_BUF + k, D)  # pinned output buffer k (and the rows) hold block b once this has passed
+
+    def _download_digests(self, k, n_chunks, flushes):
+        """(download stream, behind its wait for compute(b)) The records of block b and of the rows it completed."""
+        if not self.digests:
+            return
+        from .engine import STREAM_DOWNLOAD as D
+
+        self.eng.copy_d2h_async(self.dig[k][:n_chunks], self.d_dig[k], D)
+        self.timing["download_bytes"] += self.dig[k][:n_chunks].nbytes
+        for i, j, _ in flushes:
+            self.eng.copy_d2h_async(self.pdig[i][j], self.d_pdig[i][j], D)
+            self._count_pyramid(self.pdig[i][j].nbytes)
 
     def _count_pyramid(self, nbytes):
         self.timing["download_bytes"] += nbytes
@@ -579,6 +622,10 @@ class _DeviceBlocks:
             if not s.flush:
                 continue
             j = cur[i]
+            if self.digests:  # the finished row with its own valid z extent, before the encoder reads it
+                eng.brick_digest(self.d_row[i][j], (1, -(-lv.shape[1] // lv.chunks[1]), -(-lv.shape[2] // lv.chunks[2])),
+                                 lv.chunks, (min(lv.chunks[0], lv.shape[0] - s.row * lv.chunks[0]),) + tuple(lv.shape[1:]),
+                                 self.d_pdig[i][j])  # fmt: skip
             if self.device_codec:
                 n_chunks = -(-lv.shape[1] // lv.chunks[1]) * -(-lv.shape[2] // lv.chunks[2])
                 eng.blosc_encode_device(self.d_row[i][j], n_chunks, int(np.prod(lv.chunks)) * 2, self.d_pframes[i][j],
@@ -818,6 +865,7 @@ def destripe_zarr_store(
     rotate=False,
     lightsheet=None,
     projections=None,
+    digests=False,
 ):
     """Chunk map of ``destripe_zarr`` (``zarr_destriper.py:909-1211``) over a Zarr-v2 directory store -- the engine-level
     form (explicit configs and ``shadow_correction``); :func:`destripe_zarr` is the entry point with the reference's
@@ -932,10 +980,21 @@ def destripe_zarr_store(
     assigns (``dsx_project_u16_ref``).  No existing launch and no output byte changes.  ``LAST_RUN["projections"]`` is
     ``None``, ``"output"`` or ``"both"``, ``LAST_RUN["projection_planes"]`` the planes added (``None`` without the
     option).  A wrong key, type or shape and a store that is not uint16 raise ``ValueError`` before anything is created.
+
+    ``digests=True``: level 0 and every fused pyramid level are created with a digest manifest (``.dsxdigest.json`` /
+    ``.dsxdigest.bin`` next to the chunks, ``MiniZarrArray.create(digests=True)``; ``csrc/dsx_digest.h``): one record
+    (valid voxels, their sum, their weighted sum mod 2^64) per chunk, of the voxels as they lie in device memory in chunk
+    order behind ``planes_to_bricks`` / the pyramid kernel and in front of the encoder (``dsx_brick_digest_u16_device``,
+    one more read of them); the records come back with the frame offsets (with the bricks when there is no device codec)
+    and the writer of the block stores them at the block's own range of the file, so ranks write disjoint ranges and
+    nothing is merged.  The host path records every chunk it writes with the host build.  No chunk file and no
+    ``.zarray`` byte changes; off, no launch, allocation or file differs and a manifest left by an earlier run is
+    removed.  ``integrity.verify_store`` reads a store back against it.  ``LAST_RUN["digests"]`` is the value used.
     """
     from . import projections as proj_mod
     from . import pyramid
 
+    digests = bool(digests)
     rotate = engine_mod.rotate_flag(rotate)
     scale = pyramid.check_scale_factor(scale_factor)
     proj_mode = proj_mod.check_store_option(projections)
@@ -978,7 +1037,8 @@ def destripe_zarr_store(
                     for lv in levels]  # fmt: skip
     if rank == 0:
         for path, shape, chunks in [(output_path, out_shape, out_chunks)] + level_arrays:
-            MiniZarrArray.create(path, shape, chunks, np.uint16, compressor=compressor, dimension_separator="/")
+            MiniZarrArray.create(path, shape, chunks, np.uint16, compressor=compressor, dimension_separator="/",
+                                 digests=digests)  # fmt: skip
     if group is not None and world_size > 1:
         group.barrier()
 
@@ -986,7 +1046,7 @@ def destripe_zarr_store(
         for _ in range(1200):  # without a group: wait for rank 0's metadata of this geometry
             try:
                 arr = MiniZarrArray.open(path)
-                if arr.matches(shape, chunks, np.uint16, compressor):
+                if arr.matches(shape, chunks, np.uint16, compressor) and (arr.digest_grid is not None) == digests:
                     return arr
             except (FileNotFoundError, ValueError):
                 pass
@@ -1034,7 +1094,7 @@ def destripe_zarr_store(
     LAST_RUN.update(device_codec=device_codec, device_codec_mode=codec_mode, device_decode=bool(device_decode),
                     device_decode_mode=decode_mode, decode_routes=None, fused_pyramid=bool(levels), pyramid_levels=[lv.level for lv in levels])  # fmt: skip
     LAST_RUN["histogram_voxels"] = None if histogram is None else 0
-    LAST_RUN.update(projections=proj_mode, projection_planes=None if proj_mode is None else 0)
+    LAST_RUN.update(projections=proj_mode, projection_planes=None if proj_mode is None else 0, digests=digests)
     if can and device_retile is not False:
         if lightsheet is not None:
             eng = fl._lightsheet_engine(zyx[1:], lightsheet["percentile"], lightsheet["artifact_length"],
@@ -1052,6 +1112,7 @@ def destripe_zarr_store(
         blocks = _device_blocks(eng, src, dst, zyx, block_z, io_threads, "runs" if codec_mode == "runs" else device_codec,
                                 device_decode, (levels, pyr_arrays) if levels else None, scale)  # fmt: skip
         blocks.histogram = histogram is not None
+        blocks.enable_digests(digests)
         if histogram is not None:
             eng.volhist_reset()
         rank_zyx = (z1 - z0,) + tuple(zyx[1:])
@@ -1463,6 +1524,7 @@ def compute_multiscale(
     ome_metadata=False,
     display_window=None,
     histogram=None,
+    digests=False,
 ):
     """``compute_multiscale`` of the reference (``zarr_destriper.py:677-794``) with its signature.
 
@@ -1491,6 +1553,10 @@ def compute_multiscale(
     ``scale_factor`` ``(fz, fy, fx)``: 1 or 2 per axis, not all 1 -- ``[2, 2, 2]`` in production (``:1176``), e.g.
     ``[1, 2, 2]`` for a volume whose z step is coarser than its pixel; level ``l`` is ``previous // factor`` per axis.
     Every route takes it; anything else raises ``ValueError`` before anything is written.
+
+    ``digests=True``: every level written gets a digest manifest (``pyramid.write_pyramid_levels(digests=True)``; on the
+    pipelined route the records are taken on the device from the finished chunk rows, on the slab route by the host
+    build as the chunks are written).  ``pyramid.LAST_PYRAMID["digests"]`` says what ran.
     """
     from . import pyramid
 
@@ -1504,7 +1570,7 @@ def compute_multiscale(
     shapes = pyramid.write_pyramid_levels(str(level0), str(group_path), scale_factor=tuple(scale_factor), n_levels=n_levels,
                                           chunks=chunks, compressor=compressor, device=device, slab_planes=slab_planes,
                                           pipelined=pipelined, device_codec=device_codec, device_decode=device_decode,
-                                          io_threads=io_threads)  # fmt: skip
+                                          io_threads=io_threads, digests=bool(digests))  # fmt: skip
     if window is not None:
         _write_group_metadata(str(group_path), str(level0), image_name, n_levels, scale_factor, voxel_size, window)
     return shapes
@@ -1547,6 +1613,8 @@ def destripe_zarr(
     lightsheet=None,
     scale_factor=None,
     qc_projections=None,
+    digests=False,
+    verify=False,
 ):
     """``destripe_zarr`` of the reference (``zarr_destriper.py:909-1211``) with its 14 parameters, on the GPU chunk map.
 
@@ -1600,12 +1668,17 @@ def destripe_zarr(
     merges the ranks' arrays after the barrier, and rank 0 writes ``<tile>_projections.npz`` and the three
     ``<tile>_mip_{z,y,x}.tif`` into ``results_folder`` (``projections.write_qc``; ``"both"`` adds the input's arrays and
     the stripe gain).  Any other value, and ``world_size > 1`` with a group without ``reduce_array``, raise
-    ``ValueError`` before anything is created).
+    ``ValueError`` before anything is created), ``digests`` (every array of the tile keeps a digest manifest:
+    :func:`destripe_zarr_store` for level 0 and the fused levels, :func:`compute_multiscale` for the others) and
+    ``verify`` (implies ``digests``: once the last level is written rank 0 reads the whole tile back with
+    ``integrity.verify_store`` -- the call's ``device_decode`` and ``io_threads`` -- and raises ``ValueError`` listing
+    every chunk that does not hold what was written; ``LAST_RUN["verify"]`` is the report, ``None`` without the option).
     Returns ``(planes processed by this rank, seconds)``.
     """
     from . import projections as proj_mod
     from . import pyramid
 
+    digests = bool(digests) or bool(verify)
     rotate = engine_mod.rotate_flag(rotate)
     proj_mod.check_qc_mode(qc_projections)
     if qc_projections is not None and world_size > 1 and not hasattr(group, "reduce_array"):
@@ -1721,6 +1794,7 @@ def destripe_zarr(
         rotate=rotate,
         lightsheet=lightsheet,
         projections=qc,
+        digests=digests,
     )
     if group is not None and world_size > 1:
         group.barrier()  # level 0 of this tile is complete on every rank: the pyramid may read it
@@ -1766,10 +1840,22 @@ def destripe_zarr(
             chunks=output_chunks,
             compressor=compressor,
             device=dev,
+            digests=digests,
             **pipelined_kw,
             **ome_kw,
         )
         logger.info(f"Processing multiscale time: {time.perf_counter() - t0} seconds")
+    LAST_RUN["verify"] = None
+    if verify and rank == 0:  # every level of the tile is written (fused: by every rank, before the barrier above)
+        from . import integrity
+
+        dev = int(os.environ.get("LOCAL_RANK", rank)) if device is None else device
+        report = integrity.verify_store(str(output_destriped_zarr), device_decode=device_decode, io_threads=io_threads,
+                                        device=dev)  # fmt: skip
+        LAST_RUN["verify"] = report
+        if report["bad"]:
+            raise ValueError("verify: {} of {} chunks of {} do not hold what was written: {}".format(
+                len(report["bad"]), report["chunks"], output_destriped_zarr, integrity.format_bad(report)))  # fmt: skip
     logger.info(f"Processing destripe flatfield time: {seconds} seconds")
     return n_planes, seconds
 
@@ -1806,6 +1892,8 @@ def destripe_channel(
     rotate=False,
     scale_factor=None,
     qc_projections=None,
+    digests=False,
+    verify=False,
 ):
     """``destripe_channel`` of the reference (``zarr_destriper.py:1214-1267``), same eight parameters (the reference's
     caller passes them by keyword, ``run_capsule.py:394-403``), wired to the GPU chunk map.
@@ -1831,7 +1919,8 @@ def destripe_channel(
     every tile's :func:`destripe_zarr` (``None`` = ``[2, 2, 2]``; ``ValueError`` before anything is created otherwise).
     ``qc_projections``: ``None``, ``"output"`` or ``"both"``, handed to every tile's :func:`destripe_zarr`, which leaves
     the tile's QC files in ``results_folder`` (``ValueError`` before anything is created for any other value, and with
-    ``world_size > 1`` for a group without ``reduce_array``).
+    ``world_size > 1`` for a group without ``reduce_array``).  ``digests`` / ``verify``: handed to every tile's
+    :func:`destripe_zarr` (a digest manifest per array; read the tile back against it once it is written).
     """
     from . import projections as proj_mod
     from . import pyramid
@@ -1911,6 +2000,8 @@ def destripe_channel(
             rotate=rotate,
             scale_factor=scale_factor,
             qc_projections=qc_projections,
+            digests=digests,
+            verify=verify,
         )
         done[tile_path.name] = n
     return done

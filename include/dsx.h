@@ -351,6 +351,26 @@ int dsx_project_u16_device(dsx_ctx* ctx, const void* d_planes, int Z, int H, int
                            int first, void* d_work);
 int dsx_project_u16_ref(const void* planes, int Z, int H, int W, const dsx_projection* p, int z_off, int first);
 
+/* Content digests of the chunks a pass writes (csrc/dsx_digest.h): neither the Blosc frames nor the zstd frames of a
+ * store carry a checksum, so a chunk that decodes to the wrong voxels raises nothing; a record per chunk, taken while
+ * the voxels lie in device memory in chunk order, lets a later pass over the store say "these are the voxels the filter
+ * produced" (integrity.py).  bricks: n0 * n1 * n2 bricks of (c0, c1, c2) uint16 voxels back to back, in C order of the
+ * grid (2-byte aligned) -- what the re-tiling kernels, the pyramid kernels and the decoders leave.  (v0, v1, v2): the
+ * valid voxels the buffer covers along each axis from its chunk-aligned origin, (n_a - 1) * c_a < v_a <= n_a * c_a, so
+ * brick g has extents e_a = min(c_a, v_a - g_a * c_a); padding never enters.  out: uint64 [n0 * n1 * n2][3] (8-byte
+ * aligned), per brick {count, sum, wsum}: with m(k) splitmix64's output over (k + 1) * 0x9E3779B97F4A7C15, made odd,
+ *   count = e0 * e1 * e2,  sum = SUM v,  wsum = SUM_r m(r) * SUM_{i2 < e2} v[r, i2] * m(2^32 + i2)    (mod 2^64)
+ * over the valid voxels, r = i0 * c1 + i1 the row index in the FULL chunk.  Exact integers: device, host build and a
+ * NumPy restatement agree bit for bit.  Every weight is odd: changing one voxel changes wsum.  Not cryptographic.
+ * Shapes below 1, bricks above 2^31 voxels, rows above 2^30, extents that do not end inside the last brick, NULL or
+ * misaligned pointers and an unknown stream id are DSX_EINVAL before anything is launched.
+ * The device call zeroes the records and launches on stream `stream_id` (DSX_STREAM_*); it never synchronises.
+ * The ref call is the host build of the same arithmetic (host pointers, synchronous). */
+int dsx_brick_digest_u16_device(dsx_ctx* ctx, const void* d_bricks, int n0, int n1, int n2, int c0, int c1, int c2, int v0,
+                                int v1, int v2, void* d_out, int stream_id);
+int dsx_brick_digest_u16_ref(const void* bricks, int n0, int n1, int n2, int c0, int c1, int c2, int v0, int v1, int v2,
+                             void* out);
+
 /* Host side of the chunk map: n Zarr chunk files <-> memory (normally the pinned staging buffers) on
  * `threads` native threads -- what zarr / numcodecs do under the reference's worker processes
  * (zarr_destriper.py:336, 1042-1074).  codec: raw chunks, zlib streams, or Blosc frames -- the production

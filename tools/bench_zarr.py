@@ -7,6 +7,7 @@ download) into another store.  Prints one JSON line; the roofline of this path i
     bench_zarr.py N [raw|zlib|blosc] [device-codec|device-codec-runs] [device-decode|device-decode-any|device-decode-all]
                   [lz4|blosc-zlib|blosc-blosclz|plain-zlib] [pyramid|fused-pyramid|pipelined-pyramid] [lz4-out] [read-back]
                   [streaks|streaks-generic|streaks-march] [ome-percentile] [scale-FZ-FY-FX] [projections|projections-both]
+                  [digests] [store-sha]
 
 `device-codec` (Blosc only): the output chunks are encoded on the GPU (destripe_zarr_store(device_codec=True)); the
 line then also reports the bytes written and their ratio to the host writer's frames of the same chunks (first block).
@@ -38,6 +39,13 @@ seconds; the line reports the window and the voxels counted under "ome", and a c
 `projections`: every timed pass collects the QC projections of the planes it writes (destripe_zarr_store(projections=
 {"output": ...}); `projections-both`: of the planes it read as well), inside the timed seconds; the line reports the mode and
 the planes added under "projections", and the rows of the picked planes are held to NumPy (a mismatch fails the run).
+`digests`: every timed pass writes the digest manifests of its arrays (destripe_zarr_store(digests=True), and the
+stand-alone pyramid words' compute_multiscale(digests=True)), inside the timed seconds; the written store is then read back
+once with integrity.verify_store(device_decode=True) and once with device_decode=False, and the line reports both times,
+the chunks checked and the bad ones under "digests" (any bad chunk fails the run).
+`store-sha` (implied by `digests`): after the timed section every chunk file and .zarray of the output is read again and
+hashed (the digest sidecars left out) and the line carries "store_sha256": equal between a run with `digests` and one
+without.
 `scale-FZ-FY-FX` (with a pyramid word): the pyramid's scale factor per axis, 1 or 2 each, e.g. `scale-1-2-2` for a volume
 whose z step is coarser than its pixel (scale_factor of destripe_zarr_store / compute_multiscale); the default is 2-2-2.
 `pyramid`: after the timed level-0 pass, compute_multiscale(n_levels=3) on the store is timed too (the two-pass route);
@@ -68,6 +76,7 @@ streaks = ([{"sigma": (64.0, 128.0), "route": r} for w, r in (("streaks", "auto"
                                                                ("streaks-march", "march")) if w in sys.argv[3:]] + [None])[0]
 ome = "ome-percentile" in sys.argv[3:]
 proj_keys = ("output", "input") if "projections-both" in sys.argv[3:] else ("output",) if "projections" in sys.argv[3:] else ()
+digests = "digests" in sys.argv[3:]
 scale = ([[int(f) for f in w.split("-")[1:]] for w in sys.argv[3:] if w.startswith("scale-")] + [[2, 2, 2]])[0]
 if (lz4_out or read_back) and codec != "blosc":
     sys.exit("lz4-out / read-back: a Blosc store")
@@ -129,7 +138,7 @@ try:
                                           synth.NO_CELLS_CONFIG, None, prediction_chunksize=(64, H, W),
                                           output_chunks=(1, 1, 64, 128, 128), device=0, device_retile=True, io_threads=16, compressor=out_codec,
                                           device_codec=device_codec, device_decode=device_decode, streaks=streaks,
-                                          **({"histogram": hist} if ome else {}), **kw)
+                                          **({"histogram": hist} if ome else {}), **({"digests": True} if digests else {}), **kw)
             if ome:
                 window = zd.display_window_from_histogram(hist)
                 if level0 != group:
@@ -156,12 +165,13 @@ try:
             t0 = time.perf_counter()
             zd.compute_multiscale(level0, group, scale, 1, None, "bench", n_levels=3, compressor=out_codec, device=0,
                                   pipelined=True, device_codec=device_codec, io_threads=16,
-                                  device_decode=device_decode if codec == "blosc" else False)
+                                  device_decode=device_decode if codec == "blosc" else False, **({"digests": True} if digests else {}))
             pyramid_s = time.perf_counter() - t0
             pyr["pipelined"] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in pyramid.LAST_PYRAMID.items()}
         if two_pass:  # the route destripe_zarr takes by default: rank 0 reads level 0 back and writes the levels
             t0 = time.perf_counter()
-            zd.compute_multiscale(level0, group, scale, 1, None, "bench", n_levels=3, compressor=out_codec, device=0)
+            zd.compute_multiscale(level0, group, scale, 1, None, "bench", n_levels=3, compressor=out_codec, device=0,
+                                  **({"digests": True} if digests else {}))
             pyramid_s = time.perf_counter() - t0
         pyr = {**pyr, "scale": scale, "route": "fused" if fused else ("pipelined" if pipelined else "two-pass"), "level0_s": round(secs, 3), "pyramid_s": round(pyramid_s, 3),
                "total_s": round(secs + pyramid_s, 3), "pyramid_download_bytes": int(timing["pyramid_download_bytes"])}
@@ -182,6 +192,24 @@ try:
                    for y in range(H // 128) for x in range(W // 128))
         sizes = {"bytes_written": written, "raw_bytes": n * H * W * 2, "ratio_to_raw": round(written / (n * H * W * 2), 4),
                  "first_block_bytes": got, "first_block_host_writer_bytes": host, "size_ratio_to_host_writer": round(got / host, 4)}
+    if digests or "store-sha" in sys.argv[3:]:  # every chunk file and .zarray of the output, in path order
+        import hashlib
+        sha = hashlib.sha256()
+        for rel in sorted(os.path.relpath(os.path.join(d, f), group) for d, _, fs in os.walk(group) for f in fs
+                          if not f.startswith(".dsxdigest")):
+            sha.update(rel.encode() + b"\0")
+            with open(os.path.join(group, rel), "rb") as fh:
+                sha.update(fh.read())
+        sizes["store_sha256"] = sha.hexdigest()
+    digest_info = {}
+    if digests:  # read the written store back against its manifests: device decoders, then the host's
+        from aind_smartspim_destripe_amd import integrity
+        digest_info = {"digests": {"pass": zd.LAST_RUN.get("digests")}}
+        for key, dd in (("verify_device_decode", True), ("verify_host_decode", False)):
+            t0 = time.perf_counter()
+            report = integrity.verify_store(group, device_decode=dd, io_threads=16, device=0)
+            digest_info["digests"][key] = {"seconds": round(time.perf_counter() - t0, 3), "arrays": report["arrays"],
+                                           "chunks": report["chunks"], "bad": [list(b) for b in report["bad"][:8]]}
     if read_back:  # the written store as the input of a pass that decodes it on the device
         for rep in range(2):  # (second pass: the staging buffers of this geometry exist)
             t0 = time.perf_counter()
@@ -261,9 +289,11 @@ try:
                       "roofline": {"bound": "host link", "peak_planes_per_s": 3750, "frac": round(v / 3750.0, 3)},
                       "read_s": round(timing["read_s"], 3), "write_s": round(timing["write_s"], 3), "host_link": link,
                       "plane0_checksum": chk, "verified": verified,
-                      "filter": zd.LAST_RUN.get("filter"), "streaks_route": zd.LAST_RUN.get("streaks_route"), **decode, **sizes, **ome_info, **proj_info, **({"pyramid": pyr} if pyr else {}),
+                      "filter": zd.LAST_RUN.get("filter"), "streaks_route": zd.LAST_RUN.get("streaks_route"), **decode, **sizes, **ome_info, **proj_info, **digest_info, **({"pyramid": pyr} if pyr else {}),
                       "verification": {"planes_bit_identical_to_single_plane_runs": checked,
                                        "planes_against_the_cpu_oracle": oracle_checked, "blocks": blocks}}))
+    if digests and any(v["bad"] for k, v in digest_info["digests"].items() if k != "pass"):
+        sys.exit(3)
     if not verified or not pyr.get("verified", True):
         sys.exit(3)
 finally:
