@@ -645,6 +645,7 @@ dsx::RowArgs row_args(const Chain& c, int l) {
   a.kcut[1] = lp.kcut[1];
   a.inv_M = 1.0f / (float)lp.M;
   a.ablate = ctx->ablate;
+  a.median_lockstep = ctx->tune.median_lockstep ? 1 : 0;
   return a;
 }
 

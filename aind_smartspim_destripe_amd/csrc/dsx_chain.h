@@ -76,6 +76,8 @@ struct DsxTuning {
   int row_pack_fill = 16;     // DSX_ROW_PACK_FILL: waves per CU (one pair each) from which the merged launch is packed
   int helper = -1;            // DSX_HELPER: -1 = helper stream for unsplit cohorts only, 0 / 1 = never / always
   bool no_pipeline = false;   // DSX_NO_PIPELINE: join the sub-cohort streams at every call
+  bool median_lockstep = false;  // DSX_MEDIAN_LOCKSTEP: rf_pair_body counts both rows of a masked pair until both medians are found
+                                 // (same bits: tests/test_gpu_median_rows.py; A/B runs)
 #ifdef DSX_DIAG
   int skip_hist = 0, skip_row = 0, skip_from = 1000;  // timing-only: WRONG results (DSX_SKIP_HIST / _ROW / _COARSE)
 #endif
@@ -110,6 +112,7 @@ inline void read_tuning(DsxTuning& t) {
   t.row_pack_fill = std::max(0, env_int("DSX_ROW_PACK_FILL", 16));
   t.helper = getenv("DSX_HELPER") ? (env_int("DSX_HELPER", 0) != 0 ? 1 : 0) : -1;
   t.no_pipeline = env_int("DSX_NO_PIPELINE", 0) != 0;
+  t.median_lockstep = env_int("DSX_MEDIAN_LOCKSTEP", 0) != 0;
 #ifdef DSX_DIAG
   t.skip_hist = env_int("DSX_SKIP_HIST", 0);
   t.skip_row = env_int("DSX_SKIP_ROW", 0);

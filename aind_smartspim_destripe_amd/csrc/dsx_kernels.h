@@ -1205,6 +1205,7 @@ struct RowArgs {
   int kcut[2];         // per config: the gains vanish for kcut < k < M - kcut
   float inv_M;
   int ablate;          // diagnosis only (DSX_ABLATE): 1 = no median, 2 = no FFT passes, 4 = no spectral step
+  int median_lockstep; // DSX_MEDIAN_LOCKSTEP: rf_pair_body steps both rows of a pair until both medians are found (same bits)
 };
 
 __device__ __forceinline__ unsigned f32_key(float v) {
@@ -1608,45 +1609,53 @@ __device__ __forceinline__ void rf_pair_body(const RowArgs& a, float2* s_tw, flo
   // and row; [lo, hi) with C(lo) <= k < C(hi) shrinks by regula falsi on (value, count) alternating with
   // the midpoint of the order-preserving integer keys (which bounds the number of steps), until exactly
   // one element -- or one value, for ties -- is left; the answer is then min{x >= lo}.  The zero spike
-  // of the masked entries is probed first (C(0) and #{x <= 0}).  Both rows run in lockstep; everything
-  // but the per-value compares is wave-uniform.  (Round 1 selected on packed 16-bit key halves by 16-step
+  // of the masked entries is probed first (C(0) and #{x <= 0}).  The two rows share the step counter, each
+  // steps only while its median is needed and not yet found; everything but the per-value compares is wave-uniform.  (Round 1 selected on packed 16-bit key halves by 16-step
   // bisection plus a bucket walk: ~2.1 k vector instructions per row pair with the key packing and
   // unpacking around it; this takes ~0.9 k.)
-  float meda = 0.f, medb = 0.f;
+  float med[2] = {0.f, 0.f};
   // the medians only enter through the masked positions: skip them for a mask-free pair of rows
   const bool any_mask = __ballot((maska | maskb) != (mask_t)0) != 0ull;
   if (any_mask && !DSX_ABL(a, 1)) {
     const unsigned k1 = (unsigned)(N - 1) >> 1;
     const bool even = (N & 1) == 0;
-    auto count2 = [&](float ta, float tb, bool le) -> unsigned {  // (#a < ta) | (#b < tb) << 16, wave totals
+    // a.median_lockstep (DSX_MEDIAN_LOCKSTEP=1, A/B runs and the bit-identity test): both rows take every step until both
+    // are finished, a mask-free row included
+    const bool lockstep = a.median_lockstep != 0;
+    // need[r]: row r has a masked entry, so its median is read (wave-uniform).  A row without one starts as finished:
+    // its median stays 0 and nothing of it is counted.  (has_b == false: row b is all zeros, never masked.)
+    const bool need[2] = {lockstep || __ballot(maska != (mask_t)0) != 0ull, lockstep || __ballot(maskb != (mask_t)0) != 0ull};
+    auto count = [&](int r, float t, bool le) -> unsigned {  // #{x < t} (le: <=) of row r, wave total
       // one vector compare per value; the wave total is a scalar population count of the compare mask
-      unsigned ca = 0, cb = 0;
+      unsigned c = 0;
       for_slots<GV>(gf, nt, [&](int e) {
-        ca += (unsigned)__popcll(__ballot(le ? (va[e] <= ta) : (va[e] < ta)));
-        cb += (unsigned)__popcll(__ballot(le ? (vb[e] <= tb) : (vb[e] < tb)));
+        const float x = r ? vb[e] : va[e];
+        c += (unsigned)__popcll(__ballot(le ? (x <= t) : (x < t)));
       });
-      return ca | (cb << 16);
+      return c;
     };
     // bracket state per row r (0 = a, 1 = b), wave-uniform
-    float lo[2], hi[2];
-    unsigned clo[2], chi[2];
-    bool done[2];
+    float lo[2] = {0.f, 0.f}, hi[2] = {0.f, 0.f};
+    unsigned clo[2] = {0u, 0u}, chi[2] = {0u, 0u};
     // f = C(t) - (k + 1/2) at the two ends (Illinois variant of regula falsi: an end that survives two updates of the
     // other one in a row has its f halved, which keeps the false position from creeping towards one side)
-    float flo[2], fhi[2];
+    float flo[2] = {0.f, 0.f}, fhi[2] = {0.f, 0.f};
     int last[2] = {0, 0};
+    // A row is finished when one element -- or, for ties, one value -- is left: C(hi) - C(lo) <= 1, or lo and hi are
+    // adjacent floats (adj).  The second test needs the integer keys and is only made where they are computed anyway: on
+    // the fallback path (a probe strictly inside (lo, hi) proves that the two are not adjacent).
+    bool adj[2] = {true, true};
     const float target = (float)k1 + 0.5f;
     const float thr_up = as_f32(as_u32(thr) + 1u);  // next float above thr (thr >= 0): C(thr_up) = N
-    {
-      const unsigned c0 = count2(0.f, 0.f, false), c0e = count2(0.f, 0.f, true);
 #pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const unsigned lt = r ? (c0 >> 16) : (c0 & 0xFFFFu), le = r ? (c0e >> 16) : (c0e & 0xFFFFu);
-        done[r] = false;
+    for (int r = 0; r < 2; ++r) {
+      if (need[r]) {  // (wave-uniform)
+        const unsigned lt = count(r, 0.f, false), le = count(r, 0.f, true);
+        adj[r] = false;
         if (k1 < lt) {            // the statistic is negative
           lo[r] = -thr; clo[r] = 0u; hi[r] = 0.f; chi[r] = lt;
         } else if (k1 < le) {     // inside the zero spike: [0, denorm_min) holds the value 0 only
-          lo[r] = 0.f; clo[r] = lt; hi[r] = as_f32(1u); chi[r] = le; done[r] = true;
+          lo[r] = 0.f; clo[r] = lt; hi[r] = as_f32(1u); chi[r] = le; adj[r] = true;
         } else {                  // positive: C(denorm_min) = #{x <= 0}
           lo[r] = as_f32(1u); clo[r] = le; hi[r] = thr_up; chi[r] = (unsigned)N;
         }
@@ -1654,71 +1663,65 @@ __device__ __forceinline__ void rf_pair_body(const RowArgs& a, float2* s_tw, flo
         fhi[r] = (float)chi[r] - target;
       }
     }
-    // A row is finished when one element -- or, for ties, one value -- is left: C(hi) - C(lo) <= 1, or lo and hi are
-    // adjacent floats.  The second test needs the integer keys and is only made where they are computed anyway: on the
-    // fallback path (a probe strictly inside (lo, hi) proves that the two are not adjacent).  A finished row simply
-    // keeps running until its partner is finished too -- every step preserves C(lo) <= k < C(hi) -- so the loop body
-    // carries no per-row "done" predicates (they were most of its ~240 scalar instructions per step).
-    bool adj[2] = {done[0], done[1]};
+    // Each row steps only while it is live (needed and not finished), under a wave-uniform branch: a row whose median is
+    // not read, or whose bracket is down to one value, costs no compares, no probe and no bracket update, and the loop
+    // ends with the last live row.  The bits do not depend on it: a row's probes follow from its own state and the shared
+    // step counter `it` alone, every step preserves C(lo) <= k < C(hi), and the statistic read below, min{x >= lo}, is the
+    // same for every such bracket -- so a row may stop at its first finished state or be stepped on (lockstep: both rows
+    // until both are finished, as the loop ran before) without changing its median.
     for (int it = 0; it < 256; ++it) {
-      const bool fin0 = adj[0] || chi[0] - clo[0] <= 1u, fin1 = adj[1] || chi[1] - clo[1] <= 1u;
-      if (fin0 && fin1) break;
-      float t[2];
+      const bool fin[2] = {adj[0] || chi[0] - clo[0] <= 1u, adj[1] || chi[1] - clo[1] <= 1u};
+      if (fin[0] && fin[1]) break;
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
-        // false position aimed at rank k + 1/2 (the probe only has to lie inside the bracket: the bare v_rcp_f32 instead
-        // of an IEEE division -- 12 instructions each -- changes which values are probed, never the result); on every
-        // eighth step, and whenever it leaves the bracket, the midpoint of the integer keys halves the number of
-        // representable values left (at most 8 x 32 steps in all).  Round 2's plain regula falsi with a key midpoint on
-        // every fourth step took 9.75 counts per masked row of the synthetic planes, this takes 8.96 (NumPy model of both
-        // loops against np.median on real and adversarial rows: tools/median_model.py)
-        float tt = (lo[r] * fhi[r] - hi[r] * flo[r]) * __builtin_amdgcn_rcpf(fhi[r] - flo[r]);
-        if ((it & 7) == 7 || !(tt > lo[r] && tt < hi[r])) {  // wave-uniform
-          const unsigned kl = f32_key(lo[r]), kh = f32_key(hi[r]);
-          if (kh - kl <= 1u) adj[r] = true;
-          tt = key_f32(kl + ((kh - kl) >> 1));
-        }
-        t[r] = tt;
-      }
-      const unsigned c = count2(t[0], t[1], false);
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const unsigned cr = r ? (c >> 16) : (c & 0xFFFFu);
-        const float f = (float)cr - target;
-        if (cr <= k1) {
-          lo[r] = t[r]; clo[r] = cr; flo[r] = f;
-          if (last[r] == 1) fhi[r] *= 0.5f;
-          last[r] = 1;
-        } else {
-          hi[r] = t[r]; chi[r] = cr; fhi[r] = f;
-          if (last[r] == 2) flo[r] *= 0.5f;
-          last[r] = 2;
+        if (lockstep || !fin[r]) {  // (wave-uniform)
+          // false position aimed at rank k + 1/2 (the probe only has to lie inside the bracket: the bare v_rcp_f32 instead
+          // of an IEEE division -- 12 instructions each -- changes which values are probed, never the result); on every
+          // eighth step, and whenever it leaves the bracket, the midpoint of the integer keys halves the number of
+          // representable values left (at most 8 x 32 steps in all).  Round 2's plain regula falsi with a key midpoint on
+          // every fourth step took 9.75 counts per masked row of the synthetic planes, this takes 8.96 (NumPy model of both
+          // loops against np.median on real and adversarial rows: tools/median_model.py)
+          float tt = (lo[r] * fhi[r] - hi[r] * flo[r]) * __builtin_amdgcn_rcpf(fhi[r] - flo[r]);
+          if ((it & 7) == 7 || !(tt > lo[r] && tt < hi[r])) {  // wave-uniform
+            const unsigned kl = f32_key(lo[r]), kh = f32_key(hi[r]);
+            if (kh - kl <= 1u) adj[r] = true;
+            tt = key_f32(kl + ((kh - kl) >> 1));
+          }
+          const unsigned cr = count(r, tt, false);
+          const float f = (float)cr - target;
+          if (cr <= k1) {
+            lo[r] = tt; clo[r] = cr; flo[r] = f;
+            if (last[r] == 1) fhi[r] *= 0.5f;
+            last[r] = 1;
+          } else {
+            hi[r] = tt; chi[r] = cr; fhi[r] = f;
+            if (last[r] == 2) flo[r] *= 0.5f;
+            last[r] = 2;
+          }
         }
       }
     }
     // s_k = min{x >= lo};  even N: s_{k+1} = s_k if more than k + 1 values lie below hi, else min{x >= hi}
-    float m_lo[2] = {__builtin_huge_valf(), __builtin_huge_valf()}, m_hi[2] = {__builtin_huge_valf(), __builtin_huge_valf()};
-    for_slots<GV>(gf, nt, [&](int e) {
-      m_lo[0] = min_no_nan(m_lo[0], va[e] >= lo[0] ? va[e] : __builtin_huge_valf());
-      m_lo[1] = min_no_nan(m_lo[1], vb[e] >= lo[1] ? vb[e] : __builtin_huge_valf());
-      if (even) {
-        m_hi[0] = min_no_nan(m_hi[0], va[e] >= hi[0] ? va[e] : __builtin_huge_valf());
-        m_hi[1] = min_no_nan(m_hi[1], vb[e] >= hi[1] ? vb[e] : __builtin_huge_valf());
-      }
-    });
-    float sk[2], sk1[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-      sk[r] = wave_min_no_nan(m_lo[r]);
-      sk1[r] = sk[r];
-      if (even) {
-        const float nxt = wave_min_no_nan(m_hi[r]);
-        sk1[r] = (k1 + 1u < chi[r]) ? sk[r] : nxt;
+      if (need[r]) {  // (wave-uniform)
+        float m_lo = __builtin_huge_valf(), m_hi = __builtin_huge_valf();
+        for_slots<GV>(gf, nt, [&](int e) {
+          const float x = r ? vb[e] : va[e];
+          m_lo = min_no_nan(m_lo, x >= lo[r] ? x : __builtin_huge_valf());
+          if (even) m_hi = min_no_nan(m_hi, x >= hi[r] ? x : __builtin_huge_valf());
+        });
+        const float sk = wave_min_no_nan(m_lo);
+        float sk1 = sk;
+        if (even) {
+          const float nxt = wave_min_no_nan(m_hi);
+          sk1 = (k1 + 1u < chi[r]) ? sk : nxt;
+        }
+        med[r] = even ? 0.5f * (sk + sk1) : sk;
       }
     }
-    meda = even ? 0.5f * (sk[0] + sk1[0]) : sk[0];
-    medb = even ? 0.5f * (sk[1] + sk1[1]) : sk[1];
   }  // any_mask
+  float meda = med[0], medb = med[1];
   // The medians are wave-uniform (SGPR); ROCm 7.2's instruction selection crashes when they flow
   // into the selects / LDS stores below, so pin them into VGPRs.
   asm volatile("" : "+v"(meda), "+v"(medb));
