@@ -6,6 +6,7 @@
 //   plan <H> <W> <s0> <l0> <s1> <l1>    prints the plan (levels, dims, M, K, radices)
 //   chain key=value ...          the launches dsx_chain.h decides for one run call (switches: the DSX_* environment)
 //   chain-rules                  sweeps the geometry rules the kernels rely on (tests/test_chain_host.py)
+//   genlds                       dynamic LDS of k_fwd_gen / k_inv_gen per tap count (tests/test_wavelet_gen_cases_host.py)
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -546,7 +547,17 @@ static int cmd_chain_rules() {
   return 0;
 }
 
+// genlds: the dynamic LDS k_fwd_gen / k_inv_gen are launched with, per even tap count up to kMaxTaps' 104
+static int cmd_genlds() {
+  printf("{\"limit\": %zu, \"taps\": {", dsx::kLdsLimit);
+  for (int F = 2; F <= 104; F += 2)
+    printf("%s\"%d\": [%zu, %zu]", F > 2 ? ", " : "", F, dsx::gen_fwd_lds_bytes(F), dsx::gen_inv_lds_bytes(F));
+  printf("}}\n");
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc >= 2 && !strcmp(argv[1], "genlds")) return cmd_genlds();
   if (argc >= 2 && !strcmp(argv[1], "chain")) return cmd_chain(argc, argv);
   if (argc >= 2 && !strcmp(argv[1], "chain-rules")) return cmd_chain_rules();
   if (argc >= 3 && !strcmp(argv[1], "fft")) return cmd_fft(atoi(argv[2]));
@@ -558,6 +569,6 @@ int main(int argc, char** argv) {
     return cmd_rows(atoi(argv[2]), atoi(argv[3]), atof(argv[4]), atoi(argv[5]), atoi(argv[6]));
   if (argc >= 2 && !strcmp(argv[1], "pruned")) return cmd_pruned();
   if (argc >= 2 && !strcmp(argv[1], "swz")) return cmd_swz();
-  fprintf(stderr, "usage: pruned | swz | fft M | plan H W s0 l0 s1 l1 | rows H W sigma level lvl | chain key=value ... | chain-rules\n");
+  fprintf(stderr, "usage: pruned | swz | fft M | plan H W s0 l0 s1 l1 | rows H W sigma level lvl | chain key=value ... | chain-rules | genlds\n");
   return 2;
 }

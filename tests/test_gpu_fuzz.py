@@ -1,6 +1,7 @@
 """A short randomised parity run inside the GPU suite: 30 random cases of tools/fuzz_parity.py (plane shapes around
 the strip / lane-pair boundaries of the march kernels, uint16 / float32 input, 1-4 planes, random filter parameters
-per config) under the full statement of tests/parity_util.py.  The seed is fixed: the test is deterministic; longer
+per config) under the full statement of tests/parity_util.py; 30 more that draw the launch-geometry switches, and 30 with
+a random PyWavelets bank each through the tap-count-generic level kernels.  The seeds are fixed: the test is deterministic; longer
 runs with other seeds are a tool (profiles/r2_fuzz_parity.log: 2 492 planes)."""
 
 import os
@@ -35,6 +36,18 @@ def test_fuzz_launch_geometry_30_cases():
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         planes, _ = fuzz_parity.run(cases=30, seed=404, geometry=True)
+    assert planes >= 30
+
+
+def test_fuzz_wavelets_30_cases():
+    """30 random cases with a random PyWavelets bank each (2 ... 102 taps, every bank but dmey and rbio3.1) through the
+    tap-count-generic level kernels, on planes from 6 to 420 pixels, the oracle running on the same bank: the shared
+    row-filter, histogram and chain code behind those kernels under the same statement."""
+    import fuzz_parity
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # "level too high" for long filters on small planes
+        planes, _ = fuzz_parity.run(cases=30, seed=20261, any_wavelet=True)
     assert planes >= 30
 
 

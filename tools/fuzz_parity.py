@@ -73,112 +73,115 @@ def run(cases=40, seed=2026, eng=None, any_wavelet=False, geometry=False):
     eng = eng_mod.DestripeEngine(0) if own else eng
     t0 = time.time(); worst = 0.0; n_regime_retries = 0; n_planes = 0; n_batched = 0
     saved_env = {k: os.environ.get(k) for k in GEOMETRY}
-    for c in range(cases):
-        drawn = None
-        if geometry:  # a fresh context per case: dsx_init reads the switches
-            filtering.release_engines()
-            if own and eng is not None:
-                eng.close()
-            drawn = draw_geometry(rng, apply=geometry != "dry")
-            eng = eng_mod.DestripeEngine(0)
-            own = True
-        anchor = int(rng.choice([64, 122, 128, 244, 256, 488, 512, 732, 976, 1220, 1708, 2048]))
-        w = max(40, anchor + int(rng.integers(-9, 10)))
-        if rng.random() < 0.6: w = (w + 3) & ~3          # fused kernels need a multiple of 4
-        if rng.random() < 0.3: w = (w + 7) & ~7          # lane-pair I/O of the final kernel: multiple of 8
-        h = int(rng.integers(40, 700))
-        if geometry and rng.random() < 0.22:             # the hot widths: k_rowfinal and the compile-time FFT plans
-            w, h = int(rng.choice([2048, 2048, 2000, 1800])), int(rng.integers(64, 420)) & ~1
-        if not any_wavelet and rng.random() < 0.03:      # rows longer than one wave holds (k_rowfilter_wide), few rows
-            w = int(rng.choice([2304, 4606, 4608, 5120, 6001, 7000, 9216])) + int(rng.integers(0, 3))
-            h = int(rng.integers(12, 90))
-        if not any_wavelet and rng.random() < 0.03:      # tall and narrow: many row segments, a last one of any length
-            h = int(rng.integers(2100, 4300))
-            w = (int(rng.integers(40, 76)) + 3) & ~3
-        name = "db3"
-        if any_wavelet:
-            # (dmey is refused; rbio3.1 amplifies float32 round-off beyond 1e-4 at depth -- the reference's own float32
-            # and float64 regimes differ by 1e-3 there -- and has its own test with its own bound, tests/test_wavelets.py)
-            name = str(rng.choice([x for x in wavelets.wavelist() if x not in ("dmey", "rbio3.1")]))
-            w, h = int(rng.integers(6, 420)), int(rng.integers(6, 300))
-        n = int(rng.integers(1, 5))
-        as_f32 = rng.random() < 0.3
-        # random filter parameters: decomposition depth, low-pass width, threshold cap, fg/bg decision level
-        cells = {"wavelet": name, "level": [None, None, 1, 2, 3, 5][int(rng.integers(0, 6))],
-                 "sigma": float(rng.choice([16, 64, 100, 250])), "max_threshold": float(rng.choice([0.5, 3, 12]))}
-        nocells = {"wavelet": name, "level": [None, None, 1, 2, 4][int(rng.integers(0, 5))],
-                   "sigma": float(rng.choice([32, 128, 512])), "max_threshold": float(rng.choice([1, 12, 100]))}
-        high_int = int(rng.choice([100, 160, 2500]))
-        # the oracle takes the filter bank itself (it knows db3 by name only)
-        ocells, onocells = (dict(c, wavelet=wavelets.filter_bank(name)) if any_wavelet else c for c in (cells, nocells))
-        planes = np.stack([synth.synthetic_plane(int(rng.integers(0, 1000)), h, w) for _ in range(n)])
-        src = planes.astype(np.float32) if as_f32 else planes
-        try:
-            deltas = gpu_deltas(eng, src, high_int=high_int, cells=cells, nocells=nocells)
-        except ValueError as e:
-            if "odd plane" in str(e):  # documented limit: one config with levels, one without, on an odd plane
-                continue
-            raise
-        out, cfg = filtering.destripe_planes(src, "X_0_Y_0", nocells, cells, None,
-                                             high_int, out_dtype=np.float32, return_config=True, max_batch=n)
-        for k in range(n):
-            # The engine computes in float32 like the reference's Zarr path (float32 planes, zarr_destriper.py:1049); for
-            # uint16 input the reference's TIFF path runs in float64 and can pick the neighbouring Otsu bin on a plateau
-            # of the class-variance curve -- the two regimes of the reference differ from each other there, so a plane must
-            # satisfy the statement against ONE of them (the float64 regime is tried first).
-            err = None
-            for regime in ((np.float32,) if as_f32 else (np.uint16, np.float32)):
-                img = src[k].astype(regime)
-                which, _, _, ref, stages = oracle_plane(img, high_int=high_int, cells=ocells, nocells=onocells)
-                # (no decomposition level at all -- long filters on small planes: the result is image + 2 whatever the
-                # config, the statistic is not computed and cfg_used reads 0)
-                assert int(cfg[k]) == which or eng.levels == 0, (h, w, k)
-                cfgd = ocells if which else onocells
-                try:
-                    check_plane(out[k], img, deltas[k], ((h, w), np.dtype(regime).name, k, name, drawn), cfgd, max_flips, ref=ref, stages=stages)
-                    err = None
-                    break
-                except AssertionError as e:
-                    err = e
-                    n_regime_retries += 1
-            if err is not None:
-                # keep the failing plane: the CPU side (oracle, histograms) can then be studied without a GPU
-                try:
-                    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-                    np.savez_compressed(os.path.join(ROOT, "gpurun_out", "fuzz_fail_%d_%d.npz" % (seed, c)), plane=src[k], out=out[k],
-                                        cfg=int(cfg[k]), cells=repr(cells), nocells=repr(nocells), high_int=high_int,
-                                        otsu=np.array(deltas[k].otsu, dtype=np.float64), drawn=repr(drawn),
-                                        **{"ch%d" % lv: np.asarray(a) for lv, a in enumerate(deltas[k].ch)})
-                except Exception as save_err:  # noqa: BLE001
-                    print("could not save the failing case:", save_err)
-                raise err
-            n_planes += 1
-        # now and then: the same planes many times over, split into cohorts and sub-cohort streams -- every copy of a
-        # plane must come out bit-identical to the small run above, wherever it sits in the batch
-        if rng.random() < (0.4 if geometry else 0.12) and h * w <= (420 * 2048 if geometry else 300 * 600):
-            reps = int(rng.integers(33, 80))
-            idx = rng.integers(0, n, size=reps)
-            big = src[idx]
-            mb = int(rng.choice([16, 32, 48, reps]))
-            out_big = filtering.destripe_planes(big, "X_0_Y_0", nocells, cells, None, high_int, out_dtype=np.float32,
-                                                max_batch=mb)
-            assert np.array_equal(out_big, out[idx]), ("batch position dependence", (h, w), reps, mb, drawn)
-            n_batched += 1
-        # uint16 result path (truncation): within one count of the float result
-        out16 = filtering.destripe_planes(src, "X_0_Y_0", nocells, cells, None, high_int, out_dtype=np.uint16, max_batch=n)
-        d = np.abs(out16.astype(np.float64) - np.clip(np.floor(out.astype(np.float64)), 0, 65535))
-        assert d.max() <= 1.0, ((h, w), float(d.max()), drawn)
-        worst = max(worst, float(d.max()))
-    if geometry:
-        filtering.release_engines()
+    try:
+        for c in range(cases):
+            drawn = None
+            if geometry:  # a fresh context per case: dsx_init reads the switches
+                filtering.release_engines()
+                if own and eng is not None:
+                    eng.close()
+                drawn = draw_geometry(rng, apply=geometry != "dry")
+                eng = eng_mod.DestripeEngine(0)
+                own = True
+            anchor = int(rng.choice([64, 122, 128, 244, 256, 488, 512, 732, 976, 1220, 1708, 2048]))
+            w = max(40, anchor + int(rng.integers(-9, 10)))
+            if rng.random() < 0.6: w = (w + 3) & ~3          # fused kernels need a multiple of 4
+            if rng.random() < 0.3: w = (w + 7) & ~7          # lane-pair I/O of the final kernel: multiple of 8
+            h = int(rng.integers(40, 700))
+            if geometry and rng.random() < 0.22:             # the hot widths: k_rowfinal and the compile-time FFT plans
+                w, h = int(rng.choice([2048, 2048, 2000, 1800])), int(rng.integers(64, 420)) & ~1
+            if not any_wavelet and rng.random() < 0.03:      # rows longer than one wave holds (k_rowfilter_wide), few rows
+                w = int(rng.choice([2304, 4606, 4608, 5120, 6001, 7000, 9216])) + int(rng.integers(0, 3))
+                h = int(rng.integers(12, 90))
+            if not any_wavelet and rng.random() < 0.03:      # tall and narrow: many row segments, a last one of any length
+                h = int(rng.integers(2100, 4300))
+                w = (int(rng.integers(40, 76)) + 3) & ~3
+            name = "db3"
+            if any_wavelet:
+                # (dmey is refused; rbio3.1 amplifies float32 round-off beyond 1e-4 at depth -- the reference's own float32
+                # and float64 regimes differ by 1e-3 there -- and has its own test with its own bound, tests/test_wavelets.py)
+                name = str(rng.choice([x for x in wavelets.wavelist() if x not in ("dmey", "rbio3.1")]))
+                w, h = int(rng.integers(6, 420)), int(rng.integers(6, 300))
+            n = int(rng.integers(1, 5))
+            as_f32 = rng.random() < 0.3
+            # random filter parameters: decomposition depth, low-pass width, threshold cap, fg/bg decision level
+            cells = {"wavelet": name, "level": [None, None, 1, 2, 3, 5][int(rng.integers(0, 6))],
+                     "sigma": float(rng.choice([16, 64, 100, 250])), "max_threshold": float(rng.choice([0.5, 3, 12]))}
+            nocells = {"wavelet": name, "level": [None, None, 1, 2, 4][int(rng.integers(0, 5))],
+                       "sigma": float(rng.choice([32, 128, 512])), "max_threshold": float(rng.choice([1, 12, 100]))}
+            high_int = int(rng.choice([100, 160, 2500]))
+            # the oracle takes the filter bank itself (it knows db3 by name only)
+            ocells, onocells = (dict(c, wavelet=wavelets.filter_bank(name)) if any_wavelet else c for c in (cells, nocells))
+            planes = np.stack([synth.synthetic_plane(int(rng.integers(0, 1000)), h, w) for _ in range(n)])
+            src = planes.astype(np.float32) if as_f32 else planes
+            try:
+                deltas = gpu_deltas(eng, src, high_int=high_int, cells=cells, nocells=nocells)
+            except ValueError as e:
+                if "odd plane" in str(e):  # documented limit: one config with levels, one without, on an odd plane
+                    continue
+                raise
+            out, cfg = filtering.destripe_planes(src, "X_0_Y_0", nocells, cells, None,
+                                                 high_int, out_dtype=np.float32, return_config=True, max_batch=n)
+            for k in range(n):
+                # The engine computes in float32 like the reference's Zarr path (float32 planes, zarr_destriper.py:1049); for
+                # uint16 input the reference's TIFF path runs in float64 and can pick the neighbouring Otsu bin on a plateau
+                # of the class-variance curve -- the two regimes of the reference differ from each other there, so a plane must
+                # satisfy the statement against ONE of them (the float64 regime is tried first).
+                err = None
+                for regime in ((np.float32,) if as_f32 else (np.uint16, np.float32)):
+                    img = src[k].astype(regime)
+                    which, _, _, ref, stages = oracle_plane(img, high_int=high_int, cells=ocells, nocells=onocells)
+                    # (no decomposition level at all -- long filters on small planes: the result is image + 2 whatever the
+                    # config, the statistic is not computed and cfg_used reads 0)
+                    assert int(cfg[k]) == which or eng.levels == 0, (h, w, k)
+                    cfgd = ocells if which else onocells
+                    try:
+                        check_plane(out[k], img, deltas[k], ((h, w), np.dtype(regime).name, k, name, drawn), cfgd, max_flips, ref=ref, stages=stages)
+                        err = None
+                        break
+                    except AssertionError as e:
+                        err = e
+                        n_regime_retries += 1
+                if err is not None:
+                    # keep the failing plane: the CPU side (oracle, histograms) can then be studied without a GPU
+                    try:
+                        os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
+                        np.savez_compressed(os.path.join(ROOT, "gpurun_out", "fuzz_fail_%d_%d.npz" % (seed, c)), plane=src[k], out=out[k],
+                                            cfg=int(cfg[k]), cells=repr(cells), nocells=repr(nocells), high_int=high_int,
+                                            otsu=np.array(deltas[k].otsu, dtype=np.float64), drawn=repr(drawn),
+                                            **{"ch%d" % lv: np.asarray(a) for lv, a in enumerate(deltas[k].ch)})
+                    except Exception as save_err:  # noqa: BLE001
+                        print("could not save the failing case:", save_err)
+                    raise err
+                n_planes += 1
+            # now and then: the same planes many times over, split into cohorts and sub-cohort streams -- every copy of a
+            # plane must come out bit-identical to the small run above, wherever it sits in the batch
+            if rng.random() < (0.4 if geometry else 0.12) and h * w <= (420 * 2048 if geometry else 300 * 600):
+                reps = int(rng.integers(33, 80))
+                idx = rng.integers(0, n, size=reps)
+                big = src[idx]
+                mb = int(rng.choice([16, 32, 48, reps]))
+                out_big = filtering.destripe_planes(big, "X_0_Y_0", nocells, cells, None, high_int, out_dtype=np.float32,
+                                                    max_batch=mb)
+                assert np.array_equal(out_big, out[idx]), ("batch position dependence", (h, w), reps, mb, drawn)
+                n_batched += 1
+            # uint16 result path (truncation): within one count of the float result
+            out16 = filtering.destripe_planes(src, "X_0_Y_0", nocells, cells, None, high_int, out_dtype=np.uint16, max_batch=n)
+            d = np.abs(out16.astype(np.float64) - np.clip(np.floor(out.astype(np.float64)), 0, 65535))
+            assert d.max() <= 1.0, ((h, w), float(d.max()), drawn)
+            worst = max(worst, float(d.max()))
+    finally:
+        # whatever a case raised: later tests of the process get the switches they started with, no cached engine of a
+        # drawn geometry, and no context of this run
         for k, v in saved_env.items():
             if v is None:
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+        filtering.release_engines()
+        if own and eng is not None:
+            eng.close()
     print("fuzz: %d cases passed in %.0f s (uint16 vs floor(float32) result: max difference %.0f count; %d planes matched the float32 regime of the reference only; %d big-batch bit-identity checks)" % (cases, time.time() - t0, worst, n_regime_retries, n_batched))
-    if own:
-        eng.close()
     return n_planes, n_regime_retries
 
 
